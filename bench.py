@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — elements assembled per second of the PIHNA element-assembly hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one invocation of the assemble callback over the whole mesh: (N > 1: halo exchange of
 ghost-node DoFs over RCCL, then) evaluation of Ke/Fe for every element and scatter into the global
@@ -10,7 +10,11 @@ CSR matrix + rhs.  Inputs are resident in HBM when the timed region starts.
 Workload: BASELINE.json's metric is quoted on the 10M-tet PIHNA mesh, which fits one GPU:
 K(119) = 10,110,954 TET4 / 1,728,000 nodes, 5 unknowns (8.64 M DoFs, 648 M CSR values), synthetic
 fields, parameters of run/PIHNA/input.dat.  N > 1 partitions that SAME mesh (strong scaling).
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the K steps (`ms_per_step`),
+writes the outputs of the last step when --dump-outputs is given, and prints that line.
+--dump-outputs DIR: the CSR values and rhs of the last timed step (rank 0's rows), float64, as DIR/<name>.npy,
+64 MB at most (a fixed, seeded sample of a larger array; see dump_outputs).
+With --full the line also carries, at N = 1,
   "configs"      kernel time / elements per second / roofline fraction of the other BASELINE configurations
                  (cfg2 PIHNA K(55), cfg3 RIPF K(94), cfg5 HCC H(126) + solid H(126)) and of the general-parameter PIHNA
                  kernel on K(119), each timed here with HIP events (3 warm-ups + 10 launches);
@@ -19,7 +23,7 @@ Prints ONE JSON line on rank 0.  At N = 1 the line also carries
   "cpu_baseline" the oracle (a port of the reference loop) on the benchmark mesh itself with all host cores (+ 1 core on a sample);
   "parity"       relative residual of the timed configuration's GPU result (rhs L2, matrix Frobenius) against that CPU assembly;
   "value_with_handback"  elements per second when the CSR is downloaded to the host every step (never `value`).
-At N > 1 it carries "multi_gpu": halo bytes, ghost-element overhead, halo time, host time per step.
+At N > 1 it carries "multi_gpu": halo bytes, ghost-element overhead, host time per step (with --full also the halo time).
 """
 from __future__ import annotations
 
@@ -46,6 +50,38 @@ def algorithmic_bytes(nen, n_elem, n_node, n_owned, nvar, n_in, nnz, solid=False
     if solid:
         b += 8 * 3 * n_node + 8 * 4 * n_elem
     return b
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much .npy data in all
+
+
+def dump_outputs(out_dir, systems):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the CSR values and the rhs of each
+    (name, AssemblyContext) in `systems` -- as out_dir/<name>_csr_values.npy and out_dir/<name>_rhs.npy, float64.  An array
+    larger than its share of DUMP_BYTES is written as a sample: its entries at the sorted, de-duplicated indices of
+    np.random.default_rng(length).integers(0, length, share), the same from run to run and from build to build.  The entries
+    are gathered on the device: the CSR values of the benchmark mesh are 5 GB."""
+    import torch
+    arrays = []
+    for name, ctx in systems:
+        n_rows, nnz = ctx.csr_dims()
+        d_val, d_rhs = ctx.csr_values_device_ptr()
+        arrays += [(f"{name}_csr_values", d_val, nnz, ctx.device), (f"{name}_rhs", d_rhs, n_rows, ctx.device)]
+    share = (DUMP_BYTES // len(arrays) - 4096) // 8        # float64 entries per array; 4 kB for the .npy header
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+
+    class _View:
+        pass
+    for name, ptr, n, device in arrays:
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2, "strides": None}
+        t = torch.as_tensor(v, device=torch.device("cuda", device))
+        if n > share:
+            idx = np.unique(np.random.default_rng(n).integers(0, n, share))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(out_dir / f"{name}.npy", t.cpu().numpy())
 
 
 def host_threads():
@@ -446,6 +482,8 @@ def run_cfg5(a):
     t_host = time.perf_counter() - t0
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("hcc", hcc), ("solid", sol)])
     k_hcc, k_sol = sum(hcc.timing_samples_ms()) / a.steps, sum(sol.timing_samples_ms()) / a.steps
     stats = torch.tensor([dt, k_hcc, k_sol, t_host / a.steps * 1e6, float(hx.bytes_per_step if hx else 0), float(lp.conn.shape[0]) / max(lp.n_elem_owned, 1),
                           float(lp.n_interior) / max(lp.n_owned, 1), float(hcc.part1_nodes()) / max(lp.n_owned, 1)], dtype=torch.float64,
@@ -495,16 +533,24 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo = host-staged halo, for rehearsing N > 1 on a 1-GPU box")
     ap.add_argument("--opt", action="append", default=[], help="tuning knob key=value (rdc_set_option)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the CSR values and rhs of the last timed step (rank 0) as DIR/<name>.npy, float64, 64 MB at most")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline: at N = 1 the ones below "
+                    "(each can still be switched off on its own), at N > 1 the halo exchange alone")
     ap.add_argument("--cpu-sample", type=int, default=60, help="K(m) sample for the 1-core CPU baseline (0 = skip it)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="N = 1: time the oracle on the benchmark mesh with all host cores and "
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="N = 1, --full: time the oracle on the benchmark mesh with all host cores and "
                     "report the parity residual of the GPU result against it (0 = skip)")
-    ap.add_argument("--state-check", type=int, default=1, help="N = 1: also time the kernel on a dense state and with the background short cut off")
-    ap.add_argument("--configs", type=int, default=1, help="N = 1: also time the other BASELINE configurations (0 = skip)")
+    ap.add_argument("--state-check", type=int, default=1, help="N = 1, --full: also time the kernel on a dense state and with the background "
+                    "short cut off")
+    ap.add_argument("--configs", type=int, default=1, help="N = 1, --full: also time the other BASELINE configurations (0 = skip)")
     ap.add_argument("--configs-only", type=int, default=0, help="1: run ONLY the other BASELINE configurations and print their array (the command "
                     "tools/make_profiles_configs.sh profiles)")
-    ap.add_argument("--two-part", dest="two_part", type=int, default=1, help="N = 1: also measure the host cost of the two-part step of the N > 1 path (0 = skip)")
-    ap.add_argument("--handback", type=int, default=1, help="N = 1: also time the CSR hand-back to the host (0 = skip)")
+    ap.add_argument("--two-part", dest="two_part", type=int, default=1, help="N = 1, --full: also measure the host cost of the two-part step of "
+                    "the N > 1 path (0 = skip)")
+    ap.add_argument("--handback", type=int, default=1, help="N = 1, --full: also time the CSR hand-back to the host (0 = skip)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.configs_only:
         print(json.dumps({"configs": extra_configs()}), flush=True)
@@ -603,17 +649,21 @@ def main():
     samples = ctx.timing_samples_ms()     # HIP events around the assembly kernel of every call, on the context's stream
     kern_ms, n_calls = float(sum(samples)), len(samples)
     ctx.timing_enable(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("pihna", ctx)])
     multi = None
     if world > 1:
-        # diagnostics of the N > 1 run: the exchange alone (device time between events on this rank's stream)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fence()
-        e0.record()
-        for _ in range(a.steps):
-            hx.exchange(u_t)
-        e1.record()
-        fence()
-        halo_ms = e0.elapsed_time(e1) / a.steps
+        halo_ms = -1.0
+        if a.full:
+            # diagnostics of the N > 1 run: the exchange alone (device time between events on this rank's stream)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fence()
+            e0.record()
+            for _ in range(a.steps):
+                hx.exchange(u_t)
+            e1.record()
+            fence()
+            halo_ms = e0.elapsed_time(e1) / a.steps
         on_cpu = a.backend != "nccl"
         t = torch.tensor([dt, kern_ms / max(n_calls, 1) if not overlap else kern_ms / a.steps, halo_ms, t_host / a.steps * 1e6,
                           float(hx.bytes_per_step), float(l_conn.shape[0]) / max(lp.n_elem_owned, 1), float(len(hx.peers))],
@@ -622,7 +672,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         dt, kern_avg_ms = float(t[0]), float(t[1])
-        multi = {"halo_ms_max": float(t[2]), "halo_ms_min": float(tmin[2]), "host_enqueue_us_per_step_max": float(t[3]),
+        multi = {"halo_ms_max": float(t[2]) if a.full else None, "halo_ms_min": float(tmin[2]) if a.full else None,
+                 "host_enqueue_us_per_step_max": float(t[3]),
                  "halo_send_bytes_per_rank_max": float(t[4]), "halo_send_bytes_per_rank_min": float(tmin[4]),
                  "local_over_owned_elements_max": float(t[5]), "local_over_owned_elements_min": float(tmin[5]),
                  "peers_max": int(t[6]), "kernel_ms_per_step_max": float(t[1]), "kernel_ms_per_step_min": float(tmin[1]),
@@ -660,7 +711,7 @@ def main():
         }
         if multi:
             out["multi_gpu"] = multi
-        if world == 1:
+        if world == 1 and a.full:
             gpu_val = gpu_rhs = None
             if a.cpu_baseline:
                 gpu_val, gpu_rhs = ctx.csr_download()     # the result of the last timed step
@@ -675,7 +726,7 @@ def main():
                 out["value_with_handback"] = n_elem_global / (hb * 1e-3)
     ctx.close()
     del u_t
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         torch.cuda.empty_cache()
         if a.cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(l_conn, l_xyz, l_u, p, f"K({a.n})", a.cpu_sample, a.params, gpu_val, gpu_rhs)

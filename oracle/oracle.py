@@ -4,6 +4,7 @@ PARITY UNPINNED (the reference holds no golden vectors; see rdc_oracle.c header)
 from __future__ import annotations
 
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -43,7 +44,7 @@ _ref = None
 def build_ref():
     """oracle/_ref/libref_eig3.so: the reference's own src/eig3.C compiled where it lies (oracle/Makefile) -- only where
     /root/reference exists (this container); the GPU box uses the prebuilt file or goes without."""
-    if REF_SRC.exists():
+    if os.access(REF_SRC, os.R_OK):   # Path.exists() raises where the sources exist but are not readable by this user
         src = [HERE / "ref_eig3_wrap.cpp", REF_SRC]
         if not REF_LIB.exists() or REF_LIB.stat().st_mtime < max(p.stat().st_mtime for p in src):
             subprocess.run(["make", "-C", str(HERE), "-B", "_ref/libref_eig3.so"], check=True, capture_output=True)
