@@ -52,8 +52,10 @@ constexpr bool symmetric_moment_gen(int m) { return m != M_Epv && m != M_Edd && 
 //
 // bg ("background"): the caller knows that n = c = h = a = 0 and v > 0 at the four vertices of every visit it passes together (the
 // device: of every active lane of the wave -- a scalar branch).  Then Ve = 1 and 1 - Ve = 0 (src/pihna.C:474-499), and the nine
-// moments E(1-Ve), E(P h), E(Q h), E(n), E(c), E(h), x, y, E(dTau c), the transport moments of the c and h rows and the right-hand
-// sides of the n, c, h, a equations are sums of exact zeros: they are not evaluated and nothing is added for them.  The shipped
+// moments E(1-Ve), E(P h), E(Q h), E(n), E(c), E(h), x, y, E(dTau c) and the right-hand sides of the n, c, h, a equations are sums
+// of exact zeros: they are not evaluated and nothing is added for them.  The transport moments of the c and h rows are zero only
+// while c = h = 0 fails the threshold (Lambda >= 0): with cells_min_capacity < 0, diffuse/c and taxis/c (h) are on at c = 0
+// (src/pihna.C:504-507) and Y_c, Y_h keep their dd_ij sum_q JxW_q T dif Tau and gk_i[v] F_j(T tax Tau) parts.  The shipped
 // initial field (run/PIHNA/Brain_Model_Initial_Nodal_Field.dat) is this state at 24,880 of its 24,903 nodes.
 // (a run-time flag: as two instantiations inlined side by side the kernel spills 30 registers instead of 3.)
 template <int EXP_MODE, class Sink, bool MIRROR = true, bool GEN = false>
@@ -198,7 +200,7 @@ RDC_HD void pihna_visit(const PihnaK& k, const double (&X)[4][3], const double (
     }
   }
   // ---- cell transport (GEN): rows c (species 1) and h (species 2), gradient fields (own, v) ---------------------------------
-  if (GEN && !bg) {
+  if (GEN && !(bg && k.Lambda >= 0.0)) {   // bg: zero only while c = h = 0 fails the threshold (see above)
 #pragma unroll
     for (int sp = 1; sp <= 2; sp++) {
       const double Tdif = sp == 1 ? k.Tdif_c : k.Tdif_h, Ttax = sp == 1 ? k.Ttax_c : k.Ttax_h;

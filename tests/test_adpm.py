@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import shim_rows
+from parity import assert_csr_close
 from rdcfes_amd import adpm_params_from_dict, synth
 
 
@@ -105,7 +106,7 @@ def test_gpu_parity(oracle, nen, n, variant, scatter, kernel_variant):
     conn, xyz = synth.kuhn_tet_mesh(n, jitter=0.1, order="random") if nen == 4 else synth.hex_mesh(n, jitter=0.1, order="random")
     u, tracts = synth.adpm_fields(xyz, conn.shape[0])
     p = adpm_params_from_dict(synth.adpm_param_dict(variant), time=3.0)
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_ADPM, nen, conn, xyz, 3, p, u_old=u, elem_fibre=tracts)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_ADPM, nen, conn, xyz, 3, p, u_old=u, elem_fibre=tracts)
     with AssemblyContext(0) as ctx:
         ctx.set_kernel_variant(kernel_variant)
         ctx.mesh_upload(nen, conn, xyz, 3)
@@ -118,3 +119,4 @@ def test_gpu_parity(oracle, nen, n, variant, scatter, kernel_variant):
         val, rhs = ctx.csr_download()
     assert np.linalg.norm(rhs - rhs0) <= 1e-10 * np.linalg.norm(rhs0)
     assert np.linalg.norm(val - val0) <= 1e-10 * np.linalg.norm(val0)
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)

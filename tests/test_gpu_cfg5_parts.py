@@ -8,6 +8,7 @@
 import numpy as np
 import pytest
 
+from parity import assert_csr_close
 from rdcfes_amd import AssemblyContext, SolidMaterial, SolidParams, hcc_params_from_dict, synth
 from rdcfes_amd.context import FIELD_ELEM_FIBRE, FIELD_OLD_SOLUTION, FIELD_UNDEFORMED_XYZ
 
@@ -62,7 +63,7 @@ def test_two_part_hex8_cluster_kernels_equal_whole(frac):
                 part = lambda k, s: ctx.solid_assemble_part(sp, True, k, s.cuda_stream)
             whole()
             val0, rhs0 = ctx.csr_download()
-            rp, _ = ctx.csr_pattern()
+            rp, col = ctx.csr_pattern()
             # overwrite every row, then the two parts on two streams (part 2 concurrently with part 1: the sides wait inside)
             ctx.mesh_update_coords(Xu)
             whole()
@@ -86,6 +87,7 @@ def test_two_part_hex8_cluster_kernels_equal_whole(frac):
             s1.synchronize(); s2.synchronize()
             val, rhs = ctx.csr_download()
         assert rel(val, val0) < 1e-13 and rel(rhs, rhs0) < 1e-13, system
+        assert_csr_close(rp, col, val, val0, rhs, rhs0, 3, rtol=1e-13)
 
 
 def _two_rank_cfg5(rank, world, port, q):

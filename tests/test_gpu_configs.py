@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+from parity import assert_csr_close, assert_csr_close_chunked
 from rdcfes_amd import (AssemblyContext, SolidMaterial, SolidParams, hcc_params_from_dict, partition,
                         pihna_params_from_dict, ripf_params_from_dict, synth)
 from rdcfes_amd.context import (FIELD_AUX_NODAL, FIELD_ELEM_FIBRE, FIELD_OLD_SOLUTION, FIELD_UNDEFORMED_XYZ,
@@ -43,7 +44,7 @@ def test_cfg3_ripf_k94_against_oracle(oracle, k94, pvariant):
     conn, xyz, pattern = k94
     u, aux = synth.ripf_fields(xyz)
     p = ripf_params_from_dict(synth.ripf_param_dict(pvariant))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=u, aux=aux, pattern=pattern, threads=THREADS)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=u, aux=aux, pattern=pattern, threads=THREADS)
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 3)
         ctx.field_upload(FIELD_OLD_SOLUTION, u)
@@ -53,6 +54,7 @@ def test_cfg3_ripf_k94_against_oracle(oracle, k94, pvariant):
         rp, col = ctx.csr_pattern()
     assert np.array_equal(rp, pattern[0]) and np.array_equal(col, pattern[1])
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 # ---- cfg5 -------------------------------------------------------------------------------------------------------
@@ -70,7 +72,7 @@ def test_cfg5_hcc_h126_against_oracle(oracle, h126):
     x = Xu + synth.solid_displacement(Xu, amp=0.02 / 126 * 8)   # a deformation of a fraction of the cell size
     u = synth.hcc_fields(Xu)
     p = hcc_params_from_dict(synth.hcc_param_dict("full"))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_HCC, 8, conn, x, 3, p, u_old=u, pattern=pattern, threads=THREADS)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_HCC, 8, conn, x, 3, p, u_old=u, pattern=pattern, threads=THREADS)
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(8, conn, Xu, 3)
         ctx.mesh_update_coords(x)
@@ -78,6 +80,7 @@ def test_cfg5_hcc_h126_against_oracle(oracle, h126):
         ctx.assemble_hcc(p)
         val, rhs = ctx.csr_download()
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 def test_cfg5_solid_h126(oracle, h126):
@@ -102,9 +105,9 @@ def test_cfg5_solid_h126(oracle, h126):
     #     lie inside the slab are complete there
     k0 = n // 2 - 1
     e0, e1 = k0 * n * n, (k0 + 3) * n * n
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, 8, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
-                                       elem_material=em, materials=mats, request_jacobian=True, pattern=pattern,
-                                       e_begin=e0, e_end=e1, threads=THREADS)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, 8, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
+                                            elem_material=em, materials=mats, request_jacobian=True, pattern=pattern,
+                                            e_begin=e0, e_end=e1, threads=THREADS)
     cnt_all = np.bincount(conn.ravel(), minlength=Xu.shape[0])
     cnt_slab = np.bincount(conn[e0:e1].ravel(), minlength=Xu.shape[0])
     inner = np.flatnonzero((cnt_slab == cnt_all) & (cnt_slab > 0))
@@ -114,6 +117,7 @@ def test_cfg5_solid_h126(oracle, h126):
     lo, hi = rp[rows[0]], rp[rows[-1] + 1]      # the inner nodes are one contiguous run in the lexicographic numbering
     assert np.array_equal(rows, np.arange(rows[0], rows[-1] + 1))
     assert rel(val[lo:hi], val0[lo:hi]) < TOL
+    assert_csr_close(rp0[rows[0]:rows[-1] + 2] - lo, col0[lo:hi], val[lo:hi], val0[lo:hi], rhs[rows], rhs0[rows], 3)
     assert np.abs(em[e0:e1]).max() == 1 and np.abs(val0[lo:hi]).max() > 0
     # (2) whole mesh: a rigid translation is in the null space of the element Jacobian (no penalty sides): for every row
     #     the entries of each displacement component sum to zero
@@ -220,7 +224,7 @@ def test_headline_k119_shipped_params_default_kernel_against_oracle(oracle):
     u = synth.pihna_fields(xyz)
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
     pattern = oracle.build_pattern(4, conn, xyz.shape[0], xyz.shape[0], 5)[:2]
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_PIHNA, 4, conn, xyz, 5, p, u_old=u, pattern=pattern, threads=THREADS)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_PIHNA, 4, conn, xyz, 5, p, u_old=u, pattern=pattern, threads=THREADS)
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         ctx.field_upload(FIELD_OLD_SOLUTION, u)
@@ -228,7 +232,7 @@ def test_headline_k119_shipped_params_default_kernel_against_oracle(oracle):
         val, rhs = ctx.csr_download()
         rp, col = ctx.csr_pattern()
     assert np.array_equal(rp, pattern[0]) and np.array_equal(col, pattern[1])
-    del rp, col, pattern
+    del rp, col
 
     def rel_chunked(a, b):
         num = den = 0.0
@@ -238,3 +242,4 @@ def test_headline_k119_shipped_params_default_kernel_against_oracle(oracle):
             den += float(np.dot(b[i:i + (1 << 24)], b[i:i + (1 << 24)]))
         return (num / den) ** 0.5
     assert rel_chunked(rhs, rhs0) < TOL and rel_chunked(val, val0) < TOL
+    assert_csr_close_chunked(pattern[0], pattern[1], val, val0, rhs, rhs0, 5)

@@ -8,6 +8,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from parity import assert_csr_close
 from rdcfes_amd import (adpm_params_from_dict, hcc_params_from_dict, pihna_params_from_dict, proteas_params_from_dict,
                         ripf_params_from_dict, synth)
 
@@ -118,6 +119,7 @@ def test_callback_through_host_mirror(oracle, driver, tmp_path, model, nen):
     np.testing.assert_array_equal(rp, rp0)
     np.testing.assert_array_equal(col, col0)
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
 
 
 def test_time_step_through_host_mirror(oracle, driver, tmp_path):
@@ -161,5 +163,6 @@ def test_chunked_handback_through_host_mirror(oracle, driver, tmp_path, chunks):
     assert np.array_equal(log[1:, 0], log[:-1, 1]) and np.all(log[:, 1] >= log[:, 0])      # a partition of [0, n_nodes), in order
     val, rhs = np.fromfile(tmp_path / "val.bin"), np.fromfile(tmp_path / "rhs.bin")
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)

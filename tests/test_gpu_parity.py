@@ -4,6 +4,7 @@ applied to the matrix (Frobenius) and to A*x for a seeded random x."""
 import numpy as np
 import pytest
 
+from parity import assert_csr_close
 from rdcfes_amd import (AssemblyContext, RdcError, SolidMaterial, SolidParams, hcc_params_from_dict,
                         pihna_params_from_dict, ripf_params_from_dict, synth)
 from rdcfes_amd.context import (FIELD_AUX_NODAL, FIELD_ELEM_FIBRE, FIELD_OLD_SOLUTION, FIELD_UNDEFORMED_XYZ,
@@ -75,6 +76,7 @@ def test_parity_small_mesh(oracle, model, nen, strategy, variant, pvariant):
     np.testing.assert_array_equal(col, col0)
     assert rel(rhs, rhs0) < TOL
     assert rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
     x = np.random.default_rng(1).standard_normal(xyz.shape[0] * nv)
     assert rel(csr_matvec(rp, col, val, x), csr_matvec(rp0, col0, val0, x)) < TOL
     if nen == 8 and nv == 3 and strategy == SCATTER_ROWGATHER:
@@ -83,10 +85,12 @@ def test_parity_small_mesh(oracle, model, nen, strategy, variant, pvariant):
         for options in ((("hex_kernel", 2),), (("solid_cl_order", 1),), (("hex_kernel", 1),)):
             _, _, val, rhs = _gpu_assemble(model, nen, conn, xyz, u, aux, p, strategy, variant, options=options)
             assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL, options
+            assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
     if nen == 8 and nv == 5 and strategy == SCATTER_ROWGATHER:
         # five unknowns: the default above is the cluster kernel one equation row at a time (k_hex8_cl_rows); the pair kernels stay covered
         _, _, val, rhs = _gpu_assemble(model, nen, conn, xyz, u, aux, p, strategy, variant, options=(("hex_kernel", 1),))
         assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+        assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
 
 
 def test_hex8_cluster_kernel_on_a_ghosted_partition(oracle):
@@ -98,6 +102,7 @@ def test_hex8_cluster_kernel_on_a_ghosted_partition(oracle):
     rp, col, val, rhs = _gpu_assemble(2, 8, conn, xyz, u, None, p, SCATTER_ROWGATHER, VARIANT_GENERIC, n_owned=n_owned)
     np.testing.assert_array_equal(rp, rp0)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 @pytest.mark.parametrize("strategy", [SCATTER_COLOURED, SCATTER_ROWGATHER])
@@ -113,6 +118,7 @@ def test_parity_ghosted_partition(oracle, strategy):
     np.testing.assert_array_equal(rp, rp0)
     np.testing.assert_array_equal(col, col0)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.parametrize("pvariant", ["shipped", "realexp_shipped"])
@@ -128,7 +134,7 @@ def test_resident_element_visit_kernel_on_a_ghosted_partition(oracle, pvariant):
     p = pihna_params_from_dict(d)
     n_owned = int(0.6 * xyz.shape[0])
     conn = conn[(conn < n_owned).any(axis=1)]
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u, n_owned=n_owned)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u, n_owned=n_owned)
     with AssemblyContext(0) as ctx:
         ctx.set_option("ev_resident", 2)
         ctx.mesh_upload(4, conn, xyz, 5, n_owned=n_owned)
@@ -140,6 +146,7 @@ def test_resident_element_visit_kernel_on_a_ghosted_partition(oracle, pvariant):
             ctx.assemble_pihna(p)
             val, rhs = ctx.csr_download()
             assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+            assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 def test_parity_cfg2_full_size(oracle):
@@ -149,8 +156,10 @@ def test_parity_cfg2_full_size(oracle):
     rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     rp, col, val, rhs = _gpu_assemble(0, 4, conn, xyz, u, None, p, SCATTER_ROWGATHER, VARIANT_AUTO)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
     rp, col, val, rhs = _gpu_assemble(0, 4, conn, xyz, u, None, p, SCATTER_COLOURED, VARIANT_AUTO)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 def test_full_size_properties_10m_tets():
@@ -199,7 +208,7 @@ def test_moving_mesh_hcc(oracle):
     """assemble_hcc runs on the CURRENT (deformed) coordinates (src/coupled_hcc.C:98-114)."""
     conn, xyz, u, aux, p = _inputs(2, 8, 6, order="lex")
     xyz2 = xyz + synth.solid_displacement(xyz)
-    _, _, val0, rhs0 = oracle.assemble(2, 8, conn, xyz2, 3, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(2, 8, conn, xyz2, 3, p, u_old=u)
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(8, conn, xyz, 3)
         ctx.field_upload(FIELD_OLD_SOLUTION, u)
@@ -209,6 +218,7 @@ def test_moving_mesh_hcc(oracle):
         ctx.assemble_hcc(p)
         val, rhs = ctx.csr_download()
     assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
     assert rel(v_undeformed, val0) > 1e-4
 
 
@@ -237,8 +247,8 @@ def _solid_case(nen, n, seed=0):
 def test_solid_parity(oracle, nen, n, use_symmetry, jac, solid_kernel, solid_gather, solid_split, cl_waves):
     conn, Xu, x, em, mats, fibre, sides = _solid_case(nen, n)
     sp = SolidParams(0.4, 1.0e5, use_symmetry, 0)
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, nen, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
-                                       elem_material=em, materials=mats, request_jacobian=jac, sides=sides)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, nen, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
+                                            elem_material=em, materials=mats, request_jacobian=jac, sides=sides)
     with AssemblyContext(0) as ctx:
         ctx.set_option("solid_kernel", solid_kernel)   # 0 = default (fused cluster kernel for HEX8 tangents, else two-pass), 1 = coloured, 2 = two-pass
         ctx.set_option("solid_cl_waves", cl_waves)     # fused kernel: 31 = 3 consumer + 1 producer waves, 62 = 6 + 2
@@ -256,6 +266,7 @@ def test_solid_parity(oracle, nen, n, use_symmetry, jac, solid_kernel, solid_gat
     assert rel(rhs, rhs0) < TOL
     if jac:
         assert rel(val, val0) < TOL
+        assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
     else:
         assert np.all(val == 0.0)
     if solid_kernel == 2 and sides[0].size == 0:
@@ -273,8 +284,8 @@ def test_solid_parity_on_a_ghosted_partition(oracle, solid_kernel):
     keep = (conn < n_owned).any(axis=1)
     conn, em, fibre = conn[keep], em[keep], fibre[keep]
     sp = SolidParams(0.4, 1.0e5, 0, 0)
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, 8, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
-                                       elem_material=em, materials=mats, request_jacobian=True, n_owned=n_owned)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, 8, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
+                                            elem_material=em, materials=mats, request_jacobian=True, n_owned=n_owned)
     with AssemblyContext(0) as ctx:
         ctx.set_option("solid_kernel", solid_kernel)
         ctx.mesh_upload(8, conn, x, 3, n_owned=n_owned)
@@ -285,6 +296,7 @@ def test_solid_parity_on_a_ghosted_partition(oracle, solid_kernel):
         val, rhs = ctx.csr_download()
     assert rhs.size == 3 * n_owned
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 def test_clamp_nonnegative(oracle):
@@ -430,7 +442,7 @@ def test_pihna_option_sets(oracle, opts):
     conn, xyz = synth.kuhn_tet_mesh(9, order="lex")
     u = synth.pihna_fields(xyz)
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     with AssemblyContext(0) as ctx:
         for k, v in opts.items():
             ctx.set_option(k, v)
@@ -439,6 +451,7 @@ def test_pihna_option_sets(oracle, opts):
         ctx.assemble_pihna(p)
         val, rhs = ctx.csr_download()
     assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.parametrize("pvariant", ["full", "realexp", "taxis_v_only"])
@@ -454,7 +467,7 @@ def test_pihna_general_parameter_kernels(oracle, pvariant, opts):
     else:
         d = synth.pihna_param_dict("shipped" if "specialise" in opts else pvariant)
     p = pihna_params_from_dict(d)
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     with AssemblyContext(0) as ctx:
         two_part = opts.get("part", 0)
         if two_part:
@@ -473,6 +486,33 @@ def test_pihna_general_parameter_kernels(oracle, pvariant, opts):
             ctx.assemble_pihna(p)
         val, rhs = ctx.csr_download()
     assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+
+
+@pytest.mark.parametrize("lam", [-1e-3, 0.0, 1.0])
+@pytest.mark.parametrize("opts", [{}, {"ev_resident": 2}, {"ev_background": 0}])
+def test_pihna_background_skip_against_the_threshold(oracle, lam, opts):
+    """cells_min_capacity < 0 switches diffuse/c and taxis/c (h) on at c = h = 0 (src/pihna.C:504-507): the background short
+    cut of the 22-moment element-visit kernels (k_tet4_ev<GEN>, resident k_tet4_evq<GEN>) must keep the c/h transport
+    moments.  The (c, c) and (h, h) blocks are a few 1e-11 of the global norm: only the per-block check sees them."""
+    conn, xyz = synth.kuhn_tet_mesh(8, order="random")
+    u = synth.pihna_fields(xyz)
+    d = synth.pihna_param_dict("full")
+    d["cells_min_capacity"] = lam
+    p = pihna_params_from_dict(d)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    with AssemblyContext(0) as ctx:
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        ctx.mesh_upload(4, conn, xyz, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u)
+        ctx.assemble_pihna(p)
+        val, rhs = ctx.csr_download()
+        rp, col = ctx.csr_pattern()
+    np.testing.assert_array_equal(rp, rp0)
+    np.testing.assert_array_equal(col, col0)
+    assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.parametrize("persistent", [0, 2])
@@ -562,7 +602,7 @@ def test_two_part_assembly_ripf_element_visits(oracle):
     conn, xyz = synth.kuhn_tet_mesh(10, order="lex")
     u, aux = synth.ripf_fields(xyz)
     p = ripf_params_from_dict(synth.ripf_param_dict("full"))
-    _, _, val0, rhs0 = oracle.assemble(1, 4, conn, xyz, 3, p, u_old=u, aux=aux)
+    rp0, col0, val0, rhs0 = oracle.assemble(1, 4, conn, xyz, 3, p, u_old=u, aux=aux)
     n_int = int(0.4 * xyz.shape[0])
     with AssemblyContext(0) as ctx:
         ctx.set_option("interior_nodes", n_int)
@@ -572,6 +612,7 @@ def test_two_part_assembly_ripf_element_visits(oracle):
         ctx.assemble_ripf(p)
         val, rhs = ctx.csr_download()
         assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+        assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
         rp, _ = ctx.csr_pattern()
         ctx.field_upload(FIELD_OLD_SOLUTION, 0.5 * u)
         ctx.assemble_ripf(p)
@@ -592,6 +633,8 @@ def test_two_part_assembly_ripf_element_visits(oracle):
     assert new_rows.size > 0.5 * 3 * n_int and new_rows.max() < 3 * n_int     # part 1: most interior rows, nothing else
     assert rel(valb, val0) < TOL and rel(rhsb, rhs0) < TOL
     assert rel(valc, val0) < TOL and rel(rhsc, rhs0) < TOL
+    assert_csr_close(rp0, col0, valb, val0, rhsb, rhs0, 3)
+    assert_csr_close(rp0, col0, valc, val0, rhsc, rhs0, 3)
 
 
 def test_two_part_assembly_fallback_paths():
@@ -640,7 +683,7 @@ def test_pihna_shipped_pattern_branches(oracle, moments):
     u[(x >= 0.4) & (x < 0.5), 1:3] = 0.0                      # Ve = 1
     u[(x >= 0.5) & (x < 0.6), 3] = 0.0                        # Ve = 0
     u[x > 0.7] = 0.0                                          # empty
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     with AssemblyContext(0) as ctx:
         ctx.set_option("moments", moments)
         ctx.mesh_upload(4, conn, xyz, 5)
@@ -651,6 +694,7 @@ def test_pihna_shipped_pattern_branches(oracle, moments):
     assert np.isnan(val0).any()
     ok, okr = ~np.isnan(val0), ~np.isnan(rhs0)
     assert rel(val[ok], val0[ok]) < TOL and rel(rhs[okr], rhs0[okr]) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)           # NaN entries: in the same places, left out of the norms
     np.testing.assert_allclose(val[ok], val0[ok], rtol=1e-9, atol=1e-12 * np.abs(val0[ok]).max())
 
 
@@ -698,9 +742,10 @@ def test_two_part_assembly_on_two_streams(oracle, resident):
             val, rhs = ctx.csr_download()
             exp_u = lu.copy()
             exp_u[lp.n_owned:] *= scale
-            _, _, val0, rhs0 = oracle.assemble(0, 4, lp.conn, lp.xyz, 5, p, u_old=exp_u, n_owned=lp.n_owned)
+            rp0, col0, val0, rhs0 = oracle.assemble(0, 4, lp.conn, lp.xyz, 5, p, u_old=exp_u, n_owned=lp.n_owned)
             assert np.isfinite(val).all() and np.isfinite(rhs).all()
             assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+            assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.gpu
@@ -759,7 +804,7 @@ def test_pihna_zero_cell_sum_with_positive_vasculature(oracle, moments):
     u[slab, 2] = 0.0
     inside = slab[conn].all(axis=1)
     assert inside.sum() > 100                                   # elements whose every point has c + h + v == 0 exactly
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     with AssemblyContext(0) as ctx:
         ctx.set_option("moments", moments)
         ctx.mesh_upload(4, conn, xyz, 5)
@@ -770,6 +815,7 @@ def test_pihna_zero_cell_sum_with_positive_vasculature(oracle, moments):
     ok, okr = ~np.isnan(val0), ~np.isnan(rhs0)
     assert ok.mean() > 0.5
     assert rel(val[ok], val0[ok]) < TOL and rel(rhs[okr], rhs0[okr]) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.gpu

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from parity import assert_csr_close
 from rdcfes_amd import pihna_params_from_dict, synth
 
 
@@ -44,10 +45,11 @@ def test_ev_replay_matches_oracle(oracle, shim, order, pvariant):
     if pvariant == "shipped_realexp":
         d["cells_max_capacity/exponent"] = 2.5
     p = pihna_params_from_dict(d)
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     val, rhs, st = _ev(shim, conn, xyz, u, p, xyz.shape[0])
     assert np.isfinite(val).all() and np.isfinite(rhs).all()      # every CSR value and rhs entry is produced
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
     # an element is visited by every cluster that owns one of its nodes; a visit serves 1..4 rows
     assert st["n_rows"] == 4 * conn.shape[0]
     assert conn.shape[0] <= st["n_vis"] <= st["n_rows"]
@@ -68,10 +70,11 @@ def test_ev_replay_general_parameters(oracle, shim, order, pvariant, gen):
         d.update({"taxis_v_only": {"taxis/v": 0.3, "uptake/a/from/v": 2.0e-5}, "diffuse_c_only": {"diffuse/c": 0.2},
                   "taxis_h_only": {"taxis/h": 0.15}}[pvariant])
     p = pihna_params_from_dict(d)
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     val, rhs, st = _ev(shim, conn, xyz, u, p, xyz.shape[0], gen=gen)
     assert np.isfinite(val).all() and np.isfinite(rhs).all()
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 @pytest.mark.parametrize("pvariant", ["shipped", "full"])
@@ -83,7 +86,7 @@ def test_ev_replay_background_skip(oracle, shim, pvariant):
     bgn = (u[:, [0, 1, 2, 4]] == 0).all(1) & (u[:, 3] > 0)
     assert 0.5 < bgn[conn].all(1).mean() < 1.0                 # most elements are background, some are not
     p = pihna_params_from_dict(synth.pihna_param_dict(pvariant))
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     shim.shim_ev_set_background(0)
     try:
         val_all, rhs_all, _ = _ev(shim, conn, xyz, u, p, xyz.shape[0])
@@ -91,6 +94,7 @@ def test_ev_replay_background_skip(oracle, shim, pvariant):
         shim.shim_ev_set_background(1)
     val, rhs, _ = _ev(shim, conn, xyz, u, p, xyz.shape[0])
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
     assert rel(val, val_all) < 1e-14 and rel(rhs, rhs_all) < 1e-14
     # rows of nodes all of whose elements are background: the n, c, h, a right-hand sides are exactly 0, as upstream
     quiet = np.ones(xyz.shape[0], bool)
@@ -99,15 +103,50 @@ def test_ev_replay_background_skip(oracle, shim, pvariant):
     assert np.all(rhs0.reshape(-1, 5)[quiet][:, [0, 1, 2, 4]] == 0.0)
 
 
+def _pattern(shim, n_owned):
+    """scalar CSR pattern (nv = 5) of the last shim_prep_build, the oracle's layout"""
+    bptr = np.empty(shim.shim_prep_size(0), dtype=np.int64)
+    shim.shim_prep_copy(0, bptr.ctypes.data_as(C.c_void_p))
+    lens = np.diff(bptr[:n_owned + 1]) * 5
+    rp = np.zeros(5 * n_owned + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.repeat(lens, 5))
+    return rp
+
+
+@pytest.mark.parametrize("lam", [-1e-3, 0.0, 1.0])
+@pytest.mark.parametrize("pvariant,gen", [("full", 0), ("shipped", 0), ("shipped", 1)])
+def test_ev_replay_background_skip_threshold(oracle, shim, lam, pvariant, gen):
+    """The background short cut against the threshold of the transport terms: with cells_min_capacity < 0, diffuse/c and
+    taxis/c (h) are on at c = h = 0 (src/pihna.C:504-507), so the c/h transport moments of a background visit are not zero.
+    Every (equation, unknown) block on its own scale: the (c, c) and (h, h) blocks are a few 1e-11 of the global norm."""
+    conn, xyz = synth.kuhn_tet_mesh(8, order="random")
+    u = synth.pihna_fields(xyz)
+    d = synth.pihna_param_dict(pvariant)
+    d["cells_min_capacity"] = lam
+    p = pihna_params_from_dict(d)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    val, rhs, _ = _ev(shim, conn, xyz, u, p, xyz.shape[0], gen=gen)
+    assert np.array_equal(_pattern(shim, xyz.shape[0]), rp0)
+    assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+    shim.shim_ev_set_background(0)
+    try:
+        val_all, rhs_all, _ = _ev(shim, conn, xyz, u, p, xyz.shape[0], gen=gen)
+    finally:
+        shim.shim_ev_set_background(1)
+    assert_csr_close(rp0, col0, val, val_all, rhs, rhs_all, 5, rtol=1e-14)
+
+
 def test_ev_replay_on_a_ghosted_partition(oracle, shim):
     conn, xyz = synth.kuhn_tet_mesh(6, order="random")
     u = synth.pihna_fields(xyz)
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
     n_owned = int(0.6 * xyz.shape[0])
     conn = conn[(conn < n_owned).any(axis=1)]
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u, n_owned=n_owned)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u, n_owned=n_owned)
     val, rhs, st = _ev(shim, conn, xyz, u, p, n_owned)
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
     assert st["n_rows"] == int((conn < n_owned).sum())
 
 
@@ -125,12 +164,13 @@ def test_ev_replay_clamped_branches(oracle, shim):
     u[(x >= 0.4) & (x < 0.5), 1:3] = 0.0
     u[(x >= 0.5) & (x < 0.6), 3] = 0.0
     u[x > 0.7] = 0.0
-    _, _, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     val, rhs, _ = _ev(shim, conn, xyz, u, p, xyz.shape[0])
     assert np.isnan(val0).any()
     assert np.array_equal(np.isnan(val), np.isnan(val0)) and np.array_equal(np.isnan(rhs), np.isnan(rhs0))
     ok, okr = ~np.isnan(val0), ~np.isnan(rhs0)
     assert rel(val[ok], val0[ok]) < 1e-10 and rel(rhs[okr], rhs0[okr]) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
 # ---- coefficient-form element visits (rdc_tet4_evc.h) for the three-unknown models ------------------------------------------
@@ -162,13 +202,15 @@ def test_evc_replay_ripf(oracle, shim, order, params):
     conn, xyz = synth.kuhn_tet_mesh(6, order=order)
     u, aux = synth.ripf_fields(xyz)
     p = ripf_params_from_dict(synth.ripf_param_dict(params))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=u, aux=aux)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=u, aux=aux)
     val, rhs = _evc(shim, 1, p, conn, xyz, u, aux, xyz.shape[0])
     assert np.isfinite(val).all() and np.isfinite(rhs).all()
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
     if params == "shipped":   # the reduced instantiation of the shipped parameter pattern gives the same numbers
         val2, rhs2 = _evc(shim, 7, p, conn, xyz, u, aux, xyz.shape[0])
         assert rel(val2, val0) < 1e-10 and rel(rhs2, rhs0) < 1e-10
+        assert_csr_close(rp0, col0, val2, val0, rhs2, rhs0, 3)
 
 
 @pytest.mark.parametrize("params", ["full", "shipped"])
@@ -179,6 +221,7 @@ def test_evc_replay_hcc_on_a_ghosted_partition(oracle, shim, params):
     conn = conn[(conn < n_owned).any(axis=1)]
     u = synth.hcc_fields(xyz)
     p = hcc_params_from_dict(synth.hcc_param_dict(params))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_HCC, 4, conn, xyz, 3, p, u_old=u, n_owned=n_owned)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_HCC, 4, conn, xyz, 3, p, u_old=u, n_owned=n_owned)
     val, rhs = _evc(shim, 2 if params == "full" else 8, p, conn, xyz, u, None, n_owned)
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)

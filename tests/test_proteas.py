@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import shim_rows
+from parity import assert_csr_close
 from rdcfes_amd import proteas_params_from_dict, synth
 
 
@@ -80,7 +81,7 @@ def test_gpu_parity(oracle, nen, n, variant, scatter, kernel_variant):
     conn, xyz = synth.kuhn_tet_mesh(n, jitter=0.1, order="random") if nen == 4 else synth.hex_mesh(n, jitter=0.1, order="random")
     u, aux = synth.proteas_fields(xyz)
     p = proteas_params_from_dict(synth.proteas_param_dict(variant))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_PROTEAS, nen, conn, xyz, 5, p, u_old=u, aux=aux)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_PROTEAS, nen, conn, xyz, 5, p, u_old=u, aux=aux)
     with AssemblyContext(0) as ctx:
         ctx.set_kernel_variant(kernel_variant)
         ctx.mesh_upload(nen, conn, xyz, 5)
@@ -93,3 +94,4 @@ def test_gpu_parity(oracle, nen, n, variant, scatter, kernel_variant):
         val, rhs = ctx.csr_download()
     assert np.linalg.norm(rhs - rhs0) <= 1e-10 * np.linalg.norm(rhs0)
     assert np.linalg.norm(val - val0) <= 1e-10 * np.linalg.norm(val0)
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)

@@ -15,6 +15,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from parity import assert_csr_close, block_norms
 from rdcfes_amd import (RipfCheckParams, adpm_params_from_dict, hcc_params_from_dict, inputs, pihna_params_from_dict,
                         ripf_params_from_dict, synth)
 from rdcfes_amd import params as P
@@ -179,9 +180,19 @@ def test_gpu_pihna_shipped_initial_state(oracle, options):
     u = np.ascontiguousarray(a[-xyz.shape[0]:])
     assert int((u[:, 1] == 1000.0).sum()) == 23
     p = pihna_params_from_dict(inputs.read_model_input(G / "run_PIHNA_input.dat", P.PIHNA_KEYS))
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_PIHNA, 4, conn, xyz, 5, p, u_old=u, threads=8)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_PIHNA, 4, conn, xyz, 5, p, u_old=u, threads=8)
     val, rhs = _assemble("pihna", conn, xyz, 5, p, u, options=options)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    # (v, c) and (v, h) are exact zeros plus rounding in this state: 6.1e-28 of the (v, a) block.  The oracle does not
+    # reproduce them itself -- the same assembly with the elements reversed and their vertices rotated differs by 1.30
+    # of their norm there (2e-16 to 6e-16 in every other block) -- and the kernels measured 1.33 to 1.37.  Held to 1e-14
+    # of (v, a) as noise; the spread is asserted so that a state in which they become resolved drops the exemption.
+    _, _, val1, _ = oracle.assemble(oracle.MODEL_PIHNA, 4, np.ascontiguousarray(conn[::-1][:, [1, 2, 0, 3]]), xyz, 5, p,
+                                    u_old=u, threads=8)
+    spread, n0 = block_norms(rp0, col0, val1, val0, 5)
+    noise = {(3, 1), (3, 2)}
+    assert all(spread[b] > 1e-2 * n0[b] and n0[b] < 1e-20 * n0[3].max() for b in noise)
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5, noise_blocks=noise)
     # rows of a node whose element patch is all background: Fe_n = Fe_c = Fe_h = Fe_a = 0 (nothing to produce from)
     seeded = np.zeros(xyz.shape[0], bool)
     seeded[np.unique(conn[np.isin(conn, np.nonzero(u[:, 1])[0]).any(1)])] = True
@@ -215,8 +226,9 @@ def test_gpu_ripf_shipped_initial_state(oracle, day):
         ctx.assemble_ripf(p)
         val, rhs = ctx.csr_download()
         np.testing.assert_array_equal(ctx.field_download(FIELD_OLD_SOLUTION, 3 * n).reshape(n, 3), s0)
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=s0, aux=aux0, threads=8)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_RIPF, 4, conn, xyz, 3, p, u_old=s0, aux=aux0, threads=8)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 @pytest.mark.gpu
@@ -229,6 +241,7 @@ def test_gpu_adpm_shipped_initial_state(oracle, time):
     u = np.ascontiguousarray(np.resize(a, (xyz.shape[0], 3)))
     _, tracts = synth.adpm_fields(xyz, conn.shape[0])
     p = adpm_params_from_dict(inputs.read_model_input(G / "run_HCP102513_input.dat", P.ADPM_KEYS), time=time)
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_ADPM, 4, conn, xyz, 3, p, u_old=u, elem_fibre=tracts, threads=8)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_ADPM, 4, conn, xyz, 3, p, u_old=u, elem_fibre=tracts, threads=8)
     val, rhs = _assemble("adpm", conn, xyz, 3, p, u, tracts=tracts)
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)

@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from parity import assert_csr_close
 from rdcfes_amd import gmsh, inputs
 
 G = Path(__file__).parent / "golden"
@@ -135,8 +136,8 @@ def test_gpu_parity_on_shipped_case(oracle, name, jac):
     from rdcfes_amd import AssemblyContext, FIELD_ELEM_FIBRE, FIELD_UNDEFORMED_XYZ
     mesh, setup, em, mats, Xu, x, fibre, sides, sp = _case(name, 0.4, 1.0)
     nen = mesh.elem_type
-    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, nen, mesh.conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
-                                       elem_material=em, materials=mats, request_jacobian=jac, sides=sides)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, nen, mesh.conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
+                                            elem_material=em, materials=mats, request_jacobian=jac, sides=sides)
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(nen, mesh.conn, x, 3)
         ctx.field_upload(FIELD_UNDEFORMED_XYZ, Xu)
@@ -148,6 +149,7 @@ def test_gpu_parity_on_shipped_case(oracle, name, jac):
     assert rel(rhs, rhs0) < TOL
     if jac:
         assert rel(val, val0) < TOL
+        assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 
 
 def test_oracle_regression(oracle):
