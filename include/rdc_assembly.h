@@ -193,7 +193,8 @@ int rdc_set_kernel_variant(rdc_ctx* ctx, int variant);
  * the TET4 row-gather kernel; "ablate": 1..6 remove parts of that kernel (results are then WRONG);
  * "moments": 1 (default) evaluates PIHNA/TET4 rows in moment form when the parameters have the shipped pattern (cell
  * transport off), 0 in coefficient form -- same sums, other association; "specialise": 0 disables that parameter-
- * pattern variant altogether; "kernel", "staged", "slim", "stagger", "prefetch", "xcd", "schedule", "block", "grid",
+ * pattern variant altogether; "kernel" (TET4: 0 = default, 1 = k_tet4_rowgather, 2 = k_tet4_rg2, 3 = k_tet4_rg3, 5 = k_tet4_rg5,
+ * 7 = element-visit kernel; any other value is RDC_ERR_INVALID), "staged", "stagger", "prefetch", "xcd", "schedule", "block", "grid",
  * "ev_occupancy", "ev_lds", "evc_occupancy", "ev_resident" (1, default = whole-mesh launches of at least 56 clusters per resident workgroup run as three resident
  * workgroups per CU that fetch the whole next cluster by LDS-DMA while the current one is expanded and copied out, clusters handed
  * out by a counter; 2 = launches of any size; 0 = never) -- the others are experimental and

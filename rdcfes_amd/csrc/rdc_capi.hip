@@ -37,7 +37,7 @@ struct rdc_ctx {
   int opt_occ = 2, opt_ablate = 0, opt_kernel = 0;
   int opt_xcd = 0;      // XCD-aware workgroup order of the row-gather kernel (measured: no gain, off)
   int opt_pf = 0;       // L2 prefetch distance (workgroups) of the work lists in k_tet4_rg5; 0 = off
-  int opt_grid = 0;     // persistent grid size of the pipelined kernel (0 = 2 workgroups per CU)
+  int opt_grid = 0;     // grid size of the resident element-visit kernel (0 = its default per CU)
   int opt_sched = 1;    // LDS-conflict-aware pair schedule (takes effect at the next rdc_mesh_upload)
   int opt_special = 1;  // allow parameter-sparsity kernel variants
   int opt_part = 0;            // 0 = whole mesh, 1 = workgroups of interior nodes only, 2 = the remaining workgroups
@@ -47,7 +47,6 @@ struct rdc_ctx {
   int opt_stagger = 0;
   int opt_ldspad = 0;
   int opt_moments = 1;  // PIHNA (cell transport off) TET4: moment form of the rows
-  int opt_slim = 0;     // PIHNA: slim per-point state (re-derived per equation row); with occupancy=3 three waves per SIMD
   int opt_block = 256;  // workgroup size of the row-gather work lists (takes effect at the next rdc_mesh_upload)
   HostPrep prep;
   HostPrepEv prep_ev;          // element-visit lists (PIHNA TET4, shipped pattern); .ok = available
@@ -80,7 +79,6 @@ struct rdc_ctx {
   DevBuf rg2_desc, rg2_pair, rg2_chunk, rg2_sdesc, rg2_contrib, rg2_aux, rg2_ntab, rg4_nlist, rg4_ploc;
   DevBuf hx_nl_ptr, hx_nlist, hx_ploc;   // node-staged generic row gather (HEX8)
   int opt_staged = 1;
-  DevBuf rg4_wgntab;
   DevBuf rg5_eid;             // pair -> element list, uploaded at the first assembly of a model with per-element inputs
   bool rg5_eid_ready = false;
   DevBuf field[RDC_FIELD_COUNT];
@@ -239,7 +237,6 @@ hipError_t launch_specialised<Pihna, rdc_pihna_params>(const LaunchArgs& a, cons
   if (a.nen == 4 && a.variant != RDC_VARIANT_GENERIC && a.opt_special && PihnaNoCellTransport::applies(p)) {
     // default: one thread per element visit, moments accumulated per node block (rdc_tet4_ev.hip)
     if (a.use_ev && a.ev.n_wg > 0 && a.strategy == RDC_SCATTER_ROWGATHER) return launch_tet4_ev(a, k);
-    if (a.opt_slim && a.exp_mode == 3) return launch_tet4_fast<PihnaNoCellTransportSlim>(a, k);
     if (a.opt_moments) return launch_tet4_fast<PihnaNoCellTransportMoments>(a, k);  // same sums, moment form
     return launch_tet4_fast<PihnaNoCellTransport>(a, k);
   }
@@ -425,7 +422,6 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   a.opt_ablate = c->opt_ablate;
   a.opt_kernel = c->opt_kernel;
   a.opt_special = c->opt_special;
-  a.opt_slim = c->opt_slim;
   a.opt_moments = c->opt_moments;
   a.opt_stagger = c->opt_stagger;
   a.opt_ldspad = c->opt_ldspad;
@@ -444,7 +440,6 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     a.rg2.node_tab = (const uint16_t*)c->rg2_ntab.p;
     if (c->prep.rg4_nl_stride > 0) {
       a.rg2.nlist = (const uint32_t*)c->rg4_nlist.p;
-      a.rg2.wg_ntab = (const uint16_t*)c->rg4_wgntab.p;
       a.rg2.pair_loc = (const uint32_t*)c->rg4_ploc.p;
       a.rg2.nl_stride = c->prep.rg4_nl_stride;
       if ((M::NELEM > 0 || M::AUX_LOCAL_NODE >= 0) && !c->prep.pair_eid.empty()) {
@@ -467,8 +462,8 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     if ((rc = build_ev_lists(c, conn_h.data()))) return rc;
   }
   // element-visit kernel: default for the shipped-pattern PIHNA / TET4 ("kernel" = 0 or 7); the diagnostic knobs of the
-  // pair kernels (ablate, stamps, slim, coefficient form, occupancy 1) and "kernel" = 5 select k_tet4_rg5 instead
-  a.use_ev = c->prep_ev.ok && (c->opt_kernel == 0 || c->opt_kernel == 7) && c->opt_moments && !c->opt_slim && (!c->opt_ablate || c->opt_kernel == 7) &&
+  // pair kernels (ablate, stamps, coefficient form, occupancy 1) and "kernel" = 5 select k_tet4_rg5 instead
+  a.use_ev = c->prep_ev.ok && (c->opt_kernel == 0 || c->opt_kernel == 7) && c->opt_moments && (!c->opt_ablate || c->opt_kernel == 7) &&
              (!c->stamps.p || (c->opt_kernel == 7 && c->opt_ablate == 4)) && c->opt_occ != 1 && c->opt_ldspad == 0;
   a.opt_ev_occ = c->opt_ev_occ;
   a.opt_evc_occ = c->opt_evc_occ;
@@ -648,7 +643,7 @@ int rdc_ctx_destroy(rdc_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf* all[] = {&c->conn, &c->xyz, &c->bptr, &c->eslot, &c->elem_order, &c->first_mask, &c->first_rhs,
                    &c->pair_elem, &c->pair_local, &c->node_pair_ptr, &c->wg_node_ptr, &c->val, &c->rhs, &c->packed, &c->stamps, &c->rg2_desc, &c->rg2_pair, &c->rg2_chunk,
-                   &c->rg2_sdesc, &c->rg2_contrib, &c->rg2_aux, &c->rg2_ntab, &c->rg4_nlist, &c->rg4_ploc, &c->rg4_wgntab, &c->rg5_eid, &c->hx_nl_ptr, &c->hx_nlist, &c->hx_ploc,
+                   &c->rg2_sdesc, &c->rg2_contrib, &c->rg2_aux, &c->rg2_ntab, &c->rg4_nlist, &c->rg4_ploc, &c->rg5_eid, &c->hx_nl_ptr, &c->hx_nlist, &c->hx_ploc,
                    &c->elem_material, &c->materials, &c->side_elem, &c->side_id, &c->side_disp,
                    &c->scl_desc, &c->scl_ntab, &c->scl_eid, &c->scl_pair, &c->scl_pslot, &c->solid_ke, &c->solid_fe, &c->sg_gptr, &c->sg_gsrc, &c->sg_brow, &c->wg_max, &c->solid_post, &c->adpm_slot,
                    &c->ev_desc, &c->ev_nlist, &c->ev_vloc, &c->ev_vslot, &c->ev_ntab, &c->ev_bpart, &c->ev_perm, &c->ev_ticket};
@@ -702,7 +697,6 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
     c->opt_block = value;
   }
   else if (!std::strcmp(key, "specialise")) c->opt_special = value;
-  else if (!std::strcmp(key, "slim")) c->opt_slim = value;
   else if (!std::strcmp(key, "lds_pad")) c->opt_ldspad = value;  // k_tet4_rg5: KB of unused LDS per workgroup (diagnostic: fewer co-resident workgroups)
   else if (!std::strcmp(key, "stagger")) c->opt_stagger = value;  // k_tet4_rg5: start delay of every CU's second workgroup, in units of 1024 cycles
   else if (!std::strcmp(key, "moments")) c->opt_moments = value;  // 1 (default): shipped-pattern PIHNA/TET4 rows in moment form (rdc_tet4_pihna_moments.h), 0: coefficient form
@@ -737,8 +731,10 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
   else if (!std::strcmp(key, "evc_occupancy")) c->opt_evc_occ = value == 3 ? 3 : 2;   // k_tet4_evc: waves per SIMD its registers are bounded for
   else if (!std::strcmp(key, "ev_occupancy")) c->opt_ev_occ = value;   // element-visit kernel: 3 (default, 168 registers) or 2
   else if (!std::strcmp(key, "ev_lds")) c->opt_ev_lds = value;   // LDS bytes per workgroup the element-visit clusters are sized for (next rdc_mesh_upload)
-  else if (!std::strcmp(key, "kernel")) c->opt_kernel = value;  // 0 = default (LDS-staged node records, k_tet4_rg5), 3 = k_tet4_rg3, 4 = persistent k_tet4_rg4, 6 = k_tet4_rg6 (rg5 over work items with a tail prefetch, experimental),
-                                                                 // 1 = first row-gather kernel, 2 = staged deterministic k_tet4_rg2
+  else if (!std::strcmp(key, "kernel")) {  // 0 = default, 1 = k_tet4_rowgather, 2 = k_tet4_rg2, 3 = k_tet4_rg3, 5 = k_tet4_rg5, 7 = element-visit kernel
+    if (value != 0 && value != 1 && value != 2 && value != 3 && value != 5 && value != 7) return fail(c, RDC_ERR_INVALID, "kernel must be 0, 1, 2, 3, 5 or 7, not %d", value);
+    c->opt_kernel = value;
+  }
   else return fail(c, RDC_ERR_INVALID, "unknown option '%s'", key);
   return RDC_OK;
 }
@@ -791,7 +787,6 @@ int rdc_mesh_upload(rdc_ctx* c, int elem_type, int64_t n_elem, int64_t n_node, i
     if ((rc = dev_upload(c, c->rg2_ntab, P.node_tab))) return rc;
     if (P.rg4_nl_stride > 0) {
       if ((rc = dev_upload(c, c->rg4_nlist, P.nlist))) return rc;
-      if ((rc = dev_upload(c, c->rg4_wgntab, P.wg_ntab))) return rc;
       if ((rc = dev_upload(c, c->rg4_ploc, P.pair_loc))) return rc;
     }
   }

@@ -39,7 +39,6 @@ struct Rg2Dev {
   const uint32_t* nlist = nullptr;
   const uint32_t* pair_loc = nullptr;
   int wg_begin = 0, wg_count = -1;      // sub-range of the work items to launch (k_tet4_rg5 only; -1 = all)
-  const uint16_t* wg_ntab = nullptr;    // [n_wg][16][4]: node_tab entries of the workgroup's nodes (persistent kernel)
   const uint32_t* pair_eid = nullptr;   // element of the pair (models with per-element inputs only)
   int nl_stride = 0;
   size_t lds_bytes = 0;
@@ -90,7 +89,7 @@ struct LaunchArgs {
   int pack_part = 0;               // 0 = pack every record; 1 = owned nodes only, then record pack_event; 2 = wait for pack_event, ghosts only
   hipEvent_t pack_event = nullptr;
   int variant;     // RDC_VARIANT_*
-  int opt_occ, opt_ablate, opt_kernel, opt_special, opt_xcd, opt_grid, opt_pf, opt_slim = 0, opt_moments = 1, opt_stagger = 0, opt_ldspad = 0;  // tuning knobs (rdc_set_option)
+  int opt_occ, opt_ablate, opt_kernel, opt_special, opt_xcd, opt_grid, opt_pf, opt_moments = 1, opt_stagger = 0, opt_ldspad = 0;  // tuning knobs (rdc_set_option)
   Rg2Dev rg2;
   EvDev ev;
   ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted)

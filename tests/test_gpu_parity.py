@@ -433,10 +433,18 @@ def test_two_rank_partitioned_assembly():
     assert all(err < TOL for _, err in res), res
 
 
-@pytest.mark.parametrize("opts", [{"kernel": 7}, {"kernel": 7, "ev_occupancy": 2}, {"kernel": 5}, {"slim": 1, "occupancy": 3}, {"slim": 1}, {"kernel": 3}, {"kernel": 4}, {"kernel": 2},
-                                  {"kernel": 1}, {"occupancy": 1}, {"xcd": 1}, {"prefetch": 16}, {"specialise": 0}, {"moments": 0},
-                                  {"stagger": 8}, {"kernel": 6, "grid": 5}, {"kernel": 6, "grid": 5, "moments": 0},
-                                  {"ev_resident": 0}, {"ev_resident": 0, "kernel": 7}, {"ev_resident": 2}, {"ev_resident": 1, "grid": 7}, {"ev_resident": 1, "grid": 1}, {"ev_resident": 1, "grid": 100000}])
+# A case keeps the name it had when this list also held the retired "slim" and "kernel" = 4 / 6 cases (opts4, opts6, opts15,
+# opts16; opts3 was {"slim": 1, "occupancy": 3}, the only other case that ran k_tet4_rg5 at three waves per SIMD).
+_PIHNA_OPTION_SETS = {
+    "opts0": {"kernel": 7}, "opts1": {"kernel": 7, "ev_occupancy": 2}, "opts2": {"kernel": 5}, "opts3": {"kernel": 5, "occupancy": 3},
+    "opts5": {"kernel": 3}, "opts7": {"kernel": 2}, "opts8": {"kernel": 1}, "opts9": {"occupancy": 1}, "opts10": {"xcd": 1},
+    "opts11": {"prefetch": 16}, "opts12": {"specialise": 0}, "opts13": {"moments": 0}, "opts14": {"stagger": 8},
+    "opts17": {"ev_resident": 0}, "opts18": {"ev_resident": 0, "kernel": 7}, "opts19": {"ev_resident": 2},
+    "opts20": {"ev_resident": 1, "grid": 7}, "opts21": {"ev_resident": 1, "grid": 1}, "opts22": {"ev_resident": 1, "grid": 100000},
+}
+
+
+@pytest.mark.parametrize("opts", list(_PIHNA_OPTION_SETS.values()), ids=list(_PIHNA_OPTION_SETS))
 def test_pihna_option_sets(oracle, opts):
     """Every non-default kernel selection (rdc_set_option) of the PIHNA/TET4 path stays on the oracle."""
     conn, xyz = synth.kuhn_tet_mesh(9, order="lex")
@@ -451,6 +459,27 @@ def test_pihna_option_sets(oracle, opts):
         ctx.assemble_pihna(p)
         val, rhs = ctx.csr_download()
     assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+
+
+@pytest.mark.parametrize("key,value", [("slim", 1), ("kernel", 4), ("kernel", 6), ("kernel", 99)])
+def test_retired_and_unknown_kernel_selections_are_refused(oracle, key, value):
+    """The removed experiments ("slim", "kernel" = 4 and 6) and a "kernel" value no launch branch tests for are refused by
+    rdc_set_option itself with RDC_ERR_INVALID; the refused call changes nothing: a default assembly on the same context
+    afterwards is on the oracle."""
+    conn, xyz = synth.kuhn_tet_mesh(9, order="lex")
+    u = synth.pihna_fields(xyz)
+    p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    with AssemblyContext(0) as ctx:
+        with pytest.raises(RdcError) as e:
+            ctx.set_option(key, value)
+        assert e.value.code == 1  # RDC_ERR_INVALID
+        assert (str(value) if key == "kernel" else key) in str(e.value)  # the message names what was refused
+        ctx.mesh_upload(4, conn, xyz, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u)
+        ctx.assemble_pihna(p)
+        val, rhs = ctx.csr_download()
     assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
 
 
@@ -749,7 +778,7 @@ def test_two_part_assembly_on_two_streams(oracle, resident):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("params,opts", [("shipped", {}), ("full", {}), ("shipped", {"slim": 1}), ("shipped", {"kernel": 5}),
+@pytest.mark.parametrize("params,opts", [("shipped", {}), ("full", {}), ("shipped", {"moments": 0}), ("shipped", {"kernel": 5}),
                                          ("shipped", {"specialise": 0})])
 def test_chunked_handback_follows_the_part1_bound(params, opts):
     """rdc_part1_nodes after a part-1 call = the rows THAT call completed, whatever kernel path the parameters and options
