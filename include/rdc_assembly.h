@@ -303,6 +303,55 @@ int rdc_host_unpin(rdc_ctx* ctx, void* host_ptr);
  * tuning options; before any part-1 call since the upload it is the prediction for the default path. */
 int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 
+/* ---- device-resident linear solve: what the reference does in model.solve() (src/pihna.C:80) and in the Newton /
+ * linear solver of the solid system (src/solid_system.C:98-100,380), without handing the matrix back to the host.
+ * Additive: RDC_ABI_VERSION stays 3, nothing above changes meaning.
+ * The matrix is the context's own CSR values, walked through the node-block pattern (4 bytes of index per nvar x nvar
+ * block, no scalar row_ptr / col_idx on the device).  BiCGStab, LEFT-preconditioned by node-block Jacobi: it iterates on
+ * D^-1 A x = D^-1 b and stops on the preconditioned residual, as PETSc's KSPBCGS does by default.  Single partition only. */
+#define RDC_PRECOND_NONE 0
+#define RDC_PRECOND_JACOBI 1
+#define RDC_PRECOND_BLOCK_JACOBI 2      /* default choice of the Python wrapper */
+
+#define RDC_SOLVE_CONVERGED     0
+#define RDC_SOLVE_MAX_ITS       1       /* x holds the last iterate */
+#define RDC_SOLVE_BREAKDOWN     2       /* restarts exhausted */
+#define RDC_SOLVE_BAD_DIAGONAL  3       /* singular / non-finite diagonal (block); x untouched */
+#define RDC_SOLVE_NOT_FINITE    4       /* rhs, x0 or the iteration produced NaN/inf; x holds the last finite iterate or x0 (an entry whose update would overflow keeps its value) */
+
+typedef struct rdc_solve_params {
+  double rel_tol;        /* stop when ||D^-1 (b - A x)|| <= max(rel_tol * ||D^-1 b||, abs_tol); D = the preconditioner */
+  double abs_tol;
+  double rhs_scale;      /* b = rhs_scale * (assembled rhs): 1 for the reaction-diffusion systems, -1 for a Newton update */
+  int32_t max_its;
+  int32_t precond;       /* RDC_PRECOND_* */
+} rdc_solve_params;
+
+typedef struct rdc_solve_info {
+  int32_t reason;        /* RDC_SOLVE_* */
+  int32_t iterations;    /* BiCGStab iterations = pairs of matrix-vector products, restarts included */
+  int32_t restarts;
+  int32_t bad_blocks;    /* diagonal blocks the preconditioner could not invert */
+  double rhs_norm;       /* ||D^-1 b||_2 */
+  double residual_norm;  /* TRUE ||D^-1 (b - A x)||_2 of the returned x: the quantity the stopping test is about */
+  double plain_rhs_norm, plain_residual_norm;   /* the same without D^-1 */
+  float  device_ms;      /* device time of the whole solve (HIP events on the context stream) */
+  float  _pad;
+} rdc_solve_info;
+
+/* y[n_owned*nvar] = A * x[n_nodes*nvar], both DEVICE pointers; enqueued on the context's stream, does not synchronise.
+ * x covers owned and ghost dofs (local numbering), so a partitioned caller can exchange the ghosts and then multiply.
+ * d_x and d_y must not overlap. */
+int rdc_csr_matvec(rdc_ctx* ctx, const double* d_x, double* d_y);
+/* Solve A x = rhs_scale * rhs for the values and rhs the last assemble call left in the context.
+ * d_x: DEVICE pointer, n_owned*nvar doubles: initial guess on entry (libMesh hands KSP the current solution), solution on exit.
+ * It may be the storage of RDC_FIELD_OLD_SOLUTION (rdc_field_device_ptr): matrix and rhs are not re-read from the fields.
+ * Blocks the host until done.  Never modifies the CSR values or the rhs.
+ * A solver outcome other than convergence is not an error status: the call returns RDC_OK and info->reason tells.
+ * b = 0 gives x = 0 in 0 iterations.  RDC_ERR_UNSUPPORTED when the context has ghost nodes (a solve across partitions
+ * needs a halo exchange of the search directions inside every iteration). */
+int rdc_solve(rdc_ctx* ctx, const rdc_solve_params* p, double* d_x, rdc_solve_info* info);
+
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */
 int rdc_clamp_nonnegative(rdc_ctx* ctx, int field);

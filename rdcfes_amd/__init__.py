@@ -5,13 +5,14 @@ This Python package is the test / benchmark harness above that ABI plus the host
 logic; it contains no numerical fallback: without the built library and a GPU every compute call
 raises.
 """
-from .params import (PihnaParams, RipfParams, HccParams, SolidParams, SolidMaterial, RipfCheckParams, AdpmParams, ProteasParams, PihnaRanges, RipfRanges, AdpmRanges,
+from .params import (PihnaParams, RipfParams, HccParams, SolidParams, SolidMaterial, RipfCheckParams, AdpmParams, ProteasParams, PihnaRanges, RipfRanges, AdpmRanges, SolveParams, SolveInfo,
                      pihna_params_from_dict, ripf_params_from_dict, hcc_params_from_dict,
                      adpm_params_from_dict, proteas_params_from_dict)
 from .context import (AssemblyContext, RdcError, TET4, HEX8, SCATTER_AUTO, SCATTER_COLOURED,
                       SCATTER_ROWGATHER, FIELD_OLD_SOLUTION, FIELD_AUX_NODAL,
                       FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE, FIELD_PREV_SOLUTION, FIELD_TIME_DERIV,
-                      FIELD_RT_DOSE, FIELD_ELEM_TRACTS)
+                      FIELD_RT_DOSE, FIELD_ELEM_TRACTS, PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI,
+                      SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE)
 
 __all__ = [
     "PihnaParams", "RipfParams", "HccParams", "SolidParams", "SolidMaterial", "RipfCheckParams", "AdpmParams", "adpm_params_from_dict", "ProteasParams", "proteas_params_from_dict", "PihnaRanges", "RipfRanges", "AdpmRanges",
@@ -19,4 +20,6 @@ __all__ = [
     "AssemblyContext", "RdcError", "TET4", "HEX8", "SCATTER_AUTO", "SCATTER_COLOURED",
     "SCATTER_ROWGATHER", "FIELD_OLD_SOLUTION", "FIELD_AUX_NODAL", "FIELD_UNDEFORMED_XYZ",
     "FIELD_ELEM_FIBRE", "FIELD_PREV_SOLUTION", "FIELD_TIME_DERIV", "FIELD_RT_DOSE", "FIELD_ELEM_TRACTS",
+    "SolveParams", "SolveInfo", "PRECOND_NONE", "PRECOND_JACOBI", "PRECOND_BLOCK_JACOBI",
+    "SOLVE_CONVERGED", "SOLVE_MAX_ITS", "SOLVE_BREAKDOWN", "SOLVE_BAD_DIAGONAL", "SOLVE_NOT_FINITE",
 ]

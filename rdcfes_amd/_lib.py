@@ -4,7 +4,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams
+from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveInfo, SolveParams
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "librdc_assembly.so"
 
@@ -57,6 +57,8 @@ SIGNATURES = {
     "rdc_host_unpin": (C.c_int, [ctx_p, C.c_void_p]),
     "rdc_assemble_adpm": (C.c_int, [ctx_p, C.c_void_p]),
     "rdc_assemble_proteas": (C.c_int, [ctx_p, C.c_void_p]),
+    "rdc_csr_matvec": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
+    "rdc_solve": (C.c_int, [ctx_p, P(SolveParams), C.c_void_p, P(SolveInfo)]),
     "rdc_clamp_nonnegative": (C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_ripf_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),

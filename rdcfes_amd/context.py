@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams
+from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveInfo, SolveParams
 
 TET4, HEX8 = 4, 8
 SCATTER_AUTO, SCATTER_COLOURED, SCATTER_ROWGATHER = 0, 1, 2
@@ -14,6 +14,8 @@ FIELD_OLD_SOLUTION, FIELD_AUX_NODAL, FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE = 0,
 FIELD_PREV_SOLUTION, FIELD_TIME_DERIV, FIELD_RT_DOSE = 4, 5, 6
 FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI = 0, 1, 2
+SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
 
 
 class RdcError(RuntimeError):
@@ -265,6 +267,37 @@ class AssemblyContext:
         """rows of nodes [node_begin, node_end) into full-size host arrays given by ADDRESS (e.g. pinned torch tensors)"""
         self._ck(self._lib.rdc_csr_download_rows(self._h, int(node_begin), int(node_end), C.c_void_p(int(val_ptr) if val_ptr else None),
                                                  C.c_void_p(int(rhs_ptr) if rhs_ptr else None), 1 if asynchronous else 0))
+
+    # -- device-resident linear solve
+    def csr_matvec_device(self, x_ptr, y_ptr):
+        """y[n_owned*nvar] = A x[n_node*nvar] on device addresses; enqueued on the context's stream, no synchronise"""
+        self._ck(self._lib.rdc_csr_matvec(self._h, C.c_void_p(int(x_ptr)), C.c_void_p(int(y_ptr))))
+
+    def csr_matvec(self, x):
+        """numpy in, numpy out (tests): x over owned and ghost dofs, y over the owned rows"""
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.n_node * self.nvar:
+            raise ValueError("x must have n_node * nvar entries")
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(x).to(dev)
+        yd = torch.empty(self.n_owned * self.nvar, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.csr_matvec_device(xd.data_ptr(), yd.data_ptr())
+        self.synchronize()
+        return yd.cpu().numpy()
+
+    def solve(self, x=None, *, field=None, rel_tol=1e-8, abs_tol=0.0, max_its=10000, precond=PRECOND_BLOCK_JACOBI, rhs_scale=1.0):
+        """rdc_solve on the values and rhs of the last assemble call.  x: device address of n_owned*nvar doubles
+        (initial guess in, solution out); or field=FIELD_*: the device storage of that field is used in place."""
+        if (x is None) == (field is None):
+            raise ValueError("give either a device address or field=")
+        if field is not None:
+            x = self.field_device_ptr(int(field), self.n_node * self.nvar)
+        p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
+        info = SolveInfo()
+        self._ck(self._lib.rdc_solve(self._h, C.byref(p), C.c_void_p(int(x)), C.byref(info)))
+        return info
 
     def part1_nodes(self):
         n = C.c_int64()

@@ -12,6 +12,7 @@
 #include "rdc_tet4_pihna_moments.h"
 #include "rdc_tet4_ev.h"
 #include "rdc_solid.h"
+#include "rdc_solve.h"
 
 using namespace rdc;
 
@@ -84,6 +85,10 @@ struct rdc_ctx {
   DevBuf field[RDC_FIELD_COUNT];
   int64_t field_count[RDC_FIELD_COUNT] = {0, 0, 0, 0, 0, 0, 0};
   DevBuf wg_max;  // per-workgroup maxima of rdc_ripf_check_solution
+  // linear solve (rdc_solve.hip): block column list, uploaded at the first matvec / solve; work vectors, allocated at the first solve
+  DevBuf bcol, solve_work;
+  bool bcol_ready = false;
+  SolveScal* solve_rec = nullptr;   // pinned: the one record the host reads per iteration
   // solid
   DevBuf elem_material, materials, side_elem, side_id, side_disp;
   DevBuf adpm_slot;
@@ -646,8 +651,9 @@ int rdc_ctx_destroy(rdc_ctx* c) {
                    &c->rg2_sdesc, &c->rg2_contrib, &c->rg2_aux, &c->rg2_ntab, &c->rg4_nlist, &c->rg4_ploc, &c->rg5_eid, &c->hx_nl_ptr, &c->hx_nlist, &c->hx_ploc,
                    &c->elem_material, &c->materials, &c->side_elem, &c->side_id, &c->side_disp,
                    &c->scl_desc, &c->scl_ntab, &c->scl_eid, &c->scl_pair, &c->scl_pslot, &c->solid_ke, &c->solid_fe, &c->sg_gptr, &c->sg_gsrc, &c->sg_brow, &c->wg_max, &c->solid_post, &c->adpm_slot,
-                   &c->ev_desc, &c->ev_nlist, &c->ev_vloc, &c->ev_vslot, &c->ev_ntab, &c->ev_bpart, &c->ev_perm, &c->ev_ticket};
+                   &c->ev_desc, &c->ev_nlist, &c->ev_vloc, &c->ev_vslot, &c->ev_ntab, &c->ev_bpart, &c->ev_perm, &c->ev_ticket, &c->bcol, &c->solve_work};
   for (DevBuf* b : all) dev_free(c, *b);
+  if (c->solve_rec) (void)hipHostFree(c->solve_rec);
   for (int f = 0; f < RDC_FIELD_COUNT; f++) dev_free(c, c->field[f]);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->pack_event) (void)hipEventDestroy(c->pack_event);
@@ -812,6 +818,8 @@ int rdc_mesh_upload(rdc_ctx* c, int elem_type, int64_t n_elem, int64_t n_node, i
   dev_free(c, c->side_elem); dev_free(c, c->side_id); dev_free(c, c->side_disp);
   c->n_materials = 0; c->n_sides = 0;
   c->have_mesh = true;
+  dev_free(c, c->bcol); dev_free(c, c->solve_work);   // tied to the pattern: rebuilt at the next matvec / solve
+  c->bcol_ready = false;
   c->solid_gather_ready = false;
   c->solid_cl_state = 0;
   c->rg5_eid_ready = false;
@@ -1196,6 +1204,67 @@ int rdc_part1_nodes(const rdc_ctx* c, int64_t* n_nodes) {
   if (c->opt_interior < 0 || !c->prep.rg2_ok || c->prep.nen != 4 || c->prep.wg2.empty()) return RDC_OK;
   const int split = part1_workgroups(c);
   if (split > 0) *n_nodes = (int64_t)c->prep.wg2[(size_t)split - 1].n0 + c->prep.wg2[(size_t)split - 1].nnodes;
+  return RDC_OK;
+}
+
+// what rdc_solve.hip needs of the context; uploads the block column list the first time (4 bytes per node block)
+static int solve_view(rdc_ctx* c, bool want_work, SolveDev* d) {
+  int rc = set_device(c);
+  if (rc) return rc;
+  const HostPrep& P = c->prep;
+  if (P.nvar != 3 && P.nvar != 5) return fail(c, RDC_ERR_UNSUPPORTED, "the linear solve kernels exist for 3 and 5 unknowns per node, not %d", P.nvar);
+  if (!c->bcol_ready) {
+    if ((rc = dev_upload(c, c->bcol, P.bcol))) return rc;
+    RDC_HIP(c, hipStreamSynchronize(c->stream));
+    c->bcol_ready = true;
+  }
+  d->nvar = P.nvar; d->n_owned = P.n_owned; d->n_nodes = P.n_node;
+  d->bptr = (const int64_t*)c->bptr.p; d->bcol = (const int32_t*)c->bcol.p;
+  d->val = (const double*)c->val.p; d->rhs = (const double*)c->rhs.p;
+  d->stream = c->stream;
+  if (want_work) {
+    if ((rc = dev_alloc(c, c->solve_work, solve_work_bytes(P.nvar, P.n_owned)))) return rc;
+    if (!c->solve_rec) RDC_HIP(c, hipHostMalloc((void**)&c->solve_rec, sizeof(SolveScal), hipHostMallocDefault));
+    d->work = (double*)c->solve_work.p;
+    d->host_rec = c->solve_rec;
+  }
+  return RDC_OK;
+}
+
+int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
+  if (c->prep.n_owned == 0) return RDC_OK;   // no rows
+  SolveDev d;
+  int rc = solve_view(c, false, &d);
+  if (rc) return rc;
+  RDC_HIP(c, solve_matvec(d, d_x, d_y));
+  return RDC_OK;
+}
+
+int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (!p || !d_x || !info) return fail(c, RDC_ERR_INVALID, "null argument");
+  if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
+  if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
+    return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
+  if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
+  if (p->precond != RDC_PRECOND_NONE && p->precond != RDC_PRECOND_JACOBI && p->precond != RDC_PRECOND_BLOCK_JACOBI)
+    return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (c->prep.n_owned < c->prep.n_node)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
+                "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
+                (long long)c->prep.n_owned, (long long)c->prep.n_node);
+  if (c->prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
+    *info = rdc_solve_info();
+    return RDC_OK;
+  }
+  SolveDev d;
+  int rc = solve_view(c, true, &d);
+  if (rc) return rc;
+  RDC_HIP(c, solve_run(d, *p, d_x, info));
   return RDC_OK;
 }
 

@@ -1,0 +1,168 @@
+// rdc_solve.h — index arithmetic of the node-block CSR pattern and the inverse of a diagonal block, as the kernels of
+// rdc_solve.hip use them.  Host+device like rdc_row.h, so that a CPU build can test exactly this code
+// (tests/host_solve_shim.cpp); free of other headers of the library on purpose.
+//
+// Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
+// node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
+// contiguously as [var a][block k][var b]: scalar CSR on the outside (row n*nvar + a has len*nvar entries whose
+// columns are bcol*nvar + b), a block pattern inside -- 4 bytes of index per nvar x nvar block.
+#ifndef RDC_SOLVE_H
+#define RDC_SOLVE_H
+#include <stdint.h>
+#include <math.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RDC_SOLVE_HD __host__ __device__ __forceinline__
+#else
+#define RDC_SOLVE_HD inline
+#endif
+
+namespace rdc {
+
+// position in the CSR value array of entry (row node `node`, equation a, block k of the node, unknown b)
+RDC_SOLVE_HD int64_t csr_value_offset(const int64_t* bptr, int nvar, int64_t node, int a, int64_t k, int b) {
+  const int64_t b0 = bptr[node], len = bptr[node + 1] - b0;
+  return (int64_t)nvar * nvar * b0 + ((int64_t)a * len + k) * nvar + b;
+}
+
+// scalar column of that entry
+RDC_SOLVE_HD int64_t csr_value_column(const int64_t* bptr, const int32_t* bcol, int nvar, int64_t node, int64_t k, int b) {
+  return (int64_t)bcol[bptr[node] + k] * nvar + b;
+}
+
+// block of node `node` that couples it to itself (binary search, bcol ascends within a node); -1 if the pattern has none
+RDC_SOLVE_HD int64_t csr_diag_block(const int64_t* bptr, const int32_t* bcol, int64_t node) {
+  int64_t lo = bptr[node], hi = bptr[node + 1] - 1;
+  const int64_t b0 = lo;
+  while (lo <= hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    const int64_t c = bcol[mid];
+    if (c == node) return mid - b0;
+    if (c < node) lo = mid + 1; else hi = mid - 1;
+  }
+  return -1;
+}
+
+// false for NaN and +-inf; on the bit pattern, so that no floating-point optimisation can change its meaning
+RDC_SOLVE_HD bool solve_finite(double x) {
+  uint64_t u;
+  __builtin_memcpy(&u, &x, sizeof(u));
+  return (u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+// In-place inverse of an NV x NV block (row-major), Gauss-Jordan with partial pivoting.  Every index below is a
+// compile-time constant after unrolling (the row exchange is a chain of conditional swaps), so a kernel keeps the block in
+// registers.  Returns false -- and leaves `m` unspecified -- for a block that is singular to working precision
+// (a zero pivot column) or holds a non-finite entry; the caller must not use the result then.
+template <int NV>
+RDC_SOLVE_HD bool block_inverse(double (&m)[NV][NV]) {
+  double inv[NV][NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++)
+#pragma unroll
+    for (int j = 0; j < NV; j++) inv[i][j] = i == j ? 1.0 : 0.0;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < NV; c++) {
+    // pivot: the first row of c .. NV-1 with the largest |m[r][c]|
+    int p = c;
+    double best = fabs(m[c][c]);
+#pragma unroll
+    for (int r = c + 1; r < NV; r++) {
+      const double v = fabs(m[r][c]);
+      if (v > best) { best = v; p = r; }
+    }
+#pragma unroll
+    for (int r = c + 1; r < NV; r++) {
+      if (p == r) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) {
+          double t = m[c][j]; m[c][j] = m[r][j]; m[r][j] = t;
+          t = inv[c][j]; inv[c][j] = inv[r][j]; inv[r][j] = t;
+        }
+      }
+    }
+    const double piv = m[c][c];
+    if (!(fabs(piv) > 0.0) || !solve_finite(piv)) ok = false;   // NaN compares false: reported too
+    const double ip = 1.0 / piv;
+#pragma unroll
+    for (int j = 0; j < NV; j++) { m[c][j] *= ip; inv[c][j] *= ip; }
+#pragma unroll
+    for (int r = 0; r < NV; r++) {
+      if (r == c) continue;
+      const double f = m[r][c];
+#pragma unroll
+      for (int j = 0; j < NV; j++) { m[r][j] -= f * m[c][j]; inv[r][j] -= f * inv[c][j]; }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; i++)
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+      if (!solve_finite(inv[i][j])) ok = false;
+      m[i][j] = inv[i][j];
+    }
+  return ok;
+}
+
+// what the preconditioner stores for one node: precond 2 = inverse of the whole diagonal block, 1 = of its diagonal
+// only (point Jacobi), 0 = identity.  `d` holds the diagonal block on entry and D^-1 on exit; false = not invertible
+// (d is then the identity, so that an apply stays harmless).
+template <int NV>
+RDC_SOLVE_HD bool precond_block(double (&d)[NV][NV], int precond) {
+  bool ok = true;
+  if (precond == 2) {
+    ok = block_inverse<NV>(d);
+  } else if (precond == 1) {
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+      const double x = d[i][i];
+      if (!(fabs(x) > 0.0) || !solve_finite(x)) ok = false;
+#pragma unroll
+      for (int j = 0; j < NV; j++) d[i][j] = i == j ? 1.0 / x : 0.0;
+    }
+  }
+  if (precond == 0 || !ok) {
+#pragma unroll
+    for (int i = 0; i < NV; i++)
+#pragma unroll
+      for (int j = 0; j < NV; j++) d[i][j] = i == j ? 1.0 : 0.0;
+  }
+  return ok;
+}
+
+}  // namespace rdc
+
+#if defined(__HIPCC__)
+#include "../../include/rdc_assembly.h"
+namespace rdc {
+
+// scalars of the iteration: they live in device memory and are consumed there; the host reads one copy per iteration
+struct SolveScal {
+  double rho, alpha, omega, beta;
+  double rn2, rn2_plain, bn2, bn2_plain;   // ||r||^2 of the recurrence (or of the true residual after k_residual), plain form, rhs norms
+  int32_t flag;                            // bit 0: alpha / omega / a norm is zero or not finite; bit 1: rho == 0
+  int32_t bad_blocks;
+};
+
+// what rdc_csr_matvec / rdc_solve need of a context (rdc_capi.hip fills it)
+struct SolveDev {
+  int nvar = 0;
+  int64_t n_owned = 0, n_nodes = 0;
+  const int64_t* bptr = nullptr;
+  const int32_t* bcol = nullptr;
+  const double* val = nullptr;
+  const double* rhs = nullptr;
+  double* work = nullptr;          // solve_work_bytes() bytes
+  SolveScal* host_rec = nullptr;   // pinned
+  hipStream_t stream = nullptr;
+};
+
+size_t solve_work_bytes(int nvar, int64_t n_owned);
+hipError_t solve_matvec(const SolveDev& d, const double* x, double* y);
+hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info);
+
+}  // namespace rdc
+#endif
+#endif

@@ -1,0 +1,408 @@
+// rdc_solve.hip — device-resident linear solve on the context's own CSR values:
+// block-pattern SpMV, node-block Jacobi, left-preconditioned BiCGStab.  FP64, gfx950, plain HIP C++.
+//
+// SpMV mapping: 16 lanes per node, 4 nodes per wave, 16 per workgroup.  The nvar rows of a node share one list of
+// column nodes, so a lane computes its (block, unknown) position and gathers its x entry ONCE per 16-entry step and
+// uses it for all nvar rows; per row the 16 lanes read 16 consecutive doubles (128 B) of the value stream, every value
+// exactly once, non-temporal.  Tuned for the 15-block rows of the Kuhn meshes (75 entries = 5 steps, 94 % of the lanes
+// busy); a row of any length just takes more steps.  A row sum is the lane's own entries in ascending order followed
+// by a fixed xor butterfly over the 16 lanes: no atomics, no dependence on the launch shape, bitwise repeatable.
+//
+// Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
+// small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
+// device memory.  No floating-point atomics anywhere.
+#include <algorithm>
+#include <cmath>
+
+#include "rdc_solve.h"
+
+namespace rdc {
+namespace {
+
+constexpr int SPMV_NODES = 16;        // nodes per workgroup of k_spmv (256 threads)
+constexpr int VEC_PER_BLOCK = 1024;   // vector entries per workgroup of the update kernels (256 threads x 4)
+constexpr int MAX_BREAKDOWNS = 10;    // restarts after a break-down before RDC_SOLVE_BREAKDOWN
+
+enum { STAGE_INIT = 0, STAGE_ALPHA = 1, STAGE_OMEGA = 2, STAGE_RHO = 3 };
+
+__device__ __forceinline__ bool finite_d(double x) { return solve_finite(x); }
+
+// sums `NC` values over the workgroup in a fixed order and lets thread 0 store them to out[blockIdx.x * NC + c]
+template <int NC>
+__device__ __forceinline__ void block_partials(double (&c)[NC], double* __restrict__ out) {
+  __shared__ double sh[NC][4];
+#pragma unroll
+  for (int i = 0; i < NC; i++)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c[i] += __shfl_xor(c[i], off, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int i = 0; i < NC; i++) sh[i][wave] = c[i];
+  __syncthreads();
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int i = 0; i < NC; i++) out[(size_t)blockIdx.x * NC + i] = ((sh[i][0] + sh[i][1]) + sh[i][2]) + sh[i][3];
+}
+
+// y = A x (EPI 0) or y = D^-1 (A x) with the partials of (y, w) and (y, y) (EPI 1)
+template <int NV, int EPI>
+__global__ __launch_bounds__(256) void k_spmv(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                              const double* __restrict__ val, const double* __restrict__ x,
+                                              double* __restrict__ y, int64_t n_owned, const double* __restrict__ dinv,
+                                              const double* __restrict__ w, double* __restrict__ partials) {
+  const int lane = threadIdx.x & 15;
+  const int64_t node = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  const bool live = node < n_owned;
+  double acc[NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  if (live) {
+    const int64_t b0 = bptr[node];
+    const int L = (int)(bptr[node + 1] - b0) * NV;      // entries of one row of the node
+    const double* __restrict__ vrow = val + (int64_t)NV * NV * b0;
+    for (int j = lane; j < L; j += 16) {
+      const int k = j / NV, b = j - k * NV;
+      const double xv = x[(int64_t)bcol[b0 + k] * NV + b];
+#pragma unroll
+      for (int a = 0; a < NV; a++) acc[a] = fma(__builtin_nontemporal_load(vrow + (int64_t)a * L + j), xv, acc[a]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, 16);
+  if (EPI == 0) {
+    double out = acc[0];
+#pragma unroll
+    for (int a = 1; a < NV; a++) out = lane == a ? acc[a] : out;
+    if (live && lane < NV) y[node * NV + lane] = out;
+  } else {
+    double c[2] = {0.0, 0.0};
+    if (live && lane < NV) {
+      const double* __restrict__ drow = dinv + (node * NV + lane) * NV;
+      double z = 0.0;
+#pragma unroll
+      for (int a = 0; a < NV; a++) z = fma(drow[a], acc[a], z);
+      y[node * NV + lane] = z;
+      c[0] = z * w[node * NV + lane];
+      c[1] = z * z;
+    }
+    block_partials<2>(c, partials);
+  }
+}
+
+// D^-1 of every owned node from the CSR values (one thread per node); counts the blocks it could not invert
+template <int NV>
+__global__ __launch_bounds__(256) void k_precond_setup(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                       const double* __restrict__ val, int64_t n_owned, int precond,
+                                                       double* __restrict__ dinv, SolveScal* __restrict__ scal) {
+  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= n_owned) return;
+  const int64_t kd = csr_diag_block(bptr, bcol, node);
+  double d[NV][NV];
+  bool ok = kd >= 0;
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int b = 0; b < NV; b++) d[a][b] = ok ? val[csr_value_offset(bptr, NV, node, a, kd, b)] : 0.0;
+  ok = precond_block<NV>(d, ok ? precond : 2) && ok;
+  if (!ok) atomicAdd(&scal->bad_blocks, 1);
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int b = 0; b < NV; b++) dinv[(node * NV + a) * NV + b] = d[a][b];
+}
+
+// r = r_hat = D^-1 (scale * rhs - ax), p = v = 0; partials of ||r||^2, ||scale*rhs - ax||^2, ||D^-1 b||^2, ||b||^2
+template <int NV>
+__global__ __launch_bounds__(256) void k_residual(const double* __restrict__ rhs, double scale, const double* __restrict__ ax,
+                                                  const double* __restrict__ dinv, double* __restrict__ r, double* __restrict__ rh,
+                                                  double* __restrict__ p, double* __restrict__ v, int64_t n_owned,
+                                                  double* __restrict__ partials) {
+  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double c[4] = {0.0, 0.0, 0.0, 0.0};
+  if (node < n_owned) {
+    double b[NV], res[NV];
+#pragma unroll
+    for (int a = 0; a < NV; a++) {
+      b[a] = scale * rhs[node * NV + a];
+      res[a] = b[a] - ax[node * NV + a];
+      c[1] = fma(res[a], res[a], c[1]);
+      c[3] = fma(b[a], b[a], c[3]);
+    }
+#pragma unroll
+    for (int a = 0; a < NV; a++) {
+      double zr = 0.0, zb = 0.0;
+#pragma unroll
+      for (int q = 0; q < NV; q++) {
+        const double dq = dinv[(node * NV + a) * NV + q];
+        zr = fma(dq, res[q], zr);
+        zb = fma(dq, b[q], zb);
+      }
+      r[node * NV + a] = zr;
+      rh[node * NV + a] = zr;
+      p[node * NV + a] = 0.0;
+      v[node * NV + a] = 0.0;
+      c[0] = fma(zr, zr, c[0]);
+      c[2] = fma(zb, zb, c[2]);
+    }
+  }
+  block_partials<4>(c, partials);
+}
+
+// adds the partials of the previous kernel in a fixed order and advances the scalars (one workgroup)
+__global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage,
+                                                   SolveScal* __restrict__ scal) {
+  __shared__ double sh[4][1024];
+  const bool skip = stage != STAGE_INIT && scal->flag != 0;   // a flagged iteration wrote no partials
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if (!skip)
+    for (int64_t i = threadIdx.x; i < nparts; i += 1024)
+      for (int c = 0; c < ncomp; c++) s[c] += partials[i * ncomp + c];
+  for (int c = 0; c < 4; c++) sh[c][threadIdx.x] = s[c];
+  __syncthreads();
+  for (int off = 512; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off)
+      for (int c = 0; c < ncomp; c++) sh[c][threadIdx.x] += sh[c][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0 || skip) return;
+  const double s0 = sh[0][0], s1 = sh[1][0];
+  if (stage == STAGE_INIT) {
+    scal->rn2 = s0; scal->rn2_plain = s1; scal->bn2 = sh[2][0]; scal->bn2_plain = sh[3][0];
+    scal->rho = s0; scal->alpha = 1.0; scal->omega = 1.0; scal->beta = 0.0;   // p = v = 0: the first update gives p = r
+    scal->flag = (finite_d(s0) && finite_d(sh[2][0])) ? 0 : 1;
+  } else if (stage == STAGE_ALPHA) {
+    const double alpha = scal->rho / s0;
+    scal->alpha = alpha;
+    if (s0 == 0.0 || !finite_d(alpha)) scal->flag |= 1;
+  } else if (stage == STAGE_OMEGA) {
+    const double omega = s1 > 0.0 ? s0 / s1 : 0.0;
+    scal->omega = omega;
+    if (omega == 0.0 || !finite_d(omega)) scal->flag |= 1;
+  } else {
+    const double beta = (s0 / scal->rho) * (scal->alpha / scal->omega);
+    scal->rn2 = s1; scal->beta = beta; scal->rho = s0;
+    if (!finite_d(s1) || !finite_d(beta) || sh[2][0] != 0.0) scal->flag |= 1;
+    else if (s0 == 0.0) scal->flag |= 2;
+  }
+}
+
+// p = r + beta (p - omega v)
+__global__ __launch_bounds__(256) void k_update_p(const double* __restrict__ r, double* __restrict__ p, const double* __restrict__ v,
+                                                  const SolveScal* __restrict__ scal, int64_t n) {
+  const double beta = scal->beta, omega = scal->omega;
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) p[i] = r[i] + beta * (p[i] - omega * v[i]);
+  }
+}
+
+// s = r - alpha v
+__global__ __launch_bounds__(256) void k_update_s(const double* __restrict__ r, const double* __restrict__ v, double* __restrict__ s,
+                                                  const SolveScal* __restrict__ scal, int64_t n) {
+  if (scal->flag) return;
+  const double alpha = scal->alpha;
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) s[i] = r[i] - alpha * v[i];
+  }
+}
+
+// x += alpha p + omega s, r = s - omega t, partials of (r_hat, r) and ||r||^2.  An entry of x whose update would not be
+// finite (overflow: p, s, t themselves are finite when alpha and omega passed their checks) keeps its value and is counted;
+// the count flags the iteration, so x never holds a NaN or inf that the solver wrote.
+__global__ __launch_bounds__(256) void k_update_xr(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+                                                   const double* __restrict__ s, const double* __restrict__ t,
+                                                   const double* __restrict__ rh, const SolveScal* __restrict__ scal, int64_t n,
+                                                   double* __restrict__ partials) {
+  if (scal->flag) return;   // uniform: alpha or omega is unusable, x and r stay what they were
+  const double alpha = scal->alpha, omega = scal->omega;
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+  double c[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) {
+      const double si = s[i];
+      const double xn = x[i] + (alpha * p[i] + omega * si);
+      if (finite_d(xn)) x[i] = xn;
+      else c[2] += 1.0;
+      const double ri = si - omega * t[i];
+      r[i] = ri;
+      c[0] = fma(rh[i], ri, c[0]);
+      c[1] = fma(ri, ri, c[1]);
+    }
+  }
+  block_partials<3>(c, partials);
+}
+
+struct Work {
+  double *r, *rh, *p, *v, *s, *t, *dinv, *partials;
+  SolveScal* scal;
+  int64_t n, spmv_blocks, vec_blocks, node_blocks;
+};
+
+int64_t partial_doubles(int64_t n_owned, int nvar) {
+  const int64_t a = 2 * ((n_owned + SPMV_NODES - 1) / SPMV_NODES), b = 4 * ((n_owned + 255) / 256),
+                c = 3 * ((n_owned * nvar + VEC_PER_BLOCK - 1) / VEC_PER_BLOCK);
+  return std::max(std::max(a, b), c) + 8;
+}
+
+Work carve(const SolveDev& d) {
+  Work w;
+  w.n = d.n_owned * d.nvar;
+  const int64_t n = std::max<int64_t>(w.n, 1);
+  double* q = d.work;
+  w.r = q; q += n; w.rh = q; q += n; w.p = q; q += n; w.v = q; q += n; w.s = q; q += n; w.t = q; q += n;
+  w.dinv = q; q += n * d.nvar;
+  w.partials = q; q += partial_doubles(d.n_owned, d.nvar);
+  w.scal = (SolveScal*)q;
+  w.spmv_blocks = (d.n_owned + SPMV_NODES - 1) / SPMV_NODES;
+  w.vec_blocks = (w.n + VEC_PER_BLOCK - 1) / VEC_PER_BLOCK;
+  w.node_blocks = (d.n_owned + 255) / 256;
+  return w;
+}
+
+template <int NV>
+hipError_t spmv(const SolveDev& d, const Work* w, const double* x, double* y, const double* dot_with) {
+  const int64_t blocks = (d.n_owned + SPMV_NODES - 1) / SPMV_NODES;
+  if (blocks == 0) return hipSuccess;
+  if (dot_with)
+    hipLaunchKernelGGL((k_spmv<NV, 1>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
+                       (const double*)w->dinv, dot_with, w->partials);
+  else
+    hipLaunchKernelGGL((k_spmv<NV, 0>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
+                       (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
+  return hipGetLastError();
+}
+
+#define SOLVE_HIP(call)                 \
+  do {                                  \
+    const hipError_t e_ = (call);       \
+    if (e_ != hipSuccess) return e_;    \
+  } while (0)
+
+hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage) {
+  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage, w.scal);
+  return hipGetLastError();
+}
+
+// the one host read of an iteration: the scalar record, behind everything enqueued so far
+hipError_t read_record(const SolveDev& d, const Work& w) {
+  SOLVE_HIP(hipMemcpyAsync(d.host_rec, w.scal, sizeof(SolveScal), hipMemcpyDeviceToHost, d.stream));
+  return hipStreamSynchronize(d.stream);
+}
+
+// true residual of x: r = r_hat = D^-1 (b - A x), p = v = 0, scalars as at the start; this is also the restart
+template <int NV>
+hipError_t residual(const SolveDev& d, const Work& w, const double* x, double scale) {
+  SOLVE_HIP(spmv<NV>(d, &w, x, w.t, nullptr));
+  hipLaunchKernelGGL((k_residual<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.rhs, scale, (const double*)w.t,
+                     (const double*)w.dinv, w.r, w.rh, w.p, w.v, d.n_owned, w.partials);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(finalize(d, w, w.node_blocks, 4, STAGE_INIT));
+  return read_record(d, w);
+}
+
+template <int NV>
+hipError_t iteration(const SolveDev& d, const Work& w, double* x) {
+  const dim3 vg((unsigned)w.vec_blocks), vb(256);
+  hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
+  SOLVE_HIP(spmv<NV>(d, &w, w.p, w.v, w.rh));                       // v = D^-1 A p, (r_hat, v)
+  SOLVE_HIP(finalize(d, w, w.spmv_blocks, 2, STAGE_ALPHA));
+  hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
+  SOLVE_HIP(spmv<NV>(d, &w, w.s, w.t, w.s));                        // t = D^-1 A s, (t, s), (t, t)
+  SOLVE_HIP(finalize(d, w, w.spmv_blocks, 2, STAGE_OMEGA));
+  hipLaunchKernelGGL(k_update_xr, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
+                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
+  return read_record(d, w);
+}
+
+template <int NV>
+hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info) {
+  const Work w = carve(d);
+  const SolveScal& rec = *d.host_rec;
+  auto report = [&](int reason) {
+    info->reason = reason;
+    info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
+    info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
+  };
+  SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
+  if (w.node_blocks)
+    hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, d.n_owned,
+                       (int)p.precond, w.dinv, w.scal);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
+  info->bad_blocks = rec.bad_blocks;
+  if (rec.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
+  if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
+  if (rec.bn2 == 0.0) {   // b = 0: x = 0
+    SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)w.n * sizeof(double), d.stream));
+    SOLVE_HIP(hipStreamSynchronize(d.stream));
+    report(RDC_SOLVE_CONVERGED);
+    info->residual_norm = info->plain_residual_norm = 0.0;
+    return hipSuccess;
+  }
+  const double tol = std::max(p.rel_tol * std::sqrt(rec.bn2), p.abs_tol);
+  if (std::sqrt(rec.rn2) <= tol) { report(RDC_SOLVE_CONVERGED); return hipSuccess; }
+  int breakdowns = 0;
+  for (;;) {
+    if (info->iterations >= p.max_its) {
+      SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
+      report(rec.flag ? RDC_SOLVE_NOT_FINITE : (std::sqrt(rec.rn2) <= tol ? RDC_SOLVE_CONVERGED : RDC_SOLVE_MAX_ITS));
+      return hipSuccess;
+    }
+    SOLVE_HIP(iteration<NV>(d, w, x));
+    info->iterations++;
+    const bool claims = !(rec.flag & 1) && std::sqrt(rec.rn2) <= tol;
+    if (!claims && !rec.flag) continue;
+    if (!claims && ++breakdowns > MAX_BREAKDOWNS) {
+      SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
+      report(rec.flag ? RDC_SOLVE_NOT_FINITE : RDC_SOLVE_BREAKDOWN);
+      return hipSuccess;
+    }
+    // the recurrence says "converged", or it broke down: the TRUE residual of x decides, and is the restart
+    SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
+    if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
+    if (std::sqrt(rec.rn2) <= tol) { report(RDC_SOLVE_CONVERGED); return hipSuccess; }
+    info->restarts++;
+  }
+}
+
+}  // namespace
+
+size_t solve_work_bytes(int nvar, int64_t n_owned) {
+  const int64_t n = std::max<int64_t>(n_owned * nvar, 1);
+  return (size_t)(6 * n + n * nvar + partial_doubles(n_owned, nvar)) * sizeof(double) + sizeof(SolveScal);
+}
+
+hipError_t solve_matvec(const SolveDev& d, const double* x, double* y) {
+  if (d.nvar == 3) return spmv<3>(d, nullptr, x, y, nullptr);
+  if (d.nvar == 5) return spmv<5>(d, nullptr, x, y, nullptr);
+  return hipErrorInvalidValue;
+}
+
+hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info) {
+  *info = rdc_solve_info();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SOLVE_HIP(hipEventCreate(&e0));
+  hipError_t e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = hipEventRecord(e0, d.stream);
+  if (e == hipSuccess) e = d.nvar == 3 ? run<3>(d, p, x, info) : d.nvar == 5 ? run<5>(d, p, x, info) : hipErrorInvalidValue;
+  if (e == hipSuccess) e = hipEventRecord(e1, d.stream);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  if (e == hipSuccess) e = hipEventElapsedTime(&info->device_ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return e;
+}
+
+}  // namespace rdc

@@ -85,6 +85,24 @@ class RipfCheckParams(C.Structure):
                 ("RT_focus_fractions", C.c_int32), ("day", C.c_int32), ("_pad", C.c_int32)]
 
 
+class SolveParams(C.Structure):
+    """rdc_solve_params: stopping test on the preconditioned residual, b = rhs_scale * assembled rhs."""
+    _fields_ = [("rel_tol", _D), ("abs_tol", _D), ("rhs_scale", _D), ("max_its", C.c_int32), ("precond", C.c_int32)]
+
+
+class SolveInfo(C.Structure):
+    """rdc_solve_info: outcome of rdc_solve; residual_norm is the TRUE ||D^-1 (b - A x)|| of the returned x."""
+    _fields_ = [("reason", C.c_int32), ("iterations", C.c_int32), ("restarts", C.c_int32), ("bad_blocks", C.c_int32),
+                ("rhs_norm", _D), ("residual_norm", _D), ("plain_rhs_norm", _D), ("plain_residual_norm", _D),
+                ("device_ms", C.c_float), ("_pad", C.c_float)]
+
+    def __repr__(self):
+        return (f"SolveInfo(reason={self.reason}, iterations={self.iterations}, restarts={self.restarts}, "
+                f"bad_blocks={self.bad_blocks}, rhs_norm={self.rhs_norm:.6e}, residual_norm={self.residual_norm:.6e}, "
+                f"plain_rhs_norm={self.plain_rhs_norm:.6e}, plain_residual_norm={self.plain_residual_norm:.6e}, "
+                f"device_ms={self.device_ms:.3f})")
+
+
 # reference parameter key -> struct field
 PIHNA_KEYS = {
     "time_step": "time_step",

@@ -1,0 +1,95 @@
+"""PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
+the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
+
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2] [--dump DIR]
+
+Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
+preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
+counted on the device after the clamp.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz)."""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+import numpy as np  # noqa: E402
+
+
+def state_tensor(ctx):
+    """zero-copy torch view [n_node][nvar] of the context's FIELD_OLD_SOLUTION storage"""
+    import torch
+
+    class _View:
+        pass
+    v = _View()
+    ptr = ctx.field_device_ptr(0, ctx.n_node * ctx.nvar)
+    v.__cuda_array_interface__ = {"shape": (ctx.n_node, ctx.nvar), "typestr": "<f8", "data": (ptr, False), "version": 2, "strides": None}
+    return torch.as_tensor(v, device=torch.device("cuda", ctx.device))
+
+
+def background_share(u, conn_dev):
+    """(share of nodes, share of elements all of whose nodes) with n = c = h = a = 0 exactly; u, conn_dev: torch, on the device"""
+    bg = (u[:, 0] == 0) & (u[:, 1] == 0) & (u[:, 2] == 0) & (u[:, 4] == 0)
+    return float(bg.double().mean()), float(bg[conn_dev].all(dim=1).double().mean())
+
+
+def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None):
+    """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
+    on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there)."""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    u = state_tensor(ctx)
+    conn_dev = torch.from_numpy(np.ascontiguousarray(conn, dtype=np.int64)).to(dev)
+    ctx.timing_enable(True)
+    out = []
+    for k in range(steps):
+        ctx.assemble_pihna(params)
+        ctx.synchronize()
+        asm_ms = ctx.timing_last_ms()
+        if on_step:
+            on_step(k, "assembled", ctx)
+        info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its)
+        if on_step:
+            on_step(k, "solved", ctx)
+        ctx.clamp_nonnegative(0)
+        ctx.synchronize()
+        nodes, elems = background_share(u, conn_dev)
+        out.append(dict(step=k + 1, assembly_ms=asm_ms, solve_ms=info.device_ms, iterations=info.iterations, restarts=info.restarts,
+                        reason=info.reason, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
+                        background_nodes=nodes, background_elems=elems))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=119)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--rel-tol", type=float, default=1e-8)
+    ap.add_argument("--precond", type=int, default=2)
+    ap.add_argument("--max-its", type=int, default=20000)
+    ap.add_argument("--dump", default=None)
+    a = ap.parse_args()
+    import torch
+    torch.cuda.init()                       # before the library opens the device: one runtime initialisation order for both
+    from rdcfes_amd import AssemblyContext, pihna_params_from_dict, synth
+    conn, xyz = synth.kuhn_tet_mesh(a.n, order="lex")
+    p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+    with AssemblyContext(0) as ctx:
+        ctx.mesh_upload(4, conn, xyz, 5)
+        ctx.field_upload(0, synth.pihna_fields(xyz))
+        print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=a.precond)))
+        for rec in run(ctx, conn, p, a.steps, a.rel_tol, a.precond, a.max_its):
+            print(json.dumps(rec), flush=True)
+        if a.dump:
+            d = Path(a.dump)
+            d.mkdir(parents=True, exist_ok=True)
+            np.save(d / "state.npy", ctx.field_download(0, xyz.shape[0] * 5).reshape(-1, 5))
+            np.save(d / "conn.npy", conn)
+            np.save(d / "xyz.npy", xyz)
+
+
+if __name__ == "__main__":
+    main()
