@@ -355,7 +355,7 @@ static hipError_t launch_hex8_cl(const LaunchArgs& a, const typename M::K& k) {
     dyn_lds_once(pattr[0], (const void*)k_hex8_clp<M, EXP_MODE, CW, PW>, 80 * 1024);
     const int grid = a.cl.grid < a.cl.n_wg ? a.cl.grid : a.cl.n_wg;
     hipLaunchKernelGGL((k_hex8_clp<M, EXP_MODE, CW, PW>), dim3(grid), dim3((CW + PW) * 64), pbytes, a.stream, a.m, k, a.cl.desc, a.cl.ntab,
-                       a.cl.eid, a.cl.pair, a.cl.pslot, a.u, a.aux, a.elem, a.val, a.rhs, a.cl.n_wg, (int)((a.cl.max_row_doubles + 1) & ~(size_t)1), a.opt_ablate);
+                       a.cl.eid, a.cl.pair, a.cl.pslot, a.u, a.aux, a.elem, a.val, a.rhs, a.cl.n_wg, (int)((a.cl.max_row_doubles + 1) & ~(size_t)1), a.opt.ablate);
     return hipGetLastError();
   }
   // quadrature points per round and workgroup barrier: the model's choice (M::HEX_CL_POINTS); "prefetch" = 1 forces one
@@ -365,9 +365,9 @@ static hipError_t launch_hex8_cl(const LaunchArgs& a, const typename M::K& k) {
     static std::atomic<uint64_t> attr[1];  /* per instantiation and device */ \
     dyn_lds_once(attr[0], (const void*)k_hex8_cl<M, EXP_MODE, CW, PW, PPR>, 80 * 1024); \
     hipLaunchKernelGGL((k_hex8_cl<M, EXP_MODE, CW, PW, PPR>), dim3(a.cl.n_wg), dim3((CW + PW) * 64), bytes, a.stream, a.m, k, a.cl.desc, a.cl.ntab, \
-                       a.cl.eid, a.cl.pair, a.cl.pslot, a.u, a.aux, a.elem, a.val, a.rhs, a.opt_ablate);                             \
+                       a.cl.eid, a.cl.pair, a.cl.pslot, a.u, a.aux, a.elem, a.val, a.rhs, a.opt.ablate);                             \
   }
-  if constexpr (M::HEX_CL_POINTS == 2) { if (a.opt_pf == 1) RDC_HEX8_CL(1) else RDC_HEX8_CL(2) }
+  if constexpr (M::HEX_CL_POINTS == 2) { if (a.opt.prefetch == 1) RDC_HEX8_CL(1) else RDC_HEX8_CL(2) }
   else RDC_HEX8_CL(1)
 #undef RDC_HEX8_CL
   return hipGetLastError();

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rdc_kernels.h"
+#include "rdc_options.h"
 #include "rdc_prep.h"
 
 namespace rdc {
@@ -83,24 +84,20 @@ struct LaunchArgs {
   const uint32_t* hx_nlist = nullptr;
   const uint16_t* hx_ploc = nullptr;
   int hx_max_nodes = 0;
-  int opt_staged = 1;
   const double* elem = nullptr;  // per-element inputs ([n_elem][M::NELEM]) of models that have them (ADPM tracts)
   double* packed;  // scratch for the per-node records of the TET4 fast path
   int pack_part = 0;               // 0 = pack every record; 1 = owned nodes only, then record pack_event; 2 = wait for pack_event, ghosts only
   hipEvent_t pack_event = nullptr;
   int variant;     // RDC_VARIANT_*
-  int opt_occ, opt_ablate, opt_kernel, opt_special, opt_xcd, opt_grid, opt_pf, opt_moments = 1, opt_stagger = 0, opt_ldspad = 0;  // tuning knobs (rdc_set_option)
+  Options opt;     // the context's tuning knobs (rdc_set_option) as they were at the call; what the call derives from them has fields of its own
+  int kernel = 0;  // opt.kernel as the pair-kernel launchers read it: 5 and 7 (their choice is made before the launcher) count as 0
   Rg2Dev rg2;
   EvDev ev;
   ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted)
   bool use_ev = false;   // element-visit kernel allowed for this call
-  int opt_ev_occ = 3;
-  int opt_evc_occ = 2;
   int ev_grid = 0;           // 2 x CUs: the resident element-visit kernel launches 3/2 of it (22 moments: all of it)
-  int opt_ev_bg = 1;         // k_tet4_ev: waves all of whose visits are in the background state skip the moments that are sums of zeros (rdc_tet4_ev.h, bg)
   int* ev_ticket = nullptr;  // k_tet4_evq: cluster counter (one int, zeroed by the launch)
   bool ev_general = false;   // k_tet4_ev with every PIHNA term on (22 moments) instead of the shipped parameter pattern (16)
-  int opt_ev_resident = 1;   // k_tet4_evq: three resident workgroups per CU walking over the clusters, next cluster fetched ahead (whole-mesh launches)
   long long* stamps = nullptr;  // diagnostic phase stamps (rdc_debug_stamps)
   double* val;
   double* rhs;

@@ -26,8 +26,8 @@ static hipError_t launch_rd_impl(const LaunchArgs& a, const typename M::K& k) {
         constexpr int REC = 3 + M::NV + (M::NAUX > 0 ? M::NAUX : 0);
         const size_t tab_off = (a.lds_bytes / sizeof(double) + 3) & ~(size_t)1;  // + slice phase shift, rounded to 16 bytes
         const size_t staged_bytes = sizeof(double) * (tab_off + (size_t)a.hx_max_nodes * REC);
-        // opt_staged: 1 = where the model profits (M::HEX_STAGED), 2 = always, 0 = never
-        if ((a.opt_staged == 2 || (a.opt_staged == 1 && M::HEX_STAGED)) && a.hx_ploc && staged_bytes <= 80 * 1024) {
+        // "staged": 1 = where the model profits (M::HEX_STAGED), 2 = always, 0 = never
+        if ((a.opt.staged == 2 || (a.opt.staged == 1 && M::HEX_STAGED)) && a.hx_ploc && staged_bytes <= 80 * 1024) {
           static std::atomic<uint64_t> attr_set[1];  /* per instantiation and device */
     dyn_lds_once(attr_set[0], (const void*)k_rowgather_staged<M, NEN, EXP_MODE, BLOCK>, 80 * 1024);
           hipLaunchKernelGGL((k_rowgather_staged<M, NEN, EXP_MODE, BLOCK>), dim3(a.n_wg), dim3(BLOCK), staged_bytes, a.stream,

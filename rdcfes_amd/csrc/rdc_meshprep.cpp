@@ -472,8 +472,8 @@ std::string prep_build(int nen, int64_t n_elem, int64_t n_node, int64_t n_owned,
         int mx = 1;
         for (int64_t w = 0; w < nwg; w++) mx = std::max(mx, nuniq[w]);
         if (mx <= 256) {
-          P.rg4_nl_stride = (mx + 63) & ~63;
-          P.nlist.assign((size_t)nwg * P.rg4_nl_stride, 0);
+          P.nl_stride = (mx + 63) & ~63;
+          P.nlist.assign((size_t)nwg * P.nl_stride, 0);
           P.pair_loc.assign((size_t)nwg * block, 0xFFFFFFFFu);
 #pragma omp parallel for schedule(dynamic, 256)
           for (int64_t w = 0; w < nwg; w++) {
@@ -482,8 +482,8 @@ std::string prep_build(int nen, int64_t n_elem, int64_t n_node, int64_t n_owned,
             std::sort(tmp.begin(), tmp.end());
             tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
             if (!tmp.empty() && tmp.back() == 0xFFFFFFFFu) tmp.pop_back();
-            uint32_t* nl = &P.nlist[(size_t)w * P.rg4_nl_stride];
-            for (int x = 0; x < P.rg4_nl_stride; x++) nl[x] = tmp.empty() ? 0u : tmp[(size_t)std::min<size_t>(x, tmp.size() - 1)];
+            uint32_t* nl = &P.nlist[(size_t)w * P.nl_stride];
+            for (int x = 0; x < P.nl_stride; x++) nl[x] = tmp.empty() ? 0u : tmp[(size_t)std::min<size_t>(x, tmp.size() - 1)];
             for (int idx = 0; idx < block; idx++) {
               if (pr[idx * 4] == 0xFFFFFFFFu) continue;
               uint32_t packed = 0;
@@ -497,7 +497,7 @@ std::string prep_build(int nen, int64_t n_elem, int64_t n_node, int64_t n_owned,
         }
       }
     }
-    if (!P.rg2_ok) { P.wg2.clear(); P.pair_rec.clear(); P.chunk.clear(); P.sdesc.clear(); P.contrib.clear(); P.pair_aux.clear(); P.node_tab.clear(); P.nlist.clear(); P.pair_loc.clear(); P.pair_eid.clear(); P.rg4_nl_stride = 0; }
+    if (!P.rg2_ok) { P.wg2.clear(); P.pair_rec.clear(); P.chunk.clear(); P.sdesc.clear(); P.contrib.clear(); P.pair_aux.clear(); P.node_tab.clear(); P.nlist.clear(); P.pair_loc.clear(); P.pair_eid.clear(); P.nl_stride = 0; }
   }
   return std::string();
 }

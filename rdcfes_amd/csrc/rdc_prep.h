@@ -81,8 +81,8 @@ struct HostPrep {
   std::vector<uint16_t> node_tab;   // [n_owned][4] {rowoff, stride, nvar*diag slot, 0}: where the diagonal block sits
   // k_tet4_rg5: the distinct nodes a workgroup touches, so their records can be
   // gathered into LDS by LDS-DMA; pairs then address nodes by an 8-bit index into that list
-  int rg4_nl_stride = 0;            // list length per workgroup (multiple of 64, max over workgroups)
-  std::vector<uint32_t> nlist;      // [n_wg][rg4_nl_stride] node ids, padded with the first id
+  int nl_stride = 0;                // list length per workgroup (multiple of 64, max over workgroups)
+  std::vector<uint32_t> nlist;      // [n_wg][nl_stride] node ids, padded with the first id
   std::vector<uint32_t> pair_loc;   // [n_wg][block] four 8-bit list indices (row node in the low byte); ~0u = no pair
   std::vector<uint32_t> pair_eid;   // [n_wg][block] element of the pair (uploaded only for models with per-element inputs)
   std::vector<Chunk> chunk;

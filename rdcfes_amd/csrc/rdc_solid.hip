@@ -674,15 +674,15 @@ static void launch_two_pass(const SolidArgs& a) {
   const unsigned grid = (unsigned)((a.m.n_elem + SolidCfg<NEN>::EPB - 1) / SolidCfg<NEN>::EPB);
 #define RDC_SOLID_ELEM(JAC, SYM, JS)                                                                                \
   hipLaunchKernelGGL((k_solid_elem<NEN, JAC, SYM, JS>), dim3(grid), dim3(128 * JS), 0, a.stream, a.m, a.Xu, a.fibre, \
-                     a.elem_material, a.materials, a.params.pseudo_time, a.ke, a.fe, a.store_mode)
+                     a.elem_material, a.materials, a.params.pseudo_time, a.ke, a.fe, a.opt.solid_store)
   constexpr int JSD = (NEN == 8) ? 2 : 1;
   if (!a.request_jacobian) RDC_SOLID_ELEM(false, false, 1);
   else if (a.params.use_symmetry) RDC_SOLID_ELEM(true, true, JSD);
-  else if (a.split == 1) RDC_SOLID_ELEM(true, false, 1);
+  else if (a.opt.solid_split == 1) RDC_SOLID_ELEM(true, false, 1);
   else RDC_SOLID_ELEM(true, false, JSD);
 #undef RDC_SOLID_ELEM
   const unsigned gb = (unsigned)((a.nblocks + 255) / 256);
-  if (a.request_jacobian && a.gather == 0)
+  if (a.request_jacobian && a.opt.solid_gather == 0)
     hipLaunchKernelGGL(k_solid_gather_st, dim3(gb), dim3(256), 0, a.stream, a.nblocks, a.m.bptr, a.brow, a.gptr, a.gsrc, a.ke,
                        a.val);
   else if (a.request_jacobian)

@@ -485,30 +485,30 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   // ids -> fetch: three round trips) and the tail of the launch are not hidden and cost ~20 us whatever the size -- K(55) = 10,700
   // clusters runs 0.184 vs 0.167 ms, K(75) 0.388 vs 0.370, K(85) = 40,000 clusters 0.577 vs 0.575, K(94) 0.713 vs 0.737, K(119)
   // 1.38 vs 1.50 ("grid" > 0 or "ev_resident" = 2 force it: tests)
-  const int evq_grid = a.opt_grid > 0 ? a.opt_grid : (a.ev_grid > 0 ? (a.ev_general ? a.ev_grid : a.ev_grid / 2 * 3) : 768);   // three per CU (22 moments: two)
-  if (a.opt_ev_resident && (!a.opt_ablate || (a.opt_ablate == 4 && !a.ev_general)) && a.opt_ev_occ == 3 && !a.opt_xcd && a.opt_stagger == 0 &&
-      (a.opt_grid > 0 || a.opt_ev_resident == 2 || (int64_t)wg_count >= 56 * (int64_t)evq_grid)) {
+  const int evq_grid = a.opt.grid > 0 ? a.opt.grid : (a.ev_grid > 0 ? (a.ev_general ? a.ev_grid : a.ev_grid / 2 * 3) : 768);   // three per CU (22 moments: two)
+  if (a.opt.ev_resident && (!a.opt.ablate || (a.opt.ablate == 4 && !a.ev_general)) && a.opt.ev_occupancy == 3 && !a.opt.xcd && a.opt.stagger == 0 &&
+      (a.opt.grid > 0 || a.opt.ev_resident == 2 || (int64_t)wg_count >= 56 * (int64_t)evq_grid)) {
     int grid = evq_grid;
     if (grid > wg_count) grid = wg_count;
     const size_t bytes = ((size_t)(a.ev_general ? ev::NMG : ev::NM) * ev::NBP + 5 * ev::MAXN + (size_t)4 * E.nls * 2) * sizeof(double) + EvqLists::bytes(E.nls);
     if (!a.ev_ticket) return hipErrorInvalidValue;   // the cluster counter: zeroed by the record pack kernel in front of this launch
 #define RDC_EVQ(MODE, TLV, GENV)                                                                                                              \
   hipLaunchKernelGGL((k_tet4_evq<MODE, TLV, GENV>), dim3(grid), dim3(256), bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab, E.bpart, k, \
-                     a.packed, a.val, a.rhs, E.nls, E.wg_begin, wg_count, a.stamps, a.opt_ev_bg, a.ev_ticket + (a.pack_part == 2 ? 16 : 0), E.wg_perm)
+                     a.packed, a.val, a.rhs, E.nls, E.wg_begin, wg_count, a.stamps, a.opt.ev_background, a.ev_ticket + (a.pack_part == 2 ? 16 : 0), E.wg_perm)
     if (a.ev_general) { if (a.exp_mode == 3) RDC_EVQ(3, false, true); else RDC_EVQ(0, false, true); }
-    else if (a.opt_ablate == 4) { if (a.exp_mode == 3) RDC_EVQ(3, true, false); else RDC_EVQ(0, true, false); }
+    else if (a.opt.ablate == 4) { if (a.exp_mode == 3) RDC_EVQ(3, true, false); else RDC_EVQ(0, true, false); }
     else { if (a.exp_mode == 3) RDC_EVQ(3, false, false); else RDC_EVQ(0, false, false); }
 #undef RDC_EVQ
     return hipGetLastError();
   }
 #define RDC_EV(MODE, MINW)                                                                                          \
   hipLaunchKernelGGL((k_tet4_ev<MODE, MINW>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt_xcd ? wg_count : 0, a.opt_stagger, a.stamps, a.opt_ev_bg)
-  if (a.exp_mode == 3 && a.opt_ablate >= 1 && a.opt_ablate <= 4 && !a.ev_general) {   // diagnostic builds (1-3: timing only)
+                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
+  if (a.exp_mode == 3 && a.opt.ablate >= 1 && a.opt.ablate <= 4 && !a.ev_general) {   // diagnostic builds (1-3: timing only)
 #define RDC_EVA(X)                                                                                                    \
   hipLaunchKernelGGL((k_tet4_ev<3, 3, X>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt_xcd ? wg_count : 0, a.opt_stagger, a.stamps, a.opt_ev_bg)
-    if (a.opt_ablate == 1) RDC_EVA(1); else if (a.opt_ablate == 2) RDC_EVA(2); else if (a.opt_ablate == 3) RDC_EVA(3); else RDC_EVA(4);
+                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
+    if (a.opt.ablate == 1) RDC_EVA(1); else if (a.opt.ablate == 2) RDC_EVA(2); else if (a.opt.ablate == 3) RDC_EVA(3); else RDC_EVA(4);
 #undef RDC_EVA
     return hipGetLastError();
   }
@@ -517,13 +517,13 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
     // spills 79 registers (304 B of scratch per lane) and runs 8.8 instead of 3.0 ms on K(119) (profiles/r03_ev_ab_log.md, r03q)
 #define RDC_EVG(MODE)                                                                                                       \
   hipLaunchKernelGGL((k_tet4_ev<MODE, 2, 0, true>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt_xcd ? wg_count : 0, a.opt_stagger, a.stamps, a.opt_ev_bg)
+                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
     if (a.exp_mode == 3) RDC_EVG(3); else RDC_EVG(0);
 #undef RDC_EVG
     return hipGetLastError();
   }
-  if (a.exp_mode == 3) { if (a.opt_ev_occ == 2) RDC_EV(3, 2); else RDC_EV(3, 3); }
-  else { if (a.opt_ev_occ == 2) RDC_EV(0, 2); else RDC_EV(0, 3); }
+  if (a.exp_mode == 3) { if (a.opt.ev_occupancy == 2) RDC_EV(3, 2); else RDC_EV(3, 3); }
+  else { if (a.opt.ev_occupancy == 2) RDC_EV(0, 2); else RDC_EV(0, 3); }
 #undef RDC_EV
   return hipGetLastError();
 }

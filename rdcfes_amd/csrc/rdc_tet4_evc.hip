@@ -154,7 +154,7 @@ hipError_t launch_tet4_evc(const LaunchArgs& a, const typename M::K& k) {
 #define RDC_EVC(MODE, MINW)                                                                                                \
   hipLaunchKernelGGL((k_tet4_evc<M, MODE, MINW>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
                      E.vslot, E.ntab, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin)
-  if (a.opt_evc_occ == 3) { if (a.exp_mode == M::FAST_EXP_MODE) RDC_EVC(M::FAST_EXP_MODE, 3); else RDC_EVC(0, 3); }
+  if (a.opt.evc_occupancy == 3) { if (a.exp_mode == M::FAST_EXP_MODE) RDC_EVC(M::FAST_EXP_MODE, 3); else RDC_EVC(0, 3); }
   else { if (a.exp_mode == M::FAST_EXP_MODE) RDC_EVC(M::FAST_EXP_MODE, 2); else RDC_EVC(0, 2); }
 #undef RDC_EVC
   return hipGetLastError();

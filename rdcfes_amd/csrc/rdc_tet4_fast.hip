@@ -619,26 +619,26 @@ static hipError_t launch_fast_impl(const LaunchArgs& a, const typename M::K& k) 
   if (a.use_ev && a.ev.n_wg > 0 && a.strategy == RDC_SCATTER_ROWGATHER) return launch_tet4_evc<M>(a, k);
   // models with per-element inputs (M::NELEM > 0) or a local-node aux mask exist only as k_tet4_rg5 and k_tet4_coloured
   if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.rg2.pair_aux && a.rg2.nlist && a.rg2.block == 256 &&
-      (a.opt_kernel == 0 || M::NELEM > 0 || M::AUX_LOCAL_NODE >= 0)) {
+      (a.kernel == 0 || M::NELEM > 0 || M::AUX_LOCAL_NODE >= 0)) {
     constexpr int BLOCK = 256;
     const int nl = a.rg2.nl_stride;
     const int acc_doubles = (int)((a.rg2.lds_bytes / sizeof(double) + 3) & ~(size_t)1);  // + slice phase shift + diagonal alignment
-    // + opt_ldspad KB of unused LDS: diagnostic, lowers the number of co-resident workgroups (one per CU from ~55 KB)
-    const size_t lds_bytes = sizeof(double) * ((size_t)acc_doubles + (size_t)(Rec<M>::N / 2) * nl * 2) + (size_t)a.opt_ldspad * 1024;
+    // + "lds_pad" KB of unused LDS: diagnostic, lowers the number of co-resident workgroups (one per CU from ~55 KB)
+    const size_t lds_bytes = sizeof(double) * ((size_t)acc_doubles + (size_t)(Rec<M>::N / 2) * nl * 2) + (size_t)a.opt.lds_pad * 1024;
     const int wg_begin = a.rg2.wg_begin, wg_count = a.rg2.wg_count < 0 ? a.rg2.n_wg - a.rg2.wg_begin : a.rg2.wg_count;
     if (wg_count <= 0) return hipSuccess;
 #define RDC_RG5(MINW, ST)                                                                                          \
   hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, MINW, ST>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,     \
                      a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
-                     nl, acc_doubles, a.stamps, a.opt_pf, a.opt_xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt_stagger)
+                     nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
     if constexpr ((std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) {
       // diagnostic builds (timing only, results are wrong): LDS atomics replaced by plain stores / removed
-      if (a.opt_ablate >= 1 && a.opt_ablate <= 6) {
+      if (a.opt.ablate >= 1 && a.opt.ablate <= 6) {
 #define RDC_ABL(X)                                                                                                        \
   hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, 2, false, X>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,      \
                      a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
-                     nl, acc_doubles, a.stamps, a.opt_pf, a.opt_xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt_stagger)
-        switch (a.opt_ablate) {
+                     nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
+        switch (a.opt.ablate) {
           case 1: RDC_ABL(1); break;   // plain LDS stores instead of atomics
           case 2: RDC_ABL(2); break;   // no LDS accumulation traffic
           case 3: RDC_ABL(3); break;   // no compute phase
@@ -651,45 +651,45 @@ static hipError_t launch_fast_impl(const LaunchArgs& a, const typename M::K& k) 
       }
     }
     if constexpr (std::is_same<M, PihnaNoCellTransportMoments>::value) {
-      if (a.opt_occ == 3) { RDC_RG5(3, false); return hipGetLastError(); }
+      if (a.opt.occupancy == 3) { RDC_RG5(3, false); return hipGetLastError(); }
     }
     if (a.stamps && (std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) RDC_RG5(2, true);
-    else if (a.opt_occ == 1) RDC_RG5(1, false);
+    else if (a.opt.occupancy == 1) RDC_RG5(1, false);
     else RDC_RG5(2, false);
 #undef RDC_RG5
     return hipGetLastError();
   }
   if constexpr (M::NELEM == 0 && M::AUX_LOCAL_NODE < 0)
-  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.rg2.pair_aux && (a.opt_kernel == 0 || a.opt_kernel == 3)) {
+  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.rg2.pair_aux && (a.kernel == 0 || a.kernel == 3)) {
 #define RDC_RG3(BLOCK, MINW)                                                                                       \
   hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), a.rg2.lds_bytes, a.stream, \
-                     a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt_xcd,  \
+                     a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,  \
                      (long long*)nullptr)
     if (a.stamps && a.rg2.block == 256 && std::is_same<M, PihnaNoCellTransport>::value && EXP_MODE == 3) {
       // diagnostic build with s_memtime stamps per phase (tools/stamp_report.py); never the timed kernel
       hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, 256, 2, true>), dim3(a.rg2.n_wg), dim3(256), a.rg2.lds_bytes, a.stream,
-                         a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt_xcd,
+                         a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,
                          a.stamps);
       return hipGetLastError();
     }
     if (a.rg2.block == 128) {  // MINW counts waves per SIMD: 2 means four 128-thread workgroups per CU
-      if (a.opt_occ == 1) RDC_RG3(128, 1); else RDC_RG3(128, 2);
+      if (a.opt.occupancy == 1) RDC_RG3(128, 1); else RDC_RG3(128, 2);
     } else {
-      if (a.opt_occ == 1) RDC_RG3(256, 1);
-      else if (a.opt_occ == 3) RDC_RG3(256, 3);
+      if (a.opt.occupancy == 1) RDC_RG3(256, 1);
+      else if (a.opt.occupancy == 3) RDC_RG3(256, 3);
       else RDC_RG3(256, 2);
     }
 #undef RDC_RG3
     return hipGetLastError();
   }
   if constexpr (M::NELEM == 0 && M::AUX_LOCAL_NODE < 0)
-  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.opt_kernel == 2 && a.rg2.block == 256) {
+  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.kernel == 2 && a.rg2.block == 256) {
     constexpr int BLOCK = 256;
 #define RDC_RG2(MINW)                                                                                              \
   hipLaunchKernelGGL((k_tet4_rg2<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), 0, a.stream, a.rg2.desc, \
-                     a.rg2.pair_rec, a.rg2.chunk, a.rg2.sdesc, a.rg2.contrib, k, a.packed, a.val, a.rhs, a.opt_ablate)
-    if (a.opt_occ == 1) RDC_RG2(1);
-    else if (a.opt_occ == 3) RDC_RG2(3);
+                     a.rg2.pair_rec, a.rg2.chunk, a.rg2.sdesc, a.rg2.contrib, k, a.packed, a.val, a.rhs, a.opt.ablate)
+    if (a.opt.occupancy == 1) RDC_RG2(1);
+    else if (a.opt.occupancy == 3) RDC_RG2(3);
     else RDC_RG2(2);
 #undef RDC_RG2
     return hipGetLastError();
@@ -703,7 +703,7 @@ static hipError_t launch_fast_impl(const LaunchArgs& a, const typename M::K& k) 
                      a.m, k, a.packed, a.val, a.rhs)
       // tuning variants exist for the PIHNA / cubic-exponent instantiation only
       const bool lab = (std::is_same<M, Pihna>::value || std::is_same<M, PihnaNoCellTransport>::value) && EXP_MODE == 3;
-      const int key = lab ? a.opt_occ * 10 + a.opt_ablate : 20;
+      const int key = lab ? a.opt.occupancy * 10 + a.opt.ablate : 20;
       if (lab) {
         switch (key) {
           case 10: RDC_RG(1, 0); break;

@@ -222,9 +222,9 @@ def test_moving_mesh_hcc(oracle):
     assert rel(v_undeformed, val0) > 1e-4
 
 
-def _solid_case(nen, n, seed=0):
+def _solid_case(nen, n, seed=0, jitter=0.1):
     rng = np.random.default_rng(seed)
-    conn, Xu = synth.kuhn_tet_mesh(n, jitter=0.1, order="random") if nen == 4 else synth.hex_mesh(n, jitter=0.1, order="random")
+    conn, Xu = synth.kuhn_tet_mesh(n, jitter=jitter, order="random") if nen == 4 else synth.hex_mesh(n, jitter=jitter, order="random")
     x = Xu + synth.solid_displacement(Xu, amp=0.02)
     ne = conn.shape[0]
     cen = Xu[conn].mean(axis=1)
@@ -481,6 +481,125 @@ def test_retired_and_unknown_kernel_selections_are_refused(oracle, key, value):
         ctx.assemble_pihna(p)
         val, rhs = ctx.csr_download()
     assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+
+
+_REFUSED_THROUGH_THE_ABI = [
+    ("block", 64, "block must be 128 or 256"),
+    ("part", 3, "part must be 0, 1 or 2"),
+    ("solid_kernel", 4, "solid_kernel must be 0 (default), 1 (coloured), 2 (two-pass) or 3 (fused cluster kernel)"),
+    ("hex_kernel", 3, "hex_kernel must be 0 (cluster kernel), 1 (pair kernels) or 2 (persistent cluster kernel)"),
+    ("solid_cl_waves", 30, "solid_cl_waves must be 31 (3 consumer + 1 producer waves) or 62"),
+    ("kernel", 4, "kernel must be 0, 1, 2, 3, 5 or 7, not 4"),
+]
+
+
+def test_option_refusals_through_the_abi(oracle):
+    """Every validated key of rdc_set_option refuses a bad value with RDC_ERR_INVALID and its own message, on a context that
+    has no mesh yet; none of the refusals leaves anything behind: a default PIHNA assembly afterwards is on the oracle.
+    (The table itself is checked value by value on the CPU: tests/test_host_options.py.)"""
+    conn, xyz, u, _, p = _inputs(0, 4, 6, variant="shipped")
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    with AssemblyContext(0) as ctx:
+        for key, value, message in _REFUSED_THROUGH_THE_ABI:
+            with pytest.raises(RdcError) as e:
+                ctx.set_option(key, value)
+            assert e.value.code == 1, key  # RDC_ERR_INVALID
+            assert str(e.value) == f"rdc error 1: {message}"
+        ctx.mesh_upload(4, conn, xyz, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u)
+        ctx.assemble_pihna(p)
+        val, rhs = ctx.csr_download()
+    assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+
+
+def test_reupload_resets_mesh_state(oracle):
+    """What a part-1 call leaves behind belongs to its mesh.  Part 1 on mesh A, rdc_mesh_upload of a smaller mesh B, part 2:
+    there has been no part 1 on B, so part 2 must prepare the node data of all of B's nodes itself, like a part 2 on a
+    context that never held A (if the "part 1 has packed the owned records" flag outlives the upload, the kernel reads A's
+    records).  The rows part 2 is responsible for -- from rdc_part1_nodes upward -- are compared with that fresh context's,
+    then a whole assembly on the reused context with the oracle."""
+    p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+    conn_a, xyz_a = synth.kuhn_tet_mesh(12, order="lex")
+    conn_b, xyz_b = synth.kuhn_tet_mesh(9, order="lex")
+    assert xyz_b.shape[0] < xyz_a.shape[0] and conn_b.shape[0] < conn_a.shape[0]
+    u_a, u_b = synth.pihna_fields(xyz_a), synth.pihna_fields(xyz_b)
+    n_int_a, n_int_b = int(0.37 * xyz_a.shape[0]), int(0.37 * xyz_b.shape[0])
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn_b, xyz_b, 5, p, u_old=u_b)
+    with AssemblyContext(0) as ctx:
+        ctx.set_option("interior_nodes", n_int_b)
+        ctx.mesh_upload(4, conn_b, xyz_b, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u_b)
+        first = ctx.part1_nodes()
+        ctx.assemble_pihna_part(p, 2)
+        val_f, rhs_f = ctx.csr_download()
+    with AssemblyContext(0) as ctx:
+        ctx.set_option("interior_nodes", n_int_a)
+        ctx.mesh_upload(4, conn_a, xyz_a, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u_a)
+        ctx.assemble_pihna_part(p, 1)
+        assert ctx.part1_nodes() > 0                       # part 1 did launch (and pack) on A
+        ctx.set_option("interior_nodes", n_int_b)
+        ctx.mesh_upload(4, conn_b, xyz_b, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u_b)
+        assert ctx.part1_nodes() == first
+        ctx.assemble_pihna_part(p, 2)
+        val, rhs = ctx.csr_download()
+        ctx.assemble_pihna(p)
+        val_w, rhs_w = ctx.csr_download()
+    assert 0 <= first < xyz_b.shape[0]
+    r0 = 5 * first
+    e0 = int(rp0[r0])
+    assert np.linalg.norm(val_f[e0:]) > 0.0
+    assert_csr_close(rp0[r0:] - e0, col0[e0:], val[e0:], val_f[e0:], rhs[r0:], rhs_f[r0:], 5)
+    assert rel(val_w, val0) < TOL and rel(rhs_w, rhs0) < TOL
+    assert_csr_close(rp0, col0, val_w, val0, rhs_w, rhs0, 5)
+
+
+def test_reupload_across_element_types(oracle):
+    """One context through TET4 / five unknowns, HEX8 / three unknowns and back: the buffer groups of the mesh that left are
+    freed or rebuilt, and every list built on first use (element visits, clusters, the two-pass gather lists) is rebuilt for
+    the mesh that is there."""
+    conn_t, xyz_t, u_t, _, p_t = _inputs(0, 4, 6, variant="shipped")
+    ref_t = oracle.assemble(0, 4, conn_t, xyz_t, 5, p_t, u_old=u_t)
+    conn_h, Xu, x, em, mats, fibre, sides = _solid_case(8, 7, jitter=0.15)
+    p_h, u_h = hcc_params_from_dict(synth.hcc_param_dict("full")), synth.hcc_fields(x)
+    ref_h = oracle.assemble(2, 8, conn_h, x, 3, p_h, u_old=u_h)
+    sp = SolidParams(0.4, 1.0e5, 0, 0)
+    ref_s = oracle.assemble(oracle.MODEL_SOLID, 8, conn_h, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre, elem_material=em,
+                            materials=mats, request_jacobian=True, sides=sides)
+
+    def on_the_oracle(ctx, ref, nv):
+        rp0, col0, val0, rhs0 = ref
+        val, rhs = ctx.csr_download()
+        rp, col = ctx.csr_pattern()
+        np.testing.assert_array_equal(rp, rp0)
+        np.testing.assert_array_equal(col, col0)
+        assert rel(val, val0) < TOL and rel(rhs, rhs0) < TOL
+        assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
+
+    def tet4_round(ctx):
+        ctx.mesh_upload(4, conn_t, xyz_t, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u_t)
+        ctx.assemble_pihna(p_t)
+        on_the_oracle(ctx, ref_t, 5)
+
+    with AssemblyContext(0) as ctx:
+        tet4_round(ctx)
+        ctx.mesh_upload(8, conn_h, x, 3)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u_h)
+        ctx.assemble_hcc(p_h)
+        on_the_oracle(ctx, ref_h, 3)
+        ctx.field_upload(FIELD_UNDEFORMED_XYZ, Xu)
+        ctx.field_upload(FIELD_ELEM_FIBRE, fibre)
+        ctx.solid_set_materials(em, mats)
+        ctx.solid_set_sides(*sides)
+        ctx.solid_assemble(sp, True)                   # fused cluster kernel, on the lists the HCC call built
+        on_the_oracle(ctx, ref_s, 3)
+        ctx.solid_assemble(sp, False)                  # residual only: the two-pass form and its gather lists
+        _, rhs = ctx.csr_download()
+        assert rel(rhs, ref_s[3]) < TOL
+        tet4_round(ctx)
 
 
 @pytest.mark.parametrize("pvariant", ["full", "realexp", "taxis_v_only"])
