@@ -336,7 +336,7 @@ typedef struct rdc_solve_info {
   double residual_norm;  /* TRUE ||D^-1 (b - A x)||_2 of the returned x: the quantity the stopping test is about */
   double plain_rhs_norm, plain_residual_norm;   /* the same without D^-1 */
   float  device_ms;      /* device time of the whole solve (HIP events on the context stream) */
-  float  _pad;
+  int32_t matrix_bits;   /* width of the matrix values the ITERATION streamed: 64 (rdc_solve, or rdc_solve_mixed that fell back), 32 (rdc_solve_mixed) */
 } rdc_solve_info;
 
 /* y[n_owned*nvar] = A * x[n_nodes*nvar], both DEVICE pointers; enqueued on the context's stream, does not synchronise.
@@ -351,6 +351,31 @@ int rdc_csr_matvec(rdc_ctx* ctx, const double* d_x, double* d_y);
  * b = 0 gives x = 0 in 0 iterations.  RDC_ERR_UNSUPPORTED when the context has ghost nodes (a solve across partitions
  * needs a halo exchange of the search directions inside every iteration). */
 int rdc_solve(rdc_ctx* ctx, const rdc_solve_params* p, double* d_x, rdc_solve_info* info);
+
+/* ---- mixed precision (additive, RDC_ABI_VERSION stays 3): BiCGStab that iterates on an FP32 copy of D^-1 A.
+ * The copy is built from the current CSR values (4 bytes per value in a layout private to the library, behind the same
+ * 4-byte block index; allocated at the first use on a mesh, freed with the mesh).  Vectors, dot products and every sum
+ * stay FP64.  Everything that decides or reports -- the first residual, each confirmation of a claimed convergence and
+ * each restart, the closing residual, the norms in rdc_solve_info -- is computed from the FP64 values, so the returned
+ * x satisfies the same inequality as that of rdc_solve; only the path to it differs.
+ *
+ * rdc_solve_mixed: the contract of rdc_solve.  d_x: DEVICE pointer, n_owned*nvar doubles: initial guess on entry,
+ * solution on exit; may be the storage of RDC_FIELD_OLD_SOLUTION.  Blocks the host until done.  Never modifies the CSR
+ * values or the rhs.  A solver outcome other than convergence is not an error status: RDC_OK and info->reason tells.
+ * b = 0 gives x = 0 in 0 iterations; RDC_SOLVE_BAD_DIAGONAL leaves x untouched; RDC_ERR_UNSUPPORTED when the context
+ * has ghost nodes.  It rebuilds the FP32 copy from the current values at every call.  If an entry of D^-1 A is not
+ * finite in FP32, the call iterates on the FP64 values instead and returns exactly what rdc_solve returns;
+ * info->matrix_bits says which happened. */
+int rdc_solve_mixed(rdc_ctx* ctx, const rdc_solve_params* p, double* d_x, rdc_solve_info* info);
+/* Builds D^-1 (precond: RDC_PRECOND_*) and the FP32 copy of D^-1 A from the current values.  Enqueued on the context's
+ * stream, then synchronises to read its counters: RDC_ERR_INVALID, with a message, if a diagonal block is not invertible
+ * or an entry is not finite in FP32 (there is no usable copy then).  Works with ghost nodes: the rows are the owned ones. */
+int rdc_csr_scale_f32(rdc_ctx* ctx, int precond);
+/* y[n_owned*nvar] = fl32(D^-1 A) * x[n_nodes*nvar] with the copy the last rdc_csr_scale_f32 or rdc_solve_mixed on this
+ * mesh built; both DEVICE pointers, FP64.  The copy holds the values AS THEY WERE WHEN IT WAS BUILT: a later assemble call
+ * does not update it.  RDC_ERR_INVALID if this mesh has no copy.  Enqueued on the context's stream, does not
+ * synchronise.  d_x and d_y must not overlap. */
+int rdc_csr_matvec_f32(rdc_ctx* ctx, const double* d_x, double* d_y);
 
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */

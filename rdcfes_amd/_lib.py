@@ -59,6 +59,9 @@ SIGNATURES = {
     "rdc_assemble_proteas": (C.c_int, [ctx_p, C.c_void_p]),
     "rdc_csr_matvec": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
     "rdc_solve": (C.c_int, [ctx_p, P(SolveParams), C.c_void_p, P(SolveInfo)]),
+    "rdc_solve_mixed": (C.c_int, [ctx_p, P(SolveParams), C.c_void_p, P(SolveInfo)]),
+    "rdc_csr_scale_f32": (C.c_int, [ctx_p, C.c_int]),
+    "rdc_csr_matvec_f32": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
     "rdc_clamp_nonnegative": (C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_ripf_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),

@@ -287,16 +287,43 @@ class AssemblyContext:
         self.synchronize()
         return yd.cpu().numpy()
 
-    def solve(self, x=None, *, field=None, rel_tol=1e-8, abs_tol=0.0, max_its=10000, precond=PRECOND_BLOCK_JACOBI, rhs_scale=1.0):
+    def csr_scale_f32(self, precond=PRECOND_BLOCK_JACOBI):
+        """rdc_csr_scale_f32: builds D^-1 and the fp32 copy of D^-1 A from the current values (raises RdcError, invalid,
+        if a diagonal block is not invertible or an entry is not finite in fp32)"""
+        self._ck(self._lib.rdc_csr_scale_f32(self._h, int(precond)))
+
+    def csr_matvec_f32_device(self, x_ptr, y_ptr):
+        """y[n_owned*nvar] = fl32(D^-1 A) x[n_node*nvar] on device addresses (FP64 vectors), with the copy the last
+        csr_scale_f32 / solve(mixed=True) built; enqueued on the context's stream, no synchronise"""
+        self._ck(self._lib.rdc_csr_matvec_f32(self._h, C.c_void_p(int(x_ptr)), C.c_void_p(int(y_ptr))))
+
+    def csr_matvec_f32(self, x):
+        """numpy in, numpy out (tests), as csr_matvec"""
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.n_node * self.nvar:
+            raise ValueError("x must have n_node * nvar entries")
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(x).to(dev)
+        yd = torch.empty(self.n_owned * self.nvar, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.csr_matvec_f32_device(xd.data_ptr(), yd.data_ptr())
+        self.synchronize()
+        return yd.cpu().numpy()
+
+    def solve(self, x=None, *, field=None, rel_tol=1e-8, abs_tol=0.0, max_its=10000, precond=PRECOND_BLOCK_JACOBI, rhs_scale=1.0,
+              mixed=False):
         """rdc_solve on the values and rhs of the last assemble call.  x: device address of n_owned*nvar doubles
-        (initial guess in, solution out); or field=FIELD_*: the device storage of that field is used in place."""
+        (initial guess in, solution out); or field=FIELD_*: the device storage of that field is used in place.
+        mixed=True: rdc_solve_mixed, the iteration streams an fp32 copy of D^-1 A (info.matrix_bits tells)."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
             x = self.field_device_ptr(int(field), self.n_node * self.nvar)
         p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
         info = SolveInfo()
-        self._ck(self._lib.rdc_solve(self._h, C.byref(p), C.c_void_p(int(x)), C.byref(info)))
+        fn = self._lib.rdc_solve_mixed if mixed else self._lib.rdc_solve
+        self._ck(fn(self._h, C.byref(p), C.c_void_p(int(x)), C.byref(info)))
         return info
 
     def part1_nodes(self):

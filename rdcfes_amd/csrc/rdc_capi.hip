@@ -33,7 +33,9 @@ struct Buffers {
   struct { DevBuf desc, ntab, eid, pair, pslot; } cl;        // cluster lists of the producer / consumer HEX8 kernels
   struct { DevBuf ke, fe, gptr, gsrc, brow; } two_pass;      // solid two-pass assembly: element matrices + gather lists
   struct { DevBuf elem_material, materials, side_elem, side_id, side_disp; } solid_in;
-  struct { DevBuf bcol, work; } solve;   // linear solve (rdc_solve.hip): block column list (first matvec / solve), work vectors (first solve)
+  // linear solve (rdc_solve.hip): block column list (first matvec / solve), work vectors (first solve); fp32 copy of D^-1 A
+  // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
+  struct { DevBuf bcol, work, voff, val32; } solve;
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -54,6 +56,8 @@ struct MeshState {
   int64_t scl_part1_nodes = 0;
   size_t scl_max_row_doubles = 0;
   bool solid_gather_ready = false, rg5_eid_ready = false, bcol_ready = false;   // buf.two_pass, buf.rg2.eid, buf.solve.bcol hold this mesh's lists
+  bool voff_ready = false;           // buf.solve.voff / val32 are laid out for this mesh
+  bool f32_copy = false;             // buf.solve.val32 holds a usable fp32 copy (of the values at the time it was built)
   int64_t part1_nodes = -1;          // rows [0, part1_nodes) were complete after the LAST part-1 call (-1: none since the upload)
   bool part1_packed = false;         // part 1 of the current step has packed the owned records (consumed by part 2)
   bool solid_part1_pending = false;
@@ -1134,7 +1138,7 @@ int rdc_part1_nodes(const rdc_ctx* c, int64_t* n_nodes) {
 }
 
 // what rdc_solve.hip needs of the context; uploads the block column list the first time (4 bytes per node block)
-static int solve_view(rdc_ctx* c, bool want_work, SolveDev* d) {
+static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
   int rc = set_device(c);
   if (rc) return rc;
   const HostPrep& P = c->ms.prep;
@@ -1154,6 +1158,18 @@ static int solve_view(rdc_ctx* c, bool want_work, SolveDev* d) {
     d->work = (double*)c->buf.solve.work.p;
     d->host_rec = c->solve_rec;
   }
+  if (want_f32) {
+    if (!c->ms.voff_ready) {   // float offset of every owned node's padded rows (rdc_solve.h, f32_row_stride)
+      std::vector<int64_t> voff((size_t)P.n_owned + 1, 0);
+      for (int64_t n = 0; n < P.n_owned; n++) voff[(size_t)n + 1] = voff[(size_t)n] + P.nvar * f32_row_stride(P.nvar, P.bptr[(size_t)n + 1] - P.bptr[(size_t)n]);
+      if ((rc = dev_upload(c, c->buf.solve.voff, voff))) return rc;
+      RDC_HIP(c, hipStreamSynchronize(c->stream));
+      if ((rc = dev_alloc(c, c->buf.solve.val32, (size_t)voff.back() * sizeof(float)))) return rc;
+      c->ms.voff_ready = true;
+    }
+    d->voff = (const int64_t*)c->buf.solve.voff.p;
+    d->val32 = (float*)c->buf.solve.val32.p;
+  }
   return RDC_OK;
 }
 
@@ -1163,13 +1179,43 @@ int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
   if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
   if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
   SolveDev d;
-  int rc = solve_view(c, false, &d);
+  int rc = solve_view(c, false, false, &d);
   if (rc) return rc;
   RDC_HIP(c, solve_matvec(d, d_x, d_y));
   return RDC_OK;
 }
 
-int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) {
+int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (precond != RDC_PRECOND_NONE && precond != RDC_PRECOND_JACOBI && precond != RDC_PRECOND_BLOCK_JACOBI)
+    return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
+  c->ms.f32_copy = false;
+  SolveDev d;
+  int rc = solve_view(c, true, true, &d);
+  if (rc) return rc;
+  int bad = 0, overflow = 0;
+  if (c->ms.prep.n_owned > 0) RDC_HIP(c, solve_scale_f32(d, precond, &bad, &overflow));
+  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks are not invertible: no fp32 copy", bad);
+  if (overflow > 0) return fail(c, RDC_ERR_INVALID, "%d blocks of D^-1 A hold an entry that is not finite in fp32: no fp32 copy", overflow);
+  c->ms.f32_copy = true;
+  return RDC_OK;
+}
+
+int rdc_csr_matvec_f32(rdc_ctx* c, const double* d_x, double* d_y) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
+  if (!c->ms.f32_copy) return fail(c, RDC_ERR_INVALID, "this mesh has no fp32 copy: call rdc_csr_scale_f32 or rdc_solve_mixed first");
+  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
+  SolveDev d;
+  int rc = solve_view(c, false, true, &d);
+  if (rc) return rc;
+  RDC_HIP(c, solve_matvec_f32(d, d_x, d_y));
+  return RDC_OK;
+}
+
+static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info, bool mixed) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (!p || !d_x || !info) return fail(c, RDC_ERR_INVALID, "null argument");
@@ -1185,14 +1231,21 @@ int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info
                 (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
   if (c->ms.prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
     *info = rdc_solve_info();
+    info->matrix_bits = 64;
     return RDC_OK;
   }
   SolveDev d;
-  int rc = solve_view(c, true, &d);
+  if (mixed) c->ms.f32_copy = false;   // rebuilt from the current values by this call
+  int rc = solve_view(c, true, mixed, &d);
   if (rc) return rc;
-  RDC_HIP(c, solve_run(d, *p, d_x, info));
+  RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
+  if (mixed) c->ms.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   return RDC_OK;
 }
+
+int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, false); }
+
+int rdc_solve_mixed(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, true); }
 
 int rdc_clamp_nonnegative(rdc_ctx* c, int field) {
   if (!c) return RDC_ERR_INVALID;

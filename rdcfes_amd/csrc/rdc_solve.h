@@ -132,6 +132,42 @@ RDC_SOLVE_HD bool precond_block(double (&d)[NV][NV], int precond) {
   return ok;
 }
 
+// false for NaN and +-inf, as solve_finite
+RDC_SOLVE_HD bool solve_finite_f32(float x) {
+  uint32_t u;
+  __builtin_memcpy(&u, &x, sizeof(u));
+  return (u & 0x7f800000u) != 0x7f800000u;
+}
+
+// out = fl32(dinv * a): one block of the fp32 copy of D^-1 A that the mixed-precision iteration streams.  Every product
+// sum is accumulated in fp64 in ascending index order (separate multiply and add) and rounded to fp32 once.  Returns
+// false if an entry of `out` is not finite: the product overflows fp32 (|.| > 3.4e38) or an input is NaN / inf; the
+// caller must not iterate on such a copy.  An entry below the fp32 normal range becomes a subnormal or 0: harmless.
+template <int NV>
+RDC_SOLVE_HD bool scaled_block_f32(const double (&dinv)[NV][NV], const double (&a)[NV][NV], float (&out)[NV][NV]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)   // the kernel rounds each product, as the CPU build of the tests does
+#endif
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NV; i++)
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < NV; q++) s = s + dinv[i][q] * a[q][j];
+      out[i][j] = (float)s;
+      if (!solve_finite_f32(out[i][j])) ok = false;
+    }
+  return ok;
+}
+
+// Layout of the fp32 copy (private to rdc_solve.hip): the values of node n start at float offset voff[n] and lie as
+// [var a][block k][var b] like the fp64 values, but every one of the nvar rows is padded with zeros to a multiple of
+// 4 floats, so that each row starts 16-byte aligned whatever nvar and the row length are (nvar = 5 puts the fp64 rows
+// at odd offsets).  voff[n + 1] - voff[n] = nvar * f32_row_stride(nvar, blocks of n).
+RDC_SOLVE_HD int64_t f32_row_stride(int nvar, int64_t blocks) { return ((int64_t)nvar * blocks + 3) & ~(int64_t)3; }
+
 }  // namespace rdc
 
 #if defined(__HIPCC__)
@@ -144,6 +180,8 @@ struct SolveScal {
   double rn2, rn2_plain, bn2, bn2_plain;   // ||r||^2 of the recurrence (or of the true residual after k_residual), plain form, rhs norms
   int32_t flag;                            // bit 0: alpha / omega / a norm is zero or not finite; bit 1: rho == 0
   int32_t bad_blocks;
+  int32_t f32_overflow;                    // blocks of the fp32 copy that hold an entry which is not finite in fp32 (k_scale_f32)
+  int32_t _pad;
 };
 
 // what rdc_csr_matvec / rdc_solve need of a context (rdc_capi.hip fills it)
@@ -155,13 +193,19 @@ struct SolveDev {
   const double* val = nullptr;
   const double* rhs = nullptr;
   double* work = nullptr;          // solve_work_bytes() bytes
+  const int64_t* voff = nullptr;   // fp32 copy of D^-1 A: float offset of every owned node's values (n_owned + 1 entries) ...
+  float* val32 = nullptr;          // ... and the values, voff[n_owned] floats (layout: f32_row_stride)
   SolveScal* host_rec = nullptr;   // pinned
   hipStream_t stream = nullptr;
 };
 
 size_t solve_work_bytes(int nvar, int64_t n_owned);
 hipError_t solve_matvec(const SolveDev& d, const double* x, double* y);
-hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info);
+// mixed: iterate on the fp32 copy (built here from the current values); info->matrix_bits tells what the iteration streamed
+hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed);
+// D^-1 and the fp32 copy from the current values; synchronises to return the two counters
+hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int* overflow);
+hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y);
 
 }  // namespace rdc
 #endif

@@ -8,6 +8,14 @@
 // busy); a row of any length just takes more steps.  A row sum is the lane's own entries in ascending order followed
 // by a fixed xor butterfly over the 16 lanes: no atomics, no dependence on the launch shape, bitwise repeatable.
 //
+// Mixed precision (rdc_solve_mixed): k_scale_f32 stores fl32(D^-1 A) once per solve in a layout of its own (rdc_solve.h,
+// f32_row_stride: rows padded to 16 bytes), and the two operator applications of an iteration stream that copy with
+// k_spmv_f32: 8 lanes per node, 8 nodes per wave, 32 per workgroup; a lane reads 16 bytes (4 floats) per row and step, so
+// the 8 lanes read 128 contiguous bytes per row like the 16 lanes of k_spmv do, and it gathers its 4 x entries once for
+// all nvar rows.  x, y and every sum are FP64; the sum order is the lane's own entries ascending, then a fixed xor
+// butterfly over the 8 lanes.  No D^-1 epilogue: the copy is already scaled.  Everything that decides or reports (first
+// residual, every confirmation / restart, closing residual, norms) stays on k_spmv + k_residual over the FP64 values.
+//
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
 // device memory.  No floating-point atomics anywhere.
@@ -20,6 +28,8 @@ namespace rdc {
 namespace {
 
 constexpr int SPMV_NODES = 16;        // nodes per workgroup of k_spmv (256 threads)
+constexpr int F32_LANES = 8;          // lanes per node of k_spmv_f32 and k_scale_f32
+constexpr int F32_NODES = 32;         // nodes per workgroup of those two (256 threads)
 constexpr int VEC_PER_BLOCK = 1024;   // vector entries per workgroup of the update kernels (256 threads x 4)
 constexpr int MAX_BREAKDOWNS = 10;    // restarts after a break-down before RDC_SOLVE_BREAKDOWN
 
@@ -112,6 +122,123 @@ __global__ __launch_bounds__(256) void k_precond_setup(const int64_t* __restrict
   for (int a = 0; a < NV; a++)
 #pragma unroll
     for (int b = 0; b < NV; b++) dinv[(node * NV + a) * NV + b] = d[a][b];
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// fp32 copy of D^-1 A (layout: rdc_solve.h, f32_row_stride): 8 lanes per node, a lane takes the blocks k = lane, lane + 8, ...
+// Reads every FP64 value once (non-temporal), multiplies the block by D^-1 of the node from the left, stores the floats
+// and the zero padding of every row; counts the blocks with an entry that is not finite in fp32.  Runs after k_precond_setup.
+template <int NV>
+__global__ __launch_bounds__(256) void k_scale_f32(const int64_t* __restrict__ bptr, const int64_t* __restrict__ voff,
+                                                   const double* __restrict__ val, const double* __restrict__ dinv,
+                                                   int64_t n_owned, float* __restrict__ val32, SolveScal* __restrict__ scal) {
+  const int lane = threadIdx.x & (F32_LANES - 1);
+  const int64_t node = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  if (node >= n_owned) return;
+  const int64_t b0 = bptr[node];
+  const int len = (int)(bptr[node + 1] - b0);
+  const int L = len * NV, Lp = (int)f32_row_stride(NV, len);
+  const double* __restrict__ vrow = val + (int64_t)NV * NV * b0;
+  float* __restrict__ orow = val32 + voff[node];
+  double di[NV][NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int b = 0; b < NV; b++) di[a][b] = dinv[(node * NV + a) * NV + b];
+  int bad = 0;
+  for (int k = lane; k < len; k += F32_LANES) {
+    double blk[NV][NV];
+    float out[NV][NV];
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) blk[a][b] = __builtin_nontemporal_load(vrow + ((int64_t)a * len + k) * NV + b);
+    if (!scaled_block_f32<NV>(di, blk, out)) bad++;
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) orow[(int64_t)a * Lp + k * NV + b] = out[a][b];
+  }
+  if (lane < Lp - L)   // at most 3 padding floats per row
+#pragma unroll
+    for (int a = 0; a < NV; a++) orow[(int64_t)a * Lp + L + lane] = 0.0f;
+  if (bad) atomicAdd(&scal->f32_overflow, bad);
+}
+
+// y = A32 x on the fp32 copy (EPI 0), with the partials of (y, w) and (y, y) (EPI 1); x, y and the sums are FP64
+template <int NV, int EPI>
+__global__ __launch_bounds__(256) void k_spmv_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                  const int64_t* __restrict__ voff, const float* __restrict__ val32,
+                                                  const double* __restrict__ x, double* __restrict__ y, int64_t n_owned,
+                                                  const double* __restrict__ w, double* __restrict__ partials) {
+  const int lane = threadIdx.x & (F32_LANES - 1);
+  const int64_t node = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  const bool live = node < n_owned;
+  double acc[NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  const int64_t b0 = live ? bptr[node] : 0;
+  const int len = live ? (int)(bptr[node + 1] - b0) : 0;
+  if (len > 0) {
+    const int L = len * NV, Lp = (int)f32_row_stride(NV, len);   // entries of one row of the node, and its padded stride
+    const float* __restrict__ vrow = val32 + voff[node];
+    // x indices of the 4 entries at j .. j + 3.  Every load of the loop is unconditional -- a position past the row's end
+    // (padding, or the look-ahead behind the last step) re-reads the row's last entry and is zeroed or dropped afterwards:
+    // a load behind a per-element condition would be branched around and waited for one by one.
+    auto columns = [&](int j, int32_t (&cn)[4], int (&cb)[4]) {   // column node and unknown of the entries j .. j + 3
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const int jj = min(j + e, L - 1), k = jj / NV;
+        cb[e] = jj - k * NV;
+        cn[e] = bcol[b0 + k];
+      }
+    };
+    int32_t cn[4], nn[4];
+    int cb[4], nb[4];
+    columns(4 * lane, cn, cb);
+    for (int j = 4 * lane; j < Lp; j += 4 * F32_LANES) {
+      // the next step's column nodes are requested together with this step's values and x entries and used a step later:
+      // the bcol -> x chain then costs one memory latency per step, not two
+      columns(j + 4 * F32_LANES, nn, nb);
+      f32x4 v[NV];
+#pragma unroll
+      for (int a = 0; a < NV; a++) v[a] = __builtin_nontemporal_load((const f32x4*)(vrow + (int64_t)a * Lp + j));
+      double xv[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) xv[e] = x[(int64_t)cn[e] * NV + cb[e]];
+      __builtin_amdgcn_sched_barrier(0);   // keep the three groups of loads ahead of the arithmetic
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        xv[e] = j + e < L ? xv[e] : 0.0;
+        cn[e] = nn[e];
+        cb[e] = nb[e];
+      }
+#pragma unroll
+      for (int a = 0; a < NV; a++) {
+        acc[a] = fma((double)v[a].x, xv[0], acc[a]);
+        acc[a] = fma((double)v[a].y, xv[1], acc[a]);
+        acc[a] = fma((double)v[a].z, xv[2], acc[a]);
+        acc[a] = fma((double)v[a].w, xv[3], acc[a]);
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = F32_LANES / 2; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, F32_LANES);
+  double out = acc[0];
+#pragma unroll
+  for (int a = 1; a < NV; a++) out = lane == a ? acc[a] : out;
+  if (live && lane < NV) y[node * NV + lane] = out;
+  if (EPI == 1) {
+    double c[2] = {0.0, 0.0};
+    if (live && lane < NV) {
+      c[0] = out * w[node * NV + lane];
+      c[1] = out * out;
+    }
+    block_partials<2>(c, partials);
+  }
 }
 
 // r = r_hat = D^-1 (scale * rhs - ax), p = v = 0; partials of ||r||^2, ||scale*rhs - ax||^2, ||D^-1 b||^2, ||b||^2
@@ -245,7 +372,7 @@ __global__ __launch_bounds__(256) void k_update_xr(double* __restrict__ x, doubl
 struct Work {
   double *r, *rh, *p, *v, *s, *t, *dinv, *partials;
   SolveScal* scal;
-  int64_t n, spmv_blocks, vec_blocks, node_blocks;
+  int64_t n, spmv_blocks, f32_blocks, vec_blocks, node_blocks;
 };
 
 int64_t partial_doubles(int64_t n_owned, int nvar) {
@@ -264,6 +391,7 @@ Work carve(const SolveDev& d) {
   w.partials = q; q += partial_doubles(d.n_owned, d.nvar);
   w.scal = (SolveScal*)q;
   w.spmv_blocks = (d.n_owned + SPMV_NODES - 1) / SPMV_NODES;
+  w.f32_blocks = (d.n_owned + F32_NODES - 1) / F32_NODES;
   w.vec_blocks = (w.n + VEC_PER_BLOCK - 1) / VEC_PER_BLOCK;
   w.node_blocks = (d.n_owned + 255) / 256;
   return w;
@@ -279,6 +407,19 @@ hipError_t spmv(const SolveDev& d, const Work* w, const double* x, double* y, co
   else
     hipLaunchKernelGGL((k_spmv<NV, 0>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
                        (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
+  return hipGetLastError();
+}
+
+template <int NV>
+hipError_t spmv_f32(const SolveDev& d, const Work* w, const double* x, double* y, const double* dot_with) {
+  const int64_t blocks = (d.n_owned + F32_NODES - 1) / F32_NODES;
+  if (blocks == 0) return hipSuccess;
+  if (dot_with)
+    hipLaunchKernelGGL((k_spmv_f32<NV, 1>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.voff,
+                       (const float*)d.val32, x, y, d.n_owned, dot_with, w->partials);
+  else
+    hipLaunchKernelGGL((k_spmv_f32<NV, 0>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.voff,
+                       (const float*)d.val32, x, y, d.n_owned, (const double*)nullptr, (double*)nullptr);
   return hipGetLastError();
 }
 
@@ -310,15 +451,29 @@ hipError_t residual(const SolveDev& d, const Work& w, const double* x, double sc
   return read_record(d, w);
 }
 
+// D^-1 and, if wanted, the fp32 copy of D^-1 A from the current values (scal must have been cleared)
 template <int NV>
-hipError_t iteration(const SolveDev& d, const Work& w, double* x) {
+hipError_t setup(const SolveDev& d, const Work& w, int precond, bool f32) {
+  if (!w.node_blocks) return hipSuccess;
+  hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, d.n_owned,
+                     precond, w.dinv, w.scal);
+  if (f32)
+    hipLaunchKernelGGL((k_scale_f32<NV>), dim3((unsigned)w.f32_blocks), dim3(256), 0, d.stream, d.bptr, d.voff, d.val,
+                       (const double*)w.dinv, d.n_owned, d.val32, w.scal);
+  return hipGetLastError();
+}
+
+// one BiCGStab iteration; f32: the two operator applications stream the fp32 copy (no D^-1 epilogue, it is in the copy)
+template <int NV>
+hipError_t iteration(const SolveDev& d, const Work& w, double* x, bool f32) {
   const dim3 vg((unsigned)w.vec_blocks), vb(256);
   hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
-  SOLVE_HIP(spmv<NV>(d, &w, w.p, w.v, w.rh));                       // v = D^-1 A p, (r_hat, v)
-  SOLVE_HIP(finalize(d, w, w.spmv_blocks, 2, STAGE_ALPHA));
+  const int64_t op_blocks = f32 ? w.f32_blocks : w.spmv_blocks;
+  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, w.p, w.v, w.rh) : spmv<NV>(d, &w, w.p, w.v, w.rh));   // v = D^-1 A p, (r_hat, v)
+  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_ALPHA));
   hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
-  SOLVE_HIP(spmv<NV>(d, &w, w.s, w.t, w.s));                        // t = D^-1 A s, (t, s), (t, t)
-  SOLVE_HIP(finalize(d, w, w.spmv_blocks, 2, STAGE_OMEGA));
+  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, w.s, w.t, w.s) : spmv<NV>(d, &w, w.s, w.t, w.s));     // t = D^-1 A s, (t, s), (t, t)
+  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_OMEGA));
   hipLaunchKernelGGL(k_update_xr, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
                      (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials);
   SOLVE_HIP(hipGetLastError());
@@ -327,7 +482,7 @@ hipError_t iteration(const SolveDev& d, const Work& w, double* x) {
 }
 
 template <int NV>
-hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info) {
+hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   const Work w = carve(d);
   const SolveScal& rec = *d.host_rec;
   auto report = [&](int reason) {
@@ -336,12 +491,11 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
   };
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
-  if (w.node_blocks)
-    hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, d.n_owned,
-                       (int)p.precond, w.dinv, w.scal);
-  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(setup<NV>(d, w, (int)p.precond, mixed));
   SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
   info->bad_blocks = rec.bad_blocks;
+  const bool f32 = mixed && rec.f32_overflow == 0;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
+  info->matrix_bits = f32 ? 32 : 64;
   if (rec.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
   if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
   if (rec.bn2 == 0.0) {   // b = 0: x = 0
@@ -360,7 +514,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
       report(rec.flag ? RDC_SOLVE_NOT_FINITE : (std::sqrt(rec.rn2) <= tol ? RDC_SOLVE_CONVERGED : RDC_SOLVE_MAX_ITS));
       return hipSuccess;
     }
-    SOLVE_HIP(iteration<NV>(d, w, x));
+    SOLVE_HIP(iteration<NV>(d, w, x, f32));
     info->iterations++;
     const bool claims = !(rec.flag & 1) && std::sqrt(rec.rn2) <= tol;
     if (!claims && !rec.flag) continue;
@@ -390,13 +544,30 @@ hipError_t solve_matvec(const SolveDev& d, const double* x, double* y) {
   return hipErrorInvalidValue;
 }
 
-hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info) {
+hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y) {
+  if (d.nvar == 3) return spmv_f32<3>(d, nullptr, x, y, nullptr);
+  if (d.nvar == 5) return spmv_f32<5>(d, nullptr, x, y, nullptr);
+  return hipErrorInvalidValue;
+}
+
+hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int* overflow) {
+  const Work w = carve(d);
+  SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
+  SOLVE_HIP(d.nvar == 3 ? setup<3>(d, w, precond, true) : d.nvar == 5 ? setup<5>(d, w, precond, true) : hipErrorInvalidValue);
+  SOLVE_HIP(read_record(d, w));
+  *bad_blocks = d.host_rec->bad_blocks;
+  *overflow = d.host_rec->f32_overflow;
+  return hipSuccess;
+}
+
+hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   *info = rdc_solve_info();
+  info->matrix_bits = 64;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   SOLVE_HIP(hipEventCreate(&e0));
   hipError_t e = hipEventCreate(&e1);
   if (e == hipSuccess) e = hipEventRecord(e0, d.stream);
-  if (e == hipSuccess) e = d.nvar == 3 ? run<3>(d, p, x, info) : d.nvar == 5 ? run<5>(d, p, x, info) : hipErrorInvalidValue;
+  if (e == hipSuccess) e = d.nvar == 3 ? run<3>(d, p, x, info, mixed) : d.nvar == 5 ? run<5>(d, p, x, info, mixed) : hipErrorInvalidValue;
   if (e == hipSuccess) e = hipEventRecord(e1, d.stream);
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   if (e == hipSuccess) e = hipEventElapsedTime(&info->device_ms, e0, e1);

@@ -91,16 +91,17 @@ class SolveParams(C.Structure):
 
 
 class SolveInfo(C.Structure):
-    """rdc_solve_info: outcome of rdc_solve; residual_norm is the TRUE ||D^-1 (b - A x)|| of the returned x."""
+    """rdc_solve_info: outcome of rdc_solve / rdc_solve_mixed; residual_norm is the TRUE ||D^-1 (b - A x)|| of the returned
+    x; matrix_bits is the width of the matrix values the iteration streamed (64, or 32 for a mixed solve)."""
     _fields_ = [("reason", C.c_int32), ("iterations", C.c_int32), ("restarts", C.c_int32), ("bad_blocks", C.c_int32),
                 ("rhs_norm", _D), ("residual_norm", _D), ("plain_rhs_norm", _D), ("plain_residual_norm", _D),
-                ("device_ms", C.c_float), ("_pad", C.c_float)]
+                ("device_ms", C.c_float), ("matrix_bits", C.c_int32)]
 
     def __repr__(self):
         return (f"SolveInfo(reason={self.reason}, iterations={self.iterations}, restarts={self.restarts}, "
                 f"bad_blocks={self.bad_blocks}, rhs_norm={self.rhs_norm:.6e}, residual_norm={self.residual_norm:.6e}, "
                 f"plain_rhs_norm={self.plain_rhs_norm:.6e}, plain_residual_norm={self.plain_residual_norm:.6e}, "
-                f"device_ms={self.device_ms:.3f})")
+                f"device_ms={self.device_ms:.3f}, matrix_bits={self.matrix_bits})")
 
 
 # reference parameter key -> struct field

@@ -1,5 +1,8 @@
-"""rdc_csr_matvec (block-pattern SpMV on the context's own values) against rocsparse_dcsrmv on the same assembled
-PIHNA matrix of a Kuhn mesh K(n), alternating, median of --reps launches each after warm-up; both results are compared.
+"""rdc_csr_matvec (block-pattern SpMV on the context's own values), rdc_csr_matvec_f32 (the same pattern over the fp32
+copy of D^-1 A that rdc_solve_mixed iterates on) and rocsparse_dcsrmv on the same assembled PIHNA matrix of a Kuhn mesh
+K(n), alternating, median of --reps launches each after warm-up.  The two fp64 results are compared with each other; of
+the fp32-value result the tool checks only that two launches agree bitwise (its accuracy is held by
+tests/test_gpu_solve_mixed.py).
 
     python tools/spmv_ab.py --n 119 [--reps 25]
 
@@ -7,7 +10,10 @@ rocSPARSE is loaded with ctypes by this tool only (the product does not link it)
 built on the host and uploaded (4 B per non-zero more on the device: when that does not fit, the tool steps down to the
 largest K(n) that does -- first to what free memory suggests, then one by one -- and says which).  Also times one BiCGStab
 iteration: the device time of a solve with max_its = 2 ITS minus that of one with ITS, over ITS.
-Algorithmic bytes of the block-pattern kernel: 8 nnz + 4 blocks + 8 (rows_in + rows_out) + 8 n_owned (bptr)."""
+The same difference is taken for a mixed solve, and the set-up cost of the fp32 copy is the difference of the two kinds'
+"set-up and closing residual" figures.
+Algorithmic bytes of the block-pattern kernel: 8 nnz + 4 blocks + 8 (rows_in + rows_out) + 8 n_owned (bptr); of the
+fp32-value kernel: 4 nnz + 4 blocks + 8 (rows_in + rows_out) + 16 n_owned (bptr and the offsets of the padded rows)."""
 import argparse
 import ctypes as C
 import json
@@ -65,6 +71,7 @@ def measure(n, reps, its):
         x = torch.from_numpy(np.random.default_rng(1).uniform(-1, 1, n_rows)).to(dev)
         y_a = torch.zeros(n_rows, dtype=torch.float64, device=dev)
         y_b = torch.zeros(n_rows, dtype=torch.float64, device=dev)
+        y_c = torch.zeros(n_rows, dtype=torch.float64, device=dev)
         vptr, _ = ctx.csr_values_device_ptr()
         rs = _rocsparse()
         handle, descr = C.c_void_p(), C.c_void_p()
@@ -85,20 +92,28 @@ def measure(n, reps, its):
         def ours():
             ctx.csr_matvec_device(x.data_ptr(), y_a.data_ptr())
 
+        ctx.csr_scale_f32(2)
+
+        def ours32():
+            ctx.csr_matvec_f32_device(x.data_ptr(), y_c.data_ptr())
+
         for _ in range(3):
             ours()
+            ours32()
             roc()
         torch.cuda.synchronize()
-        t_a, t_b = [], []
-        for _ in range(reps):                      # alternate the two
+        t_a, t_b, t_c = [], [], []
+        for _ in range(reps):                      # alternate the three
             t_a += _events(torch, ours, 1)
+            t_c += _events(torch, ours32, 1)
             t_b += _events(torch, roc, 1)
         scale = torch.abs(y_b).max().item()
         diff = torch.abs(y_a - y_b).max().item()
         blocks = nnz // 25
         bytes_block = 8 * nnz + 4 * blocks + 8 * (2 * n_rows) + 8 * (n_rows // 5)
         bytes_csr = 12 * nnz + 8 * (2 * n_rows) + 4 * n_rows
-        ms_a, ms_b = float(np.median(t_a)), float(np.median(t_b))
+        bytes_f32 = 4 * nnz + 4 * blocks + 8 * (2 * n_rows) + 16 * (n_rows // 5)
+        ms_a, ms_b, ms_c = float(np.median(t_a)), float(np.median(t_b)), float(np.median(t_c))
         xs = torch.zeros(n_rows, dtype=torch.float64, device=dev)
         ctx.solve(xs.data_ptr(), rel_tol=0.0, max_its=3)          # warm-up, allocates the work vectors
         # set-up (preconditioner, first residual) and the closing residual are the same in both runs: the difference is 'its' iterations
@@ -107,6 +122,20 @@ def measure(n, reps, its):
         xs.zero_()
         info = ctx.solve(xs.data_ptr(), rel_tol=0.0, max_its=2 * its)
         ms_it = (info.device_ms - info1.device_ms) / max(info.iterations - info1.iterations, 1)
+        ctx.solve(xs.data_ptr(), rel_tol=0.0, max_its=3, mixed=True)
+        xs.zero_()
+        m1 = ctx.solve(xs.data_ptr(), rel_tol=0.0, max_its=its, mixed=True)
+        xs.zero_()
+        m2 = ctx.solve(xs.data_ptr(), rel_tol=0.0, max_its=2 * its, mixed=True)
+        assert m1.matrix_bits == 32 and m2.matrix_bits == 32
+        ms_it32 = (m2.device_ms - m1.device_ms) / max(m2.iterations - m1.iterations, 1)
+        setup64 = info1.device_ms - info1.iterations * ms_it
+        setup32 = m1.device_ms - m1.iterations * ms_it32
+        # fixed summation order: a second launch on the same x (and the same copy, rebuilt by the solves above) agrees bitwise
+        y_c2 = torch.zeros_like(y_c)
+        ctx.csr_matvec_f32_device(x.data_ptr(), y_c2.data_ptr())
+        torch.cuda.synchronize()
+        f32_repeatable = bool(torch.equal(y_c, y_c2))
         ctx.set_stream(0)
         rs.rocsparse_destroy_mat_descr(descr)
         rs.rocsparse_destroy_handle(handle)
@@ -114,10 +143,15 @@ def measure(n, reps, its):
                     block_spmv_ms=ms_a, block_spmv_min_ms=float(min(t_a)), block_bytes=bytes_block,
                     block_TBps=bytes_block / ms_a * 1e-9, block_fraction_of_8TBps=bytes_block / (ms_a * 1e-3) / HBM_PEAK,
                     rocsparse_ms=ms_b, rocsparse_min_ms=float(min(t_b)), rocsparse_bytes=bytes_csr, rocsparse_TBps=bytes_csr / ms_b * 1e-9,
+                    f32_spmv_ms=ms_c, f32_spmv_min_ms=float(min(t_c)), f32_bytes=bytes_f32, f32_TBps=bytes_f32 / ms_c * 1e-9,
+                    f32_fraction_of_8TBps=bytes_f32 / (ms_c * 1e-3) / HBM_PEAK, f32_over_block_spmv=ms_c / ms_a,
+                    f32_bitwise_repeatable=f32_repeatable,
                     max_abs_difference=diff, max_abs_y=scale,
                     bicgstab_iterations_timed=info.iterations - info1.iterations, bicgstab_ms_per_iteration=ms_it,
                     bicgstab_ms_setup_and_closing_residual=info1.device_ms - info1.iterations * ms_it,
-                    iteration_over_two_spmv=ms_it / (2.0 * ms_a))
+                    iteration_over_two_spmv=ms_it / (2.0 * ms_a),
+                    mixed_ms_per_iteration=ms_it32, mixed_ms_setup_and_closing_residual=setup32,
+                    f32_copy_setup_ms=setup32 - setup64, mixed_iteration_over_two_f32_spmv=ms_it32 / (2.0 * ms_c))
 
 
 def device_bytes(n):
@@ -125,7 +159,7 @@ def device_bytes(n):
     again as the indices), solver work vectors, the test vectors"""
     nodes = (n + 1) ** 3
     nnz = 25 * 15 * nodes
-    return 12 * nnz + 4 * nnz + 8 * 5 * nodes * (6 + 5 + 4) + 4 * nnz // 25
+    return 12 * nnz + 4 * nnz + 4 * nnz + 8 * 5 * nodes * (6 + 5 + 4) + 4 * nnz // 25   # + the fp32 copy
 
 
 def main():
@@ -152,6 +186,7 @@ def main():
             n = nxt
     rec["requested_mesh"] = f"K({a.n})"
     assert rec["max_abs_difference"] <= 1e-9 * rec["max_abs_y"], rec
+    assert rec["f32_bitwise_repeatable"], rec
     print(json.dumps(rec))
 
 

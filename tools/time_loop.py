@@ -1,11 +1,13 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2] [--dump DIR]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2] [--mixed | --ab] [--dump DIR]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
-counted on the device after the clamp.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz)."""
+counted on the device after the clamp.  --mixed solves with rdc_solve_mixed (the iteration streams an fp32 copy of D^-1 A;
+matrix_bits in every record says what ran); --ab runs the loop four times from the same initial state on one upload, in the
+order fp64, mixed, mixed, fp64, so that the two kinds are timed in one process on one device.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz)."""
 import argparse
 import json
 import sys
@@ -36,7 +38,7 @@ def background_share(u, conn_dev):
     return float(bg.double().mean()), float(bg[conn_dev].all(dim=1).double().mean())
 
 
-def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None):
+def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False):
     """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
     on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there)."""
     import torch
@@ -51,14 +53,14 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         asm_ms = ctx.timing_last_ms()
         if on_step:
             on_step(k, "assembled", ctx)
-        info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its)
+        info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
         if on_step:
             on_step(k, "solved", ctx)
         ctx.clamp_nonnegative(0)
         ctx.synchronize()
         nodes, elems = background_share(u, conn_dev)
         out.append(dict(step=k + 1, assembly_ms=asm_ms, solve_ms=info.device_ms, iterations=info.iterations, restarts=info.restarts,
-                        reason=info.reason, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
+                        reason=info.reason, matrix_bits=info.matrix_bits, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
                         background_nodes=nodes, background_elems=elems))
     return out
 
@@ -70,6 +72,8 @@ def main():
     ap.add_argument("--rel-tol", type=float, default=1e-8)
     ap.add_argument("--precond", type=int, default=2)
     ap.add_argument("--max-its", type=int, default=20000)
+    ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--ab", action="store_true")
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     import torch
@@ -79,10 +83,12 @@ def main():
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
-        ctx.field_upload(0, synth.pihna_fields(xyz))
-        print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=a.precond)))
-        for rec in run(ctx, conn, p, a.steps, a.rel_tol, a.precond, a.max_its):
-            print(json.dumps(rec), flush=True)
+        u0 = synth.pihna_fields(xyz)
+        for mixed in ((False, True, True, False) if a.ab else (a.mixed,)):
+            ctx.field_upload(0, u0)
+            print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=a.precond, mixed=mixed)))
+            for rec in run(ctx, conn, p, a.steps, a.rel_tol, a.precond, a.max_its, mixed=mixed):
+                print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
             d.mkdir(parents=True, exist_ok=True)
