@@ -110,7 +110,7 @@ struct HostPrepEv {
   };
   struct Node {            // 16 bytes per owned node of a workgroup
     uint32_t bptr;         // first node block of the node's rows (CSR value offset = nvar^2 * bptr)
-    uint16_t len, blk0;    // node blocks in the row (<= 16); index a of the node in the cluster: block (a, slot s) of the moment slice = s * 16 + a
+    uint16_t len, blk0;    // node blocks in the row (<= 16); index a of the node in the cluster: block (a, slot s) of the moment slice = evl::block(a, s)
     uint32_t obase;        // offset of the node's CSR segment inside the LDS image (same 16-byte phase as in memory)
     uint32_t node;         // node id
   };
@@ -119,10 +119,10 @@ struct HostPrepEv {
   size_t max_out_doubles = 0;
   std::vector<Desc> desc;
   std::vector<uint32_t> nlist;       // [n_wg][nls] node ids, the owned ones first, padded with the first
-  std::vector<uint32_t> vloc;        // [n_wg][256] four 8-bit list positions of the visit's vertices, owned first; ~0u = none
-  std::vector<uint32_t> vslot;       // [n_wg][256][2]: 4-bit column slot of vertex j in the row of vertex i at bits 16 (i & 1) + 4 j of word i / 2
+  std::vector<uint32_t> vloc;        // [n_wg][256] one word per visit: evl::vloc_pack / vloc_pos / vloc_rows, evl::IDLE = none
+  std::vector<uint32_t> vslot;       // [n_wg][256][2] the column slots of the visit's rows: evl::vslot_add / vslot_get
   std::vector<Node> ntab;            // [n_wg][16]
-  std::vector<uint8_t> bpart;        // [n_wg][256]: mirror block (column node -> row node) of block t = slot * 16 + node when the column node is another node of the cluster, else t itself
+  std::vector<uint8_t> bpart;        // [n_wg][256]: mirror block (column node -> row node) of block t = evl::block(node, slot) when the column node is another node of the cluster, else t itself
   // statistics: element visits and (row, visit) pairs over all workgroups
   int64_t n_visits = 0, n_rows = 0;
   int64_t n_conflicts = 0;           // rows whose node already sits at the same vertex position of their 16-lane group
@@ -137,6 +137,33 @@ struct HostPrepEv {
 // needs P.bptr / P.bcol / P.eslot of prep_build; lds_budget = LDS bytes a workgroup may use (3 workgroups per CU: 53 KB)
 // n_interior >= 0: owned nodes [0, n_interior) are "interior" (two-part assembly): clusters do not mix the two kinds
 std::string prep_build_ev(const HostPrep& P, const uint32_t* conn, size_t lds_budget_bytes, HostPrepEv& out, int64_t n_interior = -1);
+
+// The format of those lists, as the one piece of code that rdc_prep_ev.cpp (packers), the kernels k_tet4_ev / k_tet4_evq /
+// k_tet4_evc and the CPU replays of tests/host_shim.cpp (unpackers) all compile.  No HIP construct beyond the qualifiers.
+#if defined(__HIPCC__)
+#define RDC_EVL __host__ __device__ inline __attribute__((always_inline))   // the .cpp units are compiled as HIP without its runtime header
+#else
+#define RDC_EVL inline
+#endif
+namespace evl {
+// vloc word: the list positions (8 bits each, <= 254) of the visit's four vertices, the ones the cluster owns first
+constexpr uint32_t IDLE = 0xFFFFFFFFu;   // a lane without a visit
+RDC_EVL uint32_t vloc_pack(const uint32_t (&pos)[4]) { return pos[0] | pos[1] << 8 | pos[2] << 16 | pos[3] << 24; }
+RDC_EVL int vloc_pos(uint32_t pl, int j) { return (int)((pl >> (8 * j)) & 0xFF); }
+// rows the visit emits: the owned nodes come first in the node list (list position == cluster index), so r = positions below nown
+RDC_EVL int vloc_rows(const int (&li)[4], int nown) { return (li[0] < nown) + (li[1] < nown) + (li[2] < nown) + (li[3] < nown); }
+// vslot pair: the 4-bit column slot (a row has at most 16 node blocks) of vertex j in the row of vertex i, 16 bits per row, two rows per word
+RDC_EVL void vslot_add(uint32_t (&sl)[2], int i, int j, uint32_t slot) { sl[i >> 1] |= (slot & 15u) << (16 * (i & 1) + 4 * j); }
+RDC_EVL int vslot_get(uint32_t w0, uint32_t w1, int i, int j) { return (int)(((i < 2 ? w0 : w1) >> (16 * (i & 1) + 4 * j)) & 0xF); }
+// block (owned node a, slot s) of a cluster's LDS slice, and back: entry / moment m of the block lives at [m * NBP + block]
+RDC_EVL int block(int a, int s) { return s * HostPrepEv::MAXN + a; }
+RDC_EVL int block_node(int t) { return t & (HostPrepEv::MAXN - 1); }
+RDC_EVL int block_slot(int t) { return t >> 4; }   // t / MAXN
+// CSR image: the segment of a node (len blocks, nv unknowns) starts at Node::obase and is laid out as in memory, rows of nv * len
+// values; entry (a, b) of the block in slot s.  obase has the 16-byte phase of the segment in memory: seg_phase == (nv^2 * bptr) & 1
+RDC_EVL int seg_entry(int nv, int len, int a, int s, int b) { return a * (nv * len) + nv * s + b; }
+RDC_EVL int seg_phase(uint32_t obase) { return (int)(obase & 1u); }
+}  // namespace evl
 
 // ---- node clusters with producer / consumer work lists (HEX8: rdc_solid_cl.hip, rdc_hex8_cl.hip) ------------------------
 // A workgroup owns a CLUSTER of owned nodes.  Its consumer lanes each take one (owned node, incident element) PAIR and

@@ -215,9 +215,9 @@ std::string prep_build_ev(const HostPrep& P, const uint32_t* conn, size_t lds_bu
       const uint32_t n = cl[x];
       HostPrepEv::Node& nd = E.ntab[(size_t)w * MAXN + x];
       const int64_t len = P.bptr[n + 1] - P.bptr[n];
-      nd.bptr = (uint32_t)P.bptr[n]; nd.len = (uint16_t)len; nd.blk0 = (uint16_t)x; nd.node = n;   // block (x, slot s) lives at s * MAXN + x
+      nd.bptr = (uint32_t)P.bptr[n]; nd.len = (uint16_t)len; nd.blk0 = (uint16_t)x; nd.node = n;   // block (x, slot s): evl::block
       const uint32_t phase = (uint32_t)(((int64_t)nv2 * P.bptr[n]) & 1);
-      if ((ob & 1) != phase) ob++;          // the image of a segment starts at the 16-byte phase it has in memory
+      if ((uint32_t)evl::seg_phase(ob) != phase) ob++;          // the image of a segment starts at the 16-byte phase it has in memory
       nd.obase = ob;
       ob += (uint32_t)(nv2 * (size_t)len);
       blk += (uint32_t)len;
@@ -243,7 +243,7 @@ std::string prep_build_ev(const HostPrep& P, const uint32_t* conn, size_t lds_bu
           const int64_t len2 = P.bptr[c2 + 1] - P.bptr[c2];
           const int64_t s2 = std::find(row2, row2 + len2, (int32_t)n) - row2;
           if (s2 >= len2) { wfail = true; continue; }   // the node graph is symmetric
-          bp[(size_t)(b - P.bptr[n]) * MAXN + x] = (uint8_t)(s2 * MAXN + (int64_t)x2);
+          bp[evl::block((int)x, (int)(b - P.bptr[n]))] = (uint8_t)evl::block((int)x2, (int)s2);
         }
       }
     }
@@ -447,26 +447,24 @@ std::string prep_build_ev(const HostPrep& P, const uint32_t* conn, size_t lds_bu
       for (int j = v.r; j < 4; j++) perm[j] = v.rest[j - v.r];
       maxr_g[best_g] = std::max(maxr_g[best_g], v.r);
       const size_t lane = (size_t)best_g * 16 + (size_t)fill_g[best_g]++;
-      uint32_t packed = 0;
       uint32_t li[4];
       for (int j = 0; j < 4; j++) {
         const uint32_t m = conn[(int64_t)v.e * 4 + perm[j]];
-        const uint32_t pos = (uint32_t)(std::find(t.begin(), t.end(), m) - t.begin());
-        li[j] = pos;
-        packed |= pos << (8 * j);
+        li[j] = (uint32_t)(std::find(t.begin(), t.end(), m) - t.begin());
       }
-      E.vloc[(size_t)w * BLOCK + lane] = packed;
+      E.vloc[(size_t)w * BLOCK + lane] = evl::vloc_pack(li);
       rows_w[(size_t)w] += v.r;
+      uint32_t sl2[2] = {0, 0};
       for (int i = 0; i < v.r; i++) {
-        uint32_t half = 0;   // four 4-bit slots (a row has at most 16 node blocks): 16 bits per row, two rows per word
         for (int j = 0; j < 4; j++) {
           const uint32_t sl = P.eslot[(size_t)v.e * 16 + (size_t)perm[i] * 4 + (size_t)perm[j]];
           if (sl > 15) wfail = true;
-          half |= (sl & 15u) << (4 * j);
+          evl::vslot_add(sl2, i, j, sl);
         }
-        E.vslot[((size_t)w * BLOCK + lane) * 2 + (size_t)(i >> 1)] |= half << (16 * (i & 1));
         if (li[i] >= cl.size()) wfail = true;
       }
+      E.vslot[((size_t)w * BLOCK + lane) * 2] = sl2[0];
+      E.vslot[((size_t)w * BLOCK + lane) * 2 + 1] = sl2[1];
     }
     conf_w[(size_t)w] = best_pl.coll;
     instr_w[(size_t)w] = best_pl.instr;

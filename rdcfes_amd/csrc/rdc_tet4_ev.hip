@@ -11,13 +11,9 @@
 #include "rdc_internal.h"
 #include <type_traits>
 #include "rdc_tet4_ev.h"
+#include "rdc_ev_phases.h"
 
 namespace rdc {
-
-template <class M> struct RecEv {
-  static constexpr int RAW = 3 + M::NV + M::NAUX;
-  static constexpr int N = (RAW + 1) & ~1;
-};
 
 // ABL (diagnostic builds): 1 = plain LDS stores instead of atomics, 2 = no LDS accumulation traffic, 3 = no compute phase (results WRONG);
 // 4 = the real kernel with s_memtime stamps per wave and phase (results right; tools/ev_timeline.py)
@@ -80,24 +76,9 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   double* const R = lds + NM * NBP;
   double* const recs = R + 5 * MAXN;
-  // phase 0: zero [M | R], list loads, LDS-DMA of the node records.  A store moves its address and data registers to the
-  // LDS at 2 cycles per source dword and wave instruction (MI355X_MICROARCH.md, LDS): ds_write_addtid_b32 has no address
-  // register (address = M0 + offset + 4 * lane), so zeroing the 32 KB slice costs 2 cycles per 256 bytes instead of 13 per
-  // 1024 with 16-byte stores.  Wave wv clears its quarter of the slice; M0 is restored (the LDS-DMA below sets it too).
-  {
-    static_assert((NM * NBP * 8) % (4 * 1024) == 0, "zeroing: 4 waves x (NM / 2) groups of four addtid stores of 256 bytes");
-    constexpr int PER_WAVE = NM * NBP * 8 / 4;   // bytes
-    const uint32_t zbase = (uint32_t)(uintptr_t)lds + (uint32_t)__builtin_amdgcn_readfirstlane(wv) * (uint32_t)PER_WAVE;
-    const uint32_t zero = 0u;
-    uint32_t m0_saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0" : "=&s"(m0_saved) : "s"(zbase) : "memory");
-#pragma unroll
-    for (int o = 0; o < PER_WAVE; o += 1024)
-      asm volatile("ds_write_addtid_b32 %0 offset:%1\n\tds_write_addtid_b32 %0 offset:%1+256\n\tds_write_addtid_b32 %0 offset:%1+512\n\tds_write_addtid_b32 %0 offset:%1+768"
-                   :: "v"(zero), "n"(o) : "memory");
-    asm volatile("s_mov_b32 m0, %0" :: "s"(m0_saved) : "memory");
-    if (tid < 5 * MAXN) lds[NM * NBP + tid] = 0.0;
-  }
+  // phase 0: zero [M | R] (wave wv clears its quarter of the slice), list loads, LDS-DMA of the node records
+  evl::zero_slice<NM * NBP * 8>(lds, __builtin_amdgcn_readfirstlane(wv));
+  if (tid < 5 * MAXN) lds[NM * NBP + tid] = 0.0;
   const int rounds = nls >> 6;
   uint32_t nid = 0;
   if (wv < rounds) nid = nlist[(size_t)w * nls + wv * 64 + lane];
@@ -110,7 +91,7 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
     const char* src = reinterpret_cast<const char*>(rec) + (size_t)nid * (NP * 16);
 #pragma unroll
     for (int p = 0; p < NP; p++)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src + p * 16), (lds_ptr)(recs + (p * nls + wv * 64) * 2), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr)(src + p * 16), (lds_ptr)evl::rec_at(recs, nls, p, wv * 64), 16, 0, 0);
   }
   RDC_TS(1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -118,34 +99,25 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   __syncthreads();
   RDC_TS(3);
   // phase 1: element visits
-  if (pl != 0xFFFFFFFFu) {
+  if (pl != evl::IDLE) {
     double X[4][3], U[4][5];
     int li[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      li[j] = (pl >> (8 * j)) & 0xFF;
+      li[j] = evl::vloc_pos(pl, j);
       double rr[2 * NP];
 #pragma unroll
       for (int p = 0; p < NP; p++) {
-        const double2 v2 = reinterpret_cast<const double2*>(recs)[p * nls + li[j]];
+        const double2 v2 = evl::rec_piece(recs, nls, p, li[j]);
         rr[2 * p] = v2.x; rr[2 * p + 1] = v2.y;
       }
       X[j][0] = rr[0]; X[j][1] = rr[1]; X[j][2] = rr[2];
 #pragma unroll
       for (int v = 0; v < 5; v++) U[j][v] = rr[3 + v];
     }
-    const int nown = (int)d.nown;
-    // the owned vertices come first: r = number of list positions below nown
-    const int r = (li[0] < nown) + (li[1] < nown) + (li[2] < nown) + (li[3] < nown);
+    const int r = evl::vloc_rows(li, (int)d.nown);
     EvSink<ABL> sink;
-    const uint32_t sw[4] = {sl.x & 0xFFFFu, sl.x >> 16, sl.y & 0xFFFFu, sl.y >> 16};   // four 4-bit column slots per row
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int a = (i < r) ? li[i] : 0;   // owned vertices come first in the node list: list position == cluster index
-      sink.pr[i] = R + a;
-#pragma unroll
-      for (int j = 0; j < 4; j++) sink.p[i][j] = lds + a + MAXN * (int)((sw[i] >> (4 * j)) & 0xF);   // block (a, slot): slot * 16 + a
-    }
+    evl::aim(sink, lds, R, li, r, sl);
     // background state (n = c = h = a = 0, v > 0) at every vertex of every visit of this wave: a scalar flag (rdc_tet4_ev.h, bg)
     const bool bg = bg_skip && __builtin_amdgcn_ballot_w64(!ev::pihna_background(U)) == 0;
     if (ABL != 3) ev::pihna_visit<EXP_MODE, EvSink<ABL>, true, GEN>(k, X, U, r, sink, bg);   // ABL 3: no compute phase at all (data movement only)
@@ -155,9 +127,9 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   RDC_TS(4);
   __syncthreads();
   RDC_TS(5);
-  // phase 2: node block tid = slot * 16 + node: moments -> entries
+  // phase 2: node block tid = evl::block(bn, bs): moments -> entries
   double e[NM];
-  const int bn = tid & (MAXN - 1), bs = tid >> 4;
+  const int bn = evl::block_node(tid), bs = evl::block_slot(tid);
   const bool has = bn < (int)d.nown && bs < (int)snode[bn < (int)d.nown ? bn : 0].len;
   if (has) {
 #pragma unroll
@@ -177,32 +149,18 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   if (has) {
     double o[25];
     ev::pihna_expand(k, e, o);
-    const int n = bn, s = bs;
-    const int len5 = 5 * (int)snode[n].len;
-    double* dst = lds + snode[n].obase + 5 * s;
+    const int len = (int)snode[bn].len;
+    double* dst = lds + snode[bn].obase + evl::seg_entry(5, len, 0, bs, 0);   // the block's origin first: k_tet4_evq
 #pragma unroll
     for (int a = 0; a < 5; a++)
 #pragma unroll
-      for (int b = 0; b < 5; b++) dst[a * len5 + b] = o[a * 5 + b];
+      for (int b = 0; b < 5; b++) dst[evl::seg_entry(5, len, a, 0, b)] = o[a * 5 + b];
   }
   RDC_TS(7);
   __syncthreads();
   RDC_TS(8);
   // phase 3: one contiguous CSR segment per node; the image has the 16-byte phase of its segment in memory
-  for (int n = wv; n < (int)d.nown; n += 4) {
-    const HostPrepEv::Node nd = snode[n];
-    const int cnt = 25 * (int)nd.len;
-    double* out = val + (size_t)25 * nd.bptr;            // out[x] <-> img[x]
-    const double* img = lds + nd.obase;
-    const int sh = (int)(nd.obase & 1);                  // == (25 * bptr) & 1 by construction
-    typedef double v2d_t __attribute__((ext_vector_type(2)));
-    const int npair = (cnt - sh) >> 1;
-    const v2d_t* src = reinterpret_cast<const v2d_t*>(img + sh);
-    v2d_t* dstg = reinterpret_cast<v2d_t*>(out + sh);
-    for (int x = lane; x < npair; x += 64) __builtin_nontemporal_store(src[x], dstg + x);
-    if (sh && lane == 0) __builtin_nontemporal_store(img[0], out);
-    if (((cnt - sh) & 1) && lane == 1) __builtin_nontemporal_store(img[cnt - 1], out + cnt - 1);
-  }
+  for (int n = wv; n < (int)d.nown; n += 4) evl::store_segment(lds, val, 25, snode[n], lane);
   if (TL) {
     RDC_TS(9);
     if (stagger == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's stores have been acknowledged ("stagger" != 0: not waited for)
@@ -284,7 +242,7 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     if (wv < rounds) {
       const char* src = reinterpret_cast<const char*>(rec) + (size_t)nid * (NP * 16);
 #pragma unroll
-      for (int p = 0; p < NP; p++) evl_dma16(src + p * 16, recs + (p * nls + wv * 64) * 2);
+      for (int p = 0; p < NP; p++) evl_dma16(src + p * 16, evl::rec_at(recs, nls, p, wv * 64));
     }
     if (wv == 0) evl_dma16(reinterpret_cast<const char*>(vloc + (size_t)w * BLOCK) + lane * 16, lists + EvqLists::PL);
     else if (wv < 3) evl_dma16(reinterpret_cast<const char*>(vslot + (size_t)w * BLOCK * 2) + (wv - 1) * 1024 + lane * 16, lists + EvqLists::SL + (wv - 1) * 1024);
@@ -310,21 +268,10 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   for (int it = 0;; it++) {
     int lane;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));   // recomputed every iteration: never hoisted out of the loop and spilled
-    const int w = w0c;
     RDC_TS(0);
-    {   // zero [M | R] (ds_write_addtid_b32: k_tet4_ev); the image of the previous cluster has been read (barrier at its end)
-      constexpr int PER_WAVE = NM * NBP * 8 / 4;   // bytes
-      const uint32_t zbase = (uint32_t)(uintptr_t)lds + (uint32_t)wv * (uint32_t)PER_WAVE;
-      const uint32_t zero = 0u;
-      uint32_t m0_saved;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0" : "=&s"(m0_saved) : "s"(zbase) : "memory");
-#pragma unroll
-      for (int o = 0; o < PER_WAVE; o += 1024)
-        asm volatile("ds_write_addtid_b32 %0 offset:%1\n\tds_write_addtid_b32 %0 offset:%1+256\n\tds_write_addtid_b32 %0 offset:%1+512\n\tds_write_addtid_b32 %0 offset:%1+768"
-                     :: "v"(zero), "n"(o) : "memory");
-      asm volatile("s_mov_b32 m0, %0" :: "s"(m0_saved) : "memory");
-      if (wv * 64 + lane < 5 * MAXN) lds[NM * NBP + wv * 64 + lane] = 0.0;
-    }
+    // zero [M | R]; the image of the previous cluster has been read (barrier at its end)
+    evl::zero_slice<NM * NBP * 8>(lds, wv);
+    if (wv * 64 + lane < 5 * MAXN) lds[NM * NBP + wv * 64 + lane] = 0.0;
     // the one wait of the cluster: what was fetched for it while the previous one was expanded -- and that one's stores
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(tk)::"memory");
     if (pending && wv == 0 && lane == 0) s_tk[0] = tk == NONE ? NONE : 3 * (int)gridDim.x + tk;
@@ -340,38 +287,31 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
       const int nown = (int)reinterpret_cast<const HostPrepEv::Desc*>(lists + EvqLists::DESC)->nown;
       // what the expansion needs from the lists is parked where the next fetch does not land
       {
-        const int blk = (((wv & 1) << 3) | (lane >> 3)) * MAXN + (((wv >> 1) << 3) | (lane & 7));
+        const int blk = evl::block(((wv >> 1) << 3) | (lane & 7), ((wv & 1) << 3) | (lane >> 3));
         smirror[blk] = *reinterpret_cast<const uint8_t*>(lists + EvqLists::MIRROR + blk);
         if (tid < MAXN) snode[tid] = *reinterpret_cast<const HostPrepEv::Node*>(lists + EvqLists::SNODE + tid * 16);
         if (tid == 0) s_nown = nown;
       }
       // ---- element visits (phase 1 of k_tet4_ev)
-      if (pl != 0xFFFFFFFFu) {
+      if (pl != evl::IDLE) {
         double X[4][3], U[4][5];
         int li[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-          li[j] = (pl >> (8 * j)) & 0xFF;
+          li[j] = evl::vloc_pos(pl, j);
           double rr[2 * NP];
 #pragma unroll
           for (int p = 0; p < NP; p++) {
-            const double2 v2 = reinterpret_cast<const double2*>(recs)[p * nls + li[j]];
+            const double2 v2 = evl::rec_piece(recs, nls, p, li[j]);
             rr[2 * p] = v2.x; rr[2 * p + 1] = v2.y;
           }
           X[j][0] = rr[0]; X[j][1] = rr[1]; X[j][2] = rr[2];
 #pragma unroll
           for (int v = 0; v < 5; v++) U[j][v] = rr[3 + v];
         }
-        const int r = (li[0] < nown) + (li[1] < nown) + (li[2] < nown) + (li[3] < nown);
+        const int r = evl::vloc_rows(li, nown);
         EvSink<0> sink;
-        const uint32_t sw[4] = {sl.x & 0xFFFFu, sl.x >> 16, sl.y & 0xFFFFu, sl.y >> 16};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int a = (i < r) ? li[i] : 0;
-          sink.pr[i] = R + a;
-#pragma unroll
-          for (int j = 0; j < 4; j++) sink.p[i][j] = lds + a + MAXN * (int)((sw[i] >> (4 * j)) & 0xF);
-        }
+        evl::aim(sink, lds, R, li, r, sl);
         const bool bg = bg_skip && __builtin_amdgcn_ballot_w64(!ev::pihna_background(U)) == 0;   // k_tet4_ev
         ev::pihna_visit<EXP_MODE, EvSink<0>, true, GEN>(k, X, U, r, sink, bg);
       }
@@ -397,7 +337,7 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     pending = true;
     // ---- node block (bn, bs): moments -> entries; waves 0-1 hold the blocks of nodes 0-7, waves 2-3 those of nodes 8-15
     const int nown = s_nown;
-    const int bn = ((wv >> 1) << 3) | (lane & 7), bs = ((wv & 1) << 3) | (lane >> 3), blk = bs * MAXN + bn;
+    const int bn = ((wv >> 1) << 3) | (lane & 7), bs = ((wv & 1) << 3) | (lane >> 3), blk = evl::block(bn, bs);
     double e[NM];
     const bool has = bn < nown && bs < (int)snode[bn < nown ? bn : 0].len;
 #pragma unroll
@@ -428,29 +368,18 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
       if (n0 >= nown) break;   // uniform
       const uint32_t base = h == 0 ? 0u : (snode[8].obase & ~1u);   // even: the 16-byte phase of the segments is kept
       if ((wv >> 1) == h && has) {
-        const int len5 = 5 * (int)snode[bn].len;
-        double* dst = lds + (snode[bn].obase - base) + 5 * bs;
+        const int len = (int)snode[bn].len;
+        // the block's origin goes into the pointer first: as one seg_entry(5, len, a, bs, b) per entry the 16-moment instantiations
+        // spill 4-8 registers instead of 2 (20-32 B of scratch per lane)
+        double* dst = lds + (snode[bn].obase - base) + evl::seg_entry(5, len, 0, bs, 0);
 #pragma unroll
         for (int a = 0; a < 5; a++)
 #pragma unroll
-          for (int b = 0; b < 5; b++) dst[a * len5 + b] = o[a * 5 + b];
+          for (int b = 0; b < 5; b++) dst[evl::seg_entry(5, len, a, 0, b)] = o[a * 5 + b];
       }
       lds_barrier();
       const int n1 = nown < n0 + 8 ? nown : n0 + 8;
-      for (int n = n0 + wv; n < n1; n += 4) {
-        const HostPrepEv::Node nd = snode[n];
-        const int cnt = 25 * (int)nd.len;
-        double* out = val + (size_t)25 * nd.bptr;
-        const double* img = lds + (nd.obase - base);
-        const int sh = (int)(nd.obase & 1);
-        typedef double v2d_t __attribute__((ext_vector_type(2)));
-        const int npair = (cnt - sh) >> 1;
-        const v2d_t* src = reinterpret_cast<const v2d_t*>(img + sh);
-        v2d_t* dstg = reinterpret_cast<v2d_t*>(out + sh);
-        for (int x = lane; x < npair; x += 64) __builtin_nontemporal_store(src[x], dstg + x);
-        if (sh && lane == 0) __builtin_nontemporal_store(img[0], out);
-        if (((cnt - sh) & 1) && lane == 1) __builtin_nontemporal_store(img[cnt - 1], out + cnt - 1);
-      }
+      for (int n = n0 + wv; n < n1; n += 4) evl::store_segment(lds, val, 25, snode[n], lane, base);
       lds_barrier();   // the half has been read (into the stores' registers)
     }
     RDC_TS(5);
@@ -468,6 +397,24 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
 // (A first resident form, k_tet4_evp -- two workgroups per CU, a loader wave, two LDS buffers: 2.45 vs 2.11 ms in round 2 -- was removed at the end of
 // round 3: profiles/r02i_ab_evp.txt)
 
+namespace {
+// the one launch of k_tet4_ev (one workgroup per cluster) and of its resident form k_tet4_evq (`grid` workgroups walk over the clusters)
+template <int MODE, int MINW, int ABL, bool GEN>
+hipError_t launch_ev(const LaunchArgs& a, const PihnaK& k, const int wg_count, const size_t lds_bytes) {
+  const EvDev& E = a.ev;
+  hipLaunchKernelGGL((k_tet4_ev<MODE, MINW, ABL, GEN>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab,
+                     E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background);
+  return hipGetLastError();
+}
+template <int MODE, bool TL, bool GEN>
+hipError_t launch_evq(const LaunchArgs& a, const PihnaK& k, const int wg_count, const int grid, const size_t lds_bytes) {
+  const EvDev& E = a.ev;
+  hipLaunchKernelGGL((k_tet4_evq<MODE, TL, GEN>), dim3(grid), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab, E.bpart, k,
+                     a.packed, a.val, a.rhs, E.nls, E.wg_begin, wg_count, a.stamps, a.opt.ev_background, a.ev_ticket + (a.pack_part == 2 ? 16 : 0), E.wg_perm);
+  return hipGetLastError();
+}
+}
+
 hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   const EvDev& E = a.ev;
   // node records (same pack kernel and two-part rules as the pair kernels)
@@ -476,9 +423,9 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   if (a.ev_start) (void)hipEventRecord(a.ev_start, a.stream);
   const int wg_count = E.wg_count < 0 ? E.n_wg - E.wg_begin : E.wg_count;
   if (wg_count <= 0) return hipSuccess;
+  // LDS (doubles): [moment slice | rhs | node records]; k_tet4_ev lays the CSR image over them, k_tet4_evq (image halves inside the slice) puts its lists behind
   const size_t acc = (size_t)(a.ev_general ? ev::NMG : ev::NM) * ev::NBP + 5 * ev::MAXN + (size_t)4 * E.nls * 2;
-  const size_t lds_doubles = acc > E.max_out_doubles ? acc : E.max_out_doubles;
-  const size_t lds_bytes = lds_doubles * sizeof(double);
+  const bool cube = a.exp_mode == 3;   // the dedicated-exponent instantiations
   // default: pipelined resident workgroups, clusters handed out by a counter (the two parts of a two-part assembly, which may run
   // concurrently on two streams, have a counter each: ev_ticket[0] and ev_ticket[16]).  Not when a diagnostic knob of k_tet4_ev is set
   // ... and only for launches of at least 56 clusters per resident workgroup (43,000 on 256 CUs): a workgroup's start (ticket -> node
@@ -488,44 +435,25 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   const int evq_grid = a.opt.grid > 0 ? a.opt.grid : (a.ev_grid > 0 ? (a.ev_general ? a.ev_grid : a.ev_grid / 2 * 3) : 768);   // three per CU (22 moments: two)
   if (a.opt.ev_resident && (!a.opt.ablate || (a.opt.ablate == 4 && !a.ev_general)) && a.opt.ev_occupancy == 3 && !a.opt.xcd && a.opt.stagger == 0 &&
       (a.opt.grid > 0 || a.opt.ev_resident == 2 || (int64_t)wg_count >= 56 * (int64_t)evq_grid)) {
-    int grid = evq_grid;
-    if (grid > wg_count) grid = wg_count;
-    const size_t bytes = ((size_t)(a.ev_general ? ev::NMG : ev::NM) * ev::NBP + 5 * ev::MAXN + (size_t)4 * E.nls * 2) * sizeof(double) + EvqLists::bytes(E.nls);
+    const int grid = evq_grid > wg_count ? wg_count : evq_grid;
+    const size_t bytes = acc * sizeof(double) + EvqLists::bytes(E.nls);
     if (!a.ev_ticket) return hipErrorInvalidValue;   // the cluster counter: zeroed by the record pack kernel in front of this launch
-#define RDC_EVQ(MODE, TLV, GENV)                                                                                                              \
-  hipLaunchKernelGGL((k_tet4_evq<MODE, TLV, GENV>), dim3(grid), dim3(256), bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab, E.bpart, k, \
-                     a.packed, a.val, a.rhs, E.nls, E.wg_begin, wg_count, a.stamps, a.opt.ev_background, a.ev_ticket + (a.pack_part == 2 ? 16 : 0), E.wg_perm)
-    if (a.ev_general) { if (a.exp_mode == 3) RDC_EVQ(3, false, true); else RDC_EVQ(0, false, true); }
-    else if (a.opt.ablate == 4) { if (a.exp_mode == 3) RDC_EVQ(3, true, false); else RDC_EVQ(0, true, false); }
-    else { if (a.exp_mode == 3) RDC_EVQ(3, false, false); else RDC_EVQ(0, false, false); }
-#undef RDC_EVQ
-    return hipGetLastError();
+    if (a.ev_general) return cube ? launch_evq<3, false, true>(a, k, wg_count, grid, bytes) : launch_evq<0, false, true>(a, k, wg_count, grid, bytes);
+    else if (a.opt.ablate == 4) return cube ? launch_evq<3, true, false>(a, k, wg_count, grid, bytes) : launch_evq<0, true, false>(a, k, wg_count, grid, bytes);
+    else return cube ? launch_evq<3, false, false>(a, k, wg_count, grid, bytes) : launch_evq<0, false, false>(a, k, wg_count, grid, bytes);
   }
-#define RDC_EV(MODE, MINW)                                                                                          \
-  hipLaunchKernelGGL((k_tet4_ev<MODE, MINW>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
-  if (a.exp_mode == 3 && a.opt.ablate >= 1 && a.opt.ablate <= 4 && !a.ev_general) {   // diagnostic builds (1-3: timing only)
-#define RDC_EVA(X)                                                                                                    \
-  hipLaunchKernelGGL((k_tet4_ev<3, 3, X>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
-    if (a.opt.ablate == 1) RDC_EVA(1); else if (a.opt.ablate == 2) RDC_EVA(2); else if (a.opt.ablate == 3) RDC_EVA(3); else RDC_EVA(4);
-#undef RDC_EVA
-    return hipGetLastError();
+  const size_t lds_bytes = (acc > E.max_out_doubles ? acc : E.max_out_doubles) * sizeof(double);
+  if (cube && a.opt.ablate >= 1 && a.opt.ablate <= 4 && !a.ev_general) {   // diagnostic builds (1-3: timing only)
+    if (a.opt.ablate == 1) return launch_ev<3, 3, 1, false>(a, k, wg_count, lds_bytes);
+    else if (a.opt.ablate == 2) return launch_ev<3, 3, 2, false>(a, k, wg_count, lds_bytes);
+    else if (a.opt.ablate == 3) return launch_ev<3, 3, 3, false>(a, k, wg_count, lds_bytes);
+    else return launch_ev<3, 3, 4, false>(a, k, wg_count, lds_bytes);
   }
-  if (a.ev_general) {
-    // every term on: 22 moments, 54 KB of LDS.  Register budget of TWO workgroups per CU (244 registers, no scratch): at three the visit
-    // spills 79 registers (304 B of scratch per lane) and runs 8.8 instead of 3.0 ms on K(119) (profiles/r03_ev_ab_log.md, r03q)
-#define RDC_EVG(MODE)                                                                                                       \
-  hipLaunchKernelGGL((k_tet4_ev<MODE, 2, 0, true>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, \
-                     E.vslot, E.ntab, E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background)
-    if (a.exp_mode == 3) RDC_EVG(3); else RDC_EVG(0);
-#undef RDC_EVG
-    return hipGetLastError();
-  }
-  if (a.exp_mode == 3) { if (a.opt.ev_occupancy == 2) RDC_EV(3, 2); else RDC_EV(3, 3); }
-  else { if (a.opt.ev_occupancy == 2) RDC_EV(0, 2); else RDC_EV(0, 3); }
-#undef RDC_EV
-  return hipGetLastError();
+  // every term on: 22 moments, 54 KB of LDS.  Register budget of TWO workgroups per CU (244 registers, no scratch): at three the visit
+  // spills 79 registers (304 B of scratch per lane) and runs 8.8 instead of 3.0 ms on K(119) (profiles/r03_ev_ab_log.md, r03q)
+  if (a.ev_general) return cube ? launch_ev<3, 2, 0, true>(a, k, wg_count, lds_bytes) : launch_ev<0, 2, 0, true>(a, k, wg_count, lds_bytes);
+  if (cube) return a.opt.ev_occupancy == 2 ? launch_ev<3, 2, 0, false>(a, k, wg_count, lds_bytes) : launch_ev<3, 3, 0, false>(a, k, wg_count, lds_bytes);
+  else return a.opt.ev_occupancy == 2 ? launch_ev<0, 2, 0, false>(a, k, wg_count, lds_bytes) : launch_ev<0, 3, 0, false>(a, k, wg_count, lds_bytes);
 }
 
 }  // namespace rdc

@@ -12,6 +12,7 @@
 // Every CSR value is written exactly once; no global atomics, no colours.  Sums are order-dependent in the last bits.
 #include "rdc_internal.h"
 #include "rdc_tet4_ev.h"
+#include "rdc_ev_phases.h"
 #include "rdc_tet4_evc.h"
 
 namespace rdc {
@@ -66,21 +67,21 @@ k_tet4_evc(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     const char* src = reinterpret_cast<const char*>(rec) + (size_t)nid * (NP * 16);
 #pragma unroll
     for (int p = 0; p < NP; p++)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src + p * 16), (lds_ptr)(recs + (p * nls + wv * 64) * 2), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr)(src + p * 16), (lds_ptr)evl::rec_at(recs, nls, p, wv * 64), 16, 0, 0);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // phase 1: element visits
-  if (pl != 0xFFFFFFFFu) {
+  if (pl != evl::IDLE) {
     double X[4][3], U[4][NV], AX[4][NA];
     int li[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      li[j] = (pl >> (8 * j)) & 0xFF;
+      li[j] = evl::vloc_pos(pl, j);
       double rr[2 * NP];
 #pragma unroll
       for (int p = 0; p < NP; p++) {
-        const double2 v2 = reinterpret_cast<const double2*>(recs)[p * nls + li[j]];
+        const double2 v2 = evl::rec_piece(recs, nls, p, li[j]);
         rr[2 * p] = v2.x; rr[2 * p + 1] = v2.y;
       }
       X[j][0] = rr[0]; X[j][1] = rr[1]; X[j][2] = rr[2];
@@ -89,23 +90,15 @@ k_tet4_evc(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
 #pragma unroll
       for (int v = 0; v < NA; v++) AX[j][v] = M::NAUX > 0 ? rr[(3 + NV + v) % (2 * NP)] : 0.0;
     }
-    const int nown = (int)d.nown;
-    const int r = (li[0] < nown) + (li[1] < nown) + (li[2] < nown) + (li[3] < nown);   // the owned vertices come first
+    const int r = evl::vloc_rows(li, (int)d.nown);
     EvcSink<M> sink;
-    const uint32_t sw[4] = {sl.x & 0xFFFFu, sl.x >> 16, sl.y & 0xFFFFu, sl.y >> 16};   // four 4-bit column slots per row
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int a = (i < r) ? li[i] : 0;   // list position of an owned vertex == its cluster index
-      sink.pr[i] = R + a;
-#pragma unroll
-      for (int j = 0; j < 4; j++) sink.p[i][j] = lds + a + MAXN * (int)((sw[i] >> (4 * j)) & 0xF);   // block (a, slot): slot * 16 + a
-    }
+    evl::aim(sink, lds, R, li, r, sl);
     tet4_visit<M, EXP_MODE>(k, X, U, AX, r, sink);
   }
   __syncthreads();
-  // phase 2: node block tid = slot * 16 + node
+  // phase 2: node block tid = evl::block(bn, bs)
   double e[NE];
-  const int bn = tid & (MAXN - 1), bs = tid >> 4;
+  const int bn = evl::block_node(tid), bs = evl::block_slot(tid);
   const bool has = bn < (int)d.nown && bs < (int)snode[bn < (int)d.nown ? bn : 0].len;
   if (has) {
 #pragma unroll
@@ -117,29 +110,16 @@ k_tet4_evc(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   }
   __syncthreads();   // every entry has been read: the image may overwrite the slice
   if (has) {
-    const int lenv = NV * (int)snode[bn].len;
-    double* dst = lds + snode[bn].obase + NV * bs;
+    const int len = (int)snode[bn].len;
+    double* dst = lds + snode[bn].obase + evl::seg_entry(NV, len, 0, bs, 0);
 #pragma unroll
     for (int a = 0; a < NV; a++)
 #pragma unroll
-      for (int b = 0; b < NV; b++) dst[a * lenv + b] = evc_block<M>(a, b) ? e[evc_index<M>(a, b) % NE] : 0.0;
+      for (int b = 0; b < NV; b++) dst[evl::seg_entry(NV, len, a, 0, b)] = evc_block<M>(a, b) ? e[evc_index<M>(a, b) % NE] : 0.0;
   }
   __syncthreads();
   // phase 3: one contiguous CSR segment per node; the image has the 16-byte phase of its segment in memory
-  for (int n = wv; n < (int)d.nown; n += 4) {
-    const HostPrepEv::Node nd = snode[n];
-    const int cnt = NV * NV * (int)nd.len;
-    double* out = val + (size_t)(NV * NV) * nd.bptr;     // out[x] <-> img[x]
-    const double* img = lds + nd.obase;
-    const int sh = (int)(nd.obase & 1);                  // == (NV^2 * bptr) & 1 by construction
-    typedef double v2d_t __attribute__((ext_vector_type(2)));
-    const int npair = (cnt - sh) >> 1;
-    const v2d_t* src = reinterpret_cast<const v2d_t*>(img + sh);
-    v2d_t* dstg = reinterpret_cast<v2d_t*>(out + sh);
-    for (int x = lane; x < npair; x += 64) __builtin_nontemporal_store(src[x], dstg + x);
-    if (sh && lane == 0) __builtin_nontemporal_store(img[0], out);
-    if (((cnt - sh) & 1) && lane == 1) __builtin_nontemporal_store(img[cnt - 1], out + cnt - 1);
-  }
+  for (int n = wv; n < (int)d.nown; n += 4) evl::store_segment(lds, val, NV * NV, snode[n], lane);
 }
 
 // the node records have been packed by the caller (launch_fast_impl, rdc_tet4_fast.hip)

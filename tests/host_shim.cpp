@@ -125,6 +125,31 @@ struct EvHostSink {
 };
 
 
+// One visit of cluster w decoded with the functions the kernels decode it with (evl::, rdc_prep.h): list positions li and the
+// vertices' data, rows r, and where the rows add (sink.nloc, sink.blk: evl::aim on the device).  0, or 4 / 5: a position / a slot
+// outside the cluster's lists
+template <int NV, class Sink>
+int ev_decode(const HostPrepEv& E, size_t w, int x, uint32_t pl, const double* xyz, const double* u, double (&X)[4][3], double (&U)[4][NV],
+              int (&li)[4], int& r, Sink& sink) {
+  for (int j = 0; j < 4; j++) {
+    if ((li[j] = evl::vloc_pos(pl, j)) >= (int)E.desc[w].ntouch) return 4;
+    const uint32_t n = E.nlist[w * (size_t)E.nls + (size_t)li[j]];
+    for (int c = 0; c < 3; c++) X[j][c] = xyz[3 * (size_t)n + c];
+    for (int v = 0; v < NV; v++) U[j][v] = u[NV * (size_t)n + v];
+  }
+  r = evl::vloc_rows(li, (int)E.desc[w].nown);
+  const uint32_t* sl = &E.vslot[(w * HostPrepEv::BLOCK + (size_t)x) * 2];
+  for (int i = 0; i < 4; i++) {
+    sink.nloc[i] = i < r ? li[i] : 0;
+    for (int j = 0; j < 4; j++) {
+      const int slot = evl::vslot_get(sl[0], sl[1], i, j);
+      if (i < r && slot >= (int)E.ntab[w * HostPrepEv::MAXN + (size_t)li[i]].len) return 5;
+      sink.blk[i][j] = i < r ? evl::block(li[i], slot) : 0;
+    }
+  }
+  return 0;
+}
+
 // k_hex8_cl replayed on the host from the cluster lists of the last shim_cl_build and the SAME record functions
 // (hex8_cl_produce / hex8_cl_consume): per cluster the point records of its elements, then per pair the row over the eight
 // points, added into the CSR rows at the slots of the pair list.  val / rhs: the caller pre-fills NaN; covered entries are
@@ -209,32 +234,22 @@ int evc_replay(const P* p, const double* xyz, const double* u, const double* aux
     std::fill(R.begin(), R.end(), 0.0);
     for (int x = 0; x < HostPrepEv::BLOCK; x++) {
       const uint32_t pl = E.vloc[w * HostPrepEv::BLOCK + (size_t)x];
-      if (pl == 0xFFFFFFFFu) continue;
+      if (pl == evl::IDLE) continue;
       double X[4][3], U[4][NV], AX[4][NA];
       EvcHostSink<M> sink{S.data(), R.data(), {}, {}};
-      int li[4], r = 0;
-      for (int j = 0; j < 4; j++) {
-        li[j] = (int)((pl >> (8 * j)) & 0xFF);
-        const uint32_t n = E.nlist[w * (size_t)E.nls + (size_t)li[j]];
-        for (int c = 0; c < 3; c++) X[j][c] = xyz[3 * (size_t)n + c];
-        for (int v = 0; v < NV; v++) U[j][v] = u[NV * (size_t)n + v];
-        for (int v = 0; v < NA; v++) AX[j][v] = (M::NAUX > 0 && aux) ? aux[(size_t)M::NAUX * n + (M::NAUX > 0 ? v : 0)] : 0.0;
-        r += li[j] < (int)d.nown;
-      }
-      for (int i = 0; i < 4; i++) {
-        sink.nloc[i] = i < r ? li[i] : 0;
-        const uint32_t word = E.vslot[(w * HostPrepEv::BLOCK + (size_t)x) * 2 + (size_t)(i >> 1)] >> (16 * (i & 1));
-        for (int j = 0; j < 4; j++) sink.blk[i][j] = i < r ? (int)((word >> (4 * j)) & 0xF) * ev::MAXN + li[i] : 0;
-      }
+      int li[4], r;
+      if (const int bad = ev_decode(E, w, x, pl, xyz, u, X, U, li, r, sink)) return bad;
+      for (int j = 0; j < 4; j++)
+        for (int v = 0; v < NA; v++) AX[j][v] = (M::NAUX > 0 && aux) ? aux[(size_t)M::NAUX * E.nlist[w * (size_t)E.nls + (size_t)li[j]] + (M::NAUX > 0 ? v : 0)] : 0.0;
       if (fastexp) tet4_visit<M, M::FAST_EXP_MODE>(k, X, U, AX, r, sink); else tet4_visit<M, 0>(k, X, U, AX, r, sink);
     }
     for (uint32_t t = 0; t < (uint32_t)ev::NBP; t++) {
-      const uint32_t bn = t & (ev::MAXN - 1), s2 = t >> 4;
+      const uint32_t bn = (uint32_t)evl::block_node((int)t), s2 = (uint32_t)evl::block_slot((int)t);
       if (bn >= d.nown || s2 >= nt[bn].len) continue;
       const HostPrepEv::Node& nd = nt[bn];
       for (int a = 0; a < NV; a++)
         for (int b = 0; b < NV; b++)
-          val[(size_t)NV * NV * nd.bptr + (size_t)a * NV * nd.len + (size_t)NV * s2 + b] =
+          val[(size_t)NV * NV * nd.bptr + (size_t)evl::seg_entry(NV, nd.len, a, (int)s2, b)] =
               evc_block<M>(a, b) ? S[(size_t)evc_index<M>(a, b) * ev::NBP + t] : 0.0;
     }
     for (uint32_t n = 0; n < d.nown; n++)
@@ -445,33 +460,17 @@ static int ev_assemble_impl(const rdc_pihna_params* p, const double* xyz, const 
     std::fill(R.begin(), R.end(), 0.0);
     for (int x = 0; x < HostPrepEv::BLOCK; x++) {
       const uint32_t pl = E.vloc[w * HostPrepEv::BLOCK + (size_t)x];
-      if (pl == 0xFFFFFFFFu) continue;
+      if (pl == evl::IDLE) continue;
       double X[4][3], U[4][5];
       EvHostSink sink{M.data(), R.data(), {}, {}};
-      int li[4], r = 0;
-      for (int j = 0; j < 4; j++) {
-        li[j] = (int)((pl >> (8 * j)) & 0xFF);
-        if (li[j] >= (int)d.ntouch) return 4;
-        const uint32_t n = E.nlist[w * (size_t)E.nls + (size_t)li[j]];
-        for (int c = 0; c < 3; c++) X[j][c] = xyz[3 * (size_t)n + c];
-        for (int v = 0; v < 5; v++) U[j][v] = u[5 * (size_t)n + v];
-        r += li[j] < (int)d.nown;
-      }
-      for (int i = 0; i < 4; i++) {
-        sink.nloc[i] = i < r ? li[i] : 0;
-        const uint32_t word = E.vslot[(w * HostPrepEv::BLOCK + (size_t)x) * 2 + (size_t)(i >> 1)] >> (16 * (i & 1));   // 4-bit slots, two rows per word
-        for (int j = 0; j < 4; j++) {
-          const int slot = (int)((word >> (4 * j)) & 0xF);
-          sink.blk[i][j] = i < r ? slot * ev::MAXN + li[i] : 0;     // block (node a, slot s) of the slice: s * 16 + a
-          if (i < r && slot >= (int)nt[li[i]].len) return 5;
-        }
-      }
+      int li[4], r;
+      if (const int bad = ev_decode(E, w, x, pl, xyz, u, X, U, li, r, sink)) return bad;
       const bool bg = g_ev_bg && ev::pihna_background(U);   // per visit here, per wave on the device
       if (cube) ev::pihna_visit<3, EvHostSink, true, GEN>(k, X, U, r, sink, bg); else ev::pihna_visit<0, EvHostSink, true, GEN>(k, X, U, r, sink, bg);
     }
     img.assign(d.out_doubles, 0.0);
     for (uint32_t t = 0; t < (uint32_t)ev::NBP; t++) {
-      const uint32_t bn = t & (ev::MAXN - 1), s2 = t >> 4;
+      const uint32_t bn = (uint32_t)evl::block_node((int)t), s2 = (uint32_t)evl::block_slot((int)t);
       if (bn >= d.nown || s2 >= nt[bn].len) continue;
       double e[NMT], o[25];
       for (int m = 0; m < NMT; m++) e[m] = M[(size_t)m * ev::NBP + t];
@@ -483,14 +482,14 @@ static int ev_assemble_impl(const rdc_pihna_params* p, const double* xyz, const 
       const HostPrepEv::Node& nd = nt[bn];
       for (int a = 0; a < 5; a++)
         for (int b = 0; b < 5; b++) {
-          const size_t at = (size_t)nd.obase + (size_t)a * 5 * nd.len + 5 * s2 + (size_t)b;
+          const size_t at = (size_t)nd.obase + (size_t)evl::seg_entry(5, nd.len, a, (int)s2, b);
           if (at >= img.size()) return 7;
           img[at] = o[a * 5 + b];
         }
     }
     for (uint32_t n = 0; n < d.nown; n++) {
       const HostPrepEv::Node& nd = nt[n];
-      if (((25ull * nd.bptr) & 1) != (nd.obase & 1)) return 8;   // image and memory share the 16-byte phase
+      if ((int)((25ull * nd.bptr) & 1) != evl::seg_phase(nd.obase)) return 8;   // image and memory share the 16-byte phase
       for (uint32_t x = 0; x < 25u * nd.len; x++) val[25 * (size_t)nd.bptr + x] = img[(size_t)nd.obase + x];
       for (int a = 0; a < 5; a++) rhs[5 * (size_t)nd.node + a] = R[(size_t)a * ev::MAXN + n];
     }
