@@ -312,6 +312,7 @@ int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 #define RDC_PRECOND_NONE 0
 #define RDC_PRECOND_JACOBI 1
 #define RDC_PRECOND_BLOCK_JACOBI 2      /* default choice of the Python wrapper */
+#define RDC_PRECOND_MULTIGRID 3         /* block Jacobi's system, with an aggregation-multigrid cycle applied from the right (below) */
 
 #define RDC_SOLVE_CONVERGED     0
 #define RDC_SOLVE_MAX_ITS       1       /* x holds the last iterate */
@@ -376,6 +377,28 @@ int rdc_csr_scale_f32(rdc_ctx* ctx, int precond);
  * does not update it.  RDC_ERR_INVALID if this mesh has no copy.  Enqueued on the context's stream, does not
  * synchronise.  d_x and d_y must not overlap. */
 int rdc_csr_matvec_f32(rdc_ctx* ctx, const double* d_x, double* d_y);
+
+/* ---- RDC_PRECOND_MULTIGRID (rdc_solve and rdc_solve_mixed; additive: RDC_ABI_VERSION stays 3) ----
+ * The iteration runs on the system of RDC_PRECOND_BLOCK_JACOBI, D^-1 A x = D^-1 b, and a V(1,1) cycle M of an aggregation
+ * multigrid is applied from the RIGHT: the operator of the iteration is D^-1 A M, x advances along M p and M s.  The
+ * residual of the recurrence therefore stays D^-1 (b - A x): the stopping test, rel_tol / abs_tol, the confirmation of a
+ * claimed convergence on the true residual, the restarts and every field of rdc_solve_info mean exactly what they mean
+ * for RDC_PRECOND_BLOCK_JACOBI; only the number of iterations differs.
+ * Levels: aggregates of at most 8 nodes of the node-block graph (built on the host at the first multigrid solve on a mesh,
+ * deterministic), a piecewise-constant prolongation per unknown, Galerkin coarse matrices P^T A_l P in the node-block
+ * layout (FP64 in both entry points, rebuilt from the current values by every solve), damped block Jacobi as the smoother
+ * and, with 8 sweeps, on the last level.  The damping is the option "mg_omega" of rdc_set_option, in thousandths
+ * (default 600 = 0.6; accepted 1 .. 1999).  A singular or non-finite diagonal block on ANY level counts into bad_blocks
+ * and gives RDC_SOLVE_BAD_DIAGONAL with x untouched.  RDC_ERR_UNSUPPORTED with ghost nodes, and if a level would have
+ * 2^31 node blocks or more.  rdc_solve_mixed streams the fp32 copy on level 0 inside the cycle as well. */
+/* The hierarchy of the last multigrid solve on this mesh: *n_levels = its levels (the matrix itself is level 0), and for
+ * the first min(*n_levels, cap) of them nodes[l] and blocks[l] (node blocks of the level's matrix).  nodes / blocks may
+ * be NULL with cap = 0.  RDC_ERR_STATE if no multigrid solve has run on this mesh. */
+int rdc_solve_mg_levels(rdc_ctx* ctx, int32_t* n_levels, int64_t* nodes, int64_t* blocks, int cap);
+/* What the hierarchy costs: *setup_ms = device time the last multigrid solve spent on the Galerkin products and the D_l^-1
+ * (part of its rdc_solve_info.device_ms); *level_bytes = device memory the levels hold for this mesh (matrices, lists and
+ * vectors).  Either pointer may be NULL.  RDC_ERR_STATE as above. */
+int rdc_solve_mg_stats(rdc_ctx* ctx, float* setup_ms, int64_t* level_bytes);
 
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */

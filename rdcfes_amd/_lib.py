@@ -62,6 +62,8 @@ SIGNATURES = {
     "rdc_solve_mixed": (C.c_int, [ctx_p, P(SolveParams), C.c_void_p, P(SolveInfo)]),
     "rdc_csr_scale_f32": (C.c_int, [ctx_p, C.c_int]),
     "rdc_csr_matvec_f32": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
+    "rdc_solve_mg_levels": (C.c_int, [ctx_p, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_int]),
+    "rdc_solve_mg_stats": (C.c_int, [ctx_p, P(C.c_float), P(C.c_int64)]),
     "rdc_clamp_nonnegative": (C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_ripf_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),

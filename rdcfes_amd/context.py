@@ -14,7 +14,7 @@ FIELD_OLD_SOLUTION, FIELD_AUX_NODAL, FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE = 0,
 FIELD_PREV_SOLUTION, FIELD_TIME_DERIV, FIELD_RT_DOSE = 4, 5, 6
 FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI = 0, 1, 2
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1, 2, 3
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
 
 
@@ -315,7 +315,9 @@ class AssemblyContext:
               mixed=False):
         """rdc_solve on the values and rhs of the last assemble call.  x: device address of n_owned*nvar doubles
         (initial guess in, solution out); or field=FIELD_*: the device storage of that field is used in place.
-        mixed=True: rdc_solve_mixed, the iteration streams an fp32 copy of D^-1 A (info.matrix_bits tells)."""
+        mixed=True: rdc_solve_mixed, the iteration streams an fp32 copy of D^-1 A (info.matrix_bits tells).
+        precond=PRECOND_MULTIGRID: block Jacobi's system with an aggregation-multigrid cycle applied from the right: same
+        stopping test and norms, fewer iterations (mg_levels(), mg_stats(); damping: set_option("mg_omega", thousandths))."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -325,6 +327,20 @@ class AssemblyContext:
         fn = self._lib.rdc_solve_mixed if mixed else self._lib.rdc_solve
         self._ck(fn(self._h, C.byref(p), C.c_void_p(int(x)), C.byref(info)))
         return info
+
+    def mg_levels(self):
+        """[(nodes, node blocks)] of every level of the hierarchy of the last multigrid solve on this mesh, level 0 = the matrix"""
+        n = C.c_int32()
+        self._ck(self._lib.rdc_solve_mg_levels(self._h, C.byref(n), None, None, 0))
+        nodes, blocks = (C.c_int64 * n.value)(), (C.c_int64 * n.value)()
+        self._ck(self._lib.rdc_solve_mg_levels(self._h, C.byref(n), nodes, blocks, n.value))
+        return [(int(nodes[i]), int(blocks[i])) for i in range(n.value)]
+
+    def mg_stats(self):
+        """(device ms the last multigrid solve spent building the coarse matrices and their D^-1, device bytes the levels hold)"""
+        ms, nbytes = C.c_float(), C.c_int64()
+        self._ck(self._lib.rdc_solve_mg_stats(self._h, C.byref(ms), C.byref(nbytes)))
+        return ms.value, nbytes.value
 
     def part1_nodes(self):
         n = C.c_int64()

@@ -35,7 +35,8 @@ struct Buffers {
   struct { DevBuf elem_material, materials, side_elem, side_id, side_disp; } solid_in;
   // linear solve (rdc_solve.hip): block column list (first matvec / solve), work vectors (first solve); fp32 copy of D^-1 A
   // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
-  struct { DevBuf bcol, work, voff, val32; } solve;
+  // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val; } solve;
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -58,6 +59,8 @@ struct MeshState {
   bool solid_gather_ready = false, rg5_eid_ready = false, bcol_ready = false;   // buf.two_pass, buf.rg2.eid, buf.solve.bcol hold this mesh's lists
   bool voff_ready = false;           // buf.solve.voff / val32 are laid out for this mesh
   bool f32_copy = false;             // buf.solve.val32 holds a usable fp32 copy (of the values at the time it was built)
+  bool mg_ready = false;             // buf.solve.mg_idx / mg_val hold this mesh's hierarchy, mg describes it
+  MgDev mg;
   int64_t part1_nodes = -1;          // rows [0, part1_nodes) were complete after the LAST part-1 call (-1: none since the upload)
   bool part1_packed = false;         // part 1 of the current step has packed the owned records (consumed by part 2)
   bool solid_part1_pending = false;
@@ -90,6 +93,7 @@ struct rdc_ctx {
   int next_ticket = 0;
   hipEvent_t solid_part1_event = nullptr;   // recorded behind part 1 of a two-part solid assembly (the sides of part 2 wait for it)
   SolveScal* solve_rec = nullptr;   // pinned: the one record the host reads per iteration of the linear solve
+  int mg_omega_permille = MG_OMEGA_PERMILLE;   // option "mg_omega": damping of the multigrid smoother, in thousandths
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call
@@ -681,6 +685,11 @@ int rdc_set_kernel_variant(rdc_ctx* c, int v) {
 
 int rdc_set_option(rdc_ctx* c, const char* key, int value) {
   if (!c || !key) return RDC_ERR_INVALID;
+  if (!std::strcmp(key, "mg_omega")) {   // a solver setting, not a tuning option of the assembly: kept beside their table
+    if (value < 1 || value > 1999) return fail(c, RDC_ERR_INVALID, "mg_omega is the damping in thousandths, 1 .. 1999, not %d", value);
+    c->mg_omega_permille = value;
+    return RDC_OK;
+  }
   return options_set(c->opt, key, value, c->err, sizeof(c->err));
 }
 
@@ -1173,6 +1182,78 @@ static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
   return RDC_OK;
 }
 
+// The multigrid hierarchy of the mesh: built on the host and uploaded at the first multigrid solve (rdc_solve.h, mg_build),
+// two allocations carved into the arrays of every level.  d must come from solve_view(want_work).
+static int mg_view(rdc_ctx* c, SolveDev* d) {
+  const HostPrep& P = c->ms.prep;
+  MgDev& g = c->ms.mg;
+  if (!c->ms.mg_ready) {
+    std::vector<MgLevelHost> steps;
+    if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
+      return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
+    const int nv = P.nvar;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    size_t ibytes = 0, vbytes = 3 * pad((size_t)std::max<int64_t>(P.n_owned * nv, 1) * sizeof(double));
+    for (const MgLevelHost& L : steps) {
+      ibytes += pad(L.agg.size() * 4) + pad(L.mptr.size() * 8) + pad(L.member.size() * 4) + pad(L.bptr.size() * 8) + pad(L.bcol.size() * 4) +
+                pad(L.brow.size() * 4) + pad(L.cptr.size() * 8) + pad(L.cidx.size() * 4) + pad(L.cnode.size() * 4);
+      vbytes += pad(L.bcol.size() * nv * nv * sizeof(double)) + pad((size_t)L.n * nv * nv * sizeof(double)) + 3 * pad((size_t)L.n * nv * sizeof(double));
+    }
+    int rc;
+    if ((rc = dev_alloc(c, c->buf.solve.mg_idx, ibytes))) return rc;
+    if ((rc = dev_alloc(c, c->buf.solve.mg_val, vbytes))) return rc;
+    char* ip = (char*)c->buf.solve.mg_idx.p;
+    char* vp = (char*)c->buf.solve.mg_val.p;
+    hipError_t e = hipSuccess;
+    auto put = [&](const auto& v) -> const void* {   // uploads one list, returns where it lies
+      const size_t bytes = v.size() * sizeof(v[0]);
+      void* at = ip;
+      if (bytes && e == hipSuccess) e = hipMemcpyAsync(at, v.data(), bytes, hipMemcpyHostToDevice, c->stream);
+      ip += pad(bytes);
+      return at;
+    };
+    auto take = [&](size_t doubles) { double* at = (double*)vp; vp += pad(doubles * sizeof(double)); return at; };
+    g = MgDev();
+    g.n_levels = (int)steps.size() + 1;
+    g.lv[0].n = P.n_owned; g.lv[0].blocks = P.bptr[(size_t)P.n_owned];
+    const size_t n0 = (size_t)std::max<int64_t>(P.n_owned * nv, 1);
+    g.ph = take(n0); g.sh = take(n0); g.t0 = take(n0);
+    for (size_t l = 0; l < steps.size(); l++) {
+      const MgLevelHost& L = steps[l];
+      MgLevelDev& D = g.lv[l + 1];
+      D.n = L.n; D.blocks = (int64_t)L.bcol.size();
+      D.agg = (const int32_t*)put(L.agg); D.mptr = (const int64_t*)put(L.mptr); D.member = (const int32_t*)put(L.member);
+      D.bptr = (const int64_t*)put(L.bptr); D.bcol = (const int32_t*)put(L.bcol); D.brow = (const int32_t*)put(L.brow);
+      D.cptr = (const int64_t*)put(L.cptr); D.cidx = (const int32_t*)put(L.cidx); D.cnode = (const int32_t*)put(L.cnode);
+      D.val = take(L.bcol.size() * nv * nv); D.dinv = take((size_t)L.n * nv * nv);
+      D.x = take((size_t)L.n * nv); D.r = take((size_t)L.n * nv); D.t = take((size_t)L.n * nv);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host lists go out of scope
+    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the multigrid lists failed: %s", hipGetErrorString(e));
+    c->ms.mg_ready = true;
+  }
+  g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
+  g.omega = 1e-3 * c->mg_omega_permille;
+  d->mg = &g;
+  return RDC_OK;
+}
+
+int rdc_solve_mg_levels(rdc_ctx* c, int32_t* n_levels, int64_t* nodes, int64_t* blocks, int cap) {
+  if (!c || !n_levels || cap < 0 || (cap > 0 && (!nodes || !blocks))) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
+  *n_levels = c->ms.mg.n_levels;
+  for (int l = 0; l < c->ms.mg.n_levels && l < cap; l++) { nodes[l] = c->ms.mg.lv[l].n; blocks[l] = c->ms.mg.lv[l].blocks; }
+  return RDC_OK;
+}
+
+int rdc_solve_mg_stats(rdc_ctx* c, float* setup_ms, int64_t* level_bytes) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
+  if (setup_ms) *setup_ms = c->ms.mg.setup_ms;
+  if (level_bytes) *level_bytes = (int64_t)(c->buf.solve.mg_idx.bytes + c->buf.solve.mg_val.bytes);
+  return RDC_OK;
+}
+
 int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
@@ -1223,7 +1304,8 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
-  if (p->precond != RDC_PRECOND_NONE && p->precond != RDC_PRECOND_JACOBI && p->precond != RDC_PRECOND_BLOCK_JACOBI)
+  if (p->precond != RDC_PRECOND_NONE && p->precond != RDC_PRECOND_JACOBI && p->precond != RDC_PRECOND_BLOCK_JACOBI &&
+      p->precond != RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
   if (c->ms.prep.n_owned < c->ms.prep.n_node)
     return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
@@ -1238,6 +1320,7 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   if (mixed) c->ms.f32_copy = false;   // rebuilt from the current values by this call
   int rc = solve_view(c, true, mixed, &d);
   if (rc) return rc;
+  if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
   RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
   if (mixed) c->ms.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   return RDC_OK;

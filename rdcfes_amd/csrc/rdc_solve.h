@@ -1,6 +1,7 @@
 // rdc_solve.h — index arithmetic of the node-block CSR pattern and the inverse of a diagonal block, as the kernels of
 // rdc_solve.hip use them.  Host+device like rdc_row.h, so that a CPU build can test exactly this code
-// (tests/host_solve_shim.cpp); free of other headers of the library on purpose.
+// (tests/host_solve_shim.cpp); free of other headers of the library on purpose.  Further down: the host side of the
+// aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -168,6 +169,161 @@ RDC_SOLVE_HD bool scaled_block_f32(const double (&dinv)[NV][NV], const double (&
 // at odd offsets).  voff[n + 1] - voff[n] = nvar * f32_row_stride(nvar, blocks of n).
 RDC_SOLVE_HD int64_t f32_row_stride(int nvar, int64_t blocks) { return ((int64_t)nvar * blocks + 3) & ~(int64_t)3; }
 
+// ---- aggregation multigrid (precond 3).  The fixed numbers of the method, all in one place: ----
+constexpr int MG_AGG_CAP = 8;           // nodes of an aggregate built in pass 1 (root + 7 neighbours)
+constexpr int MG_MIN_FREE = 3;          // free neighbours a free node needs to become a root
+constexpr int MG_COARSEST_NODES = 40;   // no further level below a level of at most this many nodes
+constexpr int MG_MAX_LEVELS = 10;       // levels, the matrix itself (level 0) included
+constexpr int MG_COARSEST_SWEEPS = 8;   // damped block-Jacobi sweeps that stand for the solve on the last level
+constexpr int MG_OMEGA_PERMILLE = 600;  // default damping of the smoother, in thousandths (option "mg_omega")
+
+// out = dinv * a in FP64: the summand of the level-1 Galerkin sum.  Every sum in ascending index order from 0.0, separate
+// multiply and add (scaled_block_f32 without its rounding).  scaled_entry is one entry: row `drow` of dinv, column `acol` of a.
+template <int NV>
+RDC_SOLVE_HD double scaled_entry(const double (&drow)[NV], const double (&acol)[NV]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < NV; q++) s = s + drow[q] * acol[q];
+  return s;
+}
+
+template <int NV>
+RDC_SOLVE_HD void scaled_block(const double (&dinv)[NV][NV], const double (&a)[NV][NV], double (&out)[NV][NV]) {
+#pragma unroll
+  for (int i = 0; i < NV; i++)
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+      double col[NV];
+#pragma unroll
+      for (int q = 0; q < NV; q++) col[q] = a[q][j];
+      out[i][j] = scaled_entry<NV>(dinv[i], col);
+    }
+}
+
+}  // namespace rdc
+
+#include <algorithm>
+#include <vector>
+namespace rdc {
+
+// Aggregates of the node-block graph (n nodes, pattern bptr / bcol, no ghost columns); deterministic, ascending node order.
+// Pass 1: a free node with at least MG_MIN_FREE free neighbours becomes a root and takes the first MG_AGG_CAP - 1 of them.
+// Pass 2: a node still free joins the aggregate of its first neighbour that has one by then (nodes joined earlier in this
+// pass included), or becomes a singleton.  agg[n] = aggregate of node n; returns their number, *n_pass1 = those of pass 1.
+inline int64_t mg_aggregate(int64_t n, const int64_t* bptr, const int32_t* bcol, int32_t* agg, int64_t* n_pass1) {
+  for (int64_t i = 0; i < n; i++) agg[i] = -1;
+  int64_t na = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (agg[i] >= 0) continue;
+    int nfree = 0;
+    for (int64_t k = bptr[i]; k < bptr[i + 1] && nfree < MG_MIN_FREE; k++) nfree += bcol[k] != i && agg[bcol[k]] < 0;
+    if (nfree < MG_MIN_FREE) continue;
+    agg[i] = (int32_t)na;
+    int taken = 0;
+    for (int64_t k = bptr[i]; k < bptr[i + 1] && taken < MG_AGG_CAP - 1; k++)
+      if (bcol[k] != i && agg[bcol[k]] < 0) { agg[bcol[k]] = (int32_t)na; taken++; }
+    na++;
+  }
+  if (n_pass1) *n_pass1 = na;
+  for (int64_t i = 0; i < n; i++) {
+    if (agg[i] >= 0) continue;
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++)
+      if (bcol[k] != i && agg[bcol[k]] >= 0) { agg[i] = agg[bcol[k]]; break; }
+    if (agg[i] < 0) agg[i] = (int32_t)na++;
+  }
+  return na;
+}
+
+// One coarsening step: what takes level l (n_fine nodes) to level l + 1 (n nodes), all lists in ascending order.
+struct MgLevelHost {
+  int64_t n_fine = 0, n = 0, n_pass1 = 0;
+  std::vector<int32_t> agg;      // [n_fine] aggregate of a fine node: prolongation
+  std::vector<int64_t> mptr;     // [n + 1]  members of aggregate I: member[mptr[I] .. mptr[I + 1]): restriction
+  std::vector<int32_t> member;   // [n_fine]
+  std::vector<int64_t> bptr;     // [n + 1]  node-block pattern of the coarse matrix (bcol ascends within a node)
+  std::vector<int32_t> bcol;
+  std::vector<int32_t> brow;     // [coarse blocks] node of a coarse block
+  std::vector<int64_t> cptr;     // [coarse blocks + 1] fine blocks that sum into coarse block c: cidx[cptr[c] .. cptr[c + 1]),
+  std::vector<int32_t> cidx;     // [fine blocks] ... ascending = sorted by (fine node, k); cidx = bptr_fine[node] + k
+  std::vector<int32_t> cnode;    // [fine blocks] ... and the fine node of each (the value layout needs the node's row length)
+};
+
+// false: the coarse level would have 2^31 blocks or more
+inline bool mg_coarsen(int64_t n_fine, const int64_t* bptr, const int32_t* bcol, MgLevelHost& L) {
+  L = MgLevelHost();
+  L.n_fine = n_fine;
+  L.agg.resize((size_t)n_fine);
+  L.n = mg_aggregate(n_fine, bptr, bcol, L.agg.data(), &L.n_pass1);
+  const int64_t na = L.n, nblk = bptr[n_fine];
+  L.mptr.assign((size_t)na + 1, 0);
+  for (int64_t i = 0; i < n_fine; i++) L.mptr[(size_t)L.agg[i] + 1]++;
+  for (int64_t I = 0; I < na; I++) L.mptr[(size_t)I + 1] += L.mptr[(size_t)I];
+  L.member.resize((size_t)n_fine);
+  {
+    std::vector<int64_t> fill(L.mptr.begin(), L.mptr.end() - 1);
+    for (int64_t i = 0; i < n_fine; i++) L.member[(size_t)fill[(size_t)L.agg[i]]++] = (int32_t)i;
+  }
+  // coarse rows: the distinct aggregates of the columns of the members' blocks
+  L.bptr.assign((size_t)na + 1, 0);
+  std::vector<int32_t> row;
+  for (int64_t I = 0; I < na; I++) {
+    row.clear();
+    for (int64_t m = L.mptr[(size_t)I]; m < L.mptr[(size_t)I + 1]; m++)
+      for (int64_t k = bptr[L.member[(size_t)m]]; k < bptr[L.member[(size_t)m] + 1]; k++) row.push_back(L.agg[(size_t)bcol[k]]);
+    std::sort(row.begin(), row.end());
+    row.erase(std::unique(row.begin(), row.end()), row.end());
+    L.bcol.insert(L.bcol.end(), row.begin(), row.end());
+    L.brow.resize(L.bcol.size(), (int32_t)I);
+    L.bptr[(size_t)I + 1] = (int64_t)L.bcol.size();
+    if (L.bcol.size() >= ((size_t)1 << 31)) return false;
+  }
+  // coarse block of every fine block, then the lists by a counting sort (stable: ascending fine block within a coarse one)
+  const int64_t ncb = (int64_t)L.bcol.size();
+  std::vector<int32_t> cmap((size_t)nblk);
+  L.cptr.assign((size_t)ncb + 1, 0);
+  for (int64_t i = 0; i < n_fine; i++) {
+    const int64_t I = L.agg[(size_t)i];
+    const int32_t* r0 = L.bcol.data() + L.bptr[(size_t)I];
+    const int32_t* r1 = L.bcol.data() + L.bptr[(size_t)I + 1];
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
+      const int64_t c = L.bptr[(size_t)I] + (std::lower_bound(r0, r1, L.agg[(size_t)bcol[k]]) - r0);
+      cmap[(size_t)k] = (int32_t)c;
+      L.cptr[(size_t)c + 1]++;
+    }
+  }
+  for (int64_t c = 0; c < ncb; c++) L.cptr[(size_t)c + 1] += L.cptr[(size_t)c];
+  L.cidx.resize((size_t)nblk);
+  L.cnode.resize((size_t)nblk);
+  std::vector<int64_t> fill(L.cptr.begin(), L.cptr.end() - 1);
+  for (int64_t i = 0; i < n_fine; i++)
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
+      const int64_t at = fill[(size_t)cmap[(size_t)k]]++;
+      L.cidx[(size_t)at] = (int32_t)k;
+      L.cnode[(size_t)at] = (int32_t)i;
+    }
+  return true;
+}
+
+// The whole hierarchy below a matrix of n nodes: steps[l] takes level l to level l + 1.  Stops at a level of at most
+// MG_COARSEST_NODES nodes, at MG_MAX_LEVELS levels, or when a coarsening would merge nothing.  false: as mg_coarsen.
+inline bool mg_build(int64_t n, const int64_t* bptr, const int32_t* bcol, std::vector<MgLevelHost>& steps) {
+  steps.clear();
+  if (bptr[n] >= ((int64_t)1 << 31)) return false;
+  while (n > MG_COARSEST_NODES && (int)steps.size() + 1 < MG_MAX_LEVELS) {
+    MgLevelHost L;
+    if (!mg_coarsen(n, bptr, bcol, L)) return false;
+    if (L.n >= n) break;
+    steps.push_back(std::move(L));
+    n = steps.back().n;
+    bptr = steps.back().bptr.data();
+    bcol = steps.back().bcol.data();
+  }
+  return true;
+}
+
 }  // namespace rdc
 
 #if defined(__HIPCC__)
@@ -184,6 +340,27 @@ struct SolveScal {
   int32_t _pad;
 };
 
+// One level of the multigrid hierarchy on the device.  Level 0 is the matrix itself (bptr / bcol only: its values are the
+// context's, its D^-1 the solver's).  A level l >= 1 owns a matrix in the node-block layout, its D_l^-1, three vectors, and
+// the lists that take level l - 1 to it (MgLevelHost of that step).
+struct MgLevelDev {
+  int64_t n = 0, blocks = 0;
+  const int64_t* bptr = nullptr;
+  const int32_t* bcol = nullptr;
+  double *val = nullptr, *dinv = nullptr, *x = nullptr, *r = nullptr, *t = nullptr;
+  const int32_t *agg = nullptr, *member = nullptr, *brow = nullptr, *cidx = nullptr, *cnode = nullptr;
+  const int64_t *mptr = nullptr, *cptr = nullptr;
+};
+
+struct MgDev {
+  int n_levels = 0;                      // level 0 included
+  MgLevelDev lv[MG_MAX_LEVELS];
+  double *ph = nullptr, *sh = nullptr;   // M p and M s of the right-preconditioned iteration (n_owned * nvar each)
+  double* t0 = nullptr;                  // A^ x of the level-0 smoother
+  double omega = 0.0;
+  float setup_ms = 0.0f;                 // out: device time of the Galerkin products and the D_l^-1 of the last solve
+};
+
 // what rdc_csr_matvec / rdc_solve need of a context (rdc_capi.hip fills it)
 struct SolveDev {
   int nvar = 0;
@@ -197,6 +374,7 @@ struct SolveDev {
   float* val32 = nullptr;          // ... and the values, voff[n_owned] floats (layout: f32_row_stride)
   SolveScal* host_rec = nullptr;   // pinned
   hipStream_t stream = nullptr;
+  MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
 };
 
 size_t solve_work_bytes(int nvar, int64_t n_owned);

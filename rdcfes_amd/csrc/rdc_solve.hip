@@ -16,6 +16,12 @@
 // butterfly over the 8 lanes.  No D^-1 epilogue: the copy is already scaled.  Everything that decides or reports (first
 // residual, every confirmation / restart, closing residual, norms) stays on k_spmv + k_residual over the FP64 values.
 //
+// Multigrid (precond 3): a V(1,1) cycle over aggregation levels, applied from the RIGHT (v = A^ M p, t = A^ M s,
+// x += alpha M p + omega M s), so the recurrence residual and everything that decides stay what they are above.  Coarse
+// matrices live in the same node-block layout and go through k_spmv and k_precond_setup as they are; k_galerkin rebuilds
+// their values per solve (a gather in a fixed order: no atomics), k_restrict / k_prolong / k_smooth are the rest of the cycle.
+// The cycle has no inner product and no host round trip.
+//
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
 // device memory.  No floating-point atomics anywhere.
@@ -55,7 +61,7 @@ __device__ __forceinline__ void block_partials(double (&c)[NC], double* __restri
     for (int i = 0; i < NC; i++) out[(size_t)blockIdx.x * NC + i] = ((sh[i][0] + sh[i][1]) + sh[i][2]) + sh[i][3];
 }
 
-// y = A x (EPI 0) or y = D^-1 (A x) with the partials of (y, w) and (y, y) (EPI 1)
+// y = A x (EPI 0), y = D^-1 (A x) with the partials of (y, w) and (y, y) (EPI 1), or y = D^-1 (A x) alone (EPI 2)
 template <int NV, int EPI>
 __global__ __launch_bounds__(256) void k_spmv(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
                                               const double* __restrict__ val, const double* __restrict__ x,
@@ -95,10 +101,12 @@ __global__ __launch_bounds__(256) void k_spmv(const int64_t* __restrict__ bptr, 
 #pragma unroll
       for (int a = 0; a < NV; a++) z = fma(drow[a], acc[a], z);
       y[node * NV + lane] = z;
-      c[0] = z * w[node * NV + lane];
-      c[1] = z * z;
+      if (EPI == 1) {
+        c[0] = z * w[node * NV + lane];
+        c[1] = z * z;
+      }
     }
-    block_partials<2>(c, partials);
+    if (EPI == 1) block_partials<2>(c, partials);
   }
 }
 
@@ -344,10 +352,13 @@ __global__ __launch_bounds__(256) void k_update_s(const double* __restrict__ r, 
 // x += alpha p + omega s, r = s - omega t, partials of (r_hat, r) and ||r||^2.  An entry of x whose update would not be
 // finite (overflow: p, s, t themselves are finite when alpha and omega passed their checks) keeps its value and is counted;
 // the count flags the iteration, so x never holds a NaN or inf that the solver wrote.
+// RIGHT (multigrid): x advances along the preconditioned directions px = M p and sx = M s, r stays s - omega t.
+template <bool RIGHT>
 __global__ __launch_bounds__(256) void k_update_xr(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
                                                    const double* __restrict__ s, const double* __restrict__ t,
                                                    const double* __restrict__ rh, const SolveScal* __restrict__ scal, int64_t n,
-                                                   double* __restrict__ partials) {
+                                                   double* __restrict__ partials, const double* __restrict__ px,
+                                                   const double* __restrict__ sx) {
   if (scal->flag) return;   // uniform: alpha or omega is unusable, x and r stay what they were
   const double alpha = scal->alpha, omega = scal->omega;
   const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
@@ -357,7 +368,7 @@ __global__ __launch_bounds__(256) void k_update_xr(double* __restrict__ x, doubl
     const int64_t i = i0 + q * 256;
     if (i < n) {
       const double si = s[i];
-      const double xn = x[i] + (alpha * p[i] + omega * si);
+      const double xn = RIGHT ? x[i] + (alpha * px[i] + omega * sx[i]) : x[i] + (alpha * p[i] + omega * si);
       if (finite_d(xn)) x[i] = xn;
       else c[2] += 1.0;
       const double ri = si - omega * t[i];
@@ -367,6 +378,105 @@ __global__ __launch_bounds__(256) void k_update_xr(double* __restrict__ x, doubl
     }
   }
   block_partials<3>(c, partials);
+}
+
+// ---- multigrid: Galerkin product, restriction, prolongation, smoother ----
+
+// Values of a coarse level from those of the level above it: coarse block c is the sum of the fine blocks cidx[cptr[c] ..
+// cptr[c + 1]) in list order (ascending fine node, then block).  One thread per (coarse block, entry): thread g of the grid
+// owns entry (a, b) = ((g % NV^2) / NV, g % NV) of coarse block g / NV^2 whatever the launch shape, and adds its
+// contributions from 0.0 in list order: no atomics, two runs bitwise equal.  SCALE (level 0 -> 1): the summand is
+// D^-1_n A_nm (scaled_entry: FP64, ascending, no contraction); the NV lanes of a block column then read the same NV values
+// in one instruction, so the FP64 stream still crosses the memory bus once (non-temporal, as k_scale_f32 reads it).
+template <int NV, bool SCALE>
+__global__ __launch_bounds__(256) void k_galerkin(const int64_t* __restrict__ cptr, const int32_t* __restrict__ cidx,
+                                                  const int32_t* __restrict__ cnode, const int32_t* __restrict__ brow,
+                                                  int64_t coarse_blocks, const int64_t* __restrict__ fbptr,
+                                                  const double* __restrict__ fval, const double* __restrict__ fdinv,
+                                                  const int64_t* __restrict__ cbptr, double* __restrict__ cval) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t c = g / (NV * NV);
+  if (c >= coarse_blocks) return;
+  const int e = (int)(g - c * (NV * NV)), a = e / NV, b = e - a * NV;
+  double s = 0.0;
+  const int64_t i1 = cptr[c + 1];
+  for (int64_t i = cptr[c]; i < i1; i++) {
+    const int64_t n = cnode[i], fb0 = fbptr[n], flen = fbptr[n + 1] - fb0;
+    const double* __restrict__ base = fval + (int64_t)NV * NV * fb0 + ((int64_t)cidx[i] - fb0) * NV + b;   // entry (0, b) of the fine block
+    if (SCALE) {
+      double drow[NV], acol[NV];
+#pragma unroll
+      for (int q = 0; q < NV; q++) {
+        drow[q] = fdinv[(n * NV + a) * NV + q];
+        acol[q] = __builtin_nontemporal_load(base + (int64_t)q * flen * NV);
+      }
+      s = s + scaled_entry<NV>(drow, acol);
+    } else {
+      s = s + __builtin_nontemporal_load(base + (int64_t)a * flen * NV);
+    }
+  }
+  const int64_t I = brow[c], cb0 = cbptr[I], clen = cbptr[I + 1] - cb0;
+  cval[(int64_t)NV * NV * cb0 + ((int64_t)a * clen + (c - cb0)) * NV + b] = s;
+}
+
+// r_c = P^T (r - t) and the first smoothing sweep of the coarse level, x_c = w D_c^-1 r_c: one thread per aggregate, its
+// members in ascending order
+template <int NV>
+__global__ __launch_bounds__(256) void k_restrict(const int64_t* __restrict__ mptr, const int32_t* __restrict__ member,
+                                                  const double* __restrict__ r, const double* __restrict__ t,
+                                                  const double* __restrict__ cdinv, double omega, int64_t n_coarse,
+                                                  double* __restrict__ rc, double* __restrict__ xc) {
+  const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (I >= n_coarse) return;
+  double acc[NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  const int64_t m1 = mptr[I + 1];
+  for (int64_t m = mptr[I]; m < m1; m++) {
+    const int64_t n = member[m];
+#pragma unroll
+    for (int a = 0; a < NV; a++) acc[a] += r[n * NV + a] - t[n * NV + a];
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++) {
+    double z = 0.0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) z = fma(cdinv[(I * NV + a) * NV + q], acc[q], z);
+    rc[I * NV + a] = acc[a];
+    xc[I * NV + a] = omega * z;
+  }
+}
+
+// x += P x_c: one thread per fine unknown, one read of agg[n]
+template <int NV>
+__global__ __launch_bounds__(256) void k_prolong(const int32_t* __restrict__ agg, const double* __restrict__ xc, double* __restrict__ x,
+                                                 int64_t n_fine) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_fine * NV) return;
+  const int64_t n = i / NV;
+  x[i] += xc[(int64_t)agg[n] * NV + (i - n * NV)];
+}
+
+// damped block Jacobi, one thread per unknown: x = w D^-1 r (FIRST) or x += w D^-1 (r - t); IDENT: D = I (level 0, whose
+// operator D^-1 A has the identity on its block diagonal)
+template <int NV, bool IDENT, bool FIRST>
+__global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv, const double* __restrict__ r, const double* __restrict__ t,
+                                                double omega, int64_t n, double* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * NV) return;
+  double z;
+  if (IDENT) {
+    z = FIRST ? r[i] : r[i] - t[i];
+  } else {
+    const int64_t node = i / NV;
+    z = 0.0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) {
+      const double res = FIRST ? r[node * NV + q] : r[node * NV + q] - t[node * NV + q];
+      z = fma(dinv[i * NV + q], res, z);
+    }
+  }
+  x[i] = FIRST ? omega * z : x[i] + omega * z;
 }
 
 struct Work {
@@ -463,6 +573,82 @@ hipError_t setup(const SolveDev& d, const Work& w, int precond, bool f32) {
   return hipGetLastError();
 }
 
+// y = A_l x on level l of the hierarchy: level 0 is D^-1 A on the context's values (or its fp32 copy), no dot product
+template <int NV>
+hipError_t mg_operator(const SolveDev& d, const Work& w, int l, const double* x, double* y, bool f32) {
+  if (l == 0) {
+    if (f32) return spmv_f32<NV>(d, &w, x, y, nullptr);
+    hipLaunchKernelGGL((k_spmv<NV, 2>), dim3((unsigned)w.spmv_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
+                       (const double*)w.dinv, (const double*)nullptr, (double*)nullptr);
+    return hipGetLastError();
+  }
+  const MgLevelDev& L = d.mg->lv[l];
+  hipLaunchKernelGGL((k_spmv<NV, 0>), dim3((unsigned)((L.n + SPMV_NODES - 1) / SPMV_NODES)), dim3(256), 0, d.stream, L.bptr, L.bcol,
+                     (const double*)L.val, x, y, L.n, (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
+  return hipGetLastError();
+}
+
+// x += w D_l^-1 (r - A_l x)
+template <int NV>
+hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, const double* r, double* x, double* t, bool f32) {
+  const MgDev& g = *d.mg;
+  const int64_t n = l == 0 ? d.n_owned : g.lv[l].n;
+  SOLVE_HIP(mg_operator<NV>(d, w, l, x, t, f32));
+  const dim3 grid((unsigned)((n * NV + 255) / 256));
+  if (l == 0)
+    hipLaunchKernelGGL((k_smooth<NV, true, false>), grid, dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
+  else
+    hipLaunchKernelGGL((k_smooth<NV, false, false>), grid, dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
+  return hipGetLastError();
+}
+
+// out = M in: one V(1,1) cycle from a zero start.  Enqueues only; a fixed linear operator for fixed values.
+template <int NV>
+hipError_t mg_cycle(const SolveDev& d, const Work& w, const double* in, double* out, bool f32) {
+  const MgDev& g = *d.mg;
+  const int last = g.n_levels - 1;
+  auto R = [&](int l) { return l == 0 ? in : (const double*)g.lv[l].r; };
+  auto X = [&](int l) { return l == 0 ? out : g.lv[l].x; };
+  auto T = [&](int l) { return l == 0 ? g.t0 : g.lv[l].t; };
+  hipLaunchKernelGGL((k_smooth<NV, true, true>), dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, d.stream, (const double*)nullptr, in,
+                     (const double*)nullptr, g.omega, d.n_owned, out);
+  for (int l = 0; l < last; l++) {   // down: residual of the first sweep, restricted; the coarse level's first sweep rides along
+    const MgLevelDev& C = g.lv[l + 1];
+    SOLVE_HIP(mg_operator<NV>(d, w, l, X(l), T(l), f32));
+    hipLaunchKernelGGL((k_restrict<NV>), dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
+                       (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x);
+  }
+  for (int sweep = 1; sweep < MG_COARSEST_SWEEPS; sweep++) SOLVE_HIP(mg_smooth<NV>(d, w, last, R(last), X(last), T(last), f32));
+  for (int l = last - 1; l >= 0; l--) {   // up: correction, then the second sweep
+    const int64_t n = l == 0 ? d.n_owned : g.lv[l].n;
+    hipLaunchKernelGGL((k_prolong<NV>), dim3((unsigned)((n * NV + 255) / 256)), dim3(256), 0, d.stream, g.lv[l + 1].agg,
+                       (const double*)g.lv[l + 1].x, X(l), n);
+    SOLVE_HIP(mg_smooth<NV>(d, w, l, R(l), X(l), T(l), f32));
+  }
+  return hipGetLastError();
+}
+
+// values and D_l^-1 of every coarse level from the current values (behind setup(): level 1 reads D^-1); counts into bad_blocks
+template <int NV>
+hipError_t mg_setup(const SolveDev& d, const Work& w) {
+  const MgDev& g = *d.mg;
+  for (int l = 1; l < g.n_levels; l++) {
+    const MgLevelDev& C = g.lv[l];
+    const int64_t* fbptr = l == 1 ? d.bptr : g.lv[l - 1].bptr;
+    const double* fval = l == 1 ? d.val : (const double*)g.lv[l - 1].val;
+    const dim3 grid((unsigned)((C.blocks * NV * NV + 255) / 256));
+    if (l == 1)
+      hipLaunchKernelGGL((k_galerkin<NV, true>), grid, dim3(256), 0, d.stream, C.cptr, C.cidx, C.cnode, C.brow, C.blocks, fbptr, fval,
+                         (const double*)w.dinv, C.bptr, C.val);
+    else
+      hipLaunchKernelGGL((k_galerkin<NV, false>), grid, dim3(256), 0, d.stream, C.cptr, C.cidx, C.cnode, C.brow, C.blocks, fbptr, fval,
+                         (const double*)nullptr, C.bptr, C.val);
+    hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, d.stream, C.bptr, C.bcol,
+                       (const double*)C.val, C.n, (int)RDC_PRECOND_BLOCK_JACOBI, C.dinv, w.scal);
+  }
+  return hipGetLastError();
+}
+
 // one BiCGStab iteration; f32: the two operator applications stream the fp32 copy (no D^-1 epilogue, it is in the copy)
 template <int NV>
 hipError_t iteration(const SolveDev& d, const Work& w, double* x, bool f32) {
@@ -474,8 +660,29 @@ hipError_t iteration(const SolveDev& d, const Work& w, double* x, bool f32) {
   hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
   SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, w.s, w.t, w.s) : spmv<NV>(d, &w, w.s, w.t, w.s));     // t = D^-1 A s, (t, s), (t, t)
   SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_OMEGA));
-  hipLaunchKernelGGL(k_update_xr, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
-                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials);
+  hipLaunchKernelGGL(k_update_xr<false>, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
+                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, (const double*)nullptr, (const double*)nullptr);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
+  return read_record(d, w);
+}
+
+// the same iteration with the multigrid cycle applied from the right: the operator sees M p and M s, x advances along them
+template <int NV>
+hipError_t iteration_mg(const SolveDev& d, const Work& w, double* x, bool f32) {
+  const MgDev& g = *d.mg;
+  const dim3 vg((unsigned)w.vec_blocks), vb(256);
+  hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
+  const int64_t op_blocks = f32 ? w.f32_blocks : w.spmv_blocks;
+  SOLVE_HIP(mg_cycle<NV>(d, w, w.p, g.ph, f32));
+  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, g.ph, w.v, w.rh) : spmv<NV>(d, &w, g.ph, w.v, w.rh));   // v = D^-1 A M p, (r_hat, v)
+  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_ALPHA));
+  hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
+  SOLVE_HIP(mg_cycle<NV>(d, w, w.s, g.sh, f32));
+  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, g.sh, w.t, w.s) : spmv<NV>(d, &w, g.sh, w.t, w.s));     // t = D^-1 A M s, (t, s), (t, t)
+  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_OMEGA));
+  hipLaunchKernelGGL(k_update_xr<true>, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
+                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, (const double*)g.ph, (const double*)g.sh);
   SOLVE_HIP(hipGetLastError());
   SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
   return read_record(d, w);
@@ -491,7 +698,21 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
   };
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
-  SOLVE_HIP(setup<NV>(d, w, (int)p.precond, mixed));
+  const bool mg = p.precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
+  SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : (int)p.precond, mixed));
+  hipEvent_t m0 = nullptr, m1 = nullptr;
+  if (mg) {
+    SOLVE_HIP(hipEventCreate(&m0));
+    hipError_t e = hipEventCreate(&m1);
+    if (e == hipSuccess) e = hipEventRecord(m0, d.stream);
+    if (e == hipSuccess) e = mg_setup<NV>(d, w);
+    if (e == hipSuccess) e = hipEventRecord(m1, d.stream);
+    if (e == hipSuccess) e = hipEventSynchronize(m1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&d.mg->setup_ms, m0, m1);
+    (void)hipEventDestroy(m0);
+    if (m1) (void)hipEventDestroy(m1);
+    SOLVE_HIP(e);
+  }
   SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
   info->bad_blocks = rec.bad_blocks;
   const bool f32 = mixed && rec.f32_overflow == 0;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
@@ -514,7 +735,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
       report(rec.flag ? RDC_SOLVE_NOT_FINITE : (std::sqrt(rec.rn2) <= tol ? RDC_SOLVE_CONVERGED : RDC_SOLVE_MAX_ITS));
       return hipSuccess;
     }
-    SOLVE_HIP(iteration<NV>(d, w, x, f32));
+    SOLVE_HIP(mg ? iteration_mg<NV>(d, w, x, f32) : iteration<NV>(d, w, x, f32));
     info->iterations++;
     const bool claims = !(rec.flag & 1) && std::sqrt(rec.rn2) <= tol;
     if (!claims && !rec.flag) continue;

@@ -1,13 +1,17 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2] [--mixed | --ab] [--dump DIR]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--ab [precond|precision]] [--dump DIR]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
 counted on the device after the clamp.  --mixed solves with rdc_solve_mixed (the iteration streams an fp32 copy of D^-1 A;
-matrix_bits in every record says what ran); --ab runs the loop four times from the same initial state on one upload, in the
-order fp64, mixed, mixed, fp64, so that the two kinds are timed in one process on one device.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz)."""
+matrix_bits in every record says what ran).  --precond 3 is the aggregation-multigrid preconditioner: every record then also has
+the device ms the solve spent building the hierarchy (mg_setup_ms, part of solve_ms), its level sizes and the device bytes it
+holds.  --ab runs the loop four times from the same initial state on one upload, so that two kinds of solve are timed in one
+process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, multigrid, block Jacobi (all four fp64, or all
+four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond.  --dump writes the state after the
+last step as DIR/state.npy (+ conn, xyz)."""
 import argparse
 import json
 import sys
@@ -62,6 +66,9 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         out.append(dict(step=k + 1, assembly_ms=asm_ms, solve_ms=info.device_ms, iterations=info.iterations, restarts=info.restarts,
                         reason=info.reason, matrix_bits=info.matrix_bits, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
                         background_nodes=nodes, background_elems=elems))
+        if precond == 3:
+            setup_ms, level_bytes = ctx.mg_stats()
+            out[-1].update(mg_setup_ms=setup_ms, mg_level_bytes=level_bytes, mg_levels=ctx.mg_levels())
     return out
 
 
@@ -73,7 +80,7 @@ def main():
     ap.add_argument("--precond", type=int, default=2)
     ap.add_argument("--max-its", type=int, default=20000)
     ap.add_argument("--mixed", action="store_true")
-    ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision"), default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     import torch
@@ -84,10 +91,15 @@ def main():
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
-        for mixed in ((False, True, True, False) if a.ab else (a.mixed,)):
+        runs = [(a.precond, a.mixed)]
+        if a.ab == "precond":
+            runs = [(pc, a.mixed) for pc in (2, 3, 3, 2)]
+        elif a.ab == "precision":
+            runs = [(a.precond, mixed) for mixed in (False, True, True, False)]
+        for precond, mixed in runs:
             ctx.field_upload(0, u0)
-            print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=a.precond, mixed=mixed)))
-            for rec in run(ctx, conn, p, a.steps, a.rel_tol, a.precond, a.max_its, mixed=mixed):
+            print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed)))
+            for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed):
                 print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
