@@ -43,6 +43,15 @@ struct Buffers {
   DevBuf field[RDC_FIELD_COUNT];
 };
 
+// Linear solve (rdc_solve.hip): what buf.solve holds for the uploaded mesh
+struct SolveState {
+  bool bcol_ready = false;   // bcol holds this mesh's block column list
+  bool voff_ready = false;   // voff / val32 are laid out for this mesh
+  bool f32_copy = false;     // val32 holds a usable fp32 copy (of the values at the time it was built)
+  bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
+  MgDev mg;
+};
+
 // What is only meaningful for the uploaded mesh; rdc_mesh_upload starts from MeshState().
 struct MeshState {
   bool have_mesh = false;
@@ -56,11 +65,8 @@ struct MeshState {
   int scl_interior = -1, scl_n_wg_interior = 0, scl_n_wg = 0;   // "interior_nodes" the lists were built with; leading interior clusters; all clusters
   int64_t scl_part1_nodes = 0;
   size_t scl_max_row_doubles = 0;
-  bool solid_gather_ready = false, rg5_eid_ready = false, bcol_ready = false;   // buf.two_pass, buf.rg2.eid, buf.solve.bcol hold this mesh's lists
-  bool voff_ready = false;           // buf.solve.voff / val32 are laid out for this mesh
-  bool f32_copy = false;             // buf.solve.val32 holds a usable fp32 copy (of the values at the time it was built)
-  bool mg_ready = false;             // buf.solve.mg_idx / mg_val hold this mesh's hierarchy, mg describes it
-  MgDev mg;
+  bool solid_gather_ready = false, rg5_eid_ready = false;   // buf.two_pass, buf.rg2.eid hold this mesh's lists
+  SolveState solve;
   int64_t part1_nodes = -1;          // rows [0, part1_nodes) were complete after the LAST part-1 call (-1: none since the upload)
   bool part1_packed = false;         // part 1 of the current step has packed the owned records (consumed by part 2)
   bool solid_part1_pending = false;
@@ -1152,10 +1158,10 @@ static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
   if (rc) return rc;
   const HostPrep& P = c->ms.prep;
   if (P.nvar != 3 && P.nvar != 5) return fail(c, RDC_ERR_UNSUPPORTED, "the linear solve kernels exist for 3 and 5 unknowns per node, not %d", P.nvar);
-  if (!c->ms.bcol_ready) {
+  if (!c->ms.solve.bcol_ready) {
     if ((rc = dev_upload(c, c->buf.solve.bcol, P.bcol))) return rc;
     RDC_HIP(c, hipStreamSynchronize(c->stream));
-    c->ms.bcol_ready = true;
+    c->ms.solve.bcol_ready = true;
   }
   d->nvar = P.nvar; d->n_owned = P.n_owned; d->n_nodes = P.n_node;
   d->bptr = (const int64_t*)c->buf.mesh.bptr.p; d->bcol = (const int32_t*)c->buf.solve.bcol.p;
@@ -1168,13 +1174,13 @@ static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
     d->host_rec = c->solve_rec;
   }
   if (want_f32) {
-    if (!c->ms.voff_ready) {   // float offset of every owned node's padded rows (rdc_solve.h, f32_row_stride)
+    if (!c->ms.solve.voff_ready) {   // float offset of every owned node's padded rows (rdc_solve.h, f32_row_stride)
       std::vector<int64_t> voff((size_t)P.n_owned + 1, 0);
       for (int64_t n = 0; n < P.n_owned; n++) voff[(size_t)n + 1] = voff[(size_t)n] + P.nvar * f32_row_stride(P.nvar, P.bptr[(size_t)n + 1] - P.bptr[(size_t)n]);
       if ((rc = dev_upload(c, c->buf.solve.voff, voff))) return rc;
       RDC_HIP(c, hipStreamSynchronize(c->stream));
       if ((rc = dev_alloc(c, c->buf.solve.val32, (size_t)voff.back() * sizeof(float)))) return rc;
-      c->ms.voff_ready = true;
+      c->ms.solve.voff_ready = true;
     }
     d->voff = (const int64_t*)c->buf.solve.voff.p;
     d->val32 = (float*)c->buf.solve.val32.p;
@@ -1183,54 +1189,30 @@ static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
 }
 
 // The multigrid hierarchy of the mesh: built on the host and uploaded at the first multigrid solve (rdc_solve.h, mg_build),
-// two allocations carved into the arrays of every level.  d must come from solve_view(want_work).
+// two allocations that mg_place (rdc_solve.h) measures and then carves into the arrays of every level.  d must come from
+// solve_view(want_work).
 static int mg_view(rdc_ctx* c, SolveDev* d) {
   const HostPrep& P = c->ms.prep;
-  MgDev& g = c->ms.mg;
-  if (!c->ms.mg_ready) {
+  MgDev& g = c->ms.solve.mg;
+  if (!c->ms.solve.mg_ready) {
     std::vector<MgLevelHost> steps;
     if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
       return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
-    const int nv = P.nvar;
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-    size_t ibytes = 0, vbytes = 3 * pad((size_t)std::max<int64_t>(P.n_owned * nv, 1) * sizeof(double));
-    for (const MgLevelHost& L : steps) {
-      ibytes += pad(L.agg.size() * 4) + pad(L.mptr.size() * 8) + pad(L.member.size() * 4) + pad(L.bptr.size() * 8) + pad(L.bcol.size() * 4) +
-                pad(L.brow.size() * 4) + pad(L.cptr.size() * 8) + pad(L.cidx.size() * 4) + pad(L.cnode.size() * 4);
-      vbytes += pad(L.bcol.size() * nv * nv * sizeof(double)) + pad((size_t)L.n * nv * nv * sizeof(double)) + 3 * pad((size_t)L.n * nv * sizeof(double));
-    }
+    const int64_t blocks = P.bptr[(size_t)P.n_owned];
+    MgArena idx, val;
+    mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {});   // no bases: measures
     int rc;
-    if ((rc = dev_alloc(c, c->buf.solve.mg_idx, ibytes))) return rc;
-    if ((rc = dev_alloc(c, c->buf.solve.mg_val, vbytes))) return rc;
-    char* ip = (char*)c->buf.solve.mg_idx.p;
-    char* vp = (char*)c->buf.solve.mg_val.p;
+    if ((rc = dev_alloc(c, c->buf.solve.mg_idx, idx.used))) return rc;
+    if ((rc = dev_alloc(c, c->buf.solve.mg_val, val.used))) return rc;
+    idx = MgArena{(char*)c->buf.solve.mg_idx.p};
+    val = MgArena{(char*)c->buf.solve.mg_val.p};
     hipError_t e = hipSuccess;
-    auto put = [&](const auto& v) -> const void* {   // uploads one list, returns where it lies
-      const size_t bytes = v.size() * sizeof(v[0]);
-      void* at = ip;
-      if (bytes && e == hipSuccess) e = hipMemcpyAsync(at, v.data(), bytes, hipMemcpyHostToDevice, c->stream);
-      ip += pad(bytes);
-      return at;
-    };
-    auto take = [&](size_t doubles) { double* at = (double*)vp; vp += pad(doubles * sizeof(double)); return at; };
-    g = MgDev();
-    g.n_levels = (int)steps.size() + 1;
-    g.lv[0].n = P.n_owned; g.lv[0].blocks = P.bptr[(size_t)P.n_owned];
-    const size_t n0 = (size_t)std::max<int64_t>(P.n_owned * nv, 1);
-    g.ph = take(n0); g.sh = take(n0); g.t0 = take(n0);
-    for (size_t l = 0; l < steps.size(); l++) {
-      const MgLevelHost& L = steps[l];
-      MgLevelDev& D = g.lv[l + 1];
-      D.n = L.n; D.blocks = (int64_t)L.bcol.size();
-      D.agg = (const int32_t*)put(L.agg); D.mptr = (const int64_t*)put(L.mptr); D.member = (const int32_t*)put(L.member);
-      D.bptr = (const int64_t*)put(L.bptr); D.bcol = (const int32_t*)put(L.bcol); D.brow = (const int32_t*)put(L.brow);
-      D.cptr = (const int64_t*)put(L.cptr); D.cidx = (const int32_t*)put(L.cidx); D.cnode = (const int32_t*)put(L.cnode);
-      D.val = take(L.bcol.size() * nv * nv); D.dinv = take((size_t)L.n * nv * nv);
-      D.x = take((size_t)L.n * nv); D.r = take((size_t)L.n * nv); D.t = take((size_t)L.n * nv);
-    }
+    mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [&](void* at, const void* list, size_t bytes) {
+      if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
+    });
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host lists go out of scope
     if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the multigrid lists failed: %s", hipGetErrorString(e));
-    c->ms.mg_ready = true;
+    c->ms.solve.mg_ready = true;
   }
   g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
   g.omega = 1e-3 * c->mg_omega_permille;
@@ -1240,16 +1222,16 @@ static int mg_view(rdc_ctx* c, SolveDev* d) {
 
 int rdc_solve_mg_levels(rdc_ctx* c, int32_t* n_levels, int64_t* nodes, int64_t* blocks, int cap) {
   if (!c || !n_levels || cap < 0 || (cap > 0 && (!nodes || !blocks))) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
-  *n_levels = c->ms.mg.n_levels;
-  for (int l = 0; l < c->ms.mg.n_levels && l < cap; l++) { nodes[l] = c->ms.mg.lv[l].n; blocks[l] = c->ms.mg.lv[l].blocks; }
+  if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
+  *n_levels = c->ms.solve.mg.n_levels;
+  for (int l = 0; l < c->ms.solve.mg.n_levels && l < cap; l++) { nodes[l] = c->ms.solve.mg.lv[l].n; blocks[l] = c->ms.solve.mg.lv[l].blocks; }
   return RDC_OK;
 }
 
 int rdc_solve_mg_stats(rdc_ctx* c, float* setup_ms, int64_t* level_bytes) {
   if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
-  if (setup_ms) *setup_ms = c->ms.mg.setup_ms;
+  if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
+  if (setup_ms) *setup_ms = c->ms.solve.mg.setup_ms;
   if (level_bytes) *level_bytes = (int64_t)(c->buf.solve.mg_idx.bytes + c->buf.solve.mg_val.bytes);
   return RDC_OK;
 }
@@ -1266,12 +1248,16 @@ int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
   return RDC_OK;
 }
 
+static bool known_precond(int precond, bool with_multigrid) {
+  return precond == RDC_PRECOND_NONE || precond == RDC_PRECOND_JACOBI || precond == RDC_PRECOND_BLOCK_JACOBI ||
+         (with_multigrid && precond == RDC_PRECOND_MULTIGRID);
+}
+
 int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (precond != RDC_PRECOND_NONE && precond != RDC_PRECOND_JACOBI && precond != RDC_PRECOND_BLOCK_JACOBI)
-    return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
-  c->ms.f32_copy = false;
+  if (!known_precond(precond, false)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
+  c->ms.solve.f32_copy = false;
   SolveDev d;
   int rc = solve_view(c, true, true, &d);
   if (rc) return rc;
@@ -1279,7 +1265,7 @@ int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
   if (c->ms.prep.n_owned > 0) RDC_HIP(c, solve_scale_f32(d, precond, &bad, &overflow));
   if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks are not invertible: no fp32 copy", bad);
   if (overflow > 0) return fail(c, RDC_ERR_INVALID, "%d blocks of D^-1 A hold an entry that is not finite in fp32: no fp32 copy", overflow);
-  c->ms.f32_copy = true;
+  c->ms.solve.f32_copy = true;
   return RDC_OK;
 }
 
@@ -1287,7 +1273,7 @@ int rdc_csr_matvec_f32(rdc_ctx* c, const double* d_x, double* d_y) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (!c->ms.f32_copy) return fail(c, RDC_ERR_INVALID, "this mesh has no fp32 copy: call rdc_csr_scale_f32 or rdc_solve_mixed first");
+  if (!c->ms.solve.f32_copy) return fail(c, RDC_ERR_INVALID, "this mesh has no fp32 copy: call rdc_csr_scale_f32 or rdc_solve_mixed first");
   if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
   SolveDev d;
   int rc = solve_view(c, false, true, &d);
@@ -1304,9 +1290,7 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
-  if (p->precond != RDC_PRECOND_NONE && p->precond != RDC_PRECOND_JACOBI && p->precond != RDC_PRECOND_BLOCK_JACOBI &&
-      p->precond != RDC_PRECOND_MULTIGRID)
-    return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
   if (c->ms.prep.n_owned < c->ms.prep.n_node)
     return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
                 "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
@@ -1317,12 +1301,12 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
     return RDC_OK;
   }
   SolveDev d;
-  if (mixed) c->ms.f32_copy = false;   // rebuilt from the current values by this call
+  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
   int rc = solve_view(c, true, mixed, &d);
   if (rc) return rc;
   if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
   RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
-  if (mixed) c->ms.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
+  if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   return RDC_OK;
 }
 

@@ -1,7 +1,8 @@
 // rdc_solve.h — index arithmetic of the node-block CSR pattern and the inverse of a diagonal block, as the kernels of
 // rdc_solve.hip use them.  Host+device like rdc_row.h, so that a CPU build can test exactly this code
 // (tests/host_solve_shim.cpp); free of other headers of the library on purpose.  Further down: the host side of the
-// aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp).
+// aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp) and
+// the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -324,22 +325,6 @@ inline bool mg_build(int64_t n, const int64_t* bptr, const int32_t* bcol, std::v
   return true;
 }
 
-}  // namespace rdc
-
-#if defined(__HIPCC__)
-#include "../../include/rdc_assembly.h"
-namespace rdc {
-
-// scalars of the iteration: they live in device memory and are consumed there; the host reads one copy per iteration
-struct SolveScal {
-  double rho, alpha, omega, beta;
-  double rn2, rn2_plain, bn2, bn2_plain;   // ||r||^2 of the recurrence (or of the true residual after k_residual), plain form, rhs norms
-  int32_t flag;                            // bit 0: alpha / omega / a norm is zero or not finite; bit 1: rho == 0
-  int32_t bad_blocks;
-  int32_t f32_overflow;                    // blocks of the fp32 copy that hold an entry which is not finite in fp32 (k_scale_f32)
-  int32_t _pad;
-};
-
 // One level of the multigrid hierarchy on the device.  Level 0 is the matrix itself (bptr / bcol only: its values are the
 // context's, its D^-1 the solver's).  A level l >= 1 owns a matrix in the node-block layout, its D_l^-1, three vectors, and
 // the lists that take level l - 1 to it (MgLevelHost of that step).
@@ -359,6 +344,65 @@ struct MgDev {
   double* t0 = nullptr;                  // A^ x of the level-0 smoother
   double omega = 0.0;
   float setup_ms = 0.0f;                 // out: device time of the Galerkin products and the D_l^-1 of the last solve
+};
+
+// The two device arenas of a hierarchy, stated once: `idx` holds every list of every step, `val` the vectors of the iteration and
+// every matrix / D_l^-1 / vector of the levels; each array starts MG_ALIGN-aligned.  mg_place walks the levels once and fills `g`.
+// Arenas without a base measure: `used` ends at the bytes to allocate and every pointer of `g` stays null.  With a base (of at
+// least the measured bytes) they place: `g` points into them, and upload(at, source, bytes) is called for every list that is not empty.
+constexpr size_t MG_ALIGN = 256;
+
+struct MgArena {
+  char* base = nullptr;
+  size_t used = 0;
+  void* take(size_t bytes) {
+    void* at = base ? base + used : nullptr;
+    used += (bytes + MG_ALIGN - 1) & ~(MG_ALIGN - 1);
+    return at;
+  }
+};
+
+template <class Upload>
+inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_owned, int64_t blocks, MgArena& idx, MgArena& val,
+                     MgDev& g, Upload&& upload) {
+  auto list = [&](const auto& v) {
+    const size_t bytes = v.size() * sizeof(v[0]);
+    void* at = idx.take(bytes);
+    if (at && bytes) upload(at, (const void*)v.data(), bytes);
+    return (decltype(v.data()))at;
+  };
+  auto vec = [&](int64_t doubles) { return (double*)val.take((size_t)doubles * sizeof(double)); };
+  g = MgDev();
+  g.n_levels = (int)steps.size() + 1;
+  g.lv[0].n = n_owned; g.lv[0].blocks = blocks;
+  const int64_t n0 = std::max<int64_t>(n_owned * nvar, 1);
+  g.ph = vec(n0); g.sh = vec(n0); g.t0 = vec(n0);
+  for (size_t l = 0; l < steps.size(); l++) {
+    const MgLevelHost& L = steps[l];
+    MgLevelDev& D = g.lv[l + 1];
+    D.n = L.n; D.blocks = (int64_t)L.bcol.size();
+    D.agg = list(L.agg); D.mptr = list(L.mptr); D.member = list(L.member);
+    D.bptr = list(L.bptr); D.bcol = list(L.bcol); D.brow = list(L.brow);
+    D.cptr = list(L.cptr); D.cidx = list(L.cidx); D.cnode = list(L.cnode);
+    D.val = vec(D.blocks * nvar * nvar); D.dinv = vec(L.n * nvar * nvar);
+    D.x = vec(L.n * nvar); D.r = vec(L.n * nvar); D.t = vec(L.n * nvar);
+  }
+}
+
+}  // namespace rdc
+
+#if defined(__HIPCC__)
+#include "../../include/rdc_assembly.h"
+namespace rdc {
+
+// scalars of the iteration: they live in device memory and are consumed there; the host reads one copy per iteration
+struct SolveScal {
+  double rho, alpha, omega, beta;
+  double rn2, rn2_plain, bn2, bn2_plain;   // ||r||^2 of the recurrence (or of the true residual after k_residual), plain form, rhs norms
+  int32_t flag;                            // bit 0: alpha / omega / a norm is zero or not finite; bit 1: rho == 0
+  int32_t bad_blocks;
+  int32_t f32_overflow;                    // blocks of the fp32 copy that hold an entry which is not finite in fp32 (k_scale_f32)
+  int32_t _pad;
 };
 
 // what rdc_csr_matvec / rdc_solve need of a context (rdc_capi.hip fills it)

@@ -25,8 +25,12 @@
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
 // device memory.  No floating-point atomics anywhere.
+//
+// Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy and multigrid cycle are arguments), `apply`
+// the one entry to y = A_l x on any level in any form, `carve` the one statement of the work buffer's layout.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "rdc_solve.h"
 
@@ -479,65 +483,106 @@ __global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv,
   x[i] = FIRST ? omega * z : x[i] + omega * z;
 }
 
-struct Work {
-  double *r, *rh, *p, *v, *s, *t, *dinv, *partials;
-  SolveScal* scal;
-  int64_t n, spmv_blocks, f32_blocks, vec_blocks, node_blocks;
-};
+// First use of every kernel instantiation.  A code object lists template instantiations by first use; this list keeps the order
+// they have had since each was added, whatever order the launch code below uses them in, so that the device assembly of two
+// revisions can be compared byte for byte.
+#define KERNELS_OF(NV)                                                                                                          \
+  (const void*)k_galerkin<NV, true>, (const void*)k_galerkin<NV, false>, (const void*)k_residual<NV>,                            \
+  (const void*)k_smooth<NV, true, true>, (const void*)k_spmv<NV, 2>, (const void*)k_restrict<NV>,                                \
+  (const void*)k_smooth<NV, true, false>, (const void*)k_smooth<NV, false, false>, (const void*)k_prolong<NV>
+[[maybe_unused]] const void* const KERNEL_ORDER[] = {
+    (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
+    (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
+    (const void*)k_precond_setup<3>, (const void*)k_scale_f32<3>, (const void*)k_precond_setup<5>, (const void*)k_scale_f32<5>,
+    KERNELS_OF(3), (const void*)k_update_xr<true>, (const void*)k_update_xr<false>, KERNELS_OF(5)};
+#undef KERNELS_OF
 
-int64_t partial_doubles(int64_t n_owned, int nvar) {
-  const int64_t a = 2 * ((n_owned + SPMV_NODES - 1) / SPMV_NODES), b = 4 * ((n_owned + 255) / 256),
-                c = 3 * ((n_owned * nvar + VEC_PER_BLOCK - 1) / VEC_PER_BLOCK);
-  return std::max(std::max(a, b), c) + 8;
-}
+// ---- host side.  Launch shapes: every grid size has its formula here and nowhere else ----
+enum Form { PLAIN, SCALED, F32 };   // what the fine operator applies: A, D^-1 A (both on the FP64 values), or the fp32 copy of D^-1 A
 
-Work carve(const SolveDev& d) {
-  Work w;
-  w.n = d.n_owned * d.nvar;
-  const int64_t n = std::max<int64_t>(w.n, 1);
-  double* q = d.work;
-  w.r = q; q += n; w.rh = q; q += n; w.p = q; q += n; w.v = q; q += n; w.s = q; q += n; w.t = q; q += n;
-  w.dinv = q; q += n * d.nvar;
-  w.partials = q; q += partial_doubles(d.n_owned, d.nvar);
-  w.scal = (SolveScal*)q;
-  w.spmv_blocks = (d.n_owned + SPMV_NODES - 1) / SPMV_NODES;
-  w.f32_blocks = (d.n_owned + F32_NODES - 1) / F32_NODES;
-  w.vec_blocks = (w.n + VEC_PER_BLOCK - 1) / VEC_PER_BLOCK;
-  w.node_blocks = (d.n_owned + 255) / 256;
-  return w;
-}
-
-template <int NV>
-hipError_t spmv(const SolveDev& d, const Work* w, const double* x, double* y, const double* dot_with) {
-  const int64_t blocks = (d.n_owned + SPMV_NODES - 1) / SPMV_NODES;
-  if (blocks == 0) return hipSuccess;
-  if (dot_with)
-    hipLaunchKernelGGL((k_spmv<NV, 1>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
-                       (const double*)w->dinv, dot_with, w->partials);
-  else
-    hipLaunchKernelGGL((k_spmv<NV, 0>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
-                       (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
-  return hipGetLastError();
-}
-
-template <int NV>
-hipError_t spmv_f32(const SolveDev& d, const Work* w, const double* x, double* y, const double* dot_with) {
-  const int64_t blocks = (d.n_owned + F32_NODES - 1) / F32_NODES;
-  if (blocks == 0) return hipSuccess;
-  if (dot_with)
-    hipLaunchKernelGGL((k_spmv_f32<NV, 1>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.voff,
-                       (const float*)d.val32, x, y, d.n_owned, dot_with, w->partials);
-  else
-    hipLaunchKernelGGL((k_spmv_f32<NV, 0>), dim3((unsigned)blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.voff,
-                       (const float*)d.val32, x, y, d.n_owned, (const double*)nullptr, (double*)nullptr);
-  return hipGetLastError();
-}
+int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+int64_t op_blocks(int64_t nodes, Form form) { return cdiv(nodes, form == F32 ? F32_NODES : SPMV_NODES); }   // k_spmv, k_spmv_f32, k_scale_f32
+int64_t vec_blocks(int64_t entries) { return cdiv(entries, VEC_PER_BLOCK); }                                  // k_update_*
+dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
 
 #define SOLVE_HIP(call)                 \
   do {                                  \
     const hipError_t e_ = (call);       \
     if (e_ != hipSuccess) return e_;    \
   } while (0)
+
+// f(std::integral_constant<int, nvar>) for the unknowns per node the kernels are instantiated for
+template <class F>
+hipError_t by_nvar(int nvar, F&& f) {
+  if (nvar == 3) return f(std::integral_constant<int, 3>());
+  if (nvar == 5) return f(std::integral_constant<int, 5>());
+  return hipErrorInvalidValue;
+}
+
+// device time, in *ms, of what body() enqueues on the stream; returns behind it
+template <class F>
+hipError_t timed(hipStream_t stream, float* ms, F&& body) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SOLVE_HIP(hipEventCreate(&e0));
+  hipError_t e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = hipEventRecord(e0, stream);
+  if (e == hipSuccess) e = body();
+  if (e == hipSuccess) e = hipEventRecord(e1, stream);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return e;
+}
+
+// The work buffer of a solve: the one statement of its layout.  Without a base nothing is placed and `bytes` is what to allocate.
+struct Work {
+  double *r, *rh, *p, *v, *s, *t, *dinv, *partials;
+  SolveScal* scal;
+  int64_t n, vec_blocks, node_blocks;
+  size_t bytes;
+};
+
+Work carve(int nvar, int64_t n_owned, double* base) {
+  Work w;
+  w.n = n_owned * nvar;
+  w.vec_blocks = vec_blocks(w.n);
+  w.node_blocks = cdiv(n_owned, 256);
+  const int64_t n = std::max<int64_t>(w.n, 1);
+  // the largest set of partials a kernel leaves: (k_spmv, EPI 1), k_residual, k_update_xr
+  const int64_t partials = std::max(std::max(2 * op_blocks(n_owned, SCALED), 4 * w.node_blocks), 3 * w.vec_blocks) + 8;
+  int64_t used = 0;
+  auto take = [&](int64_t doubles) { double* at = base ? base + used : nullptr; used += doubles; return at; };
+  w.r = take(n); w.rh = take(n); w.p = take(n); w.v = take(n); w.s = take(n); w.t = take(n);
+  w.dinv = take(n * nvar);
+  w.partials = take(partials);
+  w.scal = (SolveScal*)take(0);
+  w.bytes = (size_t)used * sizeof(double) + sizeof(SolveScal);
+  return w;
+}
+
+// y = A_l x on level l of the hierarchy, the one entry to the three SpMV kernels.  Level 0 is the context's matrix in the form
+// asked for; a level below owns one matrix (PLAIN whatever `form` says).  dot_with: also the partials of (y, dot_with) and
+// (y, y) (SCALED and F32 only).  PLAIN and F32 without a dot product need no Work.
+template <int NV>
+hipError_t apply(const SolveDev& d, const Work* w, int l, Form form, const double* x, double* y, const double* dot_with) {
+  const MgLevelDev* L = l ? &d.mg->lv[l] : nullptr;
+  if (L) form = PLAIN;
+  if (form == PLAIN && dot_with) return hipErrorInvalidValue;
+  const int64_t n = L ? L->n : d.n_owned;
+  const dim3 grid((unsigned)op_blocks(n, form)), block(256);
+  if (!grid.x) return hipSuccess;
+  double* partials = dot_with ? w->partials : nullptr;
+  if (form == F32) {
+    hipLaunchKernelGGL((dot_with ? k_spmv_f32<NV, 1> : k_spmv_f32<NV, 0>), grid, block, 0, d.stream, d.bptr, d.bcol, d.voff,
+                       (const float*)d.val32, x, y, n, dot_with, partials);
+  } else {
+    hipLaunchKernelGGL((form == PLAIN ? k_spmv<NV, 0> : dot_with ? k_spmv<NV, 1> : k_spmv<NV, 2>), grid, block, 0, d.stream,
+                       L ? L->bptr : d.bptr, L ? L->bcol : d.bcol, L ? (const double*)L->val : d.val, x, y, n,
+                       form == PLAIN ? (const double*)nullptr : (const double*)w->dinv, dot_with, partials);
+  }
+  return hipGetLastError();
+}
 
 hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage) {
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage, w.scal);
@@ -553,7 +598,7 @@ hipError_t read_record(const SolveDev& d, const Work& w) {
 // true residual of x: r = r_hat = D^-1 (b - A x), p = v = 0, scalars as at the start; this is also the restart
 template <int NV>
 hipError_t residual(const SolveDev& d, const Work& w, const double* x, double scale) {
-  SOLVE_HIP(spmv<NV>(d, &w, x, w.t, nullptr));
+  SOLVE_HIP(apply<NV>(d, &w, 0, PLAIN, x, w.t, nullptr));
   hipLaunchKernelGGL((k_residual<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.rhs, scale, (const double*)w.t,
                      (const double*)w.dinv, w.r, w.rh, w.p, w.v, d.n_owned, w.partials);
   SOLVE_HIP(hipGetLastError());
@@ -568,62 +613,45 @@ hipError_t setup(const SolveDev& d, const Work& w, int precond, bool f32) {
   hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, d.n_owned,
                      precond, w.dinv, w.scal);
   if (f32)
-    hipLaunchKernelGGL((k_scale_f32<NV>), dim3((unsigned)w.f32_blocks), dim3(256), 0, d.stream, d.bptr, d.voff, d.val,
+    hipLaunchKernelGGL((k_scale_f32<NV>), dim3((unsigned)op_blocks(d.n_owned, F32)), dim3(256), 0, d.stream, d.bptr, d.voff, d.val,
                        (const double*)w.dinv, d.n_owned, d.val32, w.scal);
-  return hipGetLastError();
-}
-
-// y = A_l x on level l of the hierarchy: level 0 is D^-1 A on the context's values (or its fp32 copy), no dot product
-template <int NV>
-hipError_t mg_operator(const SolveDev& d, const Work& w, int l, const double* x, double* y, bool f32) {
-  if (l == 0) {
-    if (f32) return spmv_f32<NV>(d, &w, x, y, nullptr);
-    hipLaunchKernelGGL((k_spmv<NV, 2>), dim3((unsigned)w.spmv_blocks), dim3(256), 0, d.stream, d.bptr, d.bcol, d.val, x, y, d.n_owned,
-                       (const double*)w.dinv, (const double*)nullptr, (double*)nullptr);
-    return hipGetLastError();
-  }
-  const MgLevelDev& L = d.mg->lv[l];
-  hipLaunchKernelGGL((k_spmv<NV, 0>), dim3((unsigned)((L.n + SPMV_NODES - 1) / SPMV_NODES)), dim3(256), 0, d.stream, L.bptr, L.bcol,
-                     (const double*)L.val, x, y, L.n, (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
   return hipGetLastError();
 }
 
 // x += w D_l^-1 (r - A_l x)
 template <int NV>
-hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, const double* r, double* x, double* t, bool f32) {
+hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, double* t) {
   const MgDev& g = *d.mg;
-  const int64_t n = l == 0 ? d.n_owned : g.lv[l].n;
-  SOLVE_HIP(mg_operator<NV>(d, w, l, x, t, f32));
-  const dim3 grid((unsigned)((n * NV + 255) / 256));
+  const int64_t n = g.lv[l].n;
+  SOLVE_HIP(apply<NV>(d, &w, l, form, x, t, nullptr));
   if (l == 0)
-    hipLaunchKernelGGL((k_smooth<NV, true, false>), grid, dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
+    hipLaunchKernelGGL((k_smooth<NV, true, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
   else
-    hipLaunchKernelGGL((k_smooth<NV, false, false>), grid, dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
+    hipLaunchKernelGGL((k_smooth<NV, false, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
   return hipGetLastError();
 }
 
 // out = M in: one V(1,1) cycle from a zero start.  Enqueues only; a fixed linear operator for fixed values.
 template <int NV>
-hipError_t mg_cycle(const SolveDev& d, const Work& w, const double* in, double* out, bool f32) {
+hipError_t mg_cycle(const SolveDev& d, const Work& w, Form form, const double* in, double* out) {
   const MgDev& g = *d.mg;
   const int last = g.n_levels - 1;
   auto R = [&](int l) { return l == 0 ? in : (const double*)g.lv[l].r; };
   auto X = [&](int l) { return l == 0 ? out : g.lv[l].x; };
   auto T = [&](int l) { return l == 0 ? g.t0 : g.lv[l].t; };
-  hipLaunchKernelGGL((k_smooth<NV, true, true>), dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, d.stream, (const double*)nullptr, in,
+  hipLaunchKernelGGL((k_smooth<NV, true, true>), per_thread(w.n), dim3(256), 0, d.stream, (const double*)nullptr, in,
                      (const double*)nullptr, g.omega, d.n_owned, out);
   for (int l = 0; l < last; l++) {   // down: residual of the first sweep, restricted; the coarse level's first sweep rides along
     const MgLevelDev& C = g.lv[l + 1];
-    SOLVE_HIP(mg_operator<NV>(d, w, l, X(l), T(l), f32));
-    hipLaunchKernelGGL((k_restrict<NV>), dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
+    SOLVE_HIP(apply<NV>(d, &w, l, form, X(l), T(l), nullptr));
+    hipLaunchKernelGGL((k_restrict<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
                        (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x);
   }
-  for (int sweep = 1; sweep < MG_COARSEST_SWEEPS; sweep++) SOLVE_HIP(mg_smooth<NV>(d, w, last, R(last), X(last), T(last), f32));
+  for (int sweep = 1; sweep < MG_COARSEST_SWEEPS; sweep++) SOLVE_HIP(mg_smooth<NV>(d, w, last, form, R(last), X(last), T(last)));
   for (int l = last - 1; l >= 0; l--) {   // up: correction, then the second sweep
-    const int64_t n = l == 0 ? d.n_owned : g.lv[l].n;
-    hipLaunchKernelGGL((k_prolong<NV>), dim3((unsigned)((n * NV + 255) / 256)), dim3(256), 0, d.stream, g.lv[l + 1].agg,
-                       (const double*)g.lv[l + 1].x, X(l), n);
-    SOLVE_HIP(mg_smooth<NV>(d, w, l, R(l), X(l), T(l), f32));
+    const int64_t n = g.lv[l].n;
+    hipLaunchKernelGGL((k_prolong<NV>), per_thread(n * NV), dim3(256), 0, d.stream, g.lv[l + 1].agg, (const double*)g.lv[l + 1].x, X(l), n);
+    SOLVE_HIP(mg_smooth<NV>(d, w, l, form, R(l), X(l), T(l)));
   }
   return hipGetLastError();
 }
@@ -636,53 +664,37 @@ hipError_t mg_setup(const SolveDev& d, const Work& w) {
     const MgLevelDev& C = g.lv[l];
     const int64_t* fbptr = l == 1 ? d.bptr : g.lv[l - 1].bptr;
     const double* fval = l == 1 ? d.val : (const double*)g.lv[l - 1].val;
-    const dim3 grid((unsigned)((C.blocks * NV * NV + 255) / 256));
+    const dim3 grid = per_thread(C.blocks * NV * NV);
     if (l == 1)
       hipLaunchKernelGGL((k_galerkin<NV, true>), grid, dim3(256), 0, d.stream, C.cptr, C.cidx, C.cnode, C.brow, C.blocks, fbptr, fval,
                          (const double*)w.dinv, C.bptr, C.val);
     else
       hipLaunchKernelGGL((k_galerkin<NV, false>), grid, dim3(256), 0, d.stream, C.cptr, C.cidx, C.cnode, C.brow, C.blocks, fbptr, fval,
                          (const double*)nullptr, C.bptr, C.val);
-    hipLaunchKernelGGL((k_precond_setup<NV>), dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, d.stream, C.bptr, C.bcol,
+    hipLaunchKernelGGL((k_precond_setup<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.bptr, C.bcol,
                        (const double*)C.val, C.n, (int)RDC_PRECOND_BLOCK_JACOBI, C.dinv, w.scal);
   }
   return hipGetLastError();
 }
 
-// one BiCGStab iteration; f32: the two operator applications stream the fp32 copy (no D^-1 epilogue, it is in the copy)
+// One BiCGStab iteration.  form: what the operator applications stream (F32: the copy, which needs no D^-1 epilogue).
+// mg: the multigrid cycle is applied from the right, so the operator sees M p and M s and x advances along them.
 template <int NV>
-hipError_t iteration(const SolveDev& d, const Work& w, double* x, bool f32) {
+hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, bool mg) {
   const dim3 vg((unsigned)w.vec_blocks), vb(256);
+  const int64_t op_parts = op_blocks(d.n_owned, form);
+  const double* px = mg ? d.mg->ph : w.p;
+  const double* sx = mg ? d.mg->sh : w.s;
   hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
-  const int64_t op_blocks = f32 ? w.f32_blocks : w.spmv_blocks;
-  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, w.p, w.v, w.rh) : spmv<NV>(d, &w, w.p, w.v, w.rh));   // v = D^-1 A p, (r_hat, v)
-  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_ALPHA));
+  if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.p, d.mg->ph));
+  SOLVE_HIP(apply<NV>(d, &w, 0, form, px, w.v, w.rh));   // v = D^-1 A [M] p, (r_hat, v)
+  SOLVE_HIP(finalize(d, w, op_parts, 2, STAGE_ALPHA));
   hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
-  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, w.s, w.t, w.s) : spmv<NV>(d, &w, w.s, w.t, w.s));     // t = D^-1 A s, (t, s), (t, t)
-  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_OMEGA));
-  hipLaunchKernelGGL(k_update_xr<false>, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
-                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, (const double*)nullptr, (const double*)nullptr);
-  SOLVE_HIP(hipGetLastError());
-  SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
-  return read_record(d, w);
-}
-
-// the same iteration with the multigrid cycle applied from the right: the operator sees M p and M s, x advances along them
-template <int NV>
-hipError_t iteration_mg(const SolveDev& d, const Work& w, double* x, bool f32) {
-  const MgDev& g = *d.mg;
-  const dim3 vg((unsigned)w.vec_blocks), vb(256);
-  hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
-  const int64_t op_blocks = f32 ? w.f32_blocks : w.spmv_blocks;
-  SOLVE_HIP(mg_cycle<NV>(d, w, w.p, g.ph, f32));
-  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, g.ph, w.v, w.rh) : spmv<NV>(d, &w, g.ph, w.v, w.rh));   // v = D^-1 A M p, (r_hat, v)
-  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_ALPHA));
-  hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
-  SOLVE_HIP(mg_cycle<NV>(d, w, w.s, g.sh, f32));
-  SOLVE_HIP(f32 ? spmv_f32<NV>(d, &w, g.sh, w.t, w.s) : spmv<NV>(d, &w, g.sh, w.t, w.s));     // t = D^-1 A M s, (t, s), (t, t)
-  SOLVE_HIP(finalize(d, w, op_blocks, 2, STAGE_OMEGA));
-  hipLaunchKernelGGL(k_update_xr<true>, vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s, (const double*)w.t,
-                     (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, (const double*)g.ph, (const double*)g.sh);
+  if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.s, d.mg->sh));
+  SOLVE_HIP(apply<NV>(d, &w, 0, form, sx, w.t, w.s));    // t = D^-1 A [M] s, (t, s), (t, t)
+  SOLVE_HIP(finalize(d, w, op_parts, 2, STAGE_OMEGA));
+  hipLaunchKernelGGL((mg ? k_update_xr<true> : k_update_xr<false>), vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s,
+                     (const double*)w.t, (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, mg ? px : nullptr, mg ? sx : nullptr);
   SOLVE_HIP(hipGetLastError());
   SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
   return read_record(d, w);
@@ -690,7 +702,7 @@ hipError_t iteration_mg(const SolveDev& d, const Work& w, double* x, bool f32) {
 
 template <int NV>
 hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
-  const Work w = carve(d);
+  const Work w = carve(d.nvar, d.n_owned, d.work);
   const SolveScal& rec = *d.host_rec;
   auto report = [&](int reason) {
     info->reason = reason;
@@ -700,23 +712,11 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
   const bool mg = p.precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
   SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : (int)p.precond, mixed));
-  hipEvent_t m0 = nullptr, m1 = nullptr;
-  if (mg) {
-    SOLVE_HIP(hipEventCreate(&m0));
-    hipError_t e = hipEventCreate(&m1);
-    if (e == hipSuccess) e = hipEventRecord(m0, d.stream);
-    if (e == hipSuccess) e = mg_setup<NV>(d, w);
-    if (e == hipSuccess) e = hipEventRecord(m1, d.stream);
-    if (e == hipSuccess) e = hipEventSynchronize(m1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&d.mg->setup_ms, m0, m1);
-    (void)hipEventDestroy(m0);
-    if (m1) (void)hipEventDestroy(m1);
-    SOLVE_HIP(e);
-  }
+  if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
   SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
   info->bad_blocks = rec.bad_blocks;
-  const bool f32 = mixed && rec.f32_overflow == 0;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
-  info->matrix_bits = f32 ? 32 : 64;
+  const Form form = mixed && rec.f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
+  info->matrix_bits = form == F32 ? 32 : 64;
   if (rec.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
   if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
   if (rec.bn2 == 0.0) {   // b = 0: x = 0
@@ -735,7 +735,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
       report(rec.flag ? RDC_SOLVE_NOT_FINITE : (std::sqrt(rec.rn2) <= tol ? RDC_SOLVE_CONVERGED : RDC_SOLVE_MAX_ITS));
       return hipSuccess;
     }
-    SOLVE_HIP(mg ? iteration_mg<NV>(d, w, x, f32) : iteration<NV>(d, w, x, f32));
+    SOLVE_HIP(iteration<NV>(d, w, x, form, mg));
     info->iterations++;
     const bool claims = !(rec.flag & 1) && std::sqrt(rec.rn2) <= tol;
     if (!claims && !rec.flag) continue;
@@ -754,27 +754,20 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
 
 }  // namespace
 
-size_t solve_work_bytes(int nvar, int64_t n_owned) {
-  const int64_t n = std::max<int64_t>(n_owned * nvar, 1);
-  return (size_t)(6 * n + n * nvar + partial_doubles(n_owned, nvar)) * sizeof(double) + sizeof(SolveScal);
-}
+size_t solve_work_bytes(int nvar, int64_t n_owned) { return carve(nvar, n_owned, nullptr).bytes; }
 
 hipError_t solve_matvec(const SolveDev& d, const double* x, double* y) {
-  if (d.nvar == 3) return spmv<3>(d, nullptr, x, y, nullptr);
-  if (d.nvar == 5) return spmv<5>(d, nullptr, x, y, nullptr);
-  return hipErrorInvalidValue;
+  return by_nvar(d.nvar, [&](auto nv) { return apply<decltype(nv)::value>(d, nullptr, 0, PLAIN, x, y, nullptr); });
 }
 
 hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y) {
-  if (d.nvar == 3) return spmv_f32<3>(d, nullptr, x, y, nullptr);
-  if (d.nvar == 5) return spmv_f32<5>(d, nullptr, x, y, nullptr);
-  return hipErrorInvalidValue;
+  return by_nvar(d.nvar, [&](auto nv) { return apply<decltype(nv)::value>(d, nullptr, 0, F32, x, y, nullptr); });
 }
 
 hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int* overflow) {
-  const Work w = carve(d);
+  const Work w = carve(d.nvar, d.n_owned, d.work);
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
-  SOLVE_HIP(d.nvar == 3 ? setup<3>(d, w, precond, true) : d.nvar == 5 ? setup<5>(d, w, precond, true) : hipErrorInvalidValue);
+  SOLVE_HIP(by_nvar(d.nvar, [&](auto nv) { return setup<decltype(nv)::value>(d, w, precond, true); }));
   SOLVE_HIP(read_record(d, w));
   *bad_blocks = d.host_rec->bad_blocks;
   *overflow = d.host_rec->f32_overflow;
@@ -784,17 +777,9 @@ hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int*
 hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   *info = rdc_solve_info();
   info->matrix_bits = 64;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SOLVE_HIP(hipEventCreate(&e0));
-  hipError_t e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = hipEventRecord(e0, d.stream);
-  if (e == hipSuccess) e = d.nvar == 3 ? run<3>(d, p, x, info, mixed) : d.nvar == 5 ? run<5>(d, p, x, info, mixed) : hipErrorInvalidValue;
-  if (e == hipSuccess) e = hipEventRecord(e1, d.stream);
-  if (e == hipSuccess) e = hipEventSynchronize(e1);
-  if (e == hipSuccess) e = hipEventElapsedTime(&info->device_ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return e;
+  return timed(d.stream, &info->device_ms, [&] {
+    return by_nvar(d.nvar, [&](auto nv) { return run<decltype(nv)::value>(d, p, x, info, mixed); });
+  });
 }
 
 }  // namespace rdc

@@ -1,7 +1,11 @@
 // Stand-alone run of the multigrid host code of rdcfes_amd/csrc/rdc_solve.h (aggregation, coarse patterns, contribution lists)
 // for tools/asan_solve_mg.sh: no device, no Python.  Patterns: a 7-point grid graph, a hub (one node coupled to all others),
-// a chain, isolated nodes.  Returns 0 if every hierarchy has the properties tests/test_host_solve_mg.py checks.
+// a chain, isolated nodes.  Returns 0 if every hierarchy has the properties tests/test_host_solve_mg.py checks and, for 3 and 5
+// unknowns per node, the device layout of mg_place fits what it measured: host buffers of exactly the measured sizes stand in
+// for the two arenas, every list is copied into its slot and every other array is filled, so the sanitizer sees each write.
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 #include "../rdcfes_amd/csrc/rdc_solve.h"
 
@@ -48,6 +52,60 @@ Graph chain(int n, int step) {   // step > n: no edges at all
   return from_adjacency(adj);
 }
 
+// 15: the two passes disagree (the place pass does not end where the measure pass did, the measure pass set a pointer, or the
+// level sizes are not those of the steps); 16: an array is not aligned; 17: it leaves its arena; 18: two arrays overlap (an
+// array is smaller than what it holds), or a list did not arrive where its level points
+int check_layout(const Graph& g0, const std::vector<rdc::MgLevelHost>& steps, int nv) {
+  const int64_t n0 = (int64_t)g0.bptr.size() - 1;
+  rdc::MgArena idx, val;
+  rdc::MgDev g;
+  rdc::mg_place(steps, nv, n0, g0.bptr[(size_t)n0], idx, val, g, [](void*, const void*, size_t) {});
+  const size_t ibytes = idx.used, vbytes = val.used;
+  if (g.ph || g.sh || g.t0 || (g.n_levels > 1 && (g.lv[1].agg || g.lv[1].val))) return 15;
+  if (ibytes % rdc::MG_ALIGN || vbytes % rdc::MG_ALIGN || vbytes == 0) return 15;
+  char* ibuf = ibytes ? (char*)std::aligned_alloc(rdc::MG_ALIGN, ibytes) : nullptr;
+  char* vbuf = (char*)std::aligned_alloc(rdc::MG_ALIGN, vbytes);
+  idx = rdc::MgArena{ibuf};
+  val = rdc::MgArena{vbuf};
+  rdc::mg_place(steps, nv, n0, g0.bptr[(size_t)n0], idx, val, g, [](void* at, const void* list, size_t bytes) { std::memcpy(at, list, bytes); });
+  struct Span { const char* at; size_t bytes; };
+  std::vector<Span> in_idx, in_val;
+  auto lst = [&](const auto* at, const auto& v) { in_idx.push_back({(const char*)at, v.size() * sizeof(v[0])}); };
+  auto vec = [&](double* at, int64_t doubles) {
+    in_val.push_back({(const char*)at, (size_t)doubles * sizeof(double)});
+    if (at) std::memset(at, 0x5a, (size_t)doubles * sizeof(double));
+  };
+  int rc = idx.used != ibytes || val.used != vbytes ? 15 : 0;
+  if (g.n_levels != (int)steps.size() + 1 || g.lv[0].n != n0 || g.lv[0].blocks != g0.bptr[(size_t)n0]) rc = 15;
+  const int64_t nn = std::max<int64_t>(n0 * nv, 1);
+  vec(g.ph, nn); vec(g.sh, nn); vec(g.t0, nn);
+  for (size_t l = 0; l < steps.size() && !rc; l++) {
+    const rdc::MgLevelHost& L = steps[l];
+    const rdc::MgLevelDev& D = g.lv[l + 1];
+    if (D.n != L.n || D.blocks != (int64_t)L.bcol.size()) rc = 15;
+    lst(D.agg, L.agg); lst(D.mptr, L.mptr); lst(D.member, L.member); lst(D.bptr, L.bptr); lst(D.bcol, L.bcol); lst(D.brow, L.brow);
+    lst(D.cptr, L.cptr); lst(D.cidx, L.cidx); lst(D.cnode, L.cnode);
+    vec(D.val, D.blocks * nv * nv); vec(D.dinv, D.n * nv * nv); vec(D.x, D.n * nv); vec(D.r, D.n * nv); vec(D.t, D.n * nv);
+  }
+  auto spans = [](std::vector<Span>& a, const char* base, size_t bytes) {
+    for (const Span& s : a) {
+      if (!s.at || (size_t)(s.at - base) % rdc::MG_ALIGN) return 16;
+      if (s.at < base || s.at + s.bytes > base + bytes) return 17;
+    }
+    std::sort(a.begin(), a.end(), [](const Span& x, const Span& y) { return x.at < y.at; });
+    for (size_t i = 1; i < a.size(); i++)
+      if (a[i - 1].at + a[i - 1].bytes > a[i].at) return 18;
+    return 0;
+  };
+  if (!rc) rc = spans(in_idx, ibuf, ibytes);
+  if (!rc) rc = spans(in_val, vbuf, vbytes);
+  for (size_t l = 0; l < steps.size() && !rc; l++)   // the lists arrived where the level points
+    if (std::memcmp(g.lv[l + 1].cidx, steps[l].cidx.data(), steps[l].cidx.size() * 4) || std::memcmp(g.lv[l + 1].bptr, steps[l].bptr.data(), steps[l].bptr.size() * 8)) rc = 18;
+  std::free(ibuf);
+  std::free(vbuf);
+  return rc;
+}
+
 int check(const char* name, const Graph& g) {
   std::vector<rdc::MgLevelHost> steps;
   int64_t n = (int64_t)g.bptr.size() - 1;
@@ -84,6 +142,8 @@ int check(const char* name, const Graph& g) {
     n = L.n; bptr = L.bptr.data(); bcol = L.bcol.data();
   }
   std::printf("\n");
+  for (int nv : {3, 5})
+    if (int rc = check_layout(g, steps, nv)) return rc;
   if (n > rdc::MG_COARSEST_NODES && (int)steps.size() + 1 < rdc::MG_MAX_LEVELS) {   // stopped early: only if nothing merges
     rdc::MgLevelHost L;
     if (!rdc::mg_coarsen(n, bptr, bcol, L) || L.n < n) return 14;

@@ -1,9 +1,10 @@
-"""numpy / scipy restatement of the algorithm of rdc_solve (rdcfes_amd/csrc/rdc_solve.hip): BiCGStab, LEFT-preconditioned
+"""numpy / scipy restatement of the algorithm of rdc_solve (rdcfes_amd/csrc/rdc_solve.hip: run, iteration): BiCGStab, LEFT-preconditioned
 by node-block Jacobi (2), point Jacobi (1) or nothing (0), the recurrences of the host mirror's bicgstab_ilu0, the
 stopping test on the preconditioned residual ||D^-1 (b - A x)|| <= max(rel_tol ||D^-1 b||, abs_tol), the true residual
 recomputed whenever the recurrence claims convergence or breaks down (that recomputation IS the restart: r_hat = r,
 p = v = 0).  Yardstick for the iteration counts of the GPU tests, and the place where the residual checks those tests
-apply are written down once (check_solution)."""
+apply are written down once (check_solution).  bicgstab is the only driver: solve_ref_mixed and solve_ref_mg call it with
+the operator of an iteration, or a right preconditioner, of their own."""
 import numpy as np
 import scipy.sparse as sps
 
@@ -38,9 +39,15 @@ def precond_inverse(A, nv, precond):
     return M, Di, cond
 
 
-def bicgstab(A, b, x0, rel_tol, abs_tol=0.0, max_its=10000, precond=2, nv=1):
-    """-> (x, dict(reason, iterations, restarts, rhs_norm, residual_norm))"""
+def bicgstab(A, b, x0, rel_tol, abs_tol=0.0, max_its=10000, precond=2, nv=1, operator=None, right=None):
+    """-> (x, dict(reason, iterations, restarts, rhs_norm, residual_norm)).  The one driver of every yardstick; two hooks:
+    operator(y): what the two applications INSIDE an iteration compute, default M @ (A @ y) (solve_ref_mixed: the fp32 copy);
+    right(y): a right preconditioner (solve_ref_mg: the cycle), whose outputs take the place of p and s in those two
+    applications and in the update of x.  Everything that decides stays M @ (b - A @ x) whatever the hooks are."""
     M, _, _ = precond_inverse(A, nv, precond)
+    if operator is None:
+        def operator(y):
+            return M @ (A @ y)
     x = np.array(x0, dtype=np.float64, copy=True)
     info = dict(reason=CONVERGED, iterations=0, restarts=0)
     bn = float(np.linalg.norm(M @ b))
@@ -74,20 +81,22 @@ def bicgstab(A, b, x0, rel_tol, abs_tol=0.0, max_its=10000, precond=2, nv=1):
         flag = 0
         with np.errstate(all="ignore"):
             p = r + beta * (p - omega * v)
-            v = M @ (A @ p)
+            px = right(p) if right else p
+            v = operator(px)
             r0v = float(rh @ v)
             alpha = rho / r0v if r0v != 0.0 else np.inf
             if r0v == 0.0 or not np.isfinite(alpha):
                 flag = 1
             if not flag:
                 s = r - alpha * v
-                t = M @ (A @ s)
+                sx = right(s) if right else s
+                t = operator(sx)
                 ts, tt = float(t @ s), float(t @ t)
                 omega = ts / tt if tt > 0.0 else 0.0
                 if omega == 0.0 or not np.isfinite(omega):
                     flag = 1
             if not flag:
-                x += alpha * p + omega * s
+                x += alpha * px + omega * sx
                 r = s - omega * t
                 rho1, rn2 = float(rh @ r), float(r @ r)
                 beta = (rho1 / rho) * (alpha / omega)

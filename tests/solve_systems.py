@@ -1,12 +1,15 @@
 """The linear systems the solver tests run on, each described once for the oracle (CPU yardstick) and for an
-AssemblyContext (GPU): name -> System.  All single-partition; `ghosted_pihna()` gives the one partitioned case."""
+AssemblyContext (GPU): name -> System.  All single-partition; `ghosted_pihna()` gives the one partitioned case.
+At the end: what every GPU solve test does with one of them (_dev, _open, _unchanged)."""
+import copy
 from dataclasses import dataclass, field
 from pathlib import Path
 
 import numpy as np
+import scipy.sparse as sps
 
 import meshes
-from rdcfes_amd import (gmsh, hcc_params_from_dict, inputs, partition, pihna_params_from_dict, ripf_params_from_dict, synth)
+from rdcfes_amd import (AssemblyContext, gmsh, hcc_params_from_dict, inputs, partition, pihna_params_from_dict, ripf_params_from_dict, synth)
 
 G = Path(__file__).resolve().parent / "golden"
 FIELD_OLD_SOLUTION, FIELD_AUX_NODAL, FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE = 0, 1, 2, 3
@@ -147,3 +150,29 @@ def get(name):
     if name not in _CACHE:
         _CACHE[name] = MATVEC_SYSTEMS[name]()
     return _CACHE[name]
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
+
+
+def _open(name, params=None):
+    """uploaded + assembled context, the system (with `params` in place of its own), A (owned rows x all local dofs),
+    assembled rhs, raw values"""
+    s = get(name)
+    if params is not None:
+        s = copy.copy(s)
+        s.params = params
+    ctx = AssemblyContext(0)
+    s.upload(ctx)
+    s.assemble(ctx)
+    val, rhs = ctx.csr_download()
+    rp, col = ctx.csr_pattern()
+    A = sps.csr_matrix((val, col, rp), shape=(rhs.size, ctx.n_node * s.nv))
+    return ctx, s, A, rhs, val
+
+
+def _unchanged(ctx, val, rhs):
+    v, r = ctx.csr_download()
+    assert v.tobytes() == val.tobytes() and r.tobytes() == rhs.tobytes(), "CSR values / rhs were modified"

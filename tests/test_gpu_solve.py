@@ -15,6 +15,7 @@ import scipy.sparse as sps
 
 import solve_ref
 import solve_systems
+from solve_systems import _dev, _open, _unchanged
 from rdcfes_amd import AssemblyContext, RdcError
 from rdcfes_amd.context import (FIELD_OLD_SOLUTION, PRECOND_BLOCK_JACOBI, SOLVE_BAD_DIAGONAL, SOLVE_CONVERGED, SOLVE_MAX_ITS,
                                 SOLVE_NOT_FINITE)
@@ -22,28 +23,6 @@ from rdcfes_amd.context import (FIELD_OLD_SOLUTION, PRECOND_BLOCK_JACOBI, SOLVE_
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-
-
-def _open(name):
-    """uploaded + assembled context, the system, A (owned rows x all local dofs), assembled rhs, raw values"""
-    s = solve_systems.get(name)
-    ctx = AssemblyContext(0)
-    s.upload(ctx)
-    s.assemble(ctx)
-    val, rhs = ctx.csr_download()
-    rp, col = ctx.csr_pattern()
-    A = sps.csr_matrix((val, col, rp), shape=(rhs.size, ctx.n_node * s.nv))
-    return ctx, s, A, rhs, val
-
-
-def _unchanged(ctx, val, rhs):
-    v, r = ctx.csr_download()
-    assert v.tobytes() == val.tobytes() and r.tobytes() == rhs.tobytes(), "CSR values / rhs were modified"
 
 
 @pytest.mark.parametrize("name", list(solve_systems.MATVEC_SYSTEMS))

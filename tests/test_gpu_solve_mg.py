@@ -9,33 +9,15 @@ Iteration slack: the device inverts the diagonal blocks and adds its sums in an 
 yardstick's by an iteration or two at the stopping threshold: at most yardstick + 2."""
 import numpy as np
 import pytest
-import scipy.sparse as sps
 
 import solve_ref
 import solve_ref_mg
-import solve_systems
-from rdcfes_amd import AssemblyContext, RdcError
+from solve_systems import _dev, _open
+from rdcfes_amd import RdcError
 from rdcfes_amd.context import PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, SOLVE_BAD_DIAGONAL, SOLVE_CONVERGED
 
 pytestmark = pytest.mark.gpu
 SLACK = 2
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-
-
-def _open(name):
-    """uploaded + assembled context, the system, A, assembled rhs, raw values"""
-    s = solve_systems.get(name)
-    ctx = AssemblyContext(0)
-    s.upload(ctx)
-    s.assemble(ctx)
-    val, rhs = ctx.csr_download()
-    rp, col = ctx.csr_pattern()
-    A = sps.csr_matrix((val, col, rp), shape=(rhs.size, ctx.n_node * s.nv))
-    return ctx, s, A, rhs, val
 
 
 def _solve(ctx, n, **kw):

@@ -3,7 +3,6 @@ whose iteration streams an fp32 copy of D^-1 A while everything that decides sta
 test_gpu_solve.py every case assembles on the GPU, downloads values, rhs and pattern once and is judged on the host with
 scipy; the returned x is held to the UNCHANGED fp64 inequality solve_ref.check_solution, and iteration counts to
 tests/solve_ref_mixed.py (the same algorithm in numpy) on the same downloaded system."""
-import copy
 import sys
 from pathlib import Path
 
@@ -14,37 +13,13 @@ import scipy.sparse as sps
 import solve_ref
 import solve_ref_mixed
 import solve_systems
+from solve_systems import _dev, _open, _unchanged
 from rdcfes_amd import AssemblyContext, RdcError, pihna_params_from_dict, synth
 from rdcfes_amd.context import FIELD_OLD_SOLUTION, PRECOND_BLOCK_JACOBI, PRECOND_NONE, SOLVE_CONVERGED, SOLVE_MAX_ITS
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-
-
-def _open(name, params=None):
-    """uploaded + assembled context, the system, A (owned rows x all local dofs), assembled rhs, raw values"""
-    s = solve_systems.get(name)
-    if params is not None:
-        s = copy.copy(s)
-        s.params = params
-    ctx = AssemblyContext(0)
-    s.upload(ctx)
-    s.assemble(ctx)
-    val, rhs = ctx.csr_download()
-    rp, col = ctx.csr_pattern()
-    A = sps.csr_matrix((val, col, rp), shape=(rhs.size, ctx.n_node * s.nv))
-    return ctx, s, A, rhs, val
-
-
-def _unchanged(ctx, val, rhs):
-    v, r = ctx.csr_download()
-    assert v.tobytes() == val.tobytes() and r.tobytes() == rhs.tobytes(), "CSR values / rhs were modified"
 
 
 def _owned_square(A):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# AddressSanitizer + UBSan run of the multigrid host code (rdc_solve.h: aggregation, coarse patterns, contribution lists)
+# AddressSanitizer + UBSan run of the multigrid host code (rdc_solve.h: aggregation, coarse patterns, contribution lists, device layout)
 # as a stand-alone host program: no device, no Python.
 set -e
 cd "$(dirname "$0")/.."
