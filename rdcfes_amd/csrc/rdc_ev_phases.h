@@ -45,20 +45,100 @@ __device__ __forceinline__ void aim(Sink& sink, double* lds, double* R, const in
   }
 }
 
-// one wave copies the CSR segment of node nd (nv2 = nvar^2 values per block) from the LDS image to memory with 16-byte non-temporal
-// stores; `image` holds the image from offset `base` (even) on; out[x] <-> img[x]: the image has the 16-byte phase of the segment in memory
-__device__ __forceinline__ void store_segment(const double* image, double* val, const int nv2, const HostPrepEv::Node nd, const int lane,
-                                              const uint32_t base = 0) {
-  const double* img = image + (nd.obase - base);
-  double* out = val + (size_t)nv2 * nd.bptr;
-  const int cnt = nv2 * (int)nd.len, sh = seg_phase(nd.obase);
-  typedef double v2d_t __attribute__((ext_vector_type(2)));
-  const int npair = (cnt - sh) >> 1;
-  const v2d_t* src = reinterpret_cast<const v2d_t*>(img + sh);
-  v2d_t* dstg = reinterpret_cast<v2d_t*>(out + sh);
-  for (int x = lane; x < npair; x += 64) __builtin_nontemporal_store(src[x], dstg + x);
-  if (sh && lane == 0) __builtin_nontemporal_store(img[0], out);
-  if (((cnt - sh) & 1) && lane == 1) __builtin_nontemporal_store(img[cnt - 1], out + cnt - 1);
+// ---- copy-out: one contiguous CSR segment per node, from the LDS image to memory with 16-byte non-temporal stores ----------------
+typedef double v2d_t __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
+
+// a row has at most MAX_ROW_BLOCKS node blocks (the 4-bit slots of vslot_get, the slice's NBP / MAXN blocks per node), so a lane
+// reads at most seg_reads(nv2) pieces of 16 bytes of a segment of nv2 values per block: 4 for 25 values, 2 for 9
+constexpr int MAX_ROW_BLOCKS = HostPrepEv::NBP / HostPrepEv::MAXN;
+static_assert(MAX_ROW_BLOCKS == 16, "vslot_get / block_slot: four bits per column slot");
+constexpr int seg_reads(const int nv2) { return (nv2 * MAX_ROW_BLOCKS / 2 + 63) / 64; }
+
+// The compiler may not split a batch of LDS reads: the empty statement needs every value of the batch in its register, so the
+// reads in front of it are all issued before the one wait it causes (left to itself it sinks each read to its use: a round trip each)
+__device__ __forceinline__ void lds_batch() { __builtin_amdgcn_sched_barrier(0); }
+template <class T> __device__ __forceinline__ void lds_land(T& a) { asm volatile("" : "+v"(a)); }
+template <class T> __device__ __forceinline__ void lds_land(T& a, T& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+template <class T> __device__ __forceinline__ void lds_land(T& a, T& b, T& c, T& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+template <int I = 0, class T, int N> __device__ __forceinline__ void lds_land(T (&r)[N]) {
+  if constexpr (N - I >= 4) { lds_land(r[I], r[I + 1], r[I + 2], r[I + 3]); lds_land<I + 4>(r); }
+  else if constexpr (N - I >= 2) { lds_land(r[I], r[I + 1]); lds_land<I + 2>(r); }
+  else if constexpr (N - I == 1) lds_land(r[I]);
+}
+
+// the table entries of N nodes of a wave -- nodes first, first + 4, ... (uniform; first + 4 (N - 1) < MAXN) -- in scalar registers:
+// read together (wave_nodes_read; `snode`: aligned to 16 bytes) and waited for once (wave_nodes_land, behind whatever else the
+// caller reads with them)
+template <int N>
+__device__ __forceinline__ void wave_nodes_read(const HostPrepEv::Node* snode, const int first, v4u_t (&raw)[N]) {
+  static_assert(sizeof(HostPrepEv::Node) == 16, "one 16-byte LDS read per entry");
+#pragma unroll
+  for (int q = 0; q < N; q++) raw[q] = reinterpret_cast<const v4u_t*>(snode)[first + 4 * q];
+}
+template <int N>
+__device__ __forceinline__ void wave_nodes_land(v4u_t (&raw)[N], HostPrepEv::Node (&nd)[N]) {
+  lds_batch();
+  lds_land(raw);
+#pragma unroll
+  for (int q = 0; q < N; q++) {
+    const uint32_t lb = __builtin_amdgcn_readfirstlane(raw[q].y);
+    nd[q].bptr = __builtin_amdgcn_readfirstlane(raw[q].x);
+    nd[q].len = (uint16_t)(lb & 0xFFFFu); nd[q].blk0 = (uint16_t)(lb >> 16);
+    nd[q].obase = __builtin_amdgcn_readfirstlane(raw[q].z);
+    nd[q].node = __builtin_amdgcn_readfirstlane(raw[q].w);
+  }
+}
+template <int N>
+__device__ __forceinline__ void wave_nodes(const HostPrepEv::Node* snode, const int first, HostPrepEv::Node (&nd)[N]) {
+  v4u_t raw[N];
+  wave_nodes_read(snode, first, raw);
+  wave_nodes_land(raw, nd);
+}
+
+// one wave copies the CSR segments of NS nodes (NV2 = nvar^2 values per block; entries uniform, as wave_nodes gives them; on[s]:
+// uniform, false = no such node; NS = 2 wherever the registers allow it) in one go: every LDS read of the segments -- 16 bytes per lane and read, the odd head and tail
+// doubles with them -- is issued into registers of its own and waited for once, then the stores leave.  `image` holds the image
+// from offset `base` (even) on; out[x] <-> img[x]: the image has the 16-byte phase of the segment in memory.  A lane past the end of
+// its segment reads the segment's first piece (inside the image whatever the workgroup's LDS size) and stores nothing.
+template <int NV2, int NS>
+__device__ __forceinline__ void store_segments(const double* image, double* val, const HostPrepEv::Node (&nd)[NS], const bool (&on)[NS],
+                                               const int lane, const uint32_t base = 0) {
+  constexpr int NR = seg_reads(NV2);
+  v2d_t r[NS][NR];
+  double ends[NS][2];   // the odd head and tail doubles
+  const double* img[NS];
+  int cnt[NS], sh[NS], npair[NS];
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    img[s] = image + (on[s] ? nd[s].obase - base : 0u);
+    cnt[s] = on[s] ? NV2 * (int)nd[s].len : 0;
+    sh[s] = on[s] ? seg_phase(nd[s].obase) : 0;
+    npair[s] = (cnt[s] - sh[s]) >> 1;
+    const v2d_t* src = reinterpret_cast<const v2d_t*>(img[s] + sh[s]);
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+      const int x = lane + 64 * i;
+      r[s][i] = src[x < npair[s] ? x : 0];
+    }
+    ends[s][0] = img[s][0];
+    ends[s][1] = img[s][cnt[s] > 0 ? cnt[s] - 1 : 0];
+  }
+  lds_batch();
+#pragma unroll
+  for (int s = 0; s < NS; s++) { lds_land(r[s]); lds_land(ends[s]); }
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    double* out = val + (size_t)NV2 * nd[s].bptr;
+    v2d_t* dstg = reinterpret_cast<v2d_t*>(out + sh[s]);
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+      const int x = lane + 64 * i;
+      if (x < npair[s]) __builtin_nontemporal_store(r[s][i], dstg + x);
+    }
+    if (sh[s] && lane == 0) __builtin_nontemporal_store(ends[s][0], out);
+    if (((cnt[s] - sh[s]) & 1) && lane == 1) __builtin_nontemporal_store(ends[s][1], out + cnt[s] - 1);
+  }
 }
 
 }  // namespace evl

@@ -36,6 +36,30 @@ struct EvSink {
 };
 
 
+namespace {
+// the moments of node block `blk` and, added to them in the order of m, the symmetric ones of its mirror block (rdc_tet4_ev.h, MIRROR;
+// mirror == blk: none, and nothing is read for such a lane).  The mirror's are read into registers of their own right behind the
+// block's: one wait for both
+template <bool GEN, int NM>
+__device__ __forceinline__ void ev_read_moments(const double* lds, const int blk, const int mirror, double (&e)[NM]) {
+  constexpr auto sym = [](const int m) { return GEN ? ev::symmetric_moment_gen(m) : ev::symmetric_moment(m); };
+  constexpr int NS = [=]() { int n = 0; for (int m = 0; m < NM; m++) n += sym(m); return n; }();
+#pragma unroll
+  for (int m = 0; m < NM; m++) e[m] = lds[m * ev::NBP + blk];
+  if (mirror != blk) {
+    double t[NS];
+#pragma unroll
+    for (int m = 0, x = 0; m < NM; m++)
+      if (sym(m)) t[x++] = lds[m * ev::NBP + mirror];
+    evl::lds_batch();
+    evl::lds_land(t);
+#pragma unroll
+    for (int m = 0, x = 0; m < NM; m++)
+      if (sym(m)) e[m] += t[x++];
+  }
+}
+}
+
 // GEN: every term on (22 moments, rdc_tet4_ev.h); otherwise the shipped parameter pattern (16)
 template <int EXP_MODE, int MINW, int ABL = 0, bool GEN = false>
 __global__ void __launch_bounds__(256, MINW)
@@ -51,7 +75,7 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   RDC_TS(0);
   constexpr int NM = GEN ? ev::NMG : ev::NM, NBP = ev::NBP, MAXN = ev::MAXN;
   extern __shared__ __attribute__((aligned(16))) double lds[];   // [M: NM x NBP | R: 5 x MAXN | records: NP x nls x 16 B]
-  __shared__ HostPrepEv::Node snode[MAXN];
+  __shared__ __attribute__((aligned(16))) HostPrepEv::Node snode[MAXN];
   typedef __attribute__((address_space(3))) void* lds_ptr;
   typedef const __attribute__((address_space(1))) void* glb_ptr;
   // XCD-aware order: consecutive workgroup ids go to the 8 XCDs in turn (each with its own 4 MB L2), consecutive CLUSTERS are
@@ -131,15 +155,7 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   double e[NM];
   const int bn = evl::block_node(tid), bs = evl::block_slot(tid);
   const bool has = bn < (int)d.nown && bs < (int)snode[bn < (int)d.nown ? bn : 0].len;
-  if (has) {
-#pragma unroll
-    for (int m = 0; m < NM; m++) e[m] = lds[m * NBP + tid];
-    if (mirror != tid) {   // rdc_tet4_ev.h, MIRROR
-#pragma unroll
-      for (int m = 0; m < NM; m++)
-        if (GEN ? ev::symmetric_moment_gen(m) : ev::symmetric_moment(m)) e[m] += lds[m * NBP + mirror];
-    }
-  }
+  if (has) ev_read_moments<GEN>(lds, tid, mirror, e);
   if (tid < (int)d.nown * 5) {   // rhs: R[a][node] -> rhs[node * 5 + a]
     const int n = tid / 5, a = tid - n * 5;
     rhs[(size_t)snode[n].node * 5 + a] = R[a * MAXN + n];
@@ -160,7 +176,15 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
   __syncthreads();
   RDC_TS(8);
   // phase 3: one contiguous CSR segment per node; the image has the 16-byte phase of its segment in memory
-  for (int n = wv; n < (int)d.nown; n += 4) evl::store_segment(lds, val, 25, snode[n], lane);
+  {
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    HostPrepEv::Node nd[4];
+    evl::wave_nodes(snode, wvu, nd);   // nodes wv, wv + 4, wv + 8, wv + 12: two at a time
+    const HostPrepEv::Node nd01[2] = {nd[0], nd[1]}, nd23[2] = {nd[2], nd[3]};
+    const bool on01[2] = {wvu < (int)d.nown, wvu + 4 < (int)d.nown}, on23[2] = {wvu + 8 < (int)d.nown, wvu + 12 < (int)d.nown};
+    if (on01[0]) evl::store_segments<25, 2>(lds, val, nd01, on01, lane);
+    if (on23[0]) evl::store_segments<25, 2>(lds, val, nd23, on23, lane);
+  }
   if (TL) {
     RDC_TS(9);
     if (stagger == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's stores have been acknowledged ("stagger" != 0: not waited for)
@@ -215,7 +239,7 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   constexpr int BLOCK = 256, NP = 4;
   constexpr int NM = GEN ? ev::NMG : ev::NM, NBP = ev::NBP, MAXN = ev::MAXN;
   extern __shared__ __attribute__((aligned(16))) double lds[];   // [M: NM x NBP, later the image halves | R: 5 x MAXN | records: NP x nls x 16 B | lists]
-  __shared__ HostPrepEv::Node snode[MAXN];
+  __shared__ __attribute__((aligned(16))) HostPrepEv::Node snode[MAXN];
   __shared__ uint8_t smirror[NBP];
   __shared__ int s_nown;
   __shared__ int s_tk[2];
@@ -235,8 +259,9 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   // addresses: scalar loads, issued where the position becomes known and used a phase later
   auto cluster_of = [&](const int c) -> int { return c < wg_count ? (wg_perm ? (int)wg_perm[wg_begin + c] : wg_begin + c) : -1; };
   int w0c = cluster_of(c0), w1c = cluster_of(c1), w2c = cluster_of(c2);
-  long long ts[8];
-#define RDC_TS(x) if (TL) ts[x] = __builtin_amdgcn_s_memtime()
+  // stamps leave at once (lane 0, one 8-byte store each: scalar registers are short here, and six stamps kept to the end of the cluster
+  // push the spilled ones past the 64 lanes of one register); they are waited for with the cluster's own stores (c0 past the end: the last pass of the loop, no cluster)
+#define RDC_TS(x) if (TL && stamps && c0 < wg_count && lane == 0) stamps[((int64_t)c0 * 4 + wv) * 12 + x] = __builtin_amdgcn_s_memtime()
   // everything cluster `w` needs (node ids in `nid`), and the node ids of cluster `w2` into id buffer `nb2`, by LDS-DMA
   auto fetch = [&](const int w, const uint32_t nid, const int w2, const int nb2, const int lane) {
     if (wv < rounds) {
@@ -321,11 +346,20 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     RDC_TS(4);
     // ---- from here to the top of the next cluster: NO scratch (the lane index is taken from the hardware again)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-    if (c1 < wg_count) {
-      uint32_t nid = 0;
-      if (wv < rounds) nid = *reinterpret_cast<const uint32_t*>(lists + EvqLists::NL + (((it + 1) & 1) * nls + wv * 64 + lane) * 4);
-      fetch(w1c, nid, w2c, it & 1, lane);
-    }
+    // what the rest of the cluster needs from the parked lists, read in one batch (it lands with the node ids of the fetch below):
+    // the number of owned nodes, the lane's node entry and mirror block, where the second image half begins
+    const int bn = ((wv >> 1) << 3) | (lane & 7), bs = ((wv & 1) << 3) | (lane >> 3), blk = evl::block(bn, bs);
+    int nown = s_nown, mirror = (int)smirror[blk];
+    uint32_t bn_len = reinterpret_cast<const uint32_t*>(snode + bn)[1], bn_obase = snode[bn].obase;   // len | blk0 << 16
+    uint32_t base8 = snode[8].obase;   // where the second image half begins
+    uint32_t nid = 0;                  // the node ids of the fetch below
+    if (c1 < wg_count && wv < rounds) nid = *reinterpret_cast<const uint32_t*>(lists + EvqLists::NL + (((it + 1) & 1) * nls + wv * 64 + lane) * 4);
+    evl::lds_batch();
+    evl::lds_land(nown, mirror); evl::lds_land(bn_len, bn_obase); evl::lds_land(base8, nid);
+    nown = __builtin_amdgcn_readfirstlane(nown);
+    base8 = __builtin_amdgcn_readfirstlane(base8);
+    bn_len &= 0xFFFFu;
+    if (c1 < wg_count) fetch(w1c, nid, w2c, it & 1, lane);
     // the cluster after those two: one ticket per workgroup (nothing left once c2 is past the end: the counter only grows)
     tk = NONE;
     if (c2 < wg_count && wv == 0 && lane == 0) {
@@ -336,22 +370,11 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     }
     pending = true;
     // ---- node block (bn, bs): moments -> entries; waves 0-1 hold the blocks of nodes 0-7, waves 2-3 those of nodes 8-15
-    const int nown = s_nown;
-    const int bn = ((wv >> 1) << 3) | (lane & 7), bs = ((wv & 1) << 3) | (lane >> 3), blk = evl::block(bn, bs);
     double e[NM];
-    const bool has = bn < nown && bs < (int)snode[bn < nown ? bn : 0].len;
+    const bool has = bn < nown && bs < (int)bn_len;
 #pragma unroll
     for (int m = 0; m < NM; m++) e[m] = 0.0;
-    if (has) {
-      const int mirror = (int)smirror[blk];
-#pragma unroll
-      for (int m = 0; m < NM; m++) e[m] = lds[m * NBP + blk];
-      if (mirror != blk) {
-#pragma unroll
-        for (int m = 0; m < NM; m++)
-          if (GEN ? ev::symmetric_moment_gen(m) : ev::symmetric_moment(m)) e[m] += lds[m * NBP + mirror];
-      }
-    }
+    if (has) ev_read_moments<GEN>(lds, blk, mirror, e);
     {
       const int tid = wv * 64 + lane;
       if (tid < nown * 5) {
@@ -366,27 +389,32 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
     for (int h = 0; h < 2; h++) {
       const int n0 = h * 8;
       if (n0 >= nown) break;   // uniform
-      const uint32_t base = h == 0 ? 0u : (snode[8].obase & ~1u);   // even: the 16-byte phase of the segments is kept
+      const uint32_t base = h == 0 ? 0u : (base8 & ~1u);   // even: the 16-byte phase of the segments is kept
       if ((wv >> 1) == h && has) {
-        const int len = (int)snode[bn].len;
+        const int len = (int)bn_len;
         // the block's origin goes into the pointer first: as one seg_entry(5, len, a, bs, b) per entry the 16-moment instantiations
         // spill 4-8 registers instead of 2 (20-32 B of scratch per lane)
-        double* dst = lds + (snode[bn].obase - base) + evl::seg_entry(5, len, 0, bs, 0);
+        double* dst = lds + (bn_obase - base) + evl::seg_entry(5, len, 0, bs, 0);
 #pragma unroll
         for (int a = 0; a < 5; a++)
 #pragma unroll
           for (int b = 0; b < 5; b++) dst[evl::seg_entry(5, len, a, 0, b)] = o[a * 5 + b];
       }
+      // the entries of the wave's two nodes of this half (uniform: scalar registers), read behind the image writes -- their registers are
+      // not live while o[] is -- and landing at the barrier's wait
+      evl::v4u_t raw[2];
+      evl::wave_nodes_read(snode, n0 + wv, raw);
+      HostPrepEv::Node ndh[2];
+      evl::wave_nodes_land(raw, ndh);
       lds_barrier();
       const int n1 = nown < n0 + 8 ? nown : n0 + 8;
-      for (int n = n0 + wv; n < n1; n += 4) evl::store_segment(lds, val, 25, snode[n], lane, base);
+      const bool on[2] = {n0 + wv < n1, n0 + wv + 4 < n1};
+      if (on[0]) evl::store_segments<25, 2>(lds, val, ndh, on, lane, base);
       lds_barrier();   // the half has been read (into the stores' registers)
     }
     RDC_TS(5);
     if (TL && lane == 0 && stamps) {
       long long* op = stamps + ((int64_t)c0 * 4 + wv) * 12;
-#pragma unroll
-      for (int x = 0; x < 6; x++) op[x] = ts[x];
       op[11] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
     }
     c0 = c1; c1 = c2; w0c = w1c; w1c = w2c;   // c2, w2c: from the ticket, behind the barrier at the top

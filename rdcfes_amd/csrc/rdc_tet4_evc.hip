@@ -43,7 +43,7 @@ k_tet4_evc(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   constexpr int BLOCK = 256, NV = M::NV, NA = (M::NAUX > 0 ? M::NAUX : 1), NP = EvcRec<M>::N / 2, NE = evc_blocks<M>();
   constexpr int NBP = ev::NBP, MAXN = ev::MAXN;
   extern __shared__ __attribute__((aligned(16))) double lds[];   // [S: NE x NBP | R: NV x MAXN | records: NP x nls x 16 B]
-  __shared__ HostPrepEv::Node snode[MAXN];
+  __shared__ __attribute__((aligned(16))) HostPrepEv::Node snode[MAXN];
   typedef __attribute__((address_space(3))) void* lds_ptr;
   typedef const __attribute__((address_space(1))) void* glb_ptr;
   int w = (int)blockIdx.x + wg_begin;
@@ -119,7 +119,25 @@ k_tet4_evc(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
   }
   __syncthreads();
   // phase 3: one contiguous CSR segment per node; the image has the 16-byte phase of its segment in memory
-  for (int n = wv; n < (int)d.nown; n += 4) evl::store_segment(lds, val, NV * NV, snode[n], lane);
+  {
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    if constexpr (MINW == 2) {   // nodes wv, wv + 4, wv + 8, wv + 12: two at a time
+      HostPrepEv::Node nd[4];
+      evl::wave_nodes(snode, wvu, nd);
+      const HostPrepEv::Node nd01[2] = {nd[0], nd[1]}, nd23[2] = {nd[2], nd[3]};
+      const bool on01[2] = {wvu < (int)d.nown, wvu + 4 < (int)d.nown}, on23[2] = {wvu + 8 < (int)d.nown, wvu + 12 < (int)d.nown};
+      if (on01[0]) evl::store_segments<NV * NV, 2>(lds, val, nd01, on01, lane);
+      if (on23[0]) evl::store_segments<NV * NV, 2>(lds, val, nd23, on23, lane);
+    } else {                     // three workgroups per CU: the visit spills, and what a second segment keeps in registers would add to that
+#pragma unroll 1
+      for (int n = wvu; n < (int)d.nown; n += 4) {
+        HostPrepEv::Node nd1[1];
+        evl::wave_nodes(snode, n, nd1);
+        const bool on1[1] = {true};
+        evl::store_segments<NV * NV, 1>(lds, val, nd1, on1, lane);
+      }
+    }
+  }
 }
 
 // the node records have been packed by the caller (launch_fast_impl, rdc_tet4_fast.hip)
