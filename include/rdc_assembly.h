@@ -54,6 +54,7 @@ extern "C" {
 #define RDC_ERR_STATE        3   /* call order violated (e.g. assemble before mesh upload) */
 #define RDC_ERR_UNSUPPORTED  4   /* element type / model combination not implemented */
 #define RDC_ERR_ALLOC        5   /* host or device allocation failed */
+#define RDC_ERR_COMM         6   /* a communication callback of rdc_solve_dist returned non-zero */
 
 /* element types (value == nodes per element) */
 #define RDC_TET4 4
@@ -308,7 +309,8 @@ int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
  * Additive: RDC_ABI_VERSION stays 3, nothing above changes meaning.
  * The matrix is the context's own CSR values, walked through the node-block pattern (4 bytes of index per nvar x nvar
  * block, no scalar row_ptr / col_idx on the device).  BiCGStab, LEFT-preconditioned by node-block Jacobi: it iterates on
- * D^-1 A x = D^-1 b and stops on the preconditioned residual, as PETSc's KSPBCGS does by default.  Single partition only. */
+ * D^-1 A x = D^-1 b and stops on the preconditioned residual, as PETSc's KSPBCGS does by default.  rdc_solve and rdc_solve_mixed
+ * take a single partition; rdc_solve_dist (below) is the same iteration across partitions. */
 #define RDC_PRECOND_NONE 0
 #define RDC_PRECOND_JACOBI 1
 #define RDC_PRECOND_BLOCK_JACOBI 2      /* default choice of the Python wrapper */
@@ -350,7 +352,7 @@ int rdc_csr_matvec(rdc_ctx* ctx, const double* d_x, double* d_y);
  * Blocks the host until done.  Never modifies the CSR values or the rhs.
  * A solver outcome other than convergence is not an error status: the call returns RDC_OK and info->reason tells.
  * b = 0 gives x = 0 in 0 iterations.  RDC_ERR_UNSUPPORTED when the context has ghost nodes (a solve across partitions
- * needs a halo exchange of the search directions inside every iteration). */
+ * needs a halo exchange of the search directions inside every iteration: rdc_solve_dist). */
 int rdc_solve(rdc_ctx* ctx, const rdc_solve_params* p, double* d_x, rdc_solve_info* info);
 
 /* ---- mixed precision (additive, RDC_ABI_VERSION stays 3): BiCGStab that iterates on an FP32 copy of D^-1 A.
@@ -399,6 +401,54 @@ int rdc_solve_mg_levels(rdc_ctx* ctx, int32_t* n_levels, int64_t* nodes, int64_t
  * (part of its rdc_solve_info.device_ms); *level_bytes = device memory the levels hold for this mesh (matrices, lists and
  * vectors).  Either pointer may be NULL.  RDC_ERR_STATE as above. */
 int rdc_solve_mg_stats(rdc_ctx* ctx, float* setup_ms, int64_t* level_bytes);
+
+/* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
+ * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own
+ * context; the ranks together solve the global system whose rows they own.  The library itself knows no MPI and no RCCL:
+ * the communication comes in as three callbacks, which a torch.distributed harness and an MPI adapter can both supply
+ * (INTEGRATION.md).
+ *
+ * What is exchanged: per iteration the ghost values of the two search directions p and s, one exchange
+ * before each of the two operator applications; the ghost values of x before every true residual; and three all-reduces
+ * per iteration of 2, 2 and 3 doubles (6 after the first true residual, 4 after every later one).  Every inner product, norm and
+ * counter that decides anything is the all-reduced one, so reason, iterations, restarts, bad_blocks, matrix_bits and all
+ * norms of rdc_solve_info are GLOBAL and identical on every rank, and every early return (bad diagonal, not finite, the
+ * FP64 fall-back of a mixed solve, b = 0) is taken by all ranks together.
+ *
+ * Stream contract.  The callbacks run on the calling host thread, in program order.  `hip_stream` is the context's stream.
+ * What the library enqueued on it before a callback produces that callback's inputs (d_send, the d_vals of an all-reduce):
+ * the callee orders its transfer behind that work, by enqueueing on the same stream or by synchronising it.  When
+ * exchange_end or allreduce_sum returns, the received values are ordered on `hip_stream` before anything enqueued later.
+ * Between exchange_begin and exchange_end the library enqueues the operator over the rows that read no ghost value; nothing
+ * it enqueues there reads d_recv or writes d_send.  allreduce_sum must deliver the same bits on every rank (RCCL and gloo
+ * both do).  A callback returns 0, or non-zero to abort: rdc_solve_dist then returns RDC_ERR_COMM, calls no further
+ * callback, and x holds the last iterate. */
+typedef struct rdc_solve_comm {
+  void* user;
+  /* d_send: n_send*nvar doubles packed by the library in plan order; d_recv: the ghost tail of the vector being
+     exchanged (n_ghost*nvar doubles, local ghost order).  The callee slices both per peer. */
+  int (*exchange_begin)(void* user, const double* d_send, double* d_recv, void* hip_stream);
+  int (*exchange_end)(void* user, void* hip_stream);
+  int (*allreduce_sum)(void* user, double* d_vals, int32_t n, void* hip_stream);   /* in place, n <= 8 */
+} rdc_solve_comm;
+
+/* The send list of the uploaded mesh: send_nodes[i] = the owned local node whose nvar values are entry i of d_send
+ * (a node may appear more than once: once per peer that has it as a ghost).  Copied; kept until the next mesh upload.
+ * The option "interior_nodes" = n_int as it stands at this call (set it before the mesh upload, as for the two-part assembly)
+ * makes every operator application overlap the exchange with the rows of the nodes [0, n_int); unset or 0: exchange first.
+ * RDC_ERR_INVALID if a send id is not an owned node, if n_int > n_owned, or if a node below n_int has a ghost column. */
+int rdc_solve_dist_plan(rdc_ctx* ctx, int64_t n_send, const int32_t* send_nodes);   /* owned local node ids, send order */
+/* The contract of rdc_solve (mixed == 0) or rdc_solve_mixed (mixed != 0), across ranks.  d_x: DEVICE pointer, n_nodes*nvar
+ * doubles in local numbering.  On entry the owned rows hold the initial guess, the ghost rows are ignored.  On exit the
+ * owned rows hold the solution and the ghost rows the owners' values of it (the last true residual has just exchanged them),
+ * whatever info->reason is; b = 0 gives x = 0 in 0 iterations, ghost rows included; RDC_SOLVE_BAD_DIAGONAL and a first
+ * residual that is not finite leave the owned rows untouched.  precond: RDC_PRECOND_NONE, _JACOBI, _BLOCK_JACOBI;
+ * RDC_PRECOND_MULTIGRID gives RDC_ERR_UNSUPPORTED (aggregates across ranks are not built).  RDC_ERR_STATE on a context with
+ * ghost nodes that has no plan.  A context without ghosts, with an empty or no plan and a communicator of world size 1 (an
+ * exchange that does nothing, an all-reduce that leaves d_vals as they are) is legal and returns, bit for bit, what
+ * rdc_solve / rdc_solve_mixed return.  Blocks the host until done.  Never modifies the CSR values or the rhs. */
+int rdc_solve_dist(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed,
+                   double* d_x, rdc_solve_info* info);
 
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */

@@ -12,7 +12,16 @@ from .context import (AssemblyContext, RdcError, TET4, HEX8, SCATTER_AUTO, SCATT
                       SCATTER_ROWGATHER, FIELD_OLD_SOLUTION, FIELD_AUX_NODAL,
                       FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE, FIELD_PREV_SOLUTION, FIELD_TIME_DERIV,
                       FIELD_RT_DOSE, FIELD_ELEM_TRACTS, PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID,
-                      SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE)
+                      SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE, ERR_COMM)
+
+
+def __getattr__(name):
+    # halo.py needs torch; the rest of the package imports without it
+    if name == "SolveComm":
+        from .halo import SolveComm
+        return SolveComm
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 __all__ = [
     "PihnaParams", "RipfParams", "HccParams", "SolidParams", "SolidMaterial", "RipfCheckParams", "AdpmParams", "adpm_params_from_dict", "ProteasParams", "proteas_params_from_dict", "PihnaRanges", "RipfRanges", "AdpmRanges",
@@ -21,5 +30,5 @@ __all__ = [
     "SCATTER_ROWGATHER", "FIELD_OLD_SOLUTION", "FIELD_AUX_NODAL", "FIELD_UNDEFORMED_XYZ",
     "FIELD_ELEM_FIBRE", "FIELD_PREV_SOLUTION", "FIELD_TIME_DERIV", "FIELD_RT_DOSE", "FIELD_ELEM_TRACTS",
     "SolveParams", "SolveInfo", "PRECOND_NONE", "PRECOND_JACOBI", "PRECOND_BLOCK_JACOBI", "PRECOND_MULTIGRID",
-    "SOLVE_CONVERGED", "SOLVE_MAX_ITS", "SOLVE_BREAKDOWN", "SOLVE_BAD_DIAGONAL", "SOLVE_NOT_FINITE",
+    "SOLVE_CONVERGED", "SOLVE_MAX_ITS", "SOLVE_BREAKDOWN", "SOLVE_BAD_DIAGONAL", "SOLVE_NOT_FINITE", "ERR_COMM", "SolveComm",
 ]

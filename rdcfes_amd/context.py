@@ -16,6 +16,7 @@ FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1, 2, 3
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
+ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 1, 2, 3, 4, 5, 6
 
 
 class RdcError(RuntimeError):
@@ -41,6 +42,7 @@ class AssemblyContext:
         self.device = int(device)
         self.n_elem = self.n_node = self.n_owned = 0
         self.nvar = 0
+        self._dist_plan = None   # the SolveComm whose send list the uploaded mesh holds (solve_dist)
 
     # -- plumbing
     def _ck(self, rc):
@@ -96,6 +98,7 @@ class AssemblyContext:
         self._ck(self._lib.rdc_mesh_upload(self._h, int(elem_type), conn.shape[0], xyz.shape[0], n_owned,
                                            conn.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(xyz), int(nvar)))
         self.elem_type, self.n_elem, self.n_node, self.n_owned, self.nvar = elem_type, conn.shape[0], xyz.shape[0], n_owned, nvar
+        self._dist_plan = None
 
     def mesh_update_coords(self, xyz):
         xyz = np.ascontiguousarray(xyz, dtype=np.float64)
@@ -326,6 +329,36 @@ class AssemblyContext:
         info = SolveInfo()
         fn = self._lib.rdc_solve_mixed if mixed else self._lib.rdc_solve
         self._ck(fn(self._h, C.byref(p), C.c_void_p(int(x)), C.byref(info)))
+        return info
+
+    def solve_dist_plan(self, send_nodes):
+        """rdc_solve_dist_plan: the send list (owned local node ids, send order) of the uploaded mesh; reads the option
+        "interior_nodes" as it stands (set it before mesh_upload) and checks that no row below it has a ghost column"""
+        ids = np.ascontiguousarray(send_nodes, dtype=np.int32).reshape(-1)
+        self._dist_plan = None
+        self._ck(self._lib.rdc_solve_dist_plan(self._h, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def solve_dist(self, comm, x=None, *, field=None, rel_tol=1e-8, abs_tol=0.0, max_its=10000, precond=PRECOND_BLOCK_JACOBI,
+                   rhs_scale=1.0, mixed=False):
+        """rdc_solve_dist: the solve of `solve`, across the ranks of comm (halo.SolveComm), every rank calling with its own
+        context.  x: device address of n_node*nvar doubles in local numbering (owned rows: initial guess in, solution out; ghost
+        rows: ignored in, the owners' values out), or field=FIELD_*.  The returned SolveInfo is the same on every rank.  The send
+        list of comm is uploaded once per mesh.  An exception raised inside a callback of comm is re-raised here."""
+        if (x is None) == (field is None):
+            raise ValueError("give either a device address or field=")
+        if field is not None:
+            x = self.field_device_ptr(int(field), self.n_node * self.nvar)
+        if self._dist_plan is not comm:
+            self.solve_dist_plan(comm.send_nodes)
+            self._dist_plan = comm
+        p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
+        info = SolveInfo()
+        comm.error = None
+        rc = self._lib.rdc_solve_dist(self._h, C.byref(p), C.byref(comm.struct), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
+        if comm.error is not None:
+            err, comm.error = comm.error, None
+            raise err
+        self._ck(rc)
         return info
 
     def mg_levels(self):

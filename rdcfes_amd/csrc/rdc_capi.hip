@@ -36,7 +36,8 @@ struct Buffers {
   // linear solve (rdc_solve.hip): block column list (first matvec / solve), work vectors (first solve); fp32 copy of D^-1 A
   // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
   // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val; } solve;
+  // send: the send list of a partitioned solve (rdc_solve_dist_plan)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send; } solve;
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -50,6 +51,8 @@ struct SolveState {
   bool f32_copy = false;     // val32 holds a usable fp32 copy (of the values at the time it was built)
   bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
   MgDev mg;
+  bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
+  DistDims dist;
 };
 
 // What is only meaningful for the uploaded mesh; rdc_mesh_upload starts from MeshState().
@@ -1313,6 +1316,68 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
 int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, false); }
 
 int rdc_solve_mixed(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, true); }
+
+int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (n_send < 0 || (n_send > 0 && !send_nodes)) return fail(c, RDC_ERR_INVALID, "bad send list");
+  const HostPrep& P = c->ms.prep;
+  c->ms.solve.plan_ready = false;
+  const int64_t n_int = c->opt.interior_nodes > 0 ? c->opt.interior_nodes : 0;
+  int64_t where = 0;
+  switch (dist_plan_check(P.n_owned, P.bptr.data(), P.bcol.data(), n_int, n_send, send_nodes, &where)) {
+    case 1: return fail(c, RDC_ERR_INVALID, "send entry %lld is node %d, which is not one of the %lld owned nodes", (long long)where,
+                        (int)send_nodes[where], (long long)P.n_owned);
+    case 2: return fail(c, RDC_ERR_INVALID, "\"interior_nodes\" = %lld exceeds the %lld owned nodes", (long long)n_int, (long long)P.n_owned);
+    case 3: return fail(c, RDC_ERR_INVALID, "node %lld lies below \"interior_nodes\" = %lld but its row has a ghost column", (long long)where, (long long)n_int);
+    default: break;
+  }
+  int rc = set_device(c);
+  if (rc) return rc;
+  if ((rc = dev_upload(c, c->buf.solve.send, std::vector<int32_t>(send_nodes, send_nodes + n_send)))) return rc;
+  RDC_HIP(c, hipStreamSynchronize(c->stream));   // the host copy goes out of scope
+  c->ms.solve.dist.n_nodes = P.n_node; c->ms.solve.dist.n_int = n_int; c->ms.solve.dist.n_send = n_send;
+  c->ms.solve.plan_ready = true;
+  return RDC_OK;
+}
+
+int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
+  if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
+  if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
+  if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
+    return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
+  if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
+  if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (p->precond == RDC_PRECOND_MULTIGRID)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner is not available across partitions (its aggregates would cross ranks)");
+  const HostPrep& P = c->ms.prep;
+  if (P.n_owned < P.n_node && !c->ms.solve.plan_ready)
+    return fail(c, RDC_ERR_STATE, "the context has ghost nodes (%lld owned of %lld) and no send list: call rdc_solve_dist_plan first",
+                (long long)P.n_owned, (long long)P.n_node);
+  SolveDev d;
+  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
+  int rc = solve_view(c, false, mixed != 0, &d);
+  if (rc) return rc;
+  d.dist = c->ms.solve.plan_ready ? c->ms.solve.dist : DistDims{P.n_node, 0, 0};
+  d.send_nodes = (const int32_t*)c->buf.solve.send.p;
+  if ((rc = dev_alloc(c, c->buf.solve.work, solve_work_bytes(P.nvar, P.n_owned, &d.dist)))) return rc;
+  if (!c->solve_rec) RDC_HIP(c, hipHostMalloc((void**)&c->solve_rec, sizeof(SolveScal), hipHostMallocDefault));
+  d.work = (double*)c->buf.solve.work.p;
+  d.host_rec = c->solve_rec;
+  int comm_rc = 0;
+  d.comm = comm; d.comm_rc = &comm_rc;
+  const hipError_t e = solve_run(d, *p, d_x, info, mixed != 0);
+  if (comm_rc) {
+    (void)hipStreamSynchronize(c->stream);   // x holds the last iterate
+    return fail(c, RDC_ERR_COMM, "a communication callback returned %d; the solve was abandoned", comm_rc);
+  }
+  RDC_HIP(c, e);
+  if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
+  return RDC_OK;
+}
 
 int rdc_clamp_nonnegative(rdc_ctx* c, int field) {
   if (!c) return RDC_ERR_INVALID;

@@ -389,11 +389,8 @@ inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_
   }
 }
 
-}  // namespace rdc
-
-#if defined(__HIPCC__)
-#include "../../include/rdc_assembly.h"
-namespace rdc {
+// ---- the iteration's scalars, its launch shapes and the layout of its work buffer: host code without HIP, so that a CPU build
+// can test the layout (tests/host_solve_dist_shim.cpp) ----
 
 // scalars of the iteration: they live in device memory and are consumed there; the host reads one copy per iteration
 struct SolveScal {
@@ -404,6 +401,78 @@ struct SolveScal {
   int32_t f32_overflow;                    // blocks of the fp32 copy that hold an entry which is not finite in fp32 (k_scale_f32)
   int32_t _pad;
 };
+
+constexpr int SPMV_NODES = 16;        // nodes per workgroup of k_spmv (256 threads)
+constexpr int F32_LANES = 8;          // lanes per node of k_spmv_f32 and k_scale_f32
+constexpr int F32_NODES = 32;         // nodes per workgroup of those two (256 threads)
+constexpr int VEC_PER_BLOCK = 1024;   // vector entries per workgroup of the update kernels (256 threads x 4)
+constexpr int DIST_RECORD = 8;        // doubles of the record a partitioned solve hands to allreduce_sum
+
+enum Form { PLAIN, SCALED, F32 };   // what the fine operator applies: A, D^-1 A (both on the FP64 values), or the fp32 copy of D^-1 A
+
+// Launch shapes: every grid size has its formula here and nowhere else
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t op_blocks(int64_t nodes, Form form) { return cdiv(nodes, form == F32 ? F32_NODES : SPMV_NODES); }   // k_spmv, k_spmv_f32, k_scale_f32
+inline int64_t vec_blocks(int64_t entries) { return cdiv(entries, VEC_PER_BLOCK); }                                  // k_update_*
+
+// What a partitioned solve (rdc_solve_dist) adds to the dimensions of a solve: ghost nodes behind the owned ones, the leading
+// owned nodes whose rows have no ghost column (the operator runs over them while the exchange is in flight), the send list.
+struct DistDims { int64_t n_nodes = 0, n_int = 0, n_send = 0; };
+
+// workgroups, = pairs of dot-product partials, of one operator application: one range of rows, or the interior range and the
+// rest one behind the other (n_int is no multiple of the nodes per workgroup)
+inline int64_t op_parts(int64_t n_owned, int64_t n_int, Form form) { return op_blocks(n_int, form) + op_blocks(n_owned - n_int, form); }
+
+// The work buffer of a solve: the one statement of its layout.  Without a base nothing is placed and `bytes` is what to allocate.
+// dist: p and s get a ghost tail to receive into (n_nodes * nvar), partials cover the two row ranges, and the send buffer
+// (n_send * nvar) and the record of the all-reduce follow; without it the layout is that of rdc_solve, byte for byte.
+struct Work {
+  double *r, *rh, *p, *v, *s, *t, *dinv, *partials, *send, *rec;
+  SolveScal* scal;
+  int64_t n, vec_blocks, node_blocks;
+  size_t bytes;
+};
+
+inline Work carve(int nvar, int64_t n_owned, double* base, const DistDims* dist = nullptr) {
+  Work w;
+  w.n = n_owned * nvar;
+  w.vec_blocks = vec_blocks(w.n);
+  w.node_blocks = cdiv(n_owned, 256);
+  const int64_t n = std::max<int64_t>(w.n, 1);
+  const int64_t ng = dist ? std::max<int64_t>(dist->n_nodes * nvar, 1) : n;   // p and s: the operator reads their ghost entries
+  // the largest set of partials a kernel leaves: (k_spmv, EPI 1), k_residual, k_update_xr
+  const int64_t partials = std::max(std::max(2 * op_parts(n_owned, dist ? dist->n_int : 0, SCALED), 4 * w.node_blocks), 3 * w.vec_blocks) + 8;
+  int64_t used = 0;
+  auto take = [&](int64_t doubles) { double* at = base ? base + used : nullptr; used += doubles; return at; };
+  w.r = take(n); w.rh = take(n); w.p = take(ng); w.v = take(n); w.s = take(ng); w.t = take(n);
+  w.dinv = take(n * nvar);
+  w.partials = take(partials);
+  w.send = dist ? take(std::max<int64_t>(dist->n_send * nvar, 1)) : nullptr;
+  w.rec = dist ? take(DIST_RECORD) : nullptr;
+  w.scal = (SolveScal*)take(0);
+  w.bytes = (size_t)used * sizeof(double) + sizeof(SolveScal);
+  return w;
+}
+
+// The plan of a partitioned solve, checked on the host: every send id is an owned node, n_int lies in [0, n_owned], and no
+// block of a node below n_int has a ghost column (bptr / bcol: the host copy of the pattern).  0 = fine; 1 = send id
+// *where is not owned; 2 = n_int out of range; 3 = node *where below n_int has a ghost column.
+inline int dist_plan_check(int64_t n_owned, const int64_t* bptr, const int32_t* bcol, int64_t n_int, int64_t n_send,
+                           const int32_t* send_nodes, int64_t* where) {
+  for (int64_t i = 0; i < n_send; i++)
+    if (send_nodes[i] < 0 || send_nodes[i] >= n_owned) { *where = i; return 1; }
+  if (n_int < 0 || n_int > n_owned) { *where = n_int; return 2; }
+  for (int64_t node = 0; node < n_int; node++)
+    for (int64_t k = bptr[node]; k < bptr[node + 1]; k++)
+      if (bcol[k] >= n_owned) { *where = node; return 3; }
+  return 0;
+}
+
+}  // namespace rdc
+
+#if defined(__HIPCC__)
+#include "../../include/rdc_assembly.h"
+namespace rdc {
 
 // what rdc_csr_matvec / rdc_solve need of a context (rdc_capi.hip fills it)
 struct SolveDev {
@@ -419,9 +488,17 @@ struct SolveDev {
   SolveScal* host_rec = nullptr;   // pinned
   hipStream_t stream = nullptr;
   MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
+  // partitioned solve (rdc_solve_dist) only.  comm == nullptr is the single-partition path.
+  const rdc_solve_comm* comm = nullptr;
+  DistDims dist;                       // n_nodes, interior nodes, length of the send list
+  const int32_t* send_nodes = nullptr; // device copy of the send list (owned local node ids, send order)
+  int* comm_rc = nullptr;              // out: the first non-zero return of a callback; nothing is called after it
 };
 
-size_t solve_work_bytes(int nvar, int64_t n_owned);
+// what solve_run returns after a callback has failed (*SolveDev::comm_rc tells its value)
+constexpr hipError_t SOLVE_COMM_FAILED = hipErrorOperatingSystem;
+
+size_t solve_work_bytes(int nvar, int64_t n_owned, const DistDims* dist = nullptr);
 hipError_t solve_matvec(const SolveDev& d, const double* x, double* y);
 // mixed: iterate on the fp32 copy (built here from the current values); info->matrix_bits tells what the iteration streamed
 hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed);

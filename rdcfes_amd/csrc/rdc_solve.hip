@@ -26,8 +26,14 @@
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
 // device memory.  No floating-point atomics anywhere.
 //
-// Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy and multigrid cycle are arguments), `apply`
-// the one entry to y = A_l x on any level in any form, `carve` the one statement of the work buffer's layout.
+// Across partitions (rdc_solve_dist): the same driver with a communicator.  apply_halo wraps an operator application
+// into pack / exchange_begin / rows without ghost columns / exchange_end / the other rows, and k_finalize becomes k_reduce, the
+// all-reduce callback and k_advance, so that every scalar the host reads and every branch it takes is global.  Without a
+// communicator the launches are those of the single-partition path, in the same order.
+//
+// Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy, multigrid cycle and communicator are
+// arguments), `apply` the one entry to y = A_l x on any level in any form; `carve` (rdc_solve.h) is the one statement of the work
+// buffer's layout.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -37,10 +43,7 @@
 namespace rdc {
 namespace {
 
-constexpr int SPMV_NODES = 16;        // nodes per workgroup of k_spmv (256 threads)
-constexpr int F32_LANES = 8;          // lanes per node of k_spmv_f32 and k_scale_f32
-constexpr int F32_NODES = 32;         // nodes per workgroup of those two (256 threads)
-constexpr int VEC_PER_BLOCK = 1024;   // vector entries per workgroup of the update kernels (256 threads x 4)
+// (workgroup shapes of the kernels: SPMV_NODES, F32_LANES, F32_NODES, VEC_PER_BLOCK in rdc_solve.h, beside the launch formulas)
 constexpr int MAX_BREAKDOWNS = 10;    // restarts after a break-down before RDC_SOLVE_BREAKDOWN
 
 enum { STAGE_INIT = 0, STAGE_ALPHA = 1, STAGE_OMEGA = 2, STAGE_RHO = 3 };
@@ -290,11 +293,10 @@ __global__ __launch_bounds__(256) void k_residual(const double* __restrict__ rhs
   block_partials<4>(c, partials);
 }
 
-// adds the partials of the previous kernel in a fixed order and advances the scalars (one workgroup)
-__global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage,
-                                                   SolveScal* __restrict__ scal) {
-  __shared__ double sh[4][1024];
-  const bool skip = stage != STAGE_INIT && scal->flag != 0;   // a flagged iteration wrote no partials
+// the `ncomp` sums of the partials of the previous kernel, in a fixed order (one workgroup of 1024): thread 0 finds them in
+// sh[c][0] behind the call, 0.0 in the components from ncomp on.  skip: a flagged iteration wrote no partials, nothing is read.
+__device__ __forceinline__ void sum_partials(const double* __restrict__ partials, int64_t nparts, int ncomp, bool skip,
+                                             double (&sh)[4][1024]) {
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   if (!skip)
     for (int64_t i = threadIdx.x; i < nparts; i += 1024)
@@ -306,12 +308,15 @@ __global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ pa
       for (int c = 0; c < ncomp; c++) sh[c][threadIdx.x] += sh[c][threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x != 0 || skip) return;
-  const double s0 = sh[0][0], s1 = sh[1][0];
+}
+
+// The scalars of the iteration from the sums of a stage: the one statement of rho, alpha, omega, beta and the flags.  The sums
+// are those of the whole system: of this partition's partials (k_finalize), or of all partitions (k_advance).
+__device__ __forceinline__ void advance_scalars(SolveScal* __restrict__ scal, int stage, double s0, double s1, double s2, double s3) {
   if (stage == STAGE_INIT) {
-    scal->rn2 = s0; scal->rn2_plain = s1; scal->bn2 = sh[2][0]; scal->bn2_plain = sh[3][0];
+    scal->rn2 = s0; scal->rn2_plain = s1; scal->bn2 = s2; scal->bn2_plain = s3;
     scal->rho = s0; scal->alpha = 1.0; scal->omega = 1.0; scal->beta = 0.0;   // p = v = 0: the first update gives p = r
-    scal->flag = (finite_d(s0) && finite_d(sh[2][0])) ? 0 : 1;
+    scal->flag = (finite_d(s0) && finite_d(s2)) ? 0 : 1;
   } else if (stage == STAGE_ALPHA) {
     const double alpha = scal->rho / s0;
     scal->alpha = alpha;
@@ -323,9 +328,55 @@ __global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ pa
   } else {
     const double beta = (s0 / scal->rho) * (scal->alpha / scal->omega);
     scal->rn2 = s1; scal->beta = beta; scal->rho = s0;
-    if (!finite_d(s1) || !finite_d(beta) || sh[2][0] != 0.0) scal->flag |= 1;
+    if (!finite_d(s1) || !finite_d(beta) || s2 != 0.0) scal->flag |= 1;
     else if (s0 == 0.0) scal->flag |= 2;
   }
+}
+
+// adds the partials of the previous kernel in a fixed order and advances the scalars (one workgroup)
+__global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage,
+                                                   SolveScal* __restrict__ scal) {
+  __shared__ double sh[4][1024];
+  const bool skip = stage != STAGE_INIT && scal->flag != 0;   // a flagged iteration wrote no partials
+  sum_partials(partials, nparts, ncomp, skip, sh);
+  if (threadIdx.x != 0 || skip) return;
+  advance_scalars(scal, stage, sh[0][0], sh[1][0], sh[2][0], sh[3][0]);
+}
+
+// Partitioned solve: k_finalize in two halves with the all-reduce between them.  k_reduce: this partition's sums, in the same
+// fixed order, into rec[0 .. 4); counters (the first residual of a solve): rec[4], rec[5] = this partition's bad_blocks and
+// f32_overflow, counts as doubles (exact below 2^53).  A flagged iteration (the flag is the same on every partition) sends zeros.
+__global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage,
+                                                 const SolveScal* __restrict__ scal, double* __restrict__ rec, int counters) {
+  __shared__ double sh[4][1024];
+  const bool skip = stage != STAGE_INIT && scal->flag != 0;
+  sum_partials(partials, nparts, ncomp, skip, sh);
+  if (threadIdx.x != 0) return;
+  for (int c = 0; c < 4; c++) rec[c] = sh[c][0];
+  rec[4] = counters ? (double)scal->bad_blocks : 0.0;
+  rec[5] = counters ? (double)scal->f32_overflow : 0.0;
+  rec[6] = 0.0; rec[7] = 0.0;
+}
+
+// k_advance: the scalars from the all-reduced record (one thread).  Every partition computes the same bits from the same bits.
+__global__ void k_advance(const double* __restrict__ rec, int stage, SolveScal* __restrict__ scal, int counters) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (stage != STAGE_INIT && scal->flag != 0) return;
+  if (counters) {
+    scal->bad_blocks = (int32_t)rec[4];
+    scal->f32_overflow = (int32_t)rec[5];
+  }
+  advance_scalars(scal, stage, rec[0], rec[1], rec[2], rec[3]);
+}
+
+// send[i * NV + a] = x[send_nodes[i] * NV + a]: the owned values the peers hold as ghosts, in plan order (one thread per double)
+template <int NV>
+__global__ __launch_bounds__(256) void k_halo_pack(const int32_t* __restrict__ send_nodes, int64_t n_send, const double* __restrict__ x,
+                                                   double* __restrict__ send) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_send * NV) return;
+  const int64_t e = i / NV;
+  send[i] = x[(int64_t)send_nodes[e] * NV + (i - e * NV)];
 }
 
 // p = r + beta (p - omega v)
@@ -494,15 +545,11 @@ __global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv,
     (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
     (const void*)k_precond_setup<3>, (const void*)k_scale_f32<3>, (const void*)k_precond_setup<5>, (const void*)k_scale_f32<5>,
-    KERNELS_OF(3), (const void*)k_update_xr<true>, (const void*)k_update_xr<false>, KERNELS_OF(5)};
+    KERNELS_OF(3), (const void*)k_update_xr<true>, (const void*)k_update_xr<false>, KERNELS_OF(5),
+    (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>};
 #undef KERNELS_OF
 
-// ---- host side.  Launch shapes: every grid size has its formula here and nowhere else ----
-enum Form { PLAIN, SCALED, F32 };   // what the fine operator applies: A, D^-1 A (both on the FP64 values), or the fp32 copy of D^-1 A
-
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int64_t op_blocks(int64_t nodes, Form form) { return cdiv(nodes, form == F32 ? F32_NODES : SPMV_NODES); }   // k_spmv, k_spmv_f32, k_scale_f32
-int64_t vec_blocks(int64_t entries) { return cdiv(entries, VEC_PER_BLOCK); }                                  // k_update_*
+// ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
 
 #define SOLVE_HIP(call)                 \
@@ -535,57 +582,74 @@ hipError_t timed(hipStream_t stream, float* ms, F&& body) {
   return e;
 }
 
-// The work buffer of a solve: the one statement of its layout.  Without a base nothing is placed and `bytes` is what to allocate.
-struct Work {
-  double *r, *rh, *p, *v, *s, *t, *dinv, *partials;
-  SolveScal* scal;
-  int64_t n, vec_blocks, node_blocks;
-  size_t bytes;
-};
+// (the work buffer of a solve and its layout: Work, carve in rdc_solve.h)
 
-Work carve(int nvar, int64_t n_owned, double* base) {
-  Work w;
-  w.n = n_owned * nvar;
-  w.vec_blocks = vec_blocks(w.n);
-  w.node_blocks = cdiv(n_owned, 256);
-  const int64_t n = std::max<int64_t>(w.n, 1);
-  // the largest set of partials a kernel leaves: (k_spmv, EPI 1), k_residual, k_update_xr
-  const int64_t partials = std::max(std::max(2 * op_blocks(n_owned, SCALED), 4 * w.node_blocks), 3 * w.vec_blocks) + 8;
-  int64_t used = 0;
-  auto take = [&](int64_t doubles) { double* at = base ? base + used : nullptr; used += doubles; return at; };
-  w.r = take(n); w.rh = take(n); w.p = take(n); w.v = take(n); w.s = take(n); w.t = take(n);
-  w.dinv = take(n * nvar);
-  w.partials = take(partials);
-  w.scal = (SolveScal*)take(0);
-  w.bytes = (size_t)used * sizeof(double) + sizeof(SolveScal);
-  return w;
+// a callback's return: non-zero ends the solve, and nothing is called after it
+hipError_t callback(const SolveDev& d, int rc) {
+  if (rc == 0) return hipSuccess;
+  *d.comm_rc = rc;
+  return SOLVE_COMM_FAILED;
 }
 
 // y = A_l x on level l of the hierarchy, the one entry to the three SpMV kernels.  Level 0 is the context's matrix in the form
 // asked for; a level below owns one matrix (PLAIN whatever `form` says).  dot_with: also the partials of (y, dot_with) and
 // (y, y) (SCALED and F32 only).  PLAIN and F32 without a dot product need no Work.
+// n0, n1: the rows of the nodes [n0, n1) only (level 0; n1 < 0: all).  The kernels see the node n0 as their node 0: whatever they
+// index by node (bptr, voff, y, D^-1, dot_with) is shifted, whatever they reach through bptr and bcol (values, x) is not, since
+// bptr and voff hold absolute offsets.  The partials of a range lie behind those of the rows [0, n0) (op_parts).
 template <int NV>
-hipError_t apply(const SolveDev& d, const Work* w, int l, Form form, const double* x, double* y, const double* dot_with) {
+hipError_t apply(const SolveDev& d, const Work* w, int l, Form form, const double* x, double* y, const double* dot_with,
+                 int64_t n0 = 0, int64_t n1 = -1) {
   const MgLevelDev* L = l ? &d.mg->lv[l] : nullptr;
   if (L) form = PLAIN;
   if (form == PLAIN && dot_with) return hipErrorInvalidValue;
-  const int64_t n = L ? L->n : d.n_owned;
+  if (n1 < 0) n1 = L ? L->n : d.n_owned;
+  if (L && n0) return hipErrorInvalidValue;
+  const int64_t n = n1 - n0;
   const dim3 grid((unsigned)op_blocks(n, form)), block(256);
   if (!grid.x) return hipSuccess;
-  double* partials = dot_with ? w->partials : nullptr;
+  double* partials = dot_with ? w->partials + 2 * op_blocks(n0, form) : nullptr;
+  y += n0 * NV;
+  if (dot_with) dot_with += n0 * NV;
   if (form == F32) {
-    hipLaunchKernelGGL((dot_with ? k_spmv_f32<NV, 1> : k_spmv_f32<NV, 0>), grid, block, 0, d.stream, d.bptr, d.bcol, d.voff,
+    hipLaunchKernelGGL((dot_with ? k_spmv_f32<NV, 1> : k_spmv_f32<NV, 0>), grid, block, 0, d.stream, d.bptr + n0, d.bcol, d.voff + n0,
                        (const float*)d.val32, x, y, n, dot_with, partials);
   } else {
     hipLaunchKernelGGL((form == PLAIN ? k_spmv<NV, 0> : dot_with ? k_spmv<NV, 1> : k_spmv<NV, 2>), grid, block, 0, d.stream,
-                       L ? L->bptr : d.bptr, L ? L->bcol : d.bcol, L ? (const double*)L->val : d.val, x, y, n,
-                       form == PLAIN ? (const double*)nullptr : (const double*)w->dinv, dot_with, partials);
+                       (L ? L->bptr : d.bptr) + n0, L ? L->bcol : d.bcol, L ? (const double*)L->val : d.val, x, y, n,
+                       form == PLAIN ? (const double*)nullptr : (const double*)w->dinv + n0 * NV * NV, dot_with, partials);
   }
   return hipGetLastError();
 }
 
-hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage) {
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage, w.scal);
+// y = A x on level 0 of a vector whose ghost entries the peers own: pack and exchange_begin, the rows that read no ghost,
+// exchange_end, the other rows.  x is written: its ghost tail [n_owned, n_nodes) receives.  Without a communicator: apply.
+template <int NV>
+hipError_t apply_halo(const SolveDev& d, const Work& w, Form form, double* x, double* y, const double* dot_with) {
+  if (!d.comm) return apply<NV>(d, &w, 0, form, x, y, dot_with);
+  if (d.dist.n_send) {
+    hipLaunchKernelGGL((k_halo_pack<NV>), per_thread(d.dist.n_send * NV), dim3(256), 0, d.stream, d.send_nodes, d.dist.n_send,
+                       (const double*)x, w.send);
+    SOLVE_HIP(hipGetLastError());
+  }
+  SOLVE_HIP(callback(d, d.comm->exchange_begin(d.comm->user, w.send, x + d.n_owned * NV, (void*)d.stream)));
+  SOLVE_HIP(apply<NV>(d, &w, 0, form, x, y, dot_with, 0, d.dist.n_int));
+  SOLVE_HIP(callback(d, d.comm->exchange_end(d.comm->user, (void*)d.stream)));
+  return apply<NV>(d, &w, 0, form, x, y, dot_with, d.dist.n_int, d.n_owned);
+}
+
+// the scalars of a stage from the partials of the kernel before it.  With a communicator the sums cross the partitions on their
+// way (k_reduce, allreduce_sum, k_advance); counters: the record also carries bad_blocks and f32_overflow (first residual).
+hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage, bool counters = false) {
+  if (!d.comm) {
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage, w.scal);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage,
+                     (const SolveScal*)w.scal, w.rec, (int)counters);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(callback(d, d.comm->allreduce_sum(d.comm->user, w.rec, counters ? 6 : ncomp, (void*)d.stream)));
+  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, d.stream, (const double*)w.rec, stage, w.scal, (int)counters);
   return hipGetLastError();
 }
 
@@ -596,13 +660,15 @@ hipError_t read_record(const SolveDev& d, const Work& w) {
 }
 
 // true residual of x: r = r_hat = D^-1 (b - A x), p = v = 0, scalars as at the start; this is also the restart
+// (across partitions: the ghost values of x are exchanged first; first: the record carries the counters of setup)
 template <int NV>
-hipError_t residual(const SolveDev& d, const Work& w, const double* x, double scale) {
-  SOLVE_HIP(apply<NV>(d, &w, 0, PLAIN, x, w.t, nullptr));
-  hipLaunchKernelGGL((k_residual<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.rhs, scale, (const double*)w.t,
-                     (const double*)w.dinv, w.r, w.rh, w.p, w.v, d.n_owned, w.partials);
+hipError_t residual(const SolveDev& d, const Work& w, double* x, double scale, bool first = false) {
+  SOLVE_HIP(apply_halo<NV>(d, w, PLAIN, x, w.t, nullptr));
+  if (w.node_blocks)   // a partition may own no node; the single-partition entry never gets here without one
+    hipLaunchKernelGGL((k_residual<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.rhs, scale, (const double*)w.t,
+                       (const double*)w.dinv, w.r, w.rh, w.p, w.v, d.n_owned, w.partials);
   SOLVE_HIP(hipGetLastError());
-  SOLVE_HIP(finalize(d, w, w.node_blocks, 4, STAGE_INIT));
+  SOLVE_HIP(finalize(d, w, w.node_blocks, 4, STAGE_INIT, first && d.comm));
   return read_record(d, w);
 }
 
@@ -682,19 +748,21 @@ hipError_t mg_setup(const SolveDev& d, const Work& w) {
 template <int NV>
 hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, bool mg) {
   const dim3 vg((unsigned)w.vec_blocks), vb(256);
-  const int64_t op_parts = op_blocks(d.n_owned, form);
-  const double* px = mg ? d.mg->ph : w.p;
-  const double* sx = mg ? d.mg->sh : w.s;
-  hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
+  const int64_t parts = op_parts(d.n_owned, d.comm ? d.dist.n_int : 0, form);
+  double* px = mg ? d.mg->ph : w.p;   // across partitions (never with mg): p and s themselves, whose ghost tails receive
+  double* sx = mg ? d.mg->sh : w.s;
+  if (vg.x) hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
   if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.p, d.mg->ph));
-  SOLVE_HIP(apply<NV>(d, &w, 0, form, px, w.v, w.rh));   // v = D^-1 A [M] p, (r_hat, v)
-  SOLVE_HIP(finalize(d, w, op_parts, 2, STAGE_ALPHA));
-  hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
+  SOLVE_HIP(apply_halo<NV>(d, w, form, px, w.v, w.rh));   // v = D^-1 A [M] p, (r_hat, v)
+  SOLVE_HIP(finalize(d, w, parts, 2, STAGE_ALPHA));
+  if (vg.x) hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
   if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.s, d.mg->sh));
-  SOLVE_HIP(apply<NV>(d, &w, 0, form, sx, w.t, w.s));    // t = D^-1 A [M] s, (t, s), (t, t)
-  SOLVE_HIP(finalize(d, w, op_parts, 2, STAGE_OMEGA));
-  hipLaunchKernelGGL((mg ? k_update_xr<true> : k_update_xr<false>), vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s,
-                     (const double*)w.t, (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, mg ? px : nullptr, mg ? sx : nullptr);
+  SOLVE_HIP(apply_halo<NV>(d, w, form, sx, w.t, w.s));    // t = D^-1 A [M] s, (t, s), (t, t)
+  SOLVE_HIP(finalize(d, w, parts, 2, STAGE_OMEGA));
+  if (vg.x)
+    hipLaunchKernelGGL((mg ? k_update_xr<true> : k_update_xr<false>), vg, vb, 0, d.stream, x, w.r, (const double*)w.p, (const double*)w.s,
+                       (const double*)w.t, (const double*)w.rh, (const SolveScal*)w.scal, w.n, w.partials, mg ? (const double*)px : nullptr,
+                       mg ? (const double*)sx : nullptr);
   SOLVE_HIP(hipGetLastError());
   SOLVE_HIP(finalize(d, w, w.vec_blocks, 3, STAGE_RHO));
   return read_record(d, w);
@@ -702,8 +770,8 @@ hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, boo
 
 template <int NV>
 hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
-  const Work w = carve(d.nvar, d.n_owned, d.work);
-  const SolveScal& rec = *d.host_rec;
+  const Work w = carve(d.nvar, d.n_owned, d.work, d.comm ? &d.dist : nullptr);
+  const SolveScal& rec = *d.host_rec;   // across partitions: the all-reduced scalars, the same bits on every rank, so every branch below is collective
   auto report = [&](int reason) {
     info->reason = reason;
     info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
@@ -713,14 +781,14 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
   const bool mg = p.precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
   SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : (int)p.precond, mixed));
   if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
-  SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
+  SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale, true));
   info->bad_blocks = rec.bad_blocks;
   const Form form = mixed && rec.f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
   info->matrix_bits = form == F32 ? 32 : 64;
   if (rec.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
   if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
   if (rec.bn2 == 0.0) {   // b = 0: x = 0
-    SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)w.n * sizeof(double), d.stream));
+    SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)(d.comm ? d.dist.n_nodes * NV : w.n) * sizeof(double), d.stream));
     SOLVE_HIP(hipStreamSynchronize(d.stream));
     report(RDC_SOLVE_CONVERGED);
     info->residual_norm = info->plain_residual_norm = 0.0;
@@ -754,7 +822,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
 
 }  // namespace
 
-size_t solve_work_bytes(int nvar, int64_t n_owned) { return carve(nvar, n_owned, nullptr).bytes; }
+size_t solve_work_bytes(int nvar, int64_t n_owned, const DistDims* dist) { return carve(nvar, n_owned, nullptr, dist).bytes; }
 
 hipError_t solve_matvec(const SolveDev& d, const double* x, double* y) {
   return by_nvar(d.nvar, [&](auto nv) { return apply<decltype(nv)::value>(d, nullptr, 0, PLAIN, x, y, nullptr); });

@@ -6,8 +6,11 @@ all-reduce, no ring.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.distributed as dist
+
+from .params import ALLREDUCE_SUM_FN, EXCHANGE_BEGIN_FN, EXCHANGE_END_FN, SolveCommStruct
 
 
 class HaloExchange:
@@ -104,3 +107,141 @@ class HaloExchange:
             if self.host_staged:
                 self.recv_buf.copy_(self.recv_host, non_blocking=True)
             u.index_copy_(0, self.recv_idx, self.recv_buf)
+
+
+class SolveComm:
+    """The communicator of AssemblyContext.solve_dist (rdc_solve_comm of the C-ABI) on torch.distributed: the three callbacks
+    the library calls from inside its BiCGStab -- exchange_begin / exchange_end move the ghost values of one vector (the library
+    has packed the send buffer; the ghosts are the contiguous tail of the vector, grouped by owner, so the receive side needs
+    no unpack), allreduce_sum adds up to 8 doubles over the ranks.  "nccl" (RCCL) works on the device buffers, on the stream
+    the library names; "gloo" stages through pinned host buffers and synchronises that stream, as HaloExchange does: a test rig,
+    correct but no measure of speed.  Without an initialised process group the communicator is that of world size 1.
+
+    send_nodes is the send list for rdc_solve_dist_plan (peer order, per peer the order of lp.send_ids, which is the order of
+    the peer's lp.recv_ids: ascending global id on both sides).  An exception inside a callback is kept in .error and the
+    callback returns 1; solve_dist re-raises it.  Subclasses may override begin / end / allreduce (tests do)."""
+
+    def __init__(self, lp, nvar: int, device, group=None):
+        self.group, self.nvar, self.rank = group, int(nvar), lp.rank
+        self.dev = torch.device(device)
+        peers = sorted(set(lp.send_ids) | set(lp.recv_ids))
+        self.send_peers = [q for q in peers if q in lp.send_ids and len(lp.send_ids[q])]
+        self.recv_peers = [q for q in peers if q in lp.recv_ids and len(lp.recv_ids[q])]
+        self.send_nodes = (np.concatenate([np.asarray(lp.send_ids[q]) for q in self.send_peers]) if self.send_peers
+                           else np.zeros(0)).astype(np.int32)
+        self.n_send, self.n_ghost = int(self.send_nodes.size), int(lp.xyz.shape[0] - lp.n_owned)
+        # per-peer slices, in rows of nvar doubles: of the send buffer, and of the ghost tail
+        self.send_slice, self.recv_slice, o = {}, {}, 0
+        for q in self.send_peers:
+            self.send_slice[q] = (o, o + len(lp.send_ids[q]))
+            o += len(lp.send_ids[q])
+        for q in self.recv_peers:
+            ids = np.asarray(lp.recv_ids[q], dtype=np.int64)
+            if not np.array_equal(ids, np.arange(ids[0], ids[0] + ids.size)):
+                raise ValueError(f"the ghosts owned by rank {q} are not contiguous in the local numbering")
+            self.recv_slice[q] = (int(ids[0]) - lp.n_owned, int(ids[0]) - lp.n_owned + ids.size)
+        self.bytes_per_exchange = 8 * self.nvar * self.n_send
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.host_staged = self.world > 1 and dist.get_backend(group) == "gloo"
+        if self.host_staged:
+            pin = self.dev.type == "cuda"
+            mk = lambda rows: torch.empty((rows, self.nvar), dtype=torch.float64, pin_memory=pin)
+            self.send_host, self.recv_host = mk(self.n_send), mk(self.n_ghost)
+            self.vals_host = torch.empty(8, dtype=torch.float64, pin_memory=pin)
+        self.exchanges = self.allreduces = 0
+        self.error = None
+        self._views, self._streams, self._pending, self._recv = {}, {}, [], None
+        # the ctypes function objects must outlive every call that uses the struct
+        self._cb = (EXCHANGE_BEGIN_FN(self._guard(self._c_begin)), EXCHANGE_END_FN(self._guard(self._c_end)),
+                    ALLREDUCE_SUM_FN(self._guard(self._c_allreduce)))
+        self.struct = SolveCommStruct(None, *self._cb)
+
+    # -- raw addresses -> torch
+    def _view(self, addr, rows):
+        """zero-copy [rows][nvar] view of device memory at addr (the library's send buffer, a vector's ghost tail, the record)"""
+        if rows == 0 or not addr:
+            return torch.empty((0, self.nvar), dtype=torch.float64, device=self.dev)
+        key = (addr, rows)
+        if key not in self._views:
+            class _V:
+                pass
+            v = _V()
+            v.__cuda_array_interface__ = {"shape": (rows, self.nvar), "typestr": "<f8", "data": (addr, False), "version": 2, "strides": None}
+            self._views[key] = torch.as_tensor(v, device=self.dev)
+        return self._views[key]
+
+    def _stream(self, ptr):
+        if not ptr:
+            return torch.cuda.default_stream(self.dev)
+        if ptr not in self._streams:
+            self._streams[ptr] = torch.cuda.ExternalStream(ptr, device=self.dev)
+        return self._streams[ptr]
+
+    def _guard(self, f):
+        def call(*a):
+            try:
+                return int(f(*a) or 0)
+            except BaseException as e:   # must not propagate into the C caller
+                self.error = e
+                return 1
+        return call
+
+    def _c_begin(self, user, d_send, d_recv, stream):
+        return self.begin(self._view(d_send, self.n_send), self._view(d_recv, self.n_ghost), self._stream(stream))
+
+    def _c_end(self, user, stream):
+        return self.end(self._stream(stream))
+
+    def _c_allreduce(self, user, d_vals, n, stream):
+        class _V:
+            pass
+        key = ("vals", d_vals)
+        if key not in self._views:
+            v = _V()
+            v.__cuda_array_interface__ = {"shape": (8,), "typestr": "<f8", "data": (d_vals, False), "version": 2, "strides": None}
+            self._views[key] = torch.as_tensor(v, device=self.dev)
+        return self.allreduce(self._views[key][:n], self._stream(stream))
+
+    # -- the three callbacks on tensors.  send: [n_send][nvar], packed; recv: [n_ghost][nvar], the ghost tail; stream: the library's
+    def begin(self, send, recv, stream):
+        self.exchanges += 1
+        if self.world == 1 or not (self.send_peers or self.recv_peers):
+            return 0
+        with torch.cuda.stream(stream):
+            if self.host_staged:
+                if self.n_send:
+                    self.send_host.copy_(send, non_blocking=True)
+                stream.synchronize()
+                sb, rb, self._recv = self.send_host, self.recv_host, recv
+            else:
+                sb, rb, self._recv = send, recv, None
+            ops = [dist.P2POp(dist.irecv, rb[slice(*self.recv_slice[q])], q, group=self.group) for q in self.recv_peers]
+            ops += [dist.P2POp(dist.isend, sb[slice(*self.send_slice[q])], q, group=self.group) for q in self.send_peers]
+            self._pending = dist.batch_isend_irecv(ops)
+        return 0
+
+    def end(self, stream):
+        if self.world == 1 or not (self.send_peers or self.recv_peers):
+            return 0
+        with torch.cuda.stream(stream):
+            for w in self._pending:
+                w.wait()
+            self._pending = []
+            if self._recv is not None and self.n_ghost:
+                self._recv.copy_(self.recv_host, non_blocking=True)
+        return 0
+
+    def allreduce(self, vals, stream):
+        self.allreduces += 1
+        if self.world == 1:
+            return 0
+        with torch.cuda.stream(stream):
+            if self.host_staged:
+                h = self.vals_host[:vals.numel()]
+                h.copy_(vals, non_blocking=True)
+                stream.synchronize()
+                dist.all_reduce(h, group=self.group)
+                vals.copy_(h, non_blocking=True)
+            else:
+                dist.all_reduce(vals, group=self.group)
+        return 0

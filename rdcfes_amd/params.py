@@ -104,6 +104,17 @@ class SolveInfo(C.Structure):
                 f"device_ms={self.device_ms:.3f}, matrix_bits={self.matrix_bits})")
 
 
+EXCHANGE_BEGIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)   # user, d_send, d_recv, hip_stream
+EXCHANGE_END_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)                             # user, hip_stream
+ALLREDUCE_SUM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)     # user, d_vals, n, hip_stream
+
+
+class SolveCommStruct(C.Structure):
+    """rdc_solve_comm: the three communication callbacks of rdc_solve_dist (halo.SolveComm fills one)."""
+    _fields_ = [("user", C.c_void_p), ("exchange_begin", EXCHANGE_BEGIN_FN), ("exchange_end", EXCHANGE_END_FN),
+                ("allreduce_sum", ALLREDUCE_SUM_FN)]
+
+
 # reference parameter key -> struct field
 PIHNA_KEYS = {
     "time_step": "time_step",

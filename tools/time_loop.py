@@ -1,7 +1,8 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--ab [precond|precision]] [--dump DIR]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--ab [precond|precision|dist]] [--dump DIR]
+    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
@@ -10,8 +11,16 @@ matrix_bits in every record says what ran).  --precond 3 is the aggregation-mult
 the device ms the solve spent building the hierarchy (mg_setup_ms, part of solve_ms), its level sizes and the device bytes it
 holds.  --ab runs the loop four times from the same initial state on one upload, so that two kinds of solve are timed in one
 process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, multigrid, block Jacobi (all four fp64, or all
-four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond.  --dump writes the state after the
-last step as DIR/state.npy (+ conn, xyz)."""
+four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
+rdc_solve_dist, rdc_solve_dist, rdc_solve, the partitioned entry at world size 1 (its exchange moves nothing and its all-reduce
+leaves the values alone: what is timed is the pack launches, the k_reduce / k_advance split and the callbacks).  --dump writes
+the state after the last step as DIR/state.npy (+ conn, xyz).
+
+--ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
+rdc_solve_dist -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
+no halo update of its own.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
+iterations and the global true residual.  Rank r uses GPU r modulo the number of GPUs: on a one-GPU machine the ranks share it,
+and with --backend gloo every message is staged through the host -- such a run checks correctness and measures nothing."""
 import argparse
 import json
 import sys
@@ -42,9 +51,10 @@ def background_share(u, conn_dev):
     return float(bg.double().mean()), float(bg[conn_dev].all(dim=1).double().mean())
 
 
-def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False):
+def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None):
     """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
-    on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there)."""
+    on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there).
+    comm: a halo.SolveComm -- the solve is solve_dist across its ranks (the background shares are then those of the local nodes)."""
     import torch
     dev = torch.device("cuda", ctx.device)
     u = state_tensor(ctx)
@@ -57,7 +67,10 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         asm_ms = ctx.timing_last_ms()
         if on_step:
             on_step(k, "assembled", ctx)
-        info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
+        if comm is None:
+            info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
+        else:
+            info = ctx.solve_dist(comm, u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
         if on_step:
             on_step(k, "solved", ctx)
         ctx.clamp_nonnegative(0)
@@ -72,6 +85,46 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
     return out
 
 
+def rank_main(rank, world, port, a):
+    """one rank of --ranks"""
+    import os
+    from datetime import timedelta
+    import torch
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    gpu = rank % torch.cuda.device_count()
+    torch.cuda.set_device(gpu)
+    dist.init_process_group(a.backend, rank=rank, world_size=world, timeout=timedelta(seconds=300))
+    try:
+        from rdcfes_amd import AssemblyContext, SolveComm, partition, pihna_params_from_dict, synth
+        conn, xyz = synth.kuhn_tet_mesh(a.n, order="lex")
+        p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+        part = partition.partition_rcb(xyz[conn.astype(np.int64)].mean(axis=1), world)
+        lp = partition.build_local(conn, xyz, part, rank, world)
+        with AssemblyContext(gpu) as ctx:
+            ctx.set_option("interior_nodes", int(lp.n_interior))
+            ctx.mesh_upload(4, lp.conn, lp.xyz, 5, n_owned=lp.n_owned)
+            ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
+            comm = SolveComm(lp, 5, torch.device("cuda", gpu))
+            shared = world > torch.cuda.device_count()
+            head = dict(rank=rank, gpu=gpu, owned_nodes=int(lp.n_owned), interior_nodes=int(lp.n_interior),
+                        ghost_nodes=int(lp.xyz.shape[0] - lp.n_owned), halo_bytes_per_exchange=comm.bytes_per_exchange,
+                        neighbours=len(comm.send_peers), backend=a.backend,
+                        timing="correctness only: ranks share a GPU or stage through the host" if shared or a.backend == "gloo" else "device")
+            for r in range(world):     # one line per rank, in rank order
+                if r == rank:
+                    print(json.dumps(head), flush=True)
+                dist.barrier()
+            for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, a.precond, a.max_its, mixed=a.mixed, comm=comm):
+                if rank == 0:          # every figure of the solve is global and the same on every rank
+                    keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
+                    print(json.dumps({k: rec[k] for k in keep}), flush=True)
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=119)
@@ -80,9 +133,20 @@ def main():
     ap.add_argument("--precond", type=int, default=2)
     ap.add_argument("--max-its", type=int, default=20000)
     ap.add_argument("--mixed", action="store_true")
-    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision"), default=None)
+    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist"), default=None)
     ap.add_argument("--dump", default=None)
+    ap.add_argument("--ranks", type=int, default=1)
+    ap.add_argument("--backend", choices=("gloo", "nccl"), default="gloo")
     a = ap.parse_args()
+    if a.ranks > 1:
+        import socket
+        import torch.multiprocessing as mp
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        print(json.dumps(dict(mesh=f"K({a.n})", ranks=a.ranks, backend=a.backend, rel_tol=a.rel_tol, precond=a.precond, mixed=a.mixed)), flush=True)
+        mp.spawn(rank_main, args=(a.ranks, port, a), nprocs=a.ranks, join=True)
+        return
     import torch
     torch.cuda.init()                       # before the library opens the device: one runtime initialisation order for both
     from rdcfes_amd import AssemblyContext, pihna_params_from_dict, synth
@@ -91,15 +155,24 @@ def main():
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
-        runs = [(a.precond, a.mixed)]
+        runs = [(a.precond, a.mixed, False)]
         if a.ab == "precond":
-            runs = [(pc, a.mixed) for pc in (2, 3, 3, 2)]
+            runs = [(pc, a.mixed, False) for pc in (2, 3, 3, 2)]
         elif a.ab == "precision":
-            runs = [(a.precond, mixed) for mixed in (False, True, True, False)]
-        for precond, mixed in runs:
+            runs = [(a.precond, mixed, False) for mixed in (False, True, True, False)]
+        elif a.ab == "dist":
+            runs = [(a.precond, a.mixed, d) for d in (False, True, True, False)]
+        comm = None
+        if a.ab == "dist":      # world size 1: no peers, no process group
+            from rdcfes_amd import SolveComm, partition
+            lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
+                                          elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
+            comm = SolveComm(lp, 5, torch.device("cuda", 0))
+        for precond, mixed, dist_entry in runs:
             ctx.field_upload(0, u0)
-            print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed)))
-            for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed):
+            print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
+                                  entry="rdc_solve_dist, world size 1" if dist_entry else "rdc_solve")))
+            for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None):
                 print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
