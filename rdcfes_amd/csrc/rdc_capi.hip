@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "rdc_internal.h"
+#include "rdc_parts.h"
 #include "rdc_tet4_pihna_moments.h"
 #include "rdc_tet4_ev.h"
 #include "rdc_solid.h"
@@ -62,7 +63,7 @@ struct MeshState {
   HostPrepEv prep_ev;              // element-visit lists (PIHNA TET4, shipped pattern); .ok = available
   bool ev_tried = false;           // the element-visit lists of this mesh have been built (or found impossible)
   int64_t ev_perm_interior = -2;   // "interior_nodes" value the uploaded workgroup order was built for
-  int ev_part1_wg = 0;             // leading workgroups of that order whose clusters are interior
+  PartSplit ev_part1;              // the split of that order: its leading interior workgroups, the rows complete after them
   int solid_cl_state = 0;          // cluster lists: 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass is used)
   int solid_cl_waves = 31, solid_cl_order = 1;   // consumer / producer waves and pair order the lists were built for (the options at that time)
   int scl_interior = -1, scl_n_wg_interior = 0, scl_n_wg = 0;   // "interior_nodes" the lists were built with; leading interior clusters; all clusters
@@ -319,15 +320,11 @@ template <class P> bool pihna_pattern_applies(const P*) { return false; }
 template <> bool pihna_pattern_applies<rdc_pihna_params>(const rdc_pihna_params* p) { return PihnaNoCellTransport::applies(*p); }
 
 // two-part assembly on the element-visit lists: (re)builds the workgroup order for the current "interior_nodes":
-// clusters all of whose nodes are below it first
+// clusters all of whose nodes are below it first (the split itself: rdc_parts.h)
 int ev_order_for_interior(rdc_ctx* c) {
   if (c->ms.ev_perm_interior == c->opt.interior_nodes && c->buf.ev.perm.p) return RDC_OK;
-  const std::vector<HostPrepEv::Desc>& D = c->ms.prep_ev.desc;
   std::vector<uint32_t> perm;
-  perm.reserve(D.size());
-  for (size_t w = 0; w < D.size(); w++) if ((int64_t)D[w].max_node < c->opt.interior_nodes) perm.push_back((uint32_t)w);
-  c->ms.ev_part1_wg = (int)perm.size();
-  for (size_t w = 0; w < D.size(); w++) if (!((int64_t)D[w].max_node < c->opt.interior_nodes)) perm.push_back((uint32_t)w);
+  c->ms.ev_part1 = split_ev(c->ms.prep_ev.desc, c->opt.interior_nodes, &perm);
   int rc = dev_upload(c, c->buf.ev.perm, perm);
   if (rc) return rc;
   RDC_HIP(c, hipStreamSynchronize(c->stream));
@@ -335,24 +332,8 @@ int ev_order_for_interior(rdc_ctx* c) {
   return RDC_OK;
 }
 
-// two-part assembly: number of leading row-gather workgroups whose nodes all lie inside [0, interior_nodes)
-// element-visit lists: clusters are not node ranges; the rows of [0, n) are complete after part 1 when no cluster with a
-// node below n reaches up to "interior_nodes"
-int64_t ev_part1_node_bound(const rdc_ctx* c) {
-  int64_t n = c->opt.interior_nodes;
-  for (const HostPrepEv::Desc& d : c->ms.prep_ev.desc)
-    if (!((int64_t)d.max_node < c->opt.interior_nodes)) n = std::min<int64_t>(n, (int64_t)d.min_node);
-  return n < 0 ? 0 : n;
-}
-
-int part1_workgroups(const rdc_ctx* c) {
-  int lo = 0, hi = (int)c->ms.prep.wg2.size();
-  while (lo < hi) {
-    const int mid = (lo + hi) / 2;
-    if ((int64_t)c->ms.prep.wg2[(size_t)mid].n0 + c->ms.prep.wg2[(size_t)mid].nnodes <= c->opt.interior_nodes) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
+// two-part assembly: the leading row-gather workgroups that part 1 launches and the rows complete after them
+PartSplit part1_pairs(const rdc_ctx* c) { return split_pairs(c->ms.prep.wg2, c->opt.interior_nodes); }
 
 // element-visit lists (rdc_prep_ev.cpp) of the current mesh: at the upload for five unknowns (PIHNA), on the first
 // assembly for three (RIPF / HCC).  A mesh they cannot describe simply keeps the pair kernels (prep_ev.ok stays false).
@@ -518,14 +499,14 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     if (c->opt.part == 1) {
       c->ms.part1_packed = false;
       c->ms.part1_nodes = 0;
-      if (c->ms.ev_part1_wg == 0) return RDC_OK;
-      c->ms.part1_nodes = ev_part1_node_bound(c);
-      a.ev.wg_begin = 0; a.ev.wg_count = c->ms.ev_part1_wg;
+      if (c->ms.ev_part1.wg == 0) return RDC_OK;
+      c->ms.part1_nodes = c->ms.ev_part1.nodes;
+      a.ev.wg_begin = 0; a.ev.wg_count = c->ms.ev_part1.wg;
       if (!c->pack_event) RDC_HIP(c, hipEventCreateWithFlags(&c->pack_event, hipEventDisableTiming));
       a.pack_part = 1; a.pack_event = c->pack_event;
       c->ms.part1_packed = true;
     } else {
-      a.ev.wg_begin = c->ms.ev_part1_wg; a.ev.wg_count = -1;
+      a.ev.wg_begin = c->ms.ev_part1.wg; a.ev.wg_count = -1;
       if (c->ms.part1_packed) { a.pack_part = 2; a.pack_event = c->pack_event; }
       c->ms.part1_packed = false;
     }
@@ -547,20 +528,20 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     const bool sub = a.nen == 4 && a.strategy == RDC_SCATTER_ROWGATHER && a.variant != RDC_VARIANT_GENERIC && a.rg2.n_wg > 0 &&
                      a.rg2.pair_aux && a.rg2.nlist && a.rg2.block == 256 && a.kernel == 0 && c->opt.interior_nodes >= 0 &&
                      ((M::NELEM == 0 && M::AUX_LOCAL_NODE < 0) || a.rg2.pair_eid);
-    const int split = sub ? part1_workgroups(c) : 0;
+    const PartSplit pairs = sub ? part1_pairs(c) : PartSplit();
     if (c->opt.part == 1) {
       c->ms.part1_packed = false;
       c->ms.part1_nodes = 0;
-      if (!sub || split == 0) return RDC_OK;
-      c->ms.part1_nodes = (int64_t)c->ms.prep.wg2[(size_t)split - 1].n0 + c->ms.prep.wg2[(size_t)split - 1].nnodes;
-      a.rg2.wg_begin = 0; a.rg2.wg_count = split;
+      if (!sub || pairs.wg == 0) return RDC_OK;
+      c->ms.part1_nodes = pairs.nodes;
+      a.rg2.wg_begin = 0; a.rg2.wg_count = pairs.wg;
       // part 1 packs the records of the owned nodes only and part 2 those of the ghosts, ordered by an event: the two
       // parts may run on different streams (rdc_assembly.h, stream contract of the two-part assembly)
       if (!c->pack_event) RDC_HIP(c, hipEventCreateWithFlags(&c->pack_event, hipEventDisableTiming));
       a.pack_part = 1; a.pack_event = c->pack_event;
       c->ms.part1_packed = true;
     } else {
-      a.rg2.wg_begin = split; a.rg2.wg_count = -1;
+      a.rg2.wg_begin = pairs.wg; a.rg2.wg_count = -1;
       if (sub && c->ms.part1_packed) { a.pack_part = 2; a.pack_event = c->pack_event; }
       c->ms.part1_packed = false;
     }
@@ -1146,12 +1127,11 @@ int rdc_part1_nodes(const rdc_ctx* c, int64_t* n_nodes) {
   if (c->ms.part1_nodes >= 0) { *n_nodes = c->ms.part1_nodes; return RDC_OK; }
   // before any part-1 call: the prediction for the default path of the shipped-pattern PIHNA (element-visit clusters)
   if (c->opt.interior_nodes >= 0 && c->ms.prep_ev.ok && (c->opt.kernel == 0 || c->opt.kernel == 7)) {
-    *n_nodes = ev_part1_node_bound(c);
+    *n_nodes = split_ev(c->ms.prep_ev.desc, c->opt.interior_nodes).nodes;
     return RDC_OK;
   }
-  if (c->opt.interior_nodes < 0 || !c->ms.prep.rg2_ok || c->ms.prep.nen != 4 || c->ms.prep.wg2.empty()) return RDC_OK;
-  const int split = part1_workgroups(c);
-  if (split > 0) *n_nodes = (int64_t)c->ms.prep.wg2[(size_t)split - 1].n0 + c->ms.prep.wg2[(size_t)split - 1].nnodes;
+  if (c->opt.interior_nodes < 0 || !c->ms.prep.rg2_ok || c->ms.prep.nen != 4) return RDC_OK;
+  *n_nodes = part1_pairs(c).nodes;
   return RDC_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../rdcfes_amd/csrc/rdc_prep.h"
+#include "../rdcfes_amd/csrc/rdc_parts.h"
 #include "../rdcfes_amd/csrc/rdc_row.h"
 #include "../rdcfes_amd/csrc/rdc_tet4_fast.h"
 #include "../rdcfes_amd/csrc/rdc_tet4_pihna_moments.h"
@@ -315,14 +316,32 @@ int shim_prep_build(int nen, int64_t n_elem, int64_t n_node, int64_t n_owned, co
 
 // element-visit lists (rdc_prep_ev.cpp) of the mesh of the last shim_prep_build; stats[6] = workgroups, visits, rows,
 // list stride, largest CSR image (doubles), owned nodes covered
-int shim_ev_build(int64_t lds_budget, int64_t* stats) {
-  g_err = prep_build_ev(g_prep, g_conn.data(), (size_t)lds_budget, g_ev);
+// n_interior >= 0: the clusters respect that "interior_nodes" (two-part assembly)
+int shim_ev_build_interior(int64_t lds_budget, int64_t n_interior, int64_t* stats) {
+  g_err = prep_build_ev(g_prep, g_conn.data(), (size_t)lds_budget, g_ev, n_interior);
   if (!g_err.empty()) return 1;
   int64_t covered = 0;
   for (const auto& d : g_ev.desc) covered += d.nown;
   stats[0] = (int64_t)g_ev.desc.size(); stats[1] = g_ev.n_visits; stats[2] = g_ev.n_rows; stats[3] = g_ev.nls;
   stats[4] = (int64_t)g_ev.max_out_doubles; stats[5] = covered;
   return 0;
+}
+
+int shim_ev_build(int64_t lds_budget, int64_t* stats) { return shim_ev_build_interior(lds_budget, -1, stats); }
+
+// two-part assembly (rdc_parts.h): the splits of the pair lists of the last shim_prep_build and of the element-visit lists of
+// the last shim_ev_build for "interior_nodes" = interior, out[2] = work items, rows; perm[cap] (may be null): the launch order of all
+// clusters
+void shim_split_pairs(int64_t interior, int64_t* out) {
+  const PartSplit s = split_pairs(g_prep.wg2, interior);
+  out[0] = s.wg; out[1] = s.nodes;
+}
+int64_t shim_split_ev(int64_t interior, int64_t* out, uint32_t* perm, int64_t cap) {   // returns the length of the order
+  std::vector<uint32_t> order;
+  const PartSplit s = split_ev(g_ev.desc, interior, perm ? &order : nullptr);
+  out[0] = s.wg; out[1] = s.nodes;
+  if (perm) std::memcpy(perm, order.data(), std::min<size_t>(order.size(), (size_t)cap) * sizeof(uint32_t));
+  return (int64_t)order.size();
 }
 
 // cluster lists of the producer / consumer kernels (rdc_prep_cl.cpp) of the mesh of the last shim_prep_build, and a
@@ -537,6 +556,7 @@ int64_t shim_prep_size(int what) {
     case 32: return (int64_t)g_ev.n_group_rows;
     case 33: return (int64_t)g_ev.n_conflicts;
     case 34: return (int64_t)g_ev.n_pass_instr;
+    case 35: return (int64_t)g_ev.nlist.size();
     case 21: return (int64_t)g_gather.gsrc.size();
     case 22: return (int64_t)g_gather.brow.size();
     case 100: return g_prep.n_colours;
@@ -572,6 +592,7 @@ int shim_prep_copy(int what, void* dst) {
   }
 #undef CP
   if (what == 30) { std::memcpy(dst, g_ev.vloc.data(), g_ev.vloc.size() * 4); return 0; }
+  if (what == 35) { std::memcpy(dst, g_ev.nlist.data(), g_ev.nlist.size() * 4); return 0; }
   if (what == 31) { std::memcpy(dst, g_ev.desc.data(), g_ev.desc.size() * sizeof(HostPrepEv::Desc)); return 0; }
 #define CG(v) std::memcpy(dst, g_gather.v.data(), g_gather.v.size() * sizeof(g_gather.v[0])); return 0
   switch (what) {

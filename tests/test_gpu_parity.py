@@ -938,6 +938,32 @@ def test_chunked_handback_follows_the_part1_bound(params, opts):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("opts", [{}, {"kernel": 5}])
+def test_part1_bound_is_predicted_before_the_first_part1_call(opts):
+    """rdc_part1_nodes BEFORE any part-1 call since the upload (the pipelined hand-back of the benchmark sizes its first chunk
+    with it) is what the part-1 call then reports to have completed: the prediction and the call take the split from the same
+    lists (element-visit clusters by default, pair workgroups for "kernel" = 5), and both split the mesh."""
+    conn, xyz = synth.kuhn_tet_mesh(12, order="lex")
+    u = synth.pihna_fields(xyz)
+    p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+    n_int = int(0.6 * xyz.shape[0])
+    with AssemblyContext(0) as ctx:
+        ctx.set_option("interior_nodes", n_int)
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        ctx.mesh_upload(4, conn, xyz, 5)
+        ctx.field_upload(FIELD_OLD_SOLUTION, u)
+        predicted = ctx.part1_nodes()
+        ctx.assemble_pihna_part(p, 1)
+        completed = ctx.part1_nodes()
+        ctx.assemble_pihna_part(p, 2)
+        ctx.synchronize()
+    print(f"part1_nodes {opts}: predicted {predicted}, completed {completed}, interior_nodes {n_int}")
+    assert 0 < predicted <= n_int and 0 < completed <= n_int
+    assert predicted == completed
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("moments", [1, 0])
 def test_pihna_zero_cell_sum_with_positive_vasculature(oracle, moments):
     """c + h + v == 0 with v > 0 at the quadrature points (c = -v on a slab of nodes; not reachable after check_solution's
