@@ -64,11 +64,13 @@ struct MeshState {
   bool ev_tried = false;           // the element-visit lists of this mesh have been built (or found impossible)
   int64_t ev_perm_interior = -2;   // "interior_nodes" value the uploaded workgroup order was built for
   PartSplit ev_part1;              // the split of that order: its leading interior workgroups, the rows complete after them
-  int solid_cl_state = 0;          // cluster lists: 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass is used)
-  int solid_cl_waves = 31, solid_cl_order = 1;   // consumer / producer waves and pair order the lists were built for (the options at that time)
-  int scl_interior = -1, scl_n_wg_interior = 0, scl_n_wg = 0;   // "interior_nodes" the lists were built with; leading interior clusters; all clusters
-  int64_t scl_part1_nodes = 0;
-  size_t scl_max_row_doubles = 0;
+  struct ClusterLists {            // cluster lists of the HEX8 producer / consumer kernels (ensure_cluster_lists)
+    int state = 0;                 // 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass is used)
+    int waves = 31, order = 1, interior = -1;   // the options "solid_cl_waves", pair order and "interior_nodes" they were built with
+    int n_wg = 0;                  // all clusters
+    PartSplit part1;               // their leading clusters of interior nodes, the rows complete after those
+    size_t max_row_doubles = 0;
+  } cl;
   bool solid_gather_ready = false, rg5_eid_ready = false;   // buf.two_pass, buf.rg2.eid hold this mesh's lists
   SolveState solve;
   int64_t part1_nodes = -1;          // rows [0, part1_nodes) were complete after the LAST part-1 call (-1: none since the upload)
@@ -357,32 +359,24 @@ int build_ev_lists(rdc_ctx* c, const uint32_t* conn) {
 }
 
 // cluster lists of the producer / consumer HEX8 kernels (three unknowns: solid system and reaction-diffusion models share
-// them), built on first use.  solid_cl_state: 1 = ready, -1 = not available for this mesh (c->err says why).
+// them), built on first use.  ms.cl.state: 1 = ready, -1 = not available for this mesh (c->err says why).
 int ensure_cluster_lists(rdc_ctx* c, int order_of_caller) {
   int rc;
-  const int want_order = c->opt.solid_cl_order < 0 ? (c->ms.solid_cl_state == 1 ? c->ms.solid_cl_order : order_of_caller) : c->opt.solid_cl_order;
-  if (c->ms.solid_cl_state != 0 && (c->ms.solid_cl_waves != c->opt.solid_cl_waves || c->ms.solid_cl_order != want_order || c->ms.scl_interior != c->opt.interior_nodes)) c->ms.solid_cl_state = 0;
-  if (c->ms.solid_cl_state != 0) return RDC_OK;
-  const int cw = c->opt.solid_cl_waves / 10, pw = c->opt.solid_cl_waves % 10;
-  HostPrepCl::Limits lim;
-  lim.max_nodes = cw * 8; lim.max_pairs = cw * 64; lim.max_elems = pw * 64;
-  // the LDS image of the cluster's CSR rows overlays the point buffers of the solid kernel (2 x 64 pw records of 49 doubles)
-  lim.max_row_doubles = (int)(2 * pw * 64 * 49) - 3 * cw * 8 - 2;
-  if (c->ms.prep.nvar == 5) {   // k_hex8_cl_rows: the image holds one equation row of the cluster's nodes and overlays its smaller point buffers
-    lim.img_per_block = 5;
-    lim.max_row_doubles = 5 * 27 * lim.max_nodes + 5 * lim.max_nodes;
-  }
+  MeshState::ClusterLists& L = c->ms.cl;
+  const int want_order = c->opt.solid_cl_order < 0 ? (L.state == 1 ? L.order : order_of_caller) : c->opt.solid_cl_order;
+  if (L.state != 0 && (L.waves != c->opt.solid_cl_waves || L.order != want_order || L.interior != c->opt.interior_nodes)) L.state = 0;
+  if (L.state != 0) return RDC_OK;
+  HostPrepCl::Limits lim = cll::limits(c->opt.solid_cl_waves / 10, c->opt.solid_cl_waves % 10, c->ms.prep.nvar);
   lim.pair_order = want_order;
   HostPrepCl cl;
   std::vector<uint32_t> conn_h((size_t)c->ms.prep.n_elem * 8);      // the context keeps the connectivity on the device only
   RDC_HIP(c, hipMemcpyAsync(conn_h.data(), c->buf.mesh.conn.p, conn_h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   RDC_HIP(c, hipStreamSynchronize(c->stream));
   const std::string err = prep_build_cl(c->ms.prep, conn_h.data(), lim, cl, c->opt.interior_nodes);
-  c->ms.scl_interior = c->opt.interior_nodes;
-  c->ms.solid_cl_waves = c->opt.solid_cl_waves;
-  c->ms.solid_cl_order = want_order;
+  L = MeshState::ClusterLists();
+  L.interior = c->opt.interior_nodes; L.waves = c->opt.solid_cl_waves; L.order = want_order;
   if (!err.empty()) {
-    c->ms.solid_cl_state = -1;
+    L.state = -1;
     std::snprintf(c->err, sizeof(c->err), "%s", err.c_str());
     return RDC_OK;
   }
@@ -392,28 +386,27 @@ int ensure_cluster_lists(rdc_ctx* c, int order_of_caller) {
   if ((rc = dev_upload(c, c->buf.cl.pair, cl.pair))) return rc;
   if ((rc = dev_upload(c, c->buf.cl.pslot, cl.pslot))) return rc;
   RDC_HIP(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-  c->ms.scl_max_row_doubles = cl.max_row_doubles;
-  c->ms.scl_n_wg = (int)cl.desc.size();
-  c->ms.scl_n_wg_interior = (int)cl.n_wg_interior;
-  c->ms.scl_part1_nodes = cl.part1_nodes;
-  c->ms.solid_cl_state = 1;
+  L.max_row_doubles = cl.max_row_doubles;
+  L.n_wg = (int)cl.desc.size();
+  if (L.interior >= 0) L.part1 = PartSplit{(int)cl.n_wg_interior, cl.part1_nodes};
+  L.state = 1;
   return RDC_OK;
 }
 
 // part 0: every cluster; 1: the leading clusters of interior nodes; 2: the rest (the kernels index the lists by blockIdx.x)
 ClDev cluster_view(const rdc_ctx* c, int part = 0) {
+  const MeshState::ClusterLists& L = c->ms.cl;
   ClDev v;
-  v.cw = c->ms.solid_cl_waves / 10; v.pw = c->ms.solid_cl_waves % 10;
-  const int split = c->ms.scl_interior >= 0 ? c->ms.scl_n_wg_interior : 0;
-  const size_t b = part == 2 ? (size_t)split : 0;
-  v.n_wg = part == 1 ? split : (part == 2 ? c->ms.scl_n_wg - split : c->ms.scl_n_wg);
-  const size_t max_nodes = (size_t)v.cw * 8, max_pairs = (size_t)v.cw * 64, max_elems = (size_t)v.pw * 64, wpp = (size_t)c->ms.prep.nen / 4;
+  v.cw = L.waves / 10; v.pw = L.waves % 10;
+  const size_t b = part == 2 ? (size_t)L.part1.wg : 0;
+  v.n_wg = part == 1 ? L.part1.wg : (part == 2 ? L.n_wg - L.part1.wg : L.n_wg);
+  const cll::Strides S = cll::strides(v.cw, v.pw, c->ms.prep.nen);
   v.desc = (const HostPrepCl::Desc*)c->buf.cl.desc.p + b;
-  v.ntab = (const HostPrepCl::Node*)c->buf.cl.ntab.p + b * max_nodes;
-  v.eid = (const uint32_t*)c->buf.cl.eid.p + b * max_elems;
-  v.pair = (const uint32_t*)c->buf.cl.pair.p + b * max_pairs;
-  v.pslot = (const uint32_t*)c->buf.cl.pslot.p + b * max_pairs * wpp;
-  v.max_row_doubles = c->ms.scl_max_row_doubles;
+  v.ntab = (const HostPrepCl::Node*)c->buf.cl.ntab.p + b * S.node;
+  v.eid = (const uint32_t*)c->buf.cl.eid.p + b * S.elem;
+  v.pair = (const uint32_t*)c->buf.cl.pair.p + b * S.pair;
+  v.pslot = (const uint32_t*)c->buf.cl.pslot.p + b * S.pslot;
+  v.max_row_doubles = L.max_row_doubles;
   return v;
 }
 
@@ -483,7 +476,7 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   if (a.nen == 8 && (M::NV == 3 || M::NV == 5) && c->opt.hex_kernel != 1 && (c->opt.part == 0 || c->opt.hex_kernel == 0) &&
       a.strategy == RDC_SCATTER_ROWGATHER && c->opt.solid_cl_waves == 31) {
     if ((rc = ensure_cluster_lists(c, 0))) return rc;
-    hex_cl = c->ms.solid_cl_state == 1;
+    hex_cl = c->ms.cl.state == 1;
   }
   bool pattern_ok = evc_model;
   if constexpr (std::is_same<M, Pihna>::value) pattern_ok = pihna_pattern_applies(p) || c->opt.ev_general;
@@ -515,10 +508,10 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     // HEX8 cluster kernels: the cluster lists respect "interior_nodes" (interior clusters first)
     c->ms.part1_packed = false;
     if (c->opt.part == 1) {
-      c->ms.part1_nodes = c->ms.scl_interior >= 0 ? c->ms.scl_part1_nodes : 0;
-      if (c->ms.scl_interior < 0 || c->ms.scl_n_wg_interior == 0) { c->ms.part1_nodes = 0; return RDC_OK; }
+      c->ms.part1_nodes = c->ms.cl.part1.wg > 0 ? c->ms.cl.part1.nodes : 0;
+      if (c->ms.cl.part1.wg == 0) return RDC_OK;
     }
-    a.cl = cluster_view(c, c->ms.scl_interior >= 0 ? c->opt.part : (c->opt.part == 2 ? 0 : 1));
+    a.cl = cluster_view(c, c->ms.cl.interior >= 0 ? c->opt.part : (c->opt.part == 2 ? 0 : 1));
     if (a.cl.n_wg == 0) return RDC_OK;
   } else
   if (c->opt.part != 0) {
@@ -968,10 +961,10 @@ int rdc_solid_assemble(rdc_ctx* c, const rdc_solid_params* p, int request_jacobi
   int kernel = c->opt.solid_kernel == 1 ? 1 : 0;
   if ((c->opt.solid_kernel == 0 || c->opt.solid_kernel == 3) && c->ms.prep.nen == 8 && request_jacobian) {
     if ((rc = ensure_cluster_lists(c, 1))) return rc;
-    if (c->ms.solid_cl_state != 1 && c->opt.solid_kernel == 3) return fail(c, RDC_ERR_UNSUPPORTED, "fused solid kernel: %s", c->err);
-    if (c->ms.solid_cl_state == 1) {
+    if (c->ms.cl.state != 1 && c->opt.solid_kernel == 3) return fail(c, RDC_ERR_UNSUPPORTED, "fused solid kernel: %s", c->err);
+    if (c->ms.cl.state == 1) {
       kernel = 3;
-      a.cl = cluster_view(c, c->ms.scl_interior >= 0 ? c->opt.part : (c->opt.part == 1 ? 1 : 0));
+      a.cl = cluster_view(c, c->ms.cl.interior >= 0 ? c->opt.part : (c->opt.part == 1 ? 1 : 0));
     }
   } else if (c->opt.solid_kernel == 3) {
     return fail(c, RDC_ERR_UNSUPPORTED, "fused solid kernel: HEX8 tangent requests only");
@@ -980,8 +973,8 @@ int rdc_solid_assemble(rdc_ctx* c, const rdc_solid_params* p, int request_jacobi
   // (+ the penalty sides, which add into rows of both kinds) in part 2; the two-pass and coloured forms assemble everything in part 2
   if (c->opt.part == 1) {
     c->ms.part1_nodes = 0;
-    if (kernel != 3 || c->ms.scl_interior < 0 || a.cl.n_wg == 0) return RDC_OK;
-    c->ms.part1_nodes = c->ms.scl_part1_nodes;
+    if (kernel != 3 || c->ms.cl.interior < 0 || a.cl.n_wg == 0) return RDC_OK;
+    c->ms.part1_nodes = c->ms.cl.part1.nodes;
     a.n_sides = 0;
     if (!c->solid_part1_event) RDC_HIP(c, hipEventCreateWithFlags(&c->solid_part1_event, hipEventDisableTiming));
     a.done_record = c->solid_part1_event;

@@ -169,9 +169,10 @@ RDC_EVL int seg_phase(uint32_t obase) { return (int)(obase & 1u); }
 // A workgroup owns a CLUSTER of owned nodes.  Its consumer lanes each take one (owned node, incident element) PAIR and
 // accumulate that row of the element matrix over the quadrature points; its producer lanes each take one ELEMENT
 // touching the cluster and evaluate the per-point data once per point for all the pairs of the element.
+// The format of the lists (pair word, slot bytes, strides, image layout) is cll:: below.
 struct HostPrepCl {
   // max_row_doubles: LDS image of the cluster's CSR rows; img_per_block: doubles of a node block in that image (0 = nvar^2, the
-  // whole rows; nvar = one equation row at a time, as the five-unknown kernel keeps it)
+  // whole rows; nvar = one equation row at a time, as the five-unknown kernel keeps it).  What the kernels are built for: cll::limits
   struct Limits { int max_nodes = 24, max_pairs = 192, max_elems = 64, max_row_doubles = 6000, pair_order = 1, img_per_block = 0; };
   struct Desc {            // 16 bytes per workgroup
     uint16_t nown, npair, nelem, pad;
@@ -191,8 +192,8 @@ struct HostPrepCl {
   std::vector<Desc> desc;
   std::vector<Node> ntab;            // [n_wg][max_nodes]
   std::vector<uint32_t> eid;         // [n_wg][max_elems] element ids, ~0u = none
-  std::vector<uint32_t> pair;        // [n_wg][max_pairs] local element | local row node << 8 | owned-node index << 16; ~0u = none (order: rdc_prep_cl.cpp)
-  std::vector<uint32_t> pslot;       // [n_wg][max_pairs][nen / 4]: byte j = column slot of local node j in the pair's row
+  std::vector<uint32_t> pair;        // [n_wg][max_pairs] one word per pair: cll::pair_pack / pair_elem / pair_row / pair_node, cll::IDLE = none (order: rdc_prep_cl.cpp)
+  std::vector<uint32_t> pslot;       // [n_wg][max_pairs][cll::pslot_words]: the column slots of the pair's row: cll::pslot_add / pslot_get
   size_t max_row_doubles = 0;
   int64_t n_wg_interior = 0;         // leading clusters whose nodes are all interior (two-part assembly)
   int64_t part1_nodes = 0;           // the rows of nodes [0, part1_nodes) are complete after those clusters
@@ -202,6 +203,64 @@ struct HostPrepCl {
 // n_interior >= 0: owned nodes [0, n_interior) are "interior" (two-part assembly): clusters do not mix the two kinds and the
 // interior clusters come first in the lists ([0, n_wg_interior))
 std::string prep_build_cl(const HostPrep& P, const uint32_t* conn, const HostPrepCl::Limits& lim, HostPrepCl& out, int64_t n_interior = -1);
+
+// The format of those lists, as the one piece of code that rdc_prep_cl.cpp (packer), the kernels k_hex8_cl / k_hex8_clp /
+// k_hex8_cl_rows / k_solid_cl (with their phases, rdc_cl_phases.h), the launchers, rdc_capi.hip and the CPU replays of
+// tests/host_shim.cpp all compile.  No HIP construct beyond the qualifiers.
+namespace cll {
+// pair word: local element | local row node << 8 | owned-node index << 16 (8 bits each)
+constexpr uint32_t IDLE = 0xFFFFFFFFu;   // a lane without a pair / an element
+RDC_EVL uint32_t pair_pack(uint32_t le, uint32_t li, uint32_t a) { return le | li << 8 | a << 16; }
+RDC_EVL int pair_elem(uint32_t w) { return (int)(w & 0xFF); }
+RDC_EVL int pair_row(uint32_t w) { return (int)((w >> 8) & 0xFF); }
+RDC_EVL int pair_node(uint32_t w) { return (int)((w >> 16) & 0xFF); }
+// slot words of a pair: byte j = column slot (a row has at most 255 node blocks) of local node j in the pair's row
+RDC_EVL constexpr int pslot_words(int nen) { return nen / 4; }
+RDC_EVL void pslot_add(uint32_t* words, int j, uint32_t slot) { words[j >> 2] |= (slot & 0xFFu) << (8 * (j & 3)); }
+RDC_EVL int pslot_get(const uint32_t* words, int j) { return (int)((words[j >> 2] >> (8 * (j & 3))) & 0xFF); }
+RDC_EVL int pslot_get(uint32_t w0, uint32_t w1, int j) { const uint32_t w[2] = {w0, w1}; return pslot_get(w, j); }   // HEX8
+// a Node read as NODE_WORDS 32-bit words (k_hex8_clp stages the table in LDS that way): word 1 = len | off << 16
+constexpr int NODE_WORDS = 4;
+static_assert(sizeof(HostPrepCl::Node) == 4 * NODE_WORDS, "Node: four words");
+RDC_EVL int node_word_len(uint32_t w1) { return (int)(w1 & 0xFFFFu); }
+RDC_EVL int node_word_off(uint32_t w1) { return (int)(w1 >> 16); }
+// capacities of a cluster worked on by cw consumer and pw producer waves: a lane per pair / per element, a half-wave per node in the copy-out
+RDC_EVL constexpr int max_nodes(int cw) { return 8 * cw; }
+RDC_EVL constexpr int max_pairs(int cw) { return 64 * cw; }
+RDC_EVL constexpr int max_elems(int pw) { return 64 * pw; }
+// list strides per workgroup: ntab [n_wg][node], pair [n_wg][pair], eid [n_wg][elem], pslot [n_wg][pslot] (32-bit words)
+struct Strides { size_t node, pair, elem, pslot; };
+RDC_EVL constexpr Strides strides(const HostPrepCl::Limits& lim, int nen) {
+  return {(size_t)lim.max_nodes, (size_t)lim.max_pairs, (size_t)lim.max_elems, (size_t)lim.max_pairs * pslot_words(nen)};
+}
+RDC_EVL constexpr Strides strides(int cw, int pw, int nen = 8) {
+  return {(size_t)max_nodes(cw), (size_t)max_pairs(cw), (size_t)max_elems(pw), (size_t)max_pairs(cw) * pslot_words(nen)};
+}
+// LDS image of a cluster: the node segments (Node::off; whole-row images give a segment the 16-byte phase of its CSR segment, which
+// costs up to one double per node), behind them -- at an even offset -- the rhs entries; zeroed with 16-byte stores
+template <class T> RDC_EVL constexpr T even(T x) { return (x + 1) & ~(T)1; }
+RDC_EVL constexpr int rhs_offset(int row_doubles) { return even(row_doubles); }
+RDC_EVL int seg_phase(uint32_t off) { return (int)(off & 1u); }
+RDC_EVL constexpr int zero_doubles(int row_doubles, int rhs_doubles) { return 2 * ((rhs_offset(row_doubles) + rhs_doubles + 1) / 2); }
+// The image overlays the point buffers once the points are consumed: bytes of dynamic LDS of such a kernel
+RDC_EVL constexpr size_t overlay_bytes(size_t point_doubles, size_t max_row_doubles, size_t rhs_doubles) {
+  return sizeof(double) * (point_doubles > even(max_row_doubles) + rhs_doubles ? point_doubles : even(max_row_doubles) + rhs_doubles);
+}
+// k_solid_cl: doubles between the (element, point) records (47 used; odd => the records of different elements spread over the
+// banks), two buffers of max_elems records
+constexpr int SOLID_POINT_STRIDE = 49;
+RDC_EVL constexpr int solid_point_doubles(int pw) { return 2 * max_elems(pw) * SOLID_POINT_STRIDE; }
+// The limits the lists are built with for (cw, pw) waves and nvar unknowns.  Three unknowns: the image must fit the point buffers of
+// the solid kernel (the smaller ones of the reaction-diffusion kernels matter less: their LDS grows with the image); - 2 = the two
+// roundings above (rhs_offset, zero_doubles).  Five: k_hex8_cl_rows keeps one equation row, sized for structured hexahedra (27 blocks per row)
+RDC_EVL constexpr HostPrepCl::Limits limits(int cw, int pw, int nvar) {
+  HostPrepCl::Limits lim;
+  lim.max_nodes = max_nodes(cw); lim.max_pairs = max_pairs(cw); lim.max_elems = max_elems(pw);
+  lim.max_row_doubles = solid_point_doubles(pw) - 3 * max_nodes(cw) - 2;
+  if (nvar == 5) { lim.img_per_block = 5; lim.max_row_doubles = 5 * 27 * lim.max_nodes + 5 * lim.max_nodes; }
+  return lim;
+}
+}  // namespace cll
 
 // returns empty string on success, else an error message
 std::string prep_build(int nen, int64_t n_elem, int64_t n_node, int64_t n_owned, const uint32_t* conn,

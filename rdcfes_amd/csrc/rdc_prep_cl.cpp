@@ -9,7 +9,7 @@
 //
 // Pair order.  Two LDS access patterns depend on it:
 //  (a) a consumer lane reads the 47-double point record of its element at every point (376 ds_read_b64 per pair, the bulk
-//      of the kernel's LDS traffic).  Records are 49 doubles apart, so the records of 32 CONSECUTIVE local elements start in
+//      of the kernel's LDS traffic).  Records are cll::SOLID_POINT_STRIDE (odd) doubles apart, so the records of 32 CONSECUTIVE local elements start in
 //      32 different double-banks; lanes reading the same record broadcast;
 //  (b) the consumers add their rows into the LDS image with ds_add_f64, executed in four groups of 16 lanes; lanes of a
 //      group hitting the same address (same node, same column) or the same double-bank serialise (tools/lds_bank_model.hip).
@@ -161,12 +161,12 @@ std::string prep_build_cl(const HostPrep& P, const uint32_t* conn, const HostPre
   }
   const int64_t nwg = (int64_t)clusters.size();
   // ---- per-workgroup lists ------------------------------------------------------------------------------------------
+  const cll::Strides S = cll::strides(lim, nen);
   C.desc.assign((size_t)nwg, HostPrepCl::Desc{0, 0, 0, 0, 0, 0});
-  C.ntab.assign((size_t)nwg * lim.max_nodes, HostPrepCl::Node{0, 0, 0, 0, 0});
-  C.eid.assign((size_t)nwg * lim.max_elems, 0xFFFFFFFFu);
-  C.pair.assign((size_t)nwg * lim.max_pairs, 0xFFFFFFFFu);
-  const int wpp = nen / 4;
-  C.pslot.assign((size_t)nwg * lim.max_pairs * wpp, 0);
+  C.ntab.assign((size_t)nwg * S.node, HostPrepCl::Node{0, 0, 0, 0, 0});
+  C.eid.assign((size_t)nwg * S.elem, cll::IDLE);
+  C.pair.assign((size_t)nwg * S.pair, cll::IDLE);
+  C.pslot.assign((size_t)nwg * S.pslot, 0);
   int fail = 0;
   std::vector<uint32_t> rowd((size_t)nwg, 0);
 #pragma omp parallel for schedule(dynamic, 256)
@@ -186,14 +186,14 @@ std::string prep_build_cl(const HostPrep& P, const uint32_t* conn, const HostPre
     HostPrepCl::Desc& d = C.desc[(size_t)w];
     d.nown = (uint16_t)cl.size();
     d.nelem = (uint16_t)el.size();
-    std::copy(el.begin(), el.end(), C.eid.begin() + (size_t)w * lim.max_elems);
+    std::copy(el.begin(), el.end(), C.eid.begin() + (size_t)w * S.elem);
     uint32_t off = 0;
     for (size_t a = 0; a < cl.size(); a++) {
       const uint32_t n = cl[a];
-      HostPrepCl::Node& nd = C.ntab[(size_t)w * lim.max_nodes + a];
+      HostPrepCl::Node& nd = C.ntab[(size_t)w * S.node + a];
       const int64_t len = P.bptr[n + 1] - P.bptr[n];
       // whole-row images: the node's segment gets the 16-byte phase its CSR segment has in memory (copied out with 16-byte stores)
-      if (ipb == nv2 && ((off ^ (uint32_t)(nv2 * P.bptr[n])) & 1u)) off++;
+      if (ipb == nv2 && cll::seg_phase(off) != cll::seg_phase((uint32_t)(nv2 * P.bptr[n]))) off++;
       nd.bptr = (uint32_t)P.bptr[n]; nd.len = (uint16_t)len; nd.off = (uint16_t)off; nd.node = n;
       off += (uint32_t)(ipb * len);
     }
@@ -204,11 +204,11 @@ std::string prep_build_cl(const HostPrep& P, const uint32_t* conn, const HostPre
     auto emit = [&](uint32_t le, int li, size_t a) {
       const uint32_t e = el[le];
       if (np >= (uint32_t)lim.max_pairs) { fail = 1; return; }
-      C.pair[(size_t)w * lim.max_pairs + np] = le | ((uint32_t)li << 8) | ((uint32_t)a << 16);
+      C.pair[(size_t)w * S.pair + np] = cll::pair_pack(le, (uint32_t)li, (uint32_t)a);
       for (int j = 0; j < nen; j++) {
         const uint32_t s = P.eslot[(size_t)e * nen * nen + (size_t)li * nen + j];
         if (s > 255) fail = 1;
-        C.pslot[((size_t)w * lim.max_pairs + np) * wpp + j / 4] |= (s & 0xFFu) << (8 * (j % 4));
+        cll::pslot_add(&C.pslot[(size_t)w * S.pslot + (size_t)np * cll::pslot_words(nen)], j, s);
       }
       np++;
     };

@@ -21,12 +21,12 @@
 // The summation order inside a node block depends on the LDS atomics' arrival order: results are reproducible to
 // rounding, not bitwise (the two-pass form, solid_kernel = 2, is).
 #include "rdc_solid.h"
+#include "rdc_cl_phases.h"
 
 namespace rdc {
 
 namespace {
-constexpr int PSTRIDE = 49;  // 47 doubles per (element, point) record; odd stride => records of different elements spread over the banks
-typedef double cl_v2d __attribute__((ext_vector_type(2)));
+constexpr int PSTRIDE = cll::SOLID_POINT_STRIDE;  // 47 doubles per (element, point) record used
 }
 
 template <int CW, int PW, bool SYM>
@@ -36,54 +36,23 @@ k_solid_cl(const MeshDev m, const HostPrepCl::Desc* __restrict__ desc, const Hos
            const double* __restrict__ Xu, const double* __restrict__ fibre, const int32_t* __restrict__ elem_material,
            const rdc_solid_material* __restrict__ materials, const double pseudo_time, double* __restrict__ val,
            double* __restrict__ rhs, const int diag /* timing diagnostics (tools/solid_ab.py), bit mask: 1 = consumers idle, 2 = producers idle, 4 = image not zeroed, 8 = no atomics, 16 = no copy-out, 32 = no element loads; 64 = copy-out with 8-byte stores (results unchanged) */) {
-  constexpr int MAXP = CW * 64, MAXE = PW * 64, MAXN = CW * 8, NT = (CW + PW) * 64;
+  constexpr cll::Strides S = cll::strides(CW, PW);
+  constexpr int MAXP = (int)S.pair, MAXE = (int)S.elem, NT = (CW + PW) * 64;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int w = blockIdx.x;
-  // Roles rotate over the waves from workgroup to workgroup: the hardware places wave i of every workgroup on SIMD i,
-  // so with fixed roles the producers of the two workgroups of a CU (the longer instruction stream) would share a SIMD.
-  constexpr int NW = CW + PW;
-  const int tid = (int)(((threadIdx.x >> 6) + ((blockIdx.x >> 3) % NW)) % NW) * 64 + (int)(threadIdx.x & 63);
+  const int tid = cll::role_tid<CW + PW>();
   const HostPrepCl::Desc d = desc[w];
-  const bool producer = tid >= MAXP;
-  const int nimg = (int)d.row_doubles;
-  double* const img = lds;
-  double* const lrhs = lds + ((nimg + 1) & ~1);
+  const int nimg = (int)d.row_doubles, nown = (int)d.nown;
   // the image of the CSR rows of all owned nodes overlays the point buffers once the points are consumed
-  auto zero_image = [&]() {
-    cl_v2d* z = reinterpret_cast<cl_v2d*>(lds);
-    const cl_v2d zero = {0.0, 0.0};
-    for (int x = tid; x < (((nimg + 1) & ~1) + 3 * (int)d.nown + 1) / 2; x += NT) z[x] = zero;
-  };
-  // a half-wave per node: its three rows are 9 * len consecutive doubles of the CSR array, written with 16-byte stores (the
-  // node's image segment has the 16-byte phase of its CSR segment: rdc_prep_cl.cpp)
-  auto copy_out = [&]() {
-    for (int a = tid >> 5; a < (int)d.nown; a += NT / 32) {
-      const HostPrepCl::Node nd = ntab[(size_t)w * MAXN + a];
-      const int n9 = 9 * (int)nd.len, l32 = tid & 31;
-      double* dst = val + 9 * (int64_t)nd.bptr;
-      const double* src = img + nd.off;
-      const int sh = (int)(nd.off & 1), npair = (n9 - sh) >> 1;
-      const cl_v2d* s2 = reinterpret_cast<const cl_v2d*>(src + sh);
-      cl_v2d* d2 = reinterpret_cast<cl_v2d*>(dst + sh);
-      if (diag & 64) {   // 8-byte stores (timing comparison; same values)
-        for (int k = l32; k < n9; k += 32) __builtin_nontemporal_store(src[k], dst + k);
-      } else {
-        for (int k = l32; k < npair; k += 32) __builtin_nontemporal_store(s2[k], d2 + k);
-        if (sh && l32 == 0) __builtin_nontemporal_store(src[0], dst);
-        if (((n9 - sh) & 1) && l32 == 1) __builtin_nontemporal_store(src[n9 - 1], dst + n9 - 1);
-      }
-      if (l32 < 3) rhs[3 * (int64_t)nd.node + l32] = lrhs[3 * a + l32];
-    }
-  };
-  // workgroup barrier that orders LDS accesses only (no wait for the global stores in flight)
-  auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  double* const img = lds;
+  double* const lrhs = lds + cll::rhs_offset(nimg);
   // The two roles are separate code paths with the SAME sequence of workgroup barriers (the branch is uniform per wave),
   // so that the register allocator never has to hold the consumers' accumulators and the producers' element together.
-  if (producer) {
+  if (tid >= MAXP) {
     // ================= producer: the element of this lane, loaded once ======================================================
     const int pl = tid - MAXP;
-    const uint32_t e = eid[(size_t)w * MAXE + pl];
-    const bool plive = e != 0xFFFFFFFFu;
+    const uint32_t e = eid[(size_t)w * S.elem + pl];
+    const bool plive = e != cll::IDLE;
     double X[8][3], XU[8][3];
     double mu = 0.0, lame = 0.0, Kf = 0.0, A[3] = {0.0, 0.0, 0.0}, lam[3] = {1.0, 1.0, 1.0}, rlam = 1.0;
     if (plive && !(diag & 32)) {
@@ -181,10 +150,10 @@ k_solid_cl(const MeshDev m, const HostPrepCl::Desc* __restrict__ desc, const Hos
       if (plive && q + 1 < 8 && !(diag & 2)) produce(q + 1, (q + 1) & 1);
       __syncthreads();
     }
-    if (!(diag & 4)) zero_image();
-    lds_barrier();
-    lds_barrier();                  // consumers: atomics
-    if (!(diag & 16)) copy_out();
+    if (!(diag & 4)) cll::zero_image<NT>(lds, tid, nimg, 3 * nown);
+    cll::lds_barrier();
+    cll::lds_barrier();             // consumers: atomics
+    if (!(diag & 16)) cll::copy_out<3, NT>(ntab + (size_t)w * S.node, nown, tid, img, lrhs, val, rhs, diag & 64);
     return;
   }
   // ================= consumer: one (owned node, element) pair per lane ========================================================
@@ -195,10 +164,8 @@ k_solid_cl(const MeshDev m, const HostPrepCl::Desc* __restrict__ desc, const Hos
     for (int r = 0; r < 3; r++)
 #pragma unroll
       for (int c = 0; c < 3; c++) acc[j][r][c] = 0.0;
-  int le = 0, li = 0, na = 0;
-  const uint32_t pr = pair[(size_t)w * MAXP + tid];
-  const bool cvalid = pr != 0xFFFFFFFFu;
-  if (cvalid) { le = (int)(pr & 0xFF); li = (int)((pr >> 8) & 0xFF); na = (int)((pr >> 16) & 0xFF); }
+  const cll::Pair pr = cll::pair_decode(pair[(size_t)w * S.pair + tid]);
+  const int le = pr.le, li = pr.li;
   // one quadrature point: row li of the element matrix against all columns
   auto consume = [&](int b) {
     const double* pd = lds + (b * MAXE + le) * PSTRIDE;
@@ -265,26 +232,19 @@ k_solid_cl(const MeshDev m, const HostPrepCl::Desc* __restrict__ desc, const Hos
   __syncthreads();                  // producers: point 0
 #pragma unroll 1
   for (int q = 0; q < 8; q++) {
-    if (cvalid && !(diag & 1)) consume(q & 1);
+    if (pr.valid && !(diag & 1)) consume(q & 1);
     __syncthreads();
   }
   // ---- epilogue: rows added into the LDS image, image copied out ------------------------------------------------------------
-  if (!(diag & 4)) zero_image();
-  uint32_t sl0 = 0, sl1 = 0;
-  int off = 0, len3 = 0;
-  if (cvalid) {
-    sl0 = pslot[((size_t)w * MAXP + tid) * 2];
-    sl1 = pslot[((size_t)w * MAXP + tid) * 2 + 1];
-    const HostPrepCl::Node nd = ntab[(size_t)w * MAXN + na];
-    off = (int)nd.off;
-    len3 = 3 * (int)nd.len;
-  }
-  lds_barrier();
-  if (cvalid && !(diag & 8)) {
+  if (!(diag & 4)) cll::zero_image<NT>(lds, tid, nimg, 3 * nown);
+  cll::Aim aim = {0, 0, 0, 0};
+  if (pr.valid) aim = cll::pair_aim(pslot + (size_t)w * S.pslot, reinterpret_cast<const uint32_t*>(ntab + (size_t)w * S.node), tid, pr.na);
+  cll::lds_barrier();
+  if (pr.valid && !(diag & 8)) {   // acc[j][r][c], every block: not cll::add_rows (acc[a][b][j], the model's non-zero blocks)
+    const int len3 = 3 * aim.len;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      const int s = (int)(((j < 4 ? sl0 : sl1) >> (8 * (j & 3))) & 0xFF);
-      double* p = img + off + 3 * s;
+      double* p = img + aim.off + 3 * cll::pslot_get(aim.sl0, aim.sl1, j);
 #pragma unroll
       for (int r = 0; r < 3; r++)
 #pragma unroll
@@ -293,16 +253,14 @@ k_solid_cl(const MeshDev m, const HostPrepCl::Desc* __restrict__ desc, const Hos
     }
 #pragma unroll
     for (int c = 0; c < 3; c++)
-      __hip_atomic_fetch_add(lrhs + 3 * na + c, re[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(lrhs + 3 * pr.na + c, re[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
-  lds_barrier();
-  if (!(diag & 16)) copy_out();
+  cll::lds_barrier();
+  if (!(diag & 16)) cll::copy_out<3, NT>(ntab + (size_t)w * S.node, nown, tid, img, lrhs, val, rhs, diag & 64);
 }
 
 size_t solid_cl_lds_bytes(int cw, int pw, size_t max_row_doubles) {
-  const size_t points = (size_t)2 * pw * 64 * PSTRIDE;
-  const size_t image = ((max_row_doubles + 1) & ~(size_t)1) + (size_t)3 * cw * 8;
-  return sizeof(double) * (points > image ? points : image);
+  return cll::overlay_bytes((size_t)cll::solid_point_doubles(pw), max_row_doubles, (size_t)3 * cll::max_nodes(cw));
 }
 
 template <int CW, int PW>

@@ -163,12 +163,13 @@ int cl_replay(const P* p, const double* xyz, const double* u, const double* aux,
   const typename M::K k = M::derive(*p);
   const bool fastexp = exp_mode_of(M::exponent(k)) == M::FAST_EXP_MODE;
   const HostPrepCl& C = g_cl;
+  const cll::Strides S = cll::strides(C.lim, 8);
   std::vector<double> rec;
   for (size_t w = 0; w < C.desc.size(); w++) {
     const HostPrepCl::Desc& d = C.desc[w];
     rec.assign((size_t)d.nelem * 8 * R::STRIDE, 0.0);
     for (int le = 0; le < d.nelem; le++) {
-      const uint32_t e = C.eid[w * C.lim.max_elems + le];
+      const uint32_t e = C.eid[w * S.elem + le];
       double X[8][3], U[8][NV], AX[8][NA];
       for (int n = 0; n < 8; n++) {
         const uint32_t I = g_conn[(size_t)e * 8 + n];
@@ -183,22 +184,22 @@ int cl_replay(const P* p, const double* xyz, const double* u, const double* aux,
       }
     }
     for (int a = 0; a < d.nown; a++) {
-      const HostPrepCl::Node& nd = C.ntab[w * C.lim.max_nodes + a];
+      const HostPrepCl::Node& nd = C.ntab[w * S.node + a];
       for (int x = 0; x < NV * NV * (int)nd.len; x++) val[(size_t)NV * NV * nd.bptr + x] = 0.0;
       for (int v = 0; v < NV; v++) rhs[(size_t)NV * nd.node + v] = 0.0;
     }
     for (int x = 0; x < d.npair; x++) {
-      const uint32_t pr = C.pair[w * C.lim.max_pairs + x];
-      const uint32_t le = pr & 0xFF, li = (pr >> 8) & 0xFF, a = (pr >> 16) & 0xFF;
+      const uint32_t pr = C.pair[w * S.pair + x];
+      const int le = cll::pair_elem(pr), li = cll::pair_row(pr), a = cll::pair_node(pr);
       double acc[NV][NV][8], fe[NV];
       rd_row_zero<M, 8>(acc, fe);
       for (int q = 0; q < 8; q++) {
         const double* r = &rec[((size_t)le * 8 + q) * R::STRIDE];
-        if (fastexp) hex8_cl_consume<M, M::FAST_EXP_MODE>(k, r, q, (int)li, acc, fe); else hex8_cl_consume<M, 0>(k, r, q, (int)li, acc, fe);
+        if (fastexp) hex8_cl_consume<M, M::FAST_EXP_MODE>(k, r, q, li, acc, fe); else hex8_cl_consume<M, 0>(k, r, q, li, acc, fe);
       }
-      const HostPrepCl::Node& nd = C.ntab[w * C.lim.max_nodes + a];
+      const HostPrepCl::Node& nd = C.ntab[w * S.node + a];
       for (int j = 0; j < 8; j++) {
-        const uint32_t sl = (C.pslot[(w * C.lim.max_pairs + x) * 2 + j / 4] >> (8 * (j % 4))) & 0xFF;
+        const int sl = cll::pslot_get(&C.pslot[w * S.pslot + (size_t)x * cll::pslot_words(8)], j);
         for (int aa = 0; aa < NV; aa++)
           for (int b = 0; b < NV; b++) val[(size_t)NV * NV * nd.bptr + (size_t)aa * NV * nd.len + NV * sl + b] += acc[aa][b][j];
       }
@@ -355,7 +356,7 @@ void shim_cl_set_interior(int64_t n) { g_cl_interior = n; }
 int shim_cl_interior_stats(int64_t* out) {
   const HostPrepCl& C = g_cl;
   out[0] = C.n_wg_interior; out[1] = C.part1_nodes; out[2] = 0;
-  const int max_nodes = C.lim.max_nodes;
+  const size_t max_nodes = cll::strides(C.lim, g_prep.nen).node;
   for (size_t w = 0; w < C.desc.size(); w++) {
     int n_in = 0;
     for (int a = 0; a < C.desc[w].nown; a++) n_in += (int64_t)C.ntab[w * max_nodes + a].node < g_cl_interior;
@@ -367,14 +368,27 @@ int shim_cl_interior_stats(int64_t* out) {
   }
   return 0;
 }
-int shim_cl_build(int max_nodes, int max_pairs, int max_elems, int max_row_doubles, int pair_order, int64_t* stats) {
+// out6 = cll::limits(cw, pw, nvar): max_nodes, max_pairs, max_elems, max_row_doubles, pair_order, img_per_block
+void shim_cl_limits(int cw, int pw, int nvar, int* out6) {
+  const HostPrepCl::Limits lim = cll::limits(cw, pw, nvar);
+  out6[0] = lim.max_nodes; out6[1] = lim.max_pairs; out6[2] = lim.max_elems; out6[3] = lim.max_row_doubles; out6[4] = lim.pair_order; out6[5] = lim.img_per_block;
+}
+int shim_cl_max_len() {   // most node blocks in a row of the last lists
+  int len = 0;
+  for (const HostPrepCl::Node& nd : g_cl.ntab) len = std::max<int>(len, nd.len);
+  return len;
+}
+// img_per_block: HostPrepCl::Limits (0 = whole rows; nvar = one equation row, as the lists of five unknowns are built)
+int shim_cl_build_ipb(int max_nodes, int max_pairs, int max_elems, int max_row_doubles, int pair_order, int img_per_block, int64_t* stats) {
   HostPrepCl::Limits lim;
   stats[5] = 0;
   lim.max_nodes = max_nodes; lim.max_pairs = max_pairs; lim.max_elems = max_elems; lim.max_row_doubles = max_row_doubles; lim.pair_order = pair_order;
+  lim.img_per_block = img_per_block;
   g_err = prep_build_cl(g_prep, g_conn.data(), lim, g_cl, g_cl_interior);
   if (!g_err.empty()) return 1;
   const HostPrepCl& C = g_cl;
-  const int nen = g_prep.nen;
+  const int nen = g_prep.nen, nv2 = g_prep.nvar * g_prep.nvar, ipb = img_per_block > 0 ? img_per_block : nv2;
+  const cll::Strides S = cll::strides(lim, nen);
   std::vector<int32_t> npairs_of((size_t)g_prep.n_owned, 0), seen((size_t)g_prep.n_owned, 0);
   int64_t covered = 0, largest = 0, groups = 0, groups_twice = 0;
   for (size_t w = 0; w < C.desc.size(); w++) {
@@ -384,24 +398,24 @@ int shim_cl_build(int max_nodes, int max_pairs, int max_elems, int max_row_doubl
     largest = std::max<int64_t>(largest, d.nown);
     uint32_t off = 0;
     for (int a = 0; a < d.nown; a++) {
-      const HostPrepCl::Node& nd = C.ntab[w * lim.max_nodes + a];
+      const HostPrepCl::Node& nd = C.ntab[w * S.node + a];
       if ((int64_t)nd.node >= g_prep.n_owned || seen[nd.node]++) { g_err = "node listed twice"; return 3; }
-      if ((off ^ (uint32_t)(g_prep.nvar * g_prep.nvar * g_prep.bptr[nd.node])) & 1u) off++;   // the segment has the 16-byte phase of its CSR segment
+      if (ipb == nv2 && cll::seg_phase(off) != cll::seg_phase((uint32_t)(nv2 * g_prep.bptr[nd.node]))) off++;   // whole rows: the segment has the 16-byte phase of its CSR segment
       if (nd.bptr != (uint32_t)g_prep.bptr[nd.node] || nd.len != g_prep.bptr[nd.node + 1] - g_prep.bptr[nd.node] || nd.off != off) { g_err = "node table"; return 4; }
-      off += (uint32_t)(g_prep.nvar * g_prep.nvar * nd.len);
+      off += (uint32_t)(ipb * nd.len);
     }
     if (off != d.row_doubles) { g_err = "row_doubles"; return 5; }
     for (int x = 0; x < lim.max_pairs; x++) {
-      const uint32_t pr = C.pair[w * lim.max_pairs + x];
-      if (x >= d.npair) { if (pr != 0xFFFFFFFFu) { g_err = "pair beyond npair"; return 6; } continue; }
-      const uint32_t le = pr & 0xFF, li = (pr >> 8) & 0xFF, a = (pr >> 16) & 0xFF;
-      if (le >= d.nelem || (int)li >= nen || a >= d.nown) { g_err = "pair fields"; return 7; }
-      const uint32_t e = C.eid[w * lim.max_elems + le];
-      const uint32_t n = C.ntab[w * lim.max_nodes + a].node;
+      const uint32_t pr = C.pair[w * S.pair + x];
+      if (x >= d.npair) { if (pr != cll::IDLE) { g_err = "pair beyond npair"; return 6; } continue; }
+      const int le = cll::pair_elem(pr), li = cll::pair_row(pr), a = cll::pair_node(pr);
+      if (le >= d.nelem || li >= nen || a >= d.nown) { g_err = "pair fields"; return 7; }
+      const uint32_t e = C.eid[w * S.elem + le];
+      const uint32_t n = C.ntab[w * S.node + a].node;
       if (e >= (uint32_t)g_prep.n_elem || g_conn[(size_t)e * nen + li] != n) { g_err = "pair does not match the mesh"; return 8; }
       for (int j = 0; j < nen; j++) {
-        const uint32_t s = (C.pslot[(w * lim.max_pairs + x) * (nen / 4) + j / 4] >> (8 * (j % 4))) & 0xFF;
-        if (s != g_prep.eslot[(size_t)e * nen * nen + li * nen + j]) { g_err = "slot"; return 9; }
+        const int s = cll::pslot_get(&C.pslot[w * S.pslot + (size_t)x * cll::pslot_words(nen)], j);
+        if (s != (int)g_prep.eslot[(size_t)e * nen * nen + li * nen + j]) { g_err = "slot"; return 9; }
       }
       npairs_of[n]++;
     }
@@ -410,7 +424,7 @@ int shim_cl_build(int max_nodes, int max_pairs, int max_elems, int max_row_doubl
       uint64_t m[4] = {0, 0, 0, 0};
       bool twice = false;
       for (int y = x; y < x + 16; y++) {
-        const uint32_t a = (C.pair[w * lim.max_pairs + y] >> 16) & 0xFF;
+        const int a = cll::pair_node(C.pair[w * S.pair + y]);
         if (m[a >> 6] & (1ull << (a & 63))) twice = true;
         m[a >> 6] |= 1ull << (a & 63);
       }
@@ -426,6 +440,10 @@ int shim_cl_build(int max_nodes, int max_pairs, int max_elems, int max_row_doubl
   stats[0] = (int64_t)C.desc.size(); stats[1] = C.n_elem_visits; stats[2] = C.n_pairs; stats[3] = (int64_t)C.max_row_doubles;
   stats[4] = covered; stats[5] = largest; stats[6] = groups; stats[7] = groups_twice;
   return 0;
+}
+
+int shim_cl_build(int max_nodes, int max_pairs, int max_elems, int max_row_doubles, int pair_order, int64_t* stats) {
+  return shim_cl_build_ipb(max_nodes, max_pairs, max_elems, max_row_doubles, pair_order, 0, stats);
 }
 
 // model: 1 RIPF, 2 HCC, 4 ADPM, 7 RIPF reduced, 8 HCC mass only, 9 ADPM decay only (as shim_row)

@@ -1,11 +1,13 @@
-"""Unstructured TET4 meshes for the parity tests (tests/test_unstructured_meshes.py on the CPU, tests/test_gpu_unstructured.py
-on the GPU).  The Kuhn meshes of the other tests have valence 14; these reach the paths a real mesh takes:
+"""Unstructured meshes for the parity tests (TET4: tests/test_unstructured_meshes.py on the CPU, tests/test_gpu_unstructured.py
+on the GPU; HEX8: tests/test_host_cl.py, tests/test_gpu_parity.py).  The Kuhn meshes of the other tests have valence 14 and
+structured hexahedra rows of 27 node blocks; these reach the paths a real mesh takes:
 
   hydrogel   tests/golden/solid_hydrogel_tension_model.msh read as a plain TET4 mesh (5,504 tets, valence 31)
   delaunay   scipy Delaunay of a jittered 30^3 grid (179,455 tets, valence > 16: more workgroups than CUs)
   hub        a Kuhn mesh plus a hub of tetrahedra that share one vertex: a row longer than a row-gather workgroup's LDS
              budget, so that SCATTER_AUTO resolves to COLOURED
   over256    the same hub with more than 256 tetrahedra at one vertex: more colours than the colouring allows
+  hex_fan    hexahedra around an axis (51 nodes, 16 elements): a row of 51 node blocks for the HEX8 cluster kernels
 
 Fields are generated from the coordinates normalised to the unit cube (synth.*_fields expect [0, 1]^3)."""
 from pathlib import Path
@@ -83,6 +85,28 @@ def hub(n_hub, k=6):
     star = np.column_stack([np.full(n_hub, h), ids])
     xyz2 = np.vstack([xyz, new.reshape(-1, 3)])
     return orient(np.vstack([conn, star]), xyz2), np.ascontiguousarray(xyz2)
+
+
+def hex_fan(n_sectors=8, n_layers=2, seed=5):
+    """Unstructured HEX8: per layer n_sectors hexahedra around the z axis, each with the bottom face (axis node, spoke node at
+    radius 1 and angle t_s, outer node at radius 1.3 and t_s + pi / n, spoke node at t_(s+1)) and the same nodes one level up
+    as its top face; nodes permuted and jittered by 0.03.  Every element touches the axis, so the middle axis node of two
+    layers has every node of the mesh in its row: with 8 sectors 51 node blocks (a structured mesh has at most 27), which
+    is what reaches the later passes of the cluster kernels' copy-out and long image segments of odd phase."""
+    rng = np.random.default_rng(seed)
+    t = 2.0 * np.pi * np.arange(n_sectors) / n_sectors
+    ring = np.concatenate([[[0.0, 0.0]], np.column_stack([np.cos(t), np.sin(t)]),
+                           1.3 * np.column_stack([np.cos(t + np.pi / n_sectors), np.sin(t + np.pi / n_sectors)])])
+    per = ring.shape[0]                                          # axis, spokes 1 .. n, outer n + 1 .. 2 n
+    xyz = np.concatenate([np.column_stack([ring, np.full(per, 0.6 * z)]) for z in range(n_layers + 1)])
+    s = np.arange(n_sectors)
+    bottom = np.column_stack([np.zeros_like(s), 1 + s, 1 + n_sectors + s, 1 + (s + 1) % n_sectors])
+    conn = np.concatenate([np.column_stack([bottom + per * z, bottom + per * (z + 1)]) for z in range(n_layers)])
+    xyz = xyz + rng.uniform(-0.03, 0.03, xyz.shape)
+    pn = rng.permutation(xyz.shape[0])                           # new id of old node
+    inv = np.empty_like(pn)
+    inv[pn] = np.arange(pn.size)
+    return np.ascontiguousarray(pn[conn], dtype=np.uint32), np.ascontiguousarray(xyz[inv])
 
 
 def valence(conn, n_node):

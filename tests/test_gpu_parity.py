@@ -4,6 +4,7 @@ applied to the matrix (Frobenius) and to A*x for a seeded random x."""
 import numpy as np
 import pytest
 
+import meshes
 from parity import assert_csr_close
 from rdcfes_amd import (AssemblyContext, RdcError, SolidMaterial, SolidParams, hcc_params_from_dict,
                         pihna_params_from_dict, ripf_params_from_dict, synth)
@@ -295,6 +296,49 @@ def test_solid_parity_on_a_ghosted_partition(oracle, solid_kernel):
         ctx.solid_assemble(sp, True)
         val, rhs = ctx.csr_download()
     assert rhs.size == 3 * n_owned
+    assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
+
+
+# ---- the HEX8 cluster kernels on an unstructured mesh: meshes.hex_fan has a row of 51 node blocks (structured hexahedra: 27), so
+# a node's image segment is several passes of the copy-out long (tests/test_host_cl.py: the cluster lists build for it) ------------
+@pytest.mark.parametrize("model,options", [(2, ()), (2, (("hex_kernel", 2),)), (0, ())], ids=["hcc", "hcc_persistent", "pihna_rows"])
+def test_hex8_cluster_kernels_on_long_rows(oracle, model, options):
+    conn, xyz = meshes.hex_fan()
+    nv = 5 if model == 0 else 3
+    fxyz = meshes.unit_cube(xyz)
+    if model == 0:
+        p, u = pihna_params_from_dict(synth.pihna_param_dict("full")), synth.pihna_fields(fxyz, radius=1.0)
+    else:
+        p, u = hcc_params_from_dict(synth.hcc_param_dict("full")), synth.hcc_fields(fxyz)
+    rp0, col0, val0, rhs0 = oracle.assemble(model, 8, conn, xyz, nv, p, u_old=u)
+    assert np.diff(rp0).max() == nv * xyz.shape[0]
+    rp, col, val, rhs = _gpu_assemble(model, 8, conn, xyz, u, None, p, SCATTER_ROWGATHER, VARIANT_GENERIC, options=options)
+    np.testing.assert_array_equal(rp, rp0)
+    np.testing.assert_array_equal(col, col0)
+    assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, nv)
+
+
+@pytest.mark.parametrize("cl_waves", [31, 62])
+def test_solid_cluster_kernel_on_long_rows(oracle, cl_waves):
+    conn, Xu = meshes.hex_fan()
+    x = Xu + synth.solid_displacement(meshes.unit_cube(Xu), amp=0.02)
+    em = (np.arange(conn.shape[0]) % 2).astype(np.int32)
+    mats = [SolidMaterial(2.0e3, 0.4, 0.0, (0.0, 0.0, 0.0)), SolidMaterial(1.5e3, 0.35, 40.0, (0.3, 0.2, 0.1))]
+    fibre = np.random.default_rng(0).standard_normal((conn.shape[0], 3))
+    sp = SolidParams(0.4, 1.0e5, 1, 0)
+    rp0, col0, val0, rhs0 = oracle.assemble(oracle.MODEL_SOLID, 8, conn, x, 3, sp, xyz_undeformed=Xu, elem_fibre=fibre,
+                                            elem_material=em, materials=mats, request_jacobian=True)
+    with AssemblyContext(0) as ctx:
+        ctx.set_option("solid_kernel", 3)              # the fused cluster kernel or an error: no fall-back to the two-pass form
+        ctx.set_option("solid_cl_waves", cl_waves)
+        ctx.mesh_upload(8, conn, x, 3)
+        ctx.field_upload(FIELD_UNDEFORMED_XYZ, Xu)
+        ctx.field_upload(FIELD_ELEM_FIBRE, fibre)
+        ctx.solid_set_materials(em, mats)
+        ctx.solid_assemble(sp, True)
+        val, rhs = ctx.csr_download()
     assert rel(rhs, rhs0) < TOL and rel(val, val0) < TOL
     assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 3)
 

@@ -10,21 +10,39 @@ import pytest
 from rdcfes_amd import synth
 
 
-def _build(shim, nen, conn, n_node, n_owned, lim, order=1):
+def _limits(shim, cw, pw, nvar):
+    """cll::limits (rdc_prep.h): what the context builds the lists with for cw consumer / pw producer waves and nvar unknowns:
+    (max_nodes, max_pairs, max_elems, max_row_doubles, pair_order, img_per_block)"""
+    out = (C.c_int * 6)()
+    shim.shim_cl_limits(cw, pw, nvar, out)
+    return tuple(out)
+
+
+def _build(shim, nen, conn, n_node, n_owned, lim, order=1, nvar=3):
+    """lim: the first four limits, or all six of _limits (its pair_order gives way to `order`)"""
     conn = np.ascontiguousarray(conn, dtype=np.uint32)
     rc = shim.shim_prep_build(nen, C.c_int64(conn.shape[0]), C.c_int64(n_node), C.c_int64(n_owned),
-                              conn.ctypes.data_as(C.POINTER(C.c_uint32)), 3, C.c_int64(60 * 1024), 256)
+                              conn.ctypes.data_as(C.POINTER(C.c_uint32)), nvar, C.c_int64(60 * 1024), 256)
     assert rc == 0, shim.shim_prep_error()
     st = (C.c_int64 * 8)()
-    rc = shim.shim_cl_build(*lim, order, st)
+    rc = shim.shim_cl_build_ipb(*lim[:4], order, lim[5] if len(lim) > 4 else 0, st)
     assert rc == 0, (rc, shim.shim_prep_error())
     return dict(zip(("n_wg", "n_visits", "n_pairs", "max_row", "covered", "largest", "groups", "groups_twice"), list(st)))
 
 
-@pytest.mark.parametrize("lim", [(24, 192, 64, 6198), (48, 384, 128, 12398)])
+@pytest.mark.parametrize("waves,nvar,expect", [((3, 1), 3, (24, 192, 64, 6198, 0)), ((6, 2), 3, (48, 384, 128, 12398, 0)),
+                                               ((3, 1), 5, (24, 192, 64, 3360, 5))])
+def test_cluster_limits(shim, waves, nvar, expect):
+    """2 pw 64 49 - 3 8 cw - 2 (the image overlays the solid kernel's point buffers); five unknowns: 5 27 24 + 5 24, one row per image"""
+    lim = _limits(shim, *waves, nvar)
+    assert lim[:4] + lim[5:] == expect
+
+
+@pytest.mark.parametrize("lim", [(3, 1), (6, 2)])
 @pytest.mark.parametrize("order", ["lex", "random"])
 @pytest.mark.parametrize("pair_order", [0, 1])
 def test_cluster_lists_hex(shim, lim, order, pair_order):
+    lim = _limits(shim, *lim, 3)
     conn, xyz = synth.hex_mesh(9, jitter=0.1, order=order)
     st = _build(shim, 8, conn, xyz.shape[0], xyz.shape[0], lim, pair_order)
     assert st["covered"] == xyz.shape[0]
@@ -41,7 +59,7 @@ def test_cluster_lists_hex(shim, lim, order, pair_order):
 def test_cluster_lists_on_a_ghosted_partition(shim):
     conn, xyz = synth.hex_mesh(8, jitter=0.1, order="random")
     n_owned = int(0.6 * xyz.shape[0])          # nodes >= n_owned are ghosts: their rows are not assembled
-    st = _build(shim, 8, conn, xyz.shape[0], n_owned, (24, 192, 64, 6198))
+    st = _build(shim, 8, conn, xyz.shape[0], n_owned, _limits(shim, 3, 1, 3))
     assert st["covered"] == n_owned
     owned_pairs = int((conn < n_owned).sum())
     assert st["n_pairs"] == owned_pairs
@@ -59,8 +77,8 @@ def _rel(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
 
 
-def _replay(shim, model, p, conn, xyz, u, aux, tracts, n_owned, lim=(24, 192, 64, 6198), order=1):
-    _build(shim, 8, conn, xyz.shape[0], n_owned, lim, order)
+def _replay(shim, model, p, conn, xyz, u, aux, tracts, n_owned, order=1):
+    _build(shim, 8, conn, xyz.shape[0], n_owned, _limits(shim, 3, 1, 3), order)
     bptr = np.empty(shim.shim_prep_size(0), dtype=np.int64)
     shim.shim_prep_copy(0, bptr.ctypes.data_as(C.c_void_p))
     val = np.full(9 * bptr[n_owned], np.nan)
@@ -128,7 +146,7 @@ def test_cluster_lists_respect_interior_nodes(shim, pair_order):
     assert 0 < lp.n_interior < lp.n_owned
     shim.shim_cl_set_interior(C.c_int64(lp.n_interior))
     try:
-        st = _build(shim, 8, lp.conn, lp.xyz.shape[0], lp.n_owned, (24, 192, 64, 6198), pair_order)
+        st = _build(shim, 8, lp.conn, lp.xyz.shape[0], lp.n_owned, _limits(shim, 3, 1, 3), pair_order)
         out = (C.c_int64 * 3)()
         assert shim.shim_cl_interior_stats(out) == 0
     finally:
@@ -138,5 +156,31 @@ def test_cluster_lists_respect_interior_nodes(shim, pair_order):
     assert mixed == 0 and 0 < n_wg_int < st["n_wg"]
     assert 0 < part1_nodes <= lp.n_interior
     # the split costs little: at most a few clusters more than without it
-    st0 = _build(shim, 8, lp.conn, lp.xyz.shape[0], lp.n_owned, (24, 192, 64, 6198), pair_order)
+    st0 = _build(shim, 8, lp.conn, lp.xyz.shape[0], lp.n_owned, _limits(shim, 3, 1, 3), pair_order)
     assert st["n_wg"] <= 1.15 * st0["n_wg"] + 2
+
+
+# ---- an unstructured HEX8 mesh: meshes.hex_fan has a row of 51 node blocks (structured hexahedra: at most 27) --------------------
+@pytest.mark.parametrize("waves,nvar", [((3, 1), 3), ((6, 2), 3), ((3, 1), 5)])
+def test_cluster_lists_hex_fan(shim, waves, nvar):
+    """the lists build with the limits the context uses, so the GPU tests on this mesh (tests/test_gpu_parity.py) run the cluster
+    kernels and not what the context falls back to without lists"""
+    import meshes
+    conn, xyz = meshes.hex_fan()
+    assert xyz.shape[0] == 51 and conn.shape[0] == 16
+    st = _build(shim, 8, conn, xyz.shape[0], xyz.shape[0], _limits(shim, *waves, nvar), nvar=nvar)
+    assert st["covered"] == xyz.shape[0]
+    assert st["n_pairs"] == 8 * conn.shape[0]
+    assert shim.shim_cl_max_len() == 51
+
+
+def test_hex8_cluster_replay_hex_fan(oracle, shim):
+    import meshes
+    from rdcfes_amd import hcc_params_from_dict
+    conn, xyz = meshes.hex_fan()
+    u = synth.hcc_fields(meshes.unit_cube(xyz))
+    p = hcc_params_from_dict(synth.hcc_param_dict("full"))
+    _, _, val0, rhs0 = oracle.assemble(oracle.MODEL_HCC, 8, conn, xyz, 3, p, u_old=u)
+    val, rhs = _replay(shim, 2, p, conn, xyz, u, None, None, xyz.shape[0])
+    assert np.isfinite(val).all() and np.isfinite(rhs).all()
+    assert _rel(val, val0) < 1e-10 and _rel(rhs, rhs0) < 1e-10
