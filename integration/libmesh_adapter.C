@@ -4,8 +4,12 @@
 //
 // NOT COMPILED IN THIS REPOSITORY'S BUILD: it needs libMesh (d3bda6c) and PETSc (746207a), neither of
 // which exists in the build image.  It is written against the libMesh API the reference itself uses
-// (src/pihna.C:318-395, :752-755) and is exercised here only through its twin over the mock types,
-// rdcfes_amd/host/rdc_host.h, which makes exactly the same C-ABI calls in the same order.
+// (src/pihna.C:318-395, :752-755).  What names no libMesh or PETSc type -- parameter key -> struct field, the solid system's
+// material table and side list, the error path, schedule and pinning of the pipelined hand-back -- is include/rdc_marshal.h, which
+// IS compiled and tested here (tests/test_host_marshal.py) and which the host mirror, rdcfes_amd/host/rdc_host.h, runs on the GPU.
+// Left in this file, and so untested: bind(), the gathers through dof_number(), push_results(), push_results_device(),
+// hand_back(), the MatSetValues consumer of the chunked hand-back, the residual / Jacobian insertion of SolidSystemGPU.  A failing
+// C-ABI call or a missing parameter leaves a callback as an exception (std::runtime_error from marshal::check; libMesh's own).
 //
 // Usage in the reference tree:
 //   1. add this file to src/ (Makefile:7 globs src/*.C), link with -lrdc_assembly;
@@ -38,15 +42,16 @@
 #include "libmesh/transient_system.h"
 
 #include "./solid_system.h"   // the reference's own header (src/solid_system.h): SolidSystemGPU derives from it
-#include "./utils.h"          // export_integers (src/utils.h:268)
 
 #include <map>
 #include <unordered_map>
 #include <vector>
 
-#include "rdc_assembly.h"
+#include "rdc_marshal.h"
 
 using namespace libMesh;
+namespace marshal = rdc::marshal;
+using marshal::check;
 
 namespace rdc_gpu {
 
@@ -59,13 +64,19 @@ struct Binding {
   std::vector<PetscInt> row_glob;                  // global dof id of owned row r = local node * nvar + var
   std::vector<double> val, rhs, u_old;
   dof_id_type n_owned = 0;
-  bool pinned = false;                             // val / rhs registered with the HIP runtime (rdc_host_pin): async chunk copies
+  marshal::PinState pins;                          // val / rhs registered with the HIP runtime once, for the async chunk copies
   bool pattern_frozen = false;                     // MAT_NEW_NONZERO_LOCATIONS switched off after the first assembly
+  bool solid_bound = false;                        // SolidSystemGPU: materials and sides are in the context
 };
 
 static std::map<std::string, Binding> g_bindings;
 
-static void fail(rdc_ctx* c, const char* what) { libmesh_error_msg(std::string(what) + ": " + rdc_last_error(c)); }
+// Unpin the hand-back arrays and destroy the GPU contexts: call it once the systems are done with (before MPI_Finalize /
+// the end of main), or the arrays of the static map are freed at exit while still registered.  The next callback binds anew.
+void release_bindings() {
+  for (auto& kv : g_bindings) { kv.second.pins.release(kv.second.ctx); rdc_ctx_destroy(kv.second.ctx); }
+  g_bindings.clear();
+}
 
 // N > 1 ranks: ghost the dofs of every element that shares a point with a local element (see the header, item 4).
 // Call before es.init() for every system the GPU callbacks read.
@@ -79,7 +90,8 @@ void add_ghost_layer(System& sys) {
 // one rank per GPU: the device of this rank is its rank among the ranks of the same host
 static int device_of_this_rank(const Parallel::Communicator& comm) {
   int ndev = 0;
-  if (rdc_device_count(&ndev) != RDC_OK || ndev <= 0) libmesh_error_msg(rdc_last_error(nullptr));
+  check(nullptr, rdc_device_count(&ndev), "rdc_device_count");
+  if (ndev <= 0) libmesh_error_msg("no GPU visible to this rank");
   int local_rank = 0;
 #ifdef LIBMESH_HAVE_MPI
   MPI_Comm node;
@@ -88,6 +100,14 @@ static int device_of_this_rank(const Parallel::Communicator& comm) {
   MPI_Comm_free(&node);
 #endif
   return local_rank % ndev;
+}
+
+// coordinates of the binding's nodes as the mesh holds them now, [local node][3]
+static std::vector<double> node_coordinates(const MeshBase& mesh, const Binding& B) {
+  std::vector<double> xyz(3 * B.local_to_global_node.size());
+  for (size_t l = 0; l < B.local_to_global_node.size(); l++)
+    for (int d = 0; d < 3; d++) xyz[3 * l + d] = mesh.node_ref(B.local_to_global_node[l])(d);
+  return xyz;
 }
 
 // Marshal the rank's partition once: owned nodes first, then ghost nodes; elements = every active
@@ -118,18 +138,16 @@ static Binding& bind(EquationSystems& es, const std::string& name, unsigned int 
       if (it == g2l.end()) { it = g2l.emplace(g, (uint32_t)B.local_to_global_node.size()).first; B.local_to_global_node.push_back(g); }
       conn.push_back(it->second);
     }
-  std::vector<double> xyz(3 * B.local_to_global_node.size());
-  for (size_t l = 0; l < B.local_to_global_node.size(); l++)
-    for (int d = 0; d < 3; d++) xyz[3 * l + d] = mesh.node_ref(B.local_to_global_node[l])(d);
-  if (rdc_ctx_create(device_of_this_rank(mesh.comm()), &B.ctx) != RDC_OK) libmesh_error_msg(rdc_last_error(nullptr));
-  if (rdc_mesh_upload(B.ctx, nen, (int64_t)elems.size(), (int64_t)B.local_to_global_node.size(), B.n_owned, conn.data(),
-                      xyz.data(), (int)nvar) != RDC_OK) fail(B.ctx, "rdc_mesh_upload");
+  const std::vector<double> xyz = node_coordinates(mesh, B);
+  check(nullptr, rdc_ctx_create(device_of_this_rank(mesh.comm()), &B.ctx), "rdc_ctx_create");
+  check(B.ctx, rdc_mesh_upload(B.ctx, nen, (int64_t)elems.size(), (int64_t)B.local_to_global_node.size(), B.n_owned, conn.data(),
+                               xyz.data(), (int)nvar), "rdc_mesh_upload");
   // pattern with LOCAL column ids -> global PETSc dof ids (dof_number(sys, var, 0))
   int64_t n_rows = 0, nnz = 0;
-  rdc_csr_dims(B.ctx, &n_rows, &nnz);
+  check(B.ctx, rdc_csr_dims(B.ctx, &n_rows, &nnz), "rdc_csr_dims");
   std::vector<int64_t> rp(n_rows + 1);
   std::vector<int32_t> cl(nnz);
-  rdc_csr_pattern_download(B.ctx, rp.data(), cl.data());
+  check(B.ctx, rdc_csr_pattern_download(B.ctx, rp.data(), cl.data()), "rdc_csr_pattern_download");
   B.row_ptr.assign(rp.begin(), rp.end());
   B.col_glob.resize(nnz);
   for (int64_t k = 0; k < nnz; k++) {
@@ -143,18 +161,19 @@ static Binding& bind(EquationSystems& es, const std::string& name, unsigned int 
   return B;
 }
 
-// old_local_solution (ghosted) -> [local node][var], the layout of RDC_FIELD_OLD_SOLUTION
-static void gather_old_solution(const EquationSystems& es, const TransientLinearImplicitSystem& sys, Binding& B, unsigned int nvar) {
+// old_local_solution (ghosted) -> [local node][var], the layout of RDC_FIELD_OLD_SOLUTION, and into the context
+static void upload_old_solution(const EquationSystems& es, const TransientLinearImplicitSystem& sys, Binding& B, unsigned int nvar) {
   const MeshBase& mesh = es.get_mesh();
   for (size_t l = 0; l < B.local_to_global_node.size(); l++) {
     const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
     for (unsigned int v = 0; v < nvar; v++) B.u_old[l * nvar + v] = sys.old_solution(nd.dof_number(sys.number(), v, 0));   // src/pihna.C:433
   }
+  check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()), "rdc_field_upload");
 }
 
 // assembled owned rows -> system.matrix / system.rhs (what add_matrix / add_vector did, src/pihna.C:754-755)
 static void push_results(const EquationSystems& es, TransientLinearImplicitSystem& sys, Binding& B, unsigned int nvar) {
-  if (rdc_csr_download(B.ctx, B.val.data(), B.rhs.data()) != RDC_OK) fail(B.ctx, "rdc_csr_download");
+  check(B.ctx, rdc_csr_download(B.ctx, B.val.data(), B.rhs.data()), "rdc_csr_download");
   Mat A = cast_ref<PetscMatrix<Number>&>(*sys.matrix).mat();
   const MeshBase& mesh = es.get_mesh();
   for (dof_id_type l = 0; l < B.n_owned; l++) {
@@ -168,33 +187,19 @@ static void push_results(const EquationSystems& es, TransientLinearImplicitSyste
   }
 }
 
-// The same hand-back, pipelined (es.parameters "rdc/handback_chunks" > 1; mirrored and tested in rdcfes_amd/host/rdc_host.h,
-// detail::pull_results_chunked): the node range is cut into chunks, two chunk downloads are kept in flight on the context's
-// copy stream (rdc_csr_download_rows_async: behind the work enqueued so far, independent of later work), and every chunk is
-// inserted while the next travels.  The nvar rows of a node share one column set and lie back to back in the CSR array, so
-// they are ONE dense nvar x ncols block for MatSetValues: one call per node block instead of one per row (rows of different
-// nodes have different column sets: a chunk as a whole is not a dense block, so it cannot be a single call).
+// The same hand-back, pipelined ("rdc/handback_chunks" > 1): marshal::hand_back_chunked cuts the owned node range into chunks,
+// keeps two chunk downloads in flight on the context's copy stream and calls the consumer below for every chunk while the next
+// travels; B.pins keeps val / rhs registered from the first call on.  The nvar rows of a node share one column set and lie back to
+// back in the CSR array, so they are ONE dense nvar x ncols block for MatSetValues: one call per node block instead of one per row
+// (rows of different nodes have different column sets: a chunk as a whole is not a dense block, so it cannot be a single call).
 // After the first assembly the pattern is frozen (MAT_NEW_NONZERO_LOCATIONS off): PETSc then skips the search for new
 // locations and any pattern drift is an error instead of a silent reallocation.
 static void push_results_chunked(const EquationSystems& es, TransientLinearImplicitSystem& sys, Binding& B, unsigned int nvar, int n_chunks) {
   Mat A = cast_ref<PetscMatrix<Number>&>(*sys.matrix).mat();
   const MeshBase& mesh = es.get_mesh();
-  if (!B.pinned) {
-    if (rdc_host_pin(B.ctx, B.val.data(), B.val.size() * sizeof(double)) != RDC_OK) fail(B.ctx, "rdc_host_pin");
-    if (rdc_host_pin(B.ctx, B.rhs.data(), B.rhs.size() * sizeof(double)) != RDC_OK) fail(B.ctx, "rdc_host_pin");
-    B.pinned = true;
-  }
-  const int64_t n_nodes = (int64_t)B.n_owned;
-  auto bound = [&](int k) { return n_nodes * k / n_chunks; };
-  int ticket[2] = {-1, -1};
-  if (rdc_csr_download_rows_async(B.ctx, bound(0), bound(1), B.val.data(), B.rhs.data(), &ticket[0]) != RDC_OK) fail(B.ctx, "rdc_csr_download_rows_async");
   std::vector<PetscInt> rows(nvar);
-  for (int k = 0; k < n_chunks; k++) {
-    if (k + 1 < n_chunks &&
-        rdc_csr_download_rows_async(B.ctx, bound(k + 1), bound(k + 2), B.val.data(), B.rhs.data(), &ticket[(k + 1) & 1]) != RDC_OK)
-      fail(B.ctx, "rdc_csr_download_rows_async");
-    if (rdc_ticket_wait(B.ctx, ticket[k & 1]) != RDC_OK) fail(B.ctx, "rdc_ticket_wait");
-    for (int64_t l = bound(k); l < bound(k + 1); l++) {
+  marshal::hand_back_chunked(B.ctx, (int64_t)B.n_owned, n_chunks, B.val.data(), B.val.size(), B.rhs.data(), B.rhs.size(), B.pins, [&](int64_t n0, int64_t n1) {
+    for (int64_t l = n0; l < n1; l++) {
       const Node& nd = mesh.node_ref(B.local_to_global_node[(size_t)l]);
       for (unsigned int a = 0; a < nvar; a++) rows[a] = (PetscInt)nd.dof_number(sys.number(), a, 0);
       const PetscInt b = B.row_ptr[(size_t)(l * nvar)], n = B.row_ptr[(size_t)(l * nvar) + 1] - b;
@@ -202,7 +207,7 @@ static void push_results_chunked(const EquationSystems& es, TransientLinearImpli
       MatSetValues(A, (PetscInt)nvar, rows.data(), n, &B.col_glob[(size_t)b], &B.val[(size_t)b], INSERT_VALUES);
       for (unsigned int a = 0; a < nvar; a++) sys.rhs->set(rows[a], B.rhs[(size_t)(l * nvar + a)]);
     }
-  }
+  });
   if (!B.pattern_frozen) {   // takes effect for the NEXT assembly (this one may still have created locations)
     MatSetOption(A, MAT_NEW_NONZERO_LOCATIONS, PETSC_FALSE);
     B.pattern_frozen = true;
@@ -221,14 +226,14 @@ static bool push_results_device(TransientLinearImplicitSystem& sys, Binding& B) 
   PetscObjectTypeCompare((PetscObject)A, MATSEQAIJHIPSPARSE, &is_seq_hip);
   if (!is_seq_hip) return false;
   double *d_val = nullptr, *d_rhs = nullptr;
-  if (rdc_csr_values_device_ptr(B.ctx, &d_val, &d_rhs) != RDC_OK) fail(B.ctx, "rdc_csr_values_device_ptr");
+  check(B.ctx, rdc_csr_values_device_ptr(B.ctx, &d_val, &d_rhs), "rdc_csr_values_device_ptr");
   PetscScalar* a = nullptr;
   MatSeqAIJHIPSPARSEGetArrayWrite(A, &a);                 // device pointer of the CSR values, write access
-  if (rdc_synchronize(B.ctx) != RDC_OK) fail(B.ctx, "rdc_synchronize");
+  check(B.ctx, rdc_synchronize(B.ctx), "rdc_synchronize");
   if (hipMemcpy(a, d_val, B.val.size() * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) libmesh_error_msg("device hand-off copy failed");
   MatSeqAIJHIPSPARSERestoreArrayWrite(A, &a);
   // the rhs is small (nvar doubles per node): through the host as before
-  if (rdc_csr_download(B.ctx, nullptr, B.rhs.data()) != RDC_OK) fail(B.ctx, "rdc_csr_download");
+  check(B.ctx, rdc_csr_download(B.ctx, nullptr, B.rhs.data()), "rdc_csr_download");
   for (size_t r = 0; r < B.rhs.size(); r++) sys.rhs->set(B.row_glob[r], B.rhs[r]);
   return true;
 }
@@ -248,23 +253,9 @@ void assemble_pihna(EquationSystems& es, const std::string& system_name) {
   TransientLinearImplicitSystem& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   libmesh_assert_equal_to(system.n_vars(), 5);
   Binding& B = bind(es, system_name, 5);
-  rdc_pihna_params p;   // the same keys assemble_pihna reads, src/pihna.C:358-381
-  p.time_step = es.parameters.get<Real>("time_step");
-  p.cells_min_capacity = es.parameters.get<Real>("cells_min_capacity");
-  p.cells_max_capacity = es.parameters.get<Real>("cells_max_capacity");
-  p.cytokines_max_capacity = es.parameters.get<Real>("cytokines_max_capacity");
-  p.cells_max_capacity_exponent = es.parameters.get<Real>("cells_max_capacity/exponent");
-  p.necrosis_c = es.parameters.get<Real>("necrosis/c"); p.necrosis_h = es.parameters.get<Real>("necrosis/h"); p.necrosis_v = es.parameters.get<Real>("necrosis/v");
-  p.diffuse_c = es.parameters.get<Real>("diffuse/c"); p.taxis_c = es.parameters.get<Real>("taxis/c");
-  p.diffuse_h = es.parameters.get<Real>("diffuse/h"); p.taxis_h = es.parameters.get<Real>("taxis/h");
-  p.produce_c = es.parameters.get<Real>("produce/c");
-  p.switch_c2h = es.parameters.get<Real>("switch/c/to/h"); p.switch_h2c = es.parameters.get<Real>("switch/h/to/c"); p.switch_h2n = es.parameters.get<Real>("switch/h/to/n");
-  p.diffuse_v = es.parameters.get<Real>("diffuse/v"); p.taxis_v = es.parameters.get<Real>("taxis/v"); p.produce_v = es.parameters.get<Real>("produce/v");
-  p.secrete_a_c = es.parameters.get<Real>("secrete/a/from/c"); p.secrete_a_h = es.parameters.get<Real>("secrete/a/from/h");
-  p.uptake_a_v = es.parameters.get<Real>("uptake/a/from/v"); p.decay_a = es.parameters.get<Real>("decay/a");
-  gather_old_solution(es, system, B, 5);
-  if (rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload");
-  if (rdc_assemble_pihna(B.ctx, &p) != RDC_OK) fail(B.ctx, "rdc_assemble_pihna");
+  const rdc_pihna_params p = marshal::read<rdc_pihna_params>(es.parameters);   // the keys assemble_pihna reads, src/pihna.C:358-381
+  upload_old_solution(es, system, B, 5);
+  check(B.ctx, rdc_assemble_pihna(B.ctx, &p), "rdc_assemble_pihna");
   hand_back(es, system, B, 5);
 }
 
@@ -274,62 +265,10 @@ void assemble_hcc(EquationSystems& es, const std::string& system_name) {
   TransientLinearImplicitSystem& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   libmesh_assert_equal_to(system.n_vars(), 3);
   Binding& B = bind(es, system_name, 3);
-  rdc_hcc_params p;   // src/coupled_hcc.C:450-461
-  p.time_step = es.parameters.get<Real>("time_step");
-  p.cells_min_capacity = es.parameters.get<Real>("cells/min_capacity");
-  p.cells_max_capacity = es.parameters.get<Real>("cells/max_capacity");
-  p.cells_max_capacity_exponent = es.parameters.get<Real>("cells/max_capacity/exponent");
-  p.produce_l = es.parameters.get<Real>("produce/l");
-  p.diffuse_c = es.parameters.get<Real>("diffuse/c"); p.mechano_c = es.parameters.get<Real>("mechano/c"); p.produce_c = es.parameters.get<Real>("produce/c");
-  p.necrosis_l = es.parameters.get<Real>("necrosis/l"); p.necrosis_c = es.parameters.get<Real>("necrosis/c");
-  p.necrosis_pressure = es.parameters.get<Real>("necrosis/pressure");
-  const MeshBase& mesh = es.get_mesh();
-  std::vector<double> xyz(3 * B.local_to_global_node.size());
-  for (size_t l = 0; l < B.local_to_global_node.size(); l++) {
-    const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
-    for (unsigned int d = 0; d < 3; d++) xyz[3 * l + d] = nd(d);
-  }
-  if (rdc_mesh_update_coords(B.ctx, xyz.data()) != RDC_OK) fail(B.ctx, "rdc_mesh_update_coords");
-  gather_old_solution(es, system, B, 3);
-  if (rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload");
-  if (rdc_assemble_hcc(B.ctx, &p) != RDC_OK) fail(B.ctx, "rdc_assemble_hcc");
-  hand_back(es, system, B, 3);
-}
-
-// src/ripf.C:337-673: additionally reads TD vars 1, 2 (src/ripf.C:470-471) and RT var 2 (:477-478)
-void assemble_ripf(EquationSystems& es, const std::string& system_name) {
-  TransientLinearImplicitSystem& system = es.get_system<TransientLinearImplicitSystem>(system_name);
-  libmesh_assert_equal_to(system.n_vars(), 3);
-  const System& TD = es.get_system<System>("RIPF-TimeDeriv");
-  const System& RT = es.get_system<ExplicitSystem>("RT");
-  Binding& B = bind(es, system_name, 3);
-  rdc_ripf_params p;   // src/ripf.C:377-408
-  auto R = [&](const char* k) { return es.parameters.get<Real>(k); };
-  p.time_step = R("time_step");
-  p.VolFr_stroma = R("volume_fraction/stroma"); p.VolFr_parenchyma = R("volume_fraction/parenchyma");
-  p.VolFr_exponent = R("volume_fraction/exponent"); p.VolFr_min_vacant = R("volume_fraction/min_vacant");
-  p.VolFr_max_vacant = R("volume_fraction/max_vacant");
-  p.phi_cc_B = R("HU/phi/cc/build"); p.phi_cc_D = R("HU/phi/cc/decay"); p.phi_cc = R("HU/phi/cc/rate");
-  p.phi_fb_B = R("HU/phi/fb/build"); p.phi_fb_D = R("HU/phi/fb/decay"); p.phi_fb = R("HU/phi/fb/rate");
-  p.phi_tol = R("HU/phi/tolerance");
-  p.kappa = R("cc/kappa"); p.kappa_RT_c = R("cc/kappa/RT/c");
-  p.delta = R("cc/delta"); p.delta_RT_a = R("cc/delta/RT/a"); p.delta_RT_b = R("cc/delta/RT/b");
-  p.lambda = R("fb/lambda"); p.lambda_RT_r = R("fb/lambda/RT/r"); p.lambda_HU_r = R("fb/lambda/HU/r");
-  p.omicro = R("fb/omicro"); p.omicro_RT_r = R("fb/omicro/RT/r"); p.omicro_fb_b = R("fb/omicro/fb/b");
-  p.omega = R("fb/omega"); p.diffusion = R("fb/diffusion"); p.haptotaxis = R("fb/haptotaxis"); p.radiotaxis = R("fb/radiotaxis");
-  p.RT_dose_total_max = es.parameters.get<int>("RT_dose/total/max");
-  const MeshBase& mesh = es.get_mesh();
-  std::vector<double> aux(3 * B.local_to_global_node.size());
-  for (size_t l = 0; l < B.local_to_global_node.size(); l++) {
-    const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
-    aux[3 * l + 0] = TD.current_solution(nd.dof_number(TD.number(), 1, 0));
-    aux[3 * l + 1] = TD.current_solution(nd.dof_number(TD.number(), 2, 0));
-    aux[3 * l + 2] = RT.current_solution(nd.dof_number(RT.number(), 2, 0));
-  }
-  gather_old_solution(es, system, B, 3);
-  if (rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload");
-  if (rdc_field_upload(B.ctx, RDC_FIELD_AUX_NODAL, aux.data(), (int64_t)aux.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload(aux)");
-  if (rdc_assemble_ripf(B.ctx, &p) != RDC_OK) fail(B.ctx, "rdc_assemble_ripf");
+  const rdc_hcc_params p = marshal::read<rdc_hcc_params>(es.parameters);   // src/coupled_hcc.C:450-461
+  check(B.ctx, rdc_mesh_update_coords(B.ctx, node_coordinates(es.get_mesh(), B).data()), "rdc_mesh_update_coords");
+  upload_old_solution(es, system, B, 3);
+  check(B.ctx, rdc_assemble_hcc(B.ctx, &p), "rdc_assemble_hcc");
   hand_back(es, system, B, 3);
 }
 
@@ -343,6 +282,23 @@ static void gather_nodal(const EquationSystems& es, const System& sys, const Bin
   }
 }
 
+// src/ripf.C:337-673: additionally reads TD vars 1, 2 (src/ripf.C:470-471) and RT var 2 (:477-478)
+void assemble_ripf(EquationSystems& es, const std::string& system_name) {
+  TransientLinearImplicitSystem& system = es.get_system<TransientLinearImplicitSystem>(system_name);
+  libmesh_assert_equal_to(system.n_vars(), 3);
+  const System& TD = es.get_system<System>("RIPF-TimeDeriv");
+  const System& RT = es.get_system<ExplicitSystem>("RT");
+  Binding& B = bind(es, system_name, 3);
+  const rdc_ripf_params p = marshal::read<rdc_ripf_params>(es.parameters);   // src/ripf.C:377-408
+  std::vector<double> aux(3 * B.local_to_global_node.size());
+  gather_nodal(es, TD, B, 1, 2, 3, 0, aux);   // cc, fb time derivatives -> aux[.][0], aux[.][1]
+  gather_nodal(es, RT, B, 2, 1, 3, 2, aux);   // total dose -> aux[.][2]
+  upload_old_solution(es, system, B, 3);
+  check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_AUX_NODAL, aux.data(), (int64_t)aux.size()), "rdc_field_upload(aux)");
+  check(B.ctx, rdc_assemble_ripf(B.ctx, &p), "rdc_assemble_ripf");
+  hand_back(es, system, B, 3);
+}
+
 // src/adpm.C:324-652: unknowns PrP, A_b, Tau; the elemental "Tracts" system (3 CONSTANT MONOMIAL variables, :448-453)
 // becomes RDC_FIELD_ELEM_TRACTS; decay/PrP is scaled with system.time (:367-413)
 void assemble_adpm(EquationSystems& es, const std::string& system_name) {
@@ -350,26 +306,7 @@ void assemble_adpm(EquationSystems& es, const std::string& system_name) {
   libmesh_assert_equal_to(system.n_vars(), 3);
   const System& tracts = es.get_system<System>("Tracts");
   Binding& B = bind(es, system_name, 3);
-  auto R = [&](const std::string& k) { return es.parameters.get<Real>(k); };
-  rdc_adpm_params p;
-  p.time_step = R("time_step");
-  p.time = system.time;
-  p.decay_PrP_time_exponent = R("decay/PrP/time_exponent");
-  auto triple = [&](double* d, const std::string& key, const char* kind) {
-    d[0] = R(key); d[1] = R(key + "/" + kind + "/0"); d[2] = R(key + "/" + kind + "/1");
-  };
-  auto trapezoid = [&](double* d, const std::string& key) {
-    d[0] = R(key);
-    for (int i = 0; i < 4; i++) d[1 + i] = R(key + "/trapezoid/" + std::to_string(i));
-  };
-  triple(p.decay_PrP, "decay/PrP", "pulse");
-  trapezoid(p.transform_A_b, "transform/A_b"); trapezoid(p.transform_Tau, "transform/Tau");
-  triple(p.diffuse_A_b, "diffuse/A_b", "pulse"); triple(p.taxis1_A_b, "taxis_1/A_b", "pulse"); triple(p.taxis2_A_b, "taxis_2/A_b", "pulse");
-  triple(p.produce_A_b, "produce/A_b", "sigmoid"); triple(p.decay_A_b, "decay/A_b", "pulse");
-  triple(p.diffuse_Tau, "diffuse/Tau", "pulse"); triple(p.taxis1_Tau, "taxis_1/Tau", "pulse"); triple(p.taxis2_Tau, "taxis_2/Tau", "pulse");
-  triple(p.produce_Tau, "produce/Tau", "sigmoid"); triple(p.decay_Tau, "decay/Tau", "pulse");
-  p.taxis_A_b_angle = R("taxis/A_b/angle");   // already radians in es.parameters (src/adpm.C:193)
-  p.taxis_Tau_angle = R("taxis/Tau/angle");
+  const rdc_adpm_params p = marshal::read_adpm(es.parameters, system.time);   // the angles are radians already in es.parameters (src/adpm.C:193)
   // per-element tract vectors in the binding's element order
   const MeshBase& mesh = es.get_mesh();
   std::vector<double> tr(3 * B.elem_ids.size());
@@ -377,10 +314,9 @@ void assemble_adpm(EquationSystems& es, const std::string& system_name) {
     const Elem& elem = mesh.elem_ref(B.elem_ids[e]);
     for (unsigned int d = 0; d < 3; d++) tr[3 * e + d] = tracts.current_solution(elem.dof_number(tracts.number(), d, 0));
   }
-  gather_old_solution(es, system, B, 3);
-  if (rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload");
-  if (rdc_field_upload(B.ctx, RDC_FIELD_ELEM_TRACTS, tr.data(), (int64_t)tr.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload(tracts)");
-  if (rdc_assemble_adpm(B.ctx, &p) != RDC_OK) fail(B.ctx, "rdc_assemble_adpm");
+  upload_old_solution(es, system, B, 3);
+  check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_ELEM_TRACTS, tr.data(), (int64_t)tr.size()), "rdc_field_upload(tracts)");
+  check(B.ctx, rdc_assemble_adpm(B.ctx, &p), "rdc_assemble_adpm");
   hand_back(es, system, B, 3);
 }
 
@@ -391,27 +327,12 @@ void assemble_proteas_model(EquationSystems& es, const std::string& system_name)
   libmesh_assert_equal_to(system.n_vars(), 5);
   const System& AUX = es.get_system<System>("AUX");
   Binding& B = bind(es, system_name, 5);
-  auto R = [&](const char* k) { return es.parameters.get<Real>(k); };
-  rdc_proteas_params p;   // src/proteas.C:376-409
-  p.time_step = R("time_step");
-  p.cells_total_capacity = R("cells/total_capacity"); p.RT_max_dosage = R("radiotherapy/max_dosage");
-  p.host_proliferation = R("host/proliferation"); p.host_vsc_threshold = R("host/vsc_threshold");
-  p.host_RT_death_rate = R("host/RT_death_rate"); p.host_RT_exp_a = R("host/RT_exp_a"); p.host_RT_exp_b = R("host/RT_exp_b");
-  p.host_necrosis_rate = R("host/necrosis_rate");
-  p.tumour_diffusion = R("tumour/diffusion"); p.tumour_diffusion_host = R("tumour/diffusion_host");
-  p.tumour_proliferation = R("tumour/proliferation"); p.tumour_vsc_threshold = R("tumour/vsc_threshold");
-  p.tumour_RT_death_rate = R("tumour/RT_death_rate"); p.tumour_RT_exp_a = R("tumour/RT_exp_a"); p.tumour_RT_exp_b = R("tumour/RT_exp_b");
-  p.tumour_necrosis_rate = R("tumour/necrosis_rate");
-  p.necrosis_clearance = R("necrosis/clearance"); p.necrosis_slope = R("necrosis/slope"); p.necrosis_vsc_threshold = R("necrosis/vsc_threshold");
-  p.vascular_proliferation = R("vascular/proliferation"); p.vascular_necrosis_rate = R("vascular/necrosis_rate");
-  p.oedema_diffusion = R("oedema/diffusion"); p.oedema_proliferation = R("oedema/proliferation"); p.oedema_vsc_threshold = R("oedema/vsc_threshold");
-  p.oedema_RT_coeff = R("oedema/RT_coeff"); p.oedema_RT_exp = R("oedema/RT_exp"); p.oedema_reabsorption_rate = R("oedema/reabsorption_rate");
+  const rdc_proteas_params p = marshal::read<rdc_proteas_params>(es.parameters);   // src/proteas.C:376-409
   std::vector<double> aux(3 * B.local_to_global_node.size(), 0.0);
   gather_nodal(es, AUX, B, 0, 2, 3, 0, aux);
-  gather_old_solution(es, system, B, 5);
-  if (rdc_field_upload(B.ctx, RDC_FIELD_OLD_SOLUTION, B.u_old.data(), (int64_t)B.u_old.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload");
-  if (rdc_field_upload(B.ctx, RDC_FIELD_AUX_NODAL, aux.data(), (int64_t)aux.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload(aux)");
-  if (rdc_assemble_proteas(B.ctx, &p) != RDC_OK) fail(B.ctx, "rdc_assemble_proteas");
+  upload_old_solution(es, system, B, 5);
+  check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_AUX_NODAL, aux.data(), (int64_t)aux.size()), "rdc_field_upload(aux)");
+  check(B.ctx, rdc_assemble_proteas(B.ctx, &p), "rdc_assemble_proteas");
   hand_back(es, system, B, 5);
 }
 
@@ -433,46 +354,22 @@ class SolidSystemGPU : public SolidSystem {
     const System& aux = es.get_system<System>("SolidSystem::auxiliary");
     const System& fibre = es.get_system<System>("SolidSystem::fibre");
     const size_t nn = B.local_to_global_node.size(), ne = B.elem_ids.size();
-    if (!solid_bound_) {   // what does not change between Newton iterations
-      // subdomain -> material table ("material/<id>/Hyperelastic/...", src/solid_system.C:183-190)
-      std::map<subdomain_id_type, int32_t> index;
-      std::vector<rdc_solid_material> table;
-      std::vector<int32_t> em(ne);
-      for (size_t e = 0; e < ne; e++) {
-        const subdomain_id_type id = mesh.elem_ref(B.elem_ids[e]).subdomain_id();
-        auto it = index.find(id);
-        if (it == index.end()) {
-          const std::string k = "material/" + std::to_string(id) + "/Hyperelastic/";
-          rdc_solid_material m;
-          m.Young = es.parameters.get<Real>(k + "Young"); m.Poisson = es.parameters.get<Real>(k + "Poisson");
-          m.FibreStiffness = es.parameters.get<Real>(k + "FibreStiffness");
-          for (int d = 0; d < 3; d++) m.rate[d] = es.parameters.get<Real>(k + "VolumetricStretchRatio/rate_" + std::to_string(d));
-          it = index.emplace(id, (int32_t)table.size()).first;
-          table.push_back(m);
-        }
-        em[e] = it->second;
-      }
-      if (rdc_solid_set_materials(B.ctx, em.data(), (int32_t)table.size(), table.data()) != RDC_OK) fail(B.ctx, "rdc_solid_set_materials");
+    if (!B.solid_bound) {   // what does not change between Newton iterations
+      // subdomain -> material table ("material/<id>/...", src/solid_system.C:183-190)
+      const marshal::MaterialTable mt = marshal::material_table(es.parameters, (int64_t)ne, [&](int64_t e) { return mesh.elem_ref(B.elem_ids[(size_t)e]).subdomain_id(); });
+      check(B.ctx, rdc_solid_set_materials(B.ctx, mt.elem_material.data(), (int32_t)mt.table.size(), mt.table.data()), "rdc_solid_set_materials");
       // boundary sides whose id is in "BCs" (src/solid_system.C:294-306) of EVERY element of the binding, ghost layer
       // included: the library adds a side's penalty terms only into rows of nodes this rank owns, so each rank ends up
       // with the complete rows of its nodes (a side next to the partition boundary is listed on both ranks)
-      const std::set<int> bcs = export_integers(es.parameters.get<std::string>("BCs"));
-      std::vector<int64_t> se;
-      std::vector<int32_t> si;
-      std::vector<double> sd;
-      for (int bc : bcs) {
-        const Point u = es.parameters.get<Point>("BC/" + std::to_string(bc) + "/displacement");
+      const marshal::SideList sl = marshal::side_list<Point>(es.parameters, [&](int bc, auto&& emit) {
         for (size_t e = 0; e < ne; e++) {
           const Elem& elem = mesh.elem_ref(B.elem_ids[e]);
           for (auto s : elem.side_index_range())
-            if (mesh.get_boundary_info().has_boundary_id(&elem, s, cast_int<boundary_id_type>(bc))) {
-              se.push_back((int64_t)e); si.push_back((int32_t)s);
-              for (int d = 0; d < 3; d++) sd.push_back(u(d));
-            }
+            if (mesh.get_boundary_info().has_boundary_id(&elem, s, cast_int<boundary_id_type>(bc))) emit((int64_t)e, (int32_t)s);
         }
-      }
-      if (rdc_solid_set_sides(B.ctx, (int64_t)se.size(), se.data(), si.data(), sd.data()) != RDC_OK) fail(B.ctx, "rdc_solid_set_sides");
-      solid_bound_ = true;
+      });
+      check(B.ctx, rdc_solid_set_sides(B.ctx, (int64_t)sl.elem.size(), sl.elem.data(), sl.side.data(), sl.displacement.data()), "rdc_solid_set_sides");
+      B.solid_bound = true;
     }
     // current node positions = the unknowns of the current Newton iterate (FEMContext::pre_fe_reinit moves the element's
     // nodes there); undeformed positions; reference fibre
@@ -488,16 +385,12 @@ class SolidSystemGPU : public SolidSystem {
       const Elem& elem = mesh.elem_ref(B.elem_ids[e]);
       for (unsigned int d = 0; d < 3; d++) eta[3 * e + d] = fibre.current_solution(elem.dof_number(fibre.number(), d, 0));   // :204-216
     }
-    if (rdc_mesh_update_coords(B.ctx, x.data()) != RDC_OK) fail(B.ctx, "rdc_mesh_update_coords");
-    if (rdc_field_upload(B.ctx, RDC_FIELD_UNDEFORMED_XYZ, X.data(), (int64_t)X.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload(undeformed)");
-    if (rdc_field_upload(B.ctx, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()) != RDC_OK) fail(B.ctx, "rdc_field_upload(fibre)");
-    rdc_solid_params p;
-    p.pseudo_time = es.parameters.get<Real>("pseudo_time");
-    p.displacement_penalty = es.parameters.get<Real>("BCs/displacement_penalty");
-    p.use_symmetry = es.parameters.get<bool>("solver/assembly_use_symmetry") ? 1 : 0;
-    p._pad = 0;
-    if (rdc_solid_assemble(B.ctx, &p, get_jacobian ? 1 : 0) != RDC_OK) fail(B.ctx, "rdc_solid_assemble");
-    if (rdc_csr_download(B.ctx, get_jacobian ? B.val.data() : nullptr, B.rhs.data()) != RDC_OK) fail(B.ctx, "rdc_csr_download");
+    check(B.ctx, rdc_mesh_update_coords(B.ctx, x.data()), "rdc_mesh_update_coords");
+    check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_UNDEFORMED_XYZ, X.data(), (int64_t)X.size()), "rdc_field_upload(undeformed)");
+    check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()), "rdc_field_upload(fibre)");
+    const rdc_solid_params p = marshal::solid_params(es.parameters);
+    check(B.ctx, rdc_solid_assemble(B.ctx, &p, get_jacobian ? 1 : 0), "rdc_solid_assemble");
+    check(B.ctx, rdc_csr_download(B.ctx, get_jacobian ? B.val.data() : nullptr, B.rhs.data()), "rdc_csr_download");
     // owned rows -> system.matrix / system.rhs (FEMSystem::assembly zeroes them first; complete rows: no stash traffic)
     if (get_residual) this->rhs->zero();
     if (get_jacobian) this->matrix->zero();
@@ -514,9 +407,6 @@ class SolidSystemGPU : public SolidSystem {
     if (get_residual) this->rhs->close();
     if (get_jacobian) this->matrix->close();
   }
-
- private:
-  bool solid_bound_ = false;
 };
 
 }  // namespace rdc_gpu

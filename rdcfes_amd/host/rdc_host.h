@@ -11,11 +11,14 @@
 // time loop touch (EquationSystems::parameters / get_system / get_mesh, System::n_vars,
 // TransientLinearImplicitSystem::{old_local_solution, matrix, rhs, attach_assemble_function}).
 // A libMesh build uses integration/libmesh_adapter.C instead, which binds the same C-ABI calls to
-// the real libMesh objects.
+// the real libMesh objects.  What the two have in common and that names no libMesh
+// type -- parameter key -> struct field, the solid system's material table and side list, the error
+// path, the pipelined hand-back with its pinning -- is include/rdc_marshal.h, used by both; the mirror's
+// own part is the mock types and, per callback, which arrays go to which C-ABI call.
 //
 // Header-only, C++17, depends only on the C-ABI.  Errors: the reference aborts through
 // libmesh_error(); here every failing C-ABI status becomes a std::runtime_error carrying
-// rdc_last_error().
+// rdc_last_error() (marshal::check).
 #ifndef RDC_HOST_H
 #define RDC_HOST_H
 
@@ -26,12 +29,11 @@
 #include <stdexcept>
 #include <ostream>
 #include <set>
-#include <sstream>
 #include <string>
 #include <variant>
 #include <vector>
 
-#include "../../include/rdc_assembly.h"
+#include "../../include/rdc_marshal.h"
 
 namespace rdc {
 namespace host {
@@ -40,9 +42,8 @@ using Real = double;
 using Number = double;
 using dof_id_type = uint32_t;
 
-inline void check(rdc_ctx* c, int rc, const char* what) {
-  if (rc != RDC_OK) throw std::runtime_error(std::string(what) + ": " + rdc_last_error(c));
-}
+using marshal::check;
+using marshal::export_integers;   // src/utils.h:268-288
 
 // libMesh::Point as far as the parameters need it ("BC/<id>/displacement", src/solid.C:246-256)
 struct Point {
@@ -52,18 +53,6 @@ struct Point {
   double& operator()(int d) { return c[d]; }
   double operator()(int d) const { return c[d]; }
 };
-
-// src/utils.h:268-288: the integers of a blank-separated string ("BCs", "materials", "loading_time_points")
-inline std::set<int> export_integers(const std::string& s) {
-  std::set<int> numbers;
-  std::stringstream ss(s);
-  std::string tmp;
-  while (ss >> tmp) {
-    int n;
-    if (std::stringstream(tmp) >> n) numbers.insert(n);
-  }
-  return numbers;
-}
 
 // ---- libMesh::Parameters (string-keyed, typed) ------------------------------------------------
 class Parameters {
@@ -253,7 +242,7 @@ class TransientLinearImplicitSystem : public ImplicitSystem {
 class EquationSystems {
  public:
   explicit EquationSystems(Mesh& mesh, int device = 0) : mesh_(mesh), device_(device) {}
-  ~EquationSystems() { for (auto& kv : ctx_) rdc_ctx_destroy(kv.second); }
+  ~EquationSystems() { for (auto& kv : ctx_) { kv.second.pins.release(kv.second.ctx); rdc_ctx_destroy(kv.second.ctx); } }
   EquationSystems(const EquationSystems&) = delete;
   Parameters parameters;
   Mesh& get_mesh() { return mesh_; }
@@ -291,20 +280,22 @@ class EquationSystems {
   // one assembly context (GPU-resident mesh + pattern) per implicit system
   rdc_ctx* context(const std::string& system, int nvar) {
     auto it = ctx_.find(system);
-    if (it != ctx_.end()) return it->second;
+    if (it != ctx_.end()) return it->second.ctx;
     rdc_ctx* c = nullptr;
-    int rc = rdc_ctx_create(device_, &c);
-    if (rc != RDC_OK) throw std::runtime_error(std::string("rdc_ctx_create: ") + rdc_last_error(nullptr));
-    ctx_[system] = c;
+    check(nullptr, rdc_ctx_create(device_, &c), "rdc_ctx_create");
+    ctx_[system].ctx = c;
     check(c, rdc_mesh_upload(c, mesh_.elem_type(), mesh_.n_elem(), mesh_.n_nodes(), mesh_.n_nodes(),
                              mesh_.connectivity().data(), mesh_.coordinates().data(), nvar), "rdc_mesh_upload");
     return c;
   }
+  // which host arrays of the system are registered for its context's chunked hand-back: once, released with the context
+  marshal::PinState& handback_pins(const std::string& system) { return ctx_.at(system).pins; }
  private:
+  struct Context { rdc_ctx* ctx = nullptr; marshal::PinState pins; };
   Mesh& mesh_;
   int device_;
   std::map<std::string, std::unique_ptr<System>> systems_;
-  std::map<std::string, rdc_ctx*> ctx_;
+  std::map<std::string, Context> ctx_;
 };
 
 inline int bicgstab_ilu0(const SparseMatrix& A, const std::vector<double>& b, std::vector<double>& x, Real tol, int max_its) {
@@ -394,29 +385,8 @@ inline int TransientLinearImplicitSystem::solve(Real tol, int max_its) {
 // ---- the drop-in callbacks: same signature as the reference's static assemble_* -----------------
 namespace detail {
 // Hand-back of the assembled owned rows (what add_matrix / add_vector did element by element, src/pihna.C:754-755).
-// "rdc/handback_chunks" > 1 (es.parameters, int) selects the pipelined form the libMesh adapter uses (push_results_chunked in
-// integration/libmesh_adapter.C): the node range is cut into chunks, two chunk downloads are kept in flight on the context's
-// copy stream, and every chunk is consumed (there: one MatSetValues per node block; here: `consume`) while the next travels.
-template <class Consume>
-inline void pull_results_chunked(rdc_ctx* c, TransientLinearImplicitSystem& sys, int n_chunks, Consume&& consume) {
-  std::vector<double>& val = sys.matrix_storage.val;
-  std::vector<double>& rhs = sys.rhs_storage.raw();
-  const int64_t nv = (int64_t)sys.n_vars();
-  const int64_t n_nodes = (int64_t)rhs.size() / nv;
-  check(c, rdc_host_pin(c, val.data(), val.size() * sizeof(double)), "rdc_host_pin");
-  check(c, rdc_host_pin(c, rhs.data(), rhs.size() * sizeof(double)), "rdc_host_pin");
-  auto bound = [&](int k) { return n_nodes * k / n_chunks; };
-  int ticket[2] = {-1, -1};
-  check(c, rdc_csr_download_rows_async(c, bound(0), bound(1), val.data(), rhs.data(), &ticket[0]), "rdc_csr_download_rows_async");
-  for (int k = 0; k < n_chunks; k++) {
-    if (k + 1 < n_chunks)
-      check(c, rdc_csr_download_rows_async(c, bound(k + 1), bound(k + 2), val.data(), rhs.data(), &ticket[(k + 1) & 1]), "rdc_csr_download_rows_async");
-    check(c, rdc_ticket_wait(c, ticket[k & 1]), "rdc_ticket_wait");
-    consume(bound(k), bound(k + 1));     // rows of nodes [bound(k), bound(k + 1)) are in host memory
-  }
-  check(c, rdc_host_unpin(c, val.data()), "rdc_host_unpin");
-  check(c, rdc_host_unpin(c, rhs.data()), "rdc_host_unpin");
-}
+// "rdc/handback_chunks" > 1 (es.parameters, int) selects the pipelined form, marshal::hand_back_chunked, which the libMesh
+// adapter uses by default: there the consumer is one MatSetValues per node block, here it records what it was handed.
 inline void pull_results(rdc_ctx* c, TransientLinearImplicitSystem& sys) {
   const Parameters& P = sys.get_equation_systems().parameters;
   const int chunks = P.have_parameter<int>("rdc/handback_chunks") ? P.get<int>("rdc/handback_chunks") : 1;
@@ -424,33 +394,22 @@ inline void pull_results(rdc_ctx* c, TransientLinearImplicitSystem& sys) {
     // the mirror's matrix IS the destination array: the consumer only records which rows it was handed, in which order
     std::vector<int64_t>& log = sys.handback_log;
     log.clear();
-    pull_results_chunked(c, sys, chunks, [&](int64_t n0, int64_t n1) { log.push_back(n0); log.push_back(n1); });
+    std::vector<double>& val = sys.matrix_storage.val;
+    std::vector<double>& rhs = sys.rhs_storage.raw();
+    marshal::hand_back_chunked(c, (int64_t)rhs.size() / sys.n_vars(), chunks, val.data(), val.size(), rhs.data(), rhs.size(),
+                               sys.get_equation_systems().handback_pins(sys.name()),
+                               [&](int64_t n0, int64_t n1) { log.push_back(n0); log.push_back(n1); });
     return;
   }
   check(c, rdc_csr_download(c, sys.matrix_storage.val.data(), sys.rhs_storage.raw().data()), "rdc_csr_download");
 }
-inline Real getR(const Parameters& p, const char* k) { return p.get<Real>(k); }
 }  // namespace detail
 
 // src/pihna.C:318-758
 inline void assemble_pihna(EquationSystems& es, const std::string& system_name) {
   auto& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   if (system.n_vars() != 5) throw std::runtime_error("assemble_pihna: system must have 5 variables (n,c,h,v,a)");
-  const Parameters& P = es.parameters;
-  rdc_pihna_params p;
-  p.time_step = detail::getR(P, "time_step");
-  p.cells_min_capacity = detail::getR(P, "cells_min_capacity");
-  p.cells_max_capacity = detail::getR(P, "cells_max_capacity");
-  p.cytokines_max_capacity = detail::getR(P, "cytokines_max_capacity");
-  p.cells_max_capacity_exponent = detail::getR(P, "cells_max_capacity/exponent");
-  p.necrosis_c = detail::getR(P, "necrosis/c"); p.necrosis_h = detail::getR(P, "necrosis/h"); p.necrosis_v = detail::getR(P, "necrosis/v");
-  p.diffuse_c = detail::getR(P, "diffuse/c"); p.taxis_c = detail::getR(P, "taxis/c");
-  p.diffuse_h = detail::getR(P, "diffuse/h"); p.taxis_h = detail::getR(P, "taxis/h");
-  p.produce_c = detail::getR(P, "produce/c");
-  p.switch_c2h = detail::getR(P, "switch/c/to/h"); p.switch_h2c = detail::getR(P, "switch/h/to/c"); p.switch_h2n = detail::getR(P, "switch/h/to/n");
-  p.diffuse_v = detail::getR(P, "diffuse/v"); p.taxis_v = detail::getR(P, "taxis/v"); p.produce_v = detail::getR(P, "produce/v");
-  p.secrete_a_c = detail::getR(P, "secrete/a/from/c"); p.secrete_a_h = detail::getR(P, "secrete/a/from/h");
-  p.uptake_a_v = detail::getR(P, "uptake/a/from/v"); p.decay_a = detail::getR(P, "decay/a");
+  const rdc_pihna_params p = marshal::read<rdc_pihna_params>(es.parameters);
   rdc_ctx* c = es.context(system_name, 5);
   check(c, rdc_field_upload(c, RDC_FIELD_OLD_SOLUTION, system.old_local_solution.raw().data(), system.old_local_solution.size()), "old solution");
   check(c, rdc_assemble_pihna(c, &p), "rdc_assemble_pihna");
@@ -463,22 +422,7 @@ inline void assemble_ripf(EquationSystems& es, const std::string& system_name) {
   if (system.n_vars() != 3) throw std::runtime_error("assemble_ripf: system must have 3 variables (HU,cc,fb)");
   System& TD = es.get_system<System>("RIPF-TimeDeriv");
   System& RT = es.get_system<System>("RT");
-  const Parameters& P = es.parameters;
-  rdc_ripf_params p{};
-  p.time_step = detail::getR(P, "time_step");
-  p.VolFr_stroma = detail::getR(P, "volume_fraction/stroma"); p.VolFr_parenchyma = detail::getR(P, "volume_fraction/parenchyma");
-  p.VolFr_exponent = detail::getR(P, "volume_fraction/exponent"); p.VolFr_min_vacant = detail::getR(P, "volume_fraction/min_vacant");
-  p.VolFr_max_vacant = detail::getR(P, "volume_fraction/max_vacant");
-  p.phi_cc_B = detail::getR(P, "HU/phi/cc/build"); p.phi_cc_D = detail::getR(P, "HU/phi/cc/decay"); p.phi_cc = detail::getR(P, "HU/phi/cc/rate");
-  p.phi_fb_B = detail::getR(P, "HU/phi/fb/build"); p.phi_fb_D = detail::getR(P, "HU/phi/fb/decay"); p.phi_fb = detail::getR(P, "HU/phi/fb/rate");
-  p.phi_tol = detail::getR(P, "HU/phi/tolerance");
-  p.kappa = detail::getR(P, "cc/kappa"); p.kappa_RT_c = detail::getR(P, "cc/kappa/RT/c");
-  p.delta = detail::getR(P, "cc/delta"); p.delta_RT_a = detail::getR(P, "cc/delta/RT/a"); p.delta_RT_b = detail::getR(P, "cc/delta/RT/b");
-  p.lambda = detail::getR(P, "fb/lambda"); p.lambda_RT_r = detail::getR(P, "fb/lambda/RT/r"); p.lambda_HU_r = detail::getR(P, "fb/lambda/HU/r");
-  p.omicro = detail::getR(P, "fb/omicro"); p.omicro_RT_r = detail::getR(P, "fb/omicro/RT/r"); p.omicro_fb_b = detail::getR(P, "fb/omicro/fb/b");
-  p.omega = detail::getR(P, "fb/omega"); p.diffusion = detail::getR(P, "fb/diffusion");
-  p.haptotaxis = detail::getR(P, "fb/haptotaxis"); p.radiotaxis = detail::getR(P, "fb/radiotaxis");
-  p.RT_dose_total_max = P.get<int>("RT_dose/total/max");
+  const rdc_ripf_params p = marshal::read<rdc_ripf_params>(es.parameters);
   const int64_t nn = es.get_mesh().n_nodes();
   std::vector<double> aux((size_t)nn * 3);
   for (int64_t n = 0; n < nn; n++) {
@@ -497,14 +441,7 @@ inline void assemble_ripf(EquationSystems& es, const std::string& system_name) {
 inline void assemble_hcc(EquationSystems& es, const std::string& system_name) {
   auto& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   if (system.n_vars() != 3) throw std::runtime_error("assemble_hcc: system must have 3 variables (l,c,n)");
-  const Parameters& P = es.parameters;
-  rdc_hcc_params p{};
-  p.time_step = detail::getR(P, "time_step");
-  p.cells_min_capacity = detail::getR(P, "cells/min_capacity"); p.cells_max_capacity = detail::getR(P, "cells/max_capacity");
-  p.cells_max_capacity_exponent = detail::getR(P, "cells/max_capacity/exponent");
-  p.produce_l = detail::getR(P, "produce/l");
-  p.diffuse_c = detail::getR(P, "diffuse/c"); p.mechano_c = detail::getR(P, "mechano/c"); p.produce_c = detail::getR(P, "produce/c");
-  p.necrosis_l = detail::getR(P, "necrosis/l"); p.necrosis_c = detail::getR(P, "necrosis/c"); p.necrosis_pressure = detail::getR(P, "necrosis/pressure");
+  const rdc_hcc_params p = marshal::read<rdc_hcc_params>(es.parameters);
   rdc_ctx* c = es.context(system_name, 3);
   check(c, rdc_mesh_update_coords(c, es.get_mesh().coordinates().data()), "rdc_mesh_update_coords");
   check(c, rdc_field_upload(c, RDC_FIELD_OLD_SOLUTION, system.old_local_solution.raw().data(), system.old_local_solution.size()), "old solution");
@@ -517,28 +454,7 @@ inline void assemble_adpm(EquationSystems& es, const std::string& system_name) {
   auto& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   if (system.n_vars() != 3) throw std::runtime_error("assemble_adpm: system must have 3 variables (PrP,A_b,Tau)");
   System& tracts = es.get_system<System>("Tracts");
-  const Parameters& P = es.parameters;
-  rdc_adpm_params p{};
-  p.time_step = detail::getR(P, "time_step");
-  p.time = system.time;
-  p.decay_PrP_time_exponent = detail::getR(P, "decay/PrP/time_exponent");
-  auto triple = [&](double* dst, const std::string& key, const char* kind) {
-    dst[0] = detail::getR(P, key.c_str());
-    dst[1] = detail::getR(P, (key + "/" + kind + "/0").c_str());
-    dst[2] = detail::getR(P, (key + "/" + kind + "/1").c_str());
-  };
-  auto trapezoid = [&](double* dst, const std::string& key) {
-    dst[0] = detail::getR(P, key.c_str());
-    for (int i = 0; i < 4; i++) dst[1 + i] = detail::getR(P, (key + "/trapezoid/" + std::to_string(i)).c_str());
-  };
-  triple(p.decay_PrP, "decay/PrP", "pulse");
-  trapezoid(p.transform_A_b, "transform/A_b"); trapezoid(p.transform_Tau, "transform/Tau");
-  triple(p.diffuse_A_b, "diffuse/A_b", "pulse"); triple(p.taxis1_A_b, "taxis_1/A_b", "pulse"); triple(p.taxis2_A_b, "taxis_2/A_b", "pulse");
-  triple(p.produce_A_b, "produce/A_b", "sigmoid"); triple(p.decay_A_b, "decay/A_b", "pulse");
-  triple(p.diffuse_Tau, "diffuse/Tau", "pulse"); triple(p.taxis1_Tau, "taxis_1/Tau", "pulse"); triple(p.taxis2_Tau, "taxis_2/Tau", "pulse");
-  triple(p.produce_Tau, "produce/Tau", "sigmoid"); triple(p.decay_Tau, "decay/Tau", "pulse");
-  p.taxis_A_b_angle = detail::getR(P, "taxis/A_b/angle");  // radians: input() stores degrees_to_radians(...), src/adpm.C:193
-  p.taxis_Tau_angle = detail::getR(P, "taxis/Tau/angle");
+  const rdc_adpm_params p = marshal::read_adpm(es.parameters, system.time);   // the angles are radians there: input() converts, src/adpm.C:193
   rdc_ctx* c = es.context(system_name, 3);
   check(c, rdc_field_upload(c, RDC_FIELD_OLD_SOLUTION, system.old_local_solution.raw().data(), system.old_local_solution.size()), "old solution");
   check(c, rdc_field_upload(c, RDC_FIELD_ELEM_TRACTS, tracts.solution.raw().data(), tracts.solution.size()), "tracts");
@@ -551,23 +467,7 @@ inline void assemble_proteas_model(EquationSystems& es, const std::string& syste
   auto& system = es.get_system<TransientLinearImplicitSystem>(system_name);
   if (system.n_vars() != 5) throw std::runtime_error("assemble_proteas_model: system must have 5 variables");
   System& AUX = es.get_system<System>("AUX");
-  const Parameters& P = es.parameters;
-  rdc_proteas_params p{};
-  p.time_step = detail::getR(P, "time_step");
-  p.cells_total_capacity = detail::getR(P, "cells/total_capacity"); p.RT_max_dosage = detail::getR(P, "radiotherapy/max_dosage");
-  p.host_proliferation = detail::getR(P, "host/proliferation"); p.host_vsc_threshold = detail::getR(P, "host/vsc_threshold");
-  p.host_RT_death_rate = detail::getR(P, "host/RT_death_rate"); p.host_RT_exp_a = detail::getR(P, "host/RT_exp_a");
-  p.host_RT_exp_b = detail::getR(P, "host/RT_exp_b"); p.host_necrosis_rate = detail::getR(P, "host/necrosis_rate");
-  p.tumour_diffusion = detail::getR(P, "tumour/diffusion"); p.tumour_diffusion_host = detail::getR(P, "tumour/diffusion_host");
-  p.tumour_proliferation = detail::getR(P, "tumour/proliferation"); p.tumour_vsc_threshold = detail::getR(P, "tumour/vsc_threshold");
-  p.tumour_RT_death_rate = detail::getR(P, "tumour/RT_death_rate"); p.tumour_RT_exp_a = detail::getR(P, "tumour/RT_exp_a");
-  p.tumour_RT_exp_b = detail::getR(P, "tumour/RT_exp_b"); p.tumour_necrosis_rate = detail::getR(P, "tumour/necrosis_rate");
-  p.necrosis_clearance = detail::getR(P, "necrosis/clearance"); p.necrosis_slope = detail::getR(P, "necrosis/slope");
-  p.necrosis_vsc_threshold = detail::getR(P, "necrosis/vsc_threshold");
-  p.vascular_proliferation = detail::getR(P, "vascular/proliferation"); p.vascular_necrosis_rate = detail::getR(P, "vascular/necrosis_rate");
-  p.oedema_diffusion = detail::getR(P, "oedema/diffusion"); p.oedema_proliferation = detail::getR(P, "oedema/proliferation");
-  p.oedema_vsc_threshold = detail::getR(P, "oedema/vsc_threshold"); p.oedema_RT_coeff = detail::getR(P, "oedema/RT_coeff");
-  p.oedema_RT_exp = detail::getR(P, "oedema/RT_exp"); p.oedema_reabsorption_rate = detail::getR(P, "oedema/reabsorption_rate");
+  const rdc_proteas_params p = marshal::read<rdc_proteas_params>(es.parameters);
   const int64_t nn = es.get_mesh().n_nodes();
   std::vector<double> aux((size_t)nn * 3, 0.0);
   for (int64_t n = 0; n < nn; n++) {
@@ -596,13 +496,7 @@ inline void check_solution(EquationSystems& es, const std::string& system_name) 
 // thresholded element-volume sums, which the device computes from the current solution; header at time 0
 inline void save_solution_pihna(std::ostream& csv, EquationSystems& es) {
   auto& system = es.get_system<TransientLinearImplicitSystem>("PIHNA");
-  const Parameters& P = es.parameters;
-  rdc_pihna_ranges r;
-  r.active_tumor_min = detail::getR(P, "range/active_tumor/min"); r.active_tumor_max = detail::getR(P, "range/active_tumor/max");
-  r.necrotic_min = detail::getR(P, "range/necrotic/min"); r.necrotic_max = detail::getR(P, "range/necrotic/max");
-  r.vascularity_min = detail::getR(P, "range/vascularity/min"); r.vascularity_max = detail::getR(P, "range/vascularity/max");
-  r.total_cell_min = detail::getR(P, "range/total_cell/min"); r.total_cell_max = detail::getR(P, "range/total_cell/max");
-  r.cells_max_capacity = detail::getR(P, "cells_max_capacity");
+  const rdc_pihna_ranges r = marshal::read<rdc_pihna_ranges>(es.parameters);
   rdc_ctx* c = es.context("PIHNA", 5);
   double v[4];
   check(c, rdc_field_upload(c, RDC_FIELD_OLD_SOLUTION, system.solution.raw().data(), system.solution.size()), "solution");
@@ -615,10 +509,7 @@ inline void save_solution_pihna(std::ostream& csv, EquationSystems& es) {
 // save_solution of RIPF (src/ripf.C:777-866): time, tumour volume, fibrosis volume (upstream writes no header)
 inline void save_solution_ripf(std::ostream& csv, EquationSystems& es) {
   auto& system = es.get_system<TransientLinearImplicitSystem>("RIPF");
-  const Parameters& P = es.parameters;
-  rdc_ripf_ranges r;
-  r.cc_HU_min = detail::getR(P, "range_cc/HU/min"); r.cc_HU_max = detail::getR(P, "range_cc/HU/max"); r.cc_min = detail::getR(P, "range_cc/min");
-  r.fb_HU_min = detail::getR(P, "range_fb/HU/min"); r.fb_HU_max = detail::getR(P, "range_fb/HU/max"); r.fb_min = detail::getR(P, "range_fb/min");
+  const rdc_ripf_ranges r = marshal::read<rdc_ripf_ranges>(es.parameters);
   rdc_ctx* c = es.context("RIPF", 3);
   double v[2];
   check(c, rdc_field_upload(c, RDC_FIELD_OLD_SOLUTION, system.solution.raw().data(), system.solution.size()), "solution");
@@ -715,43 +606,18 @@ inline void SolidSystem::bind(rdc_ctx* c) {
   const Parameters& P = es_.parameters;
   const Mesh& mesh = es_.get_mesh();
   // materials: one table entry per subdomain id present in the mesh (string-keyed lookups per element upstream)
-  std::map<int32_t, int32_t> index;
-  std::vector<rdc_solid_material> table;
-  std::vector<int32_t> elem_material((size_t)mesh.n_elem());
-  for (int64_t e = 0; e < mesh.n_elem(); e++) {
-    const int32_t id = mesh.subdomain_id(e);
-    auto it = index.find(id);
-    if (it == index.end()) {
-      const std::string k = "material/" + std::to_string(id) + "/Hyperelastic/";
-      rdc_solid_material m;
-      m.Young = P.get<Real>(k + "Young"); m.Poisson = P.get<Real>(k + "Poisson"); m.FibreStiffness = P.get<Real>(k + "FibreStiffness");
-      for (int d = 0; d < 3; d++) m.rate[d] = P.get<Real>(k + "VolumetricStretchRatio/rate_" + std::to_string(d));
-      it = index.emplace(id, (int32_t)table.size()).first;
-      table.push_back(m);
-    }
-    elem_material[(size_t)e] = it->second;
-  }
-  check(c, rdc_solid_set_materials(c, elem_material.data(), (int32_t)table.size(), table.data()), "rdc_solid_set_materials");
-  // sides: every boundary side whose id is in "BCs", with "BC/<id>/displacement" (NaN component = unconstrained)
-  const std::set<int> bcs = export_integers(P.get<std::string>("BCs"));
-  std::vector<int64_t> se;
-  std::vector<int32_t> si;
-  std::vector<double> sd;
-  for (int bc : bcs) {   // ascending id, then mesh order: the order FEMSystem::assembly meets them does not matter for a sum
-    const Point& u = P.get<Point>("BC/" + std::to_string(bc) + "/displacement");
-    for (const Mesh::BoundarySide& s : mesh.boundary_sides()) {
-      if (s.id != bc) continue;
-      se.push_back(s.elem); si.push_back(s.side);
-      for (int d = 0; d < 3; d++) sd.push_back(u(d));
-    }
-  }
-  check(c, rdc_solid_set_sides(c, (int64_t)se.size(), se.data(), si.data(), sd.data()), "rdc_solid_set_sides");
+  const marshal::MaterialTable mt = marshal::material_table(P, mesh.n_elem(), [&](int64_t e) { return mesh.subdomain_id(e); });
+  check(c, rdc_solid_set_materials(c, mt.elem_material.data(), (int32_t)mt.table.size(), mt.table.data()), "rdc_solid_set_materials");
+  // sides: ascending id, then mesh order: the order FEMSystem::assembly meets them does not matter for a sum
+  const marshal::SideList sl = marshal::side_list<Point>(P, [&](int bc, auto&& emit) {
+    for (const Mesh::BoundarySide& s : mesh.boundary_sides()) if (s.id == bc) emit(s.elem, s.side);
+  });
+  check(c, rdc_solid_set_sides(c, (int64_t)sl.elem.size(), sl.elem.data(), sl.side.data(), sl.displacement.data()), "rdc_solid_set_sides");
   bound_ = true;
 }
 
 inline void SolidSystem::assembly(bool get_residual, bool get_jacobian) {
   (void)get_residual;   // the residual always comes with the call, as in element_time_derivative
-  const Parameters& P = es_.parameters;
   rdc_ctx* c = es_.context(name_, 3);
   if (!bound_) bind(c);
   System& aux = es_.get_system<System>("SolidSystem::auxiliary");
@@ -765,10 +631,7 @@ inline void SolidSystem::assembly(bool get_residual, bool get_jacobian) {
   for (int64_t e = 0; e < ne; e++)
     for (int d = 0; d < 3; d++) eta[(size_t)e * 3 + d] = fibre.current_local_solution(e * nf + d);
   check(c, rdc_field_upload(c, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()), "fibre field");
-  rdc_solid_params p{};
-  p.pseudo_time = P.get<Real>("pseudo_time");
-  p.displacement_penalty = P.get<Real>("BCs/displacement_penalty");
-  p.use_symmetry = P.get<bool>("solver/assembly_use_symmetry") ? 1 : 0;
+  const rdc_solid_params p = marshal::solid_params(es_.parameters);
   check(c, rdc_solid_assemble(c, &p, get_jacobian ? 1 : 0), "rdc_solid_assemble");
   check(c, rdc_csr_download(c, get_jacobian ? matrix_storage.val.data() : nullptr, rhs_storage.raw().data()), "rdc_csr_download");
   last.assemblies++;
@@ -816,7 +679,6 @@ inline void SolidSystem::run_solver() {
 }
 
 inline void SolidSystem::post_process() {
-  const Parameters& P = es_.parameters;
   rdc_ctx* c = es_.context(name_, 3);
   if (!bound_) bind(c);
   System& aux = es_.get_system<System>("SolidSystem::auxiliary");
@@ -831,9 +693,7 @@ inline void SolidSystem::post_process() {
   for (int64_t e = 0; e < ne; e++)
     for (int d = 0; d < 3; d++) eta[(size_t)e * 3 + d] = fibre.current_local_solution(e * nf + d);
   check(c, rdc_field_upload(c, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()), "fibre field");
-  rdc_solid_params p{};
-  p.pseudo_time = P.get<Real>("pseudo_time");
-  p.displacement_penalty = P.get<Real>("BCs/displacement_penalty");
+  const rdc_solid_params p = marshal::solid_params(es_.parameters);   // "solver/assembly_use_symmetry" plays no part in it
   check(c, rdc_solid_post_process(c, &p, press.solution.raw().data(), vm.solution.raw().data(), cur.data()), "rdc_solid_post_process");
   for (int64_t e = 0; e < ne; e++)
     for (int d = 0; d < 3; d++) fibre.solution.set(e * nf + 3 + d, cur[(size_t)e * 3 + d]);   // fibre_current_* (:526-527)

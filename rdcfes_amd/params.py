@@ -164,6 +164,13 @@ HCC_DEFAULTS = {k: 0.0 for k in HCC_KEYS}
 HCC_DEFAULTS.update({"time_step": 1.0e-9, "cells/max_capacity": 1.0, "cells/max_capacity/exponent": 1.0})
 
 
+# save_solution's keys (no defaults: the drivers set them from the input file)
+PIHNA_RANGES_KEYS = {f"range/{q}/{m}": f"{q}_{m}" for q in ("active_tumor", "necrotic", "vascularity", "total_cell")
+                     for m in ("min", "max")}
+PIHNA_RANGES_KEYS["cells_max_capacity"] = "cells_max_capacity"
+RIPF_RANGES_KEYS = {f"range_{s}/{k}": f"{s}_{k.replace('/', '_')}" for s in ("cc", "fb") for k in ("HU/min", "HU/max", "min")}
+
+
 def _from_dict(cls, keys, defaults, d):
     unknown = set(d) - set(keys)
     if unknown:

@@ -27,10 +27,11 @@ template <class T> void write_raw(const std::string& f, const std::vector<T>& v)
 }
 
 int main(int argc, char** argv) {
-  if (argc < 4) { std::fprintf(stderr, "usage: driver <dir> <model: pihna|ripf|hcc|adpm|proteas> <elem_type> [solve]\n"); return 2; }
+  if (argc < 4) { std::fprintf(stderr, "usage: driver <dir> <model: pihna|ripf|hcc|adpm|proteas> <elem_type> [solve|twice]\n"); return 2; }
   const std::string dir = argv[1], model_name = argv[2];
   const int elem_type = std::atoi(argv[3]);
   const bool do_solve = argc > 4 && std::string(argv[4]) == "solve";
+  const bool twice = argc > 4 && std::string(argv[4]) == "twice";   // two assemblies of one system: the second hand-back finds the arrays pinned
   try {
     Mesh mesh(elem_type, read_raw<uint32_t>(dir + "/conn.bin"), read_raw<double>(dir + "/xyz.bin"));
     EquationSystems es(mesh);
@@ -100,6 +101,7 @@ int main(int argc, char** argv) {
       write_raw(dir + "/solution.bin", model->solution.raw());
     } else {
       model->assemble();
+      if (twice) model->assemble();
     }
     {  // check_solution(): the clamp of the solved state runs on the device through the same context
       std::vector<double> keep = model->solution.raw();

@@ -166,3 +166,27 @@ def test_chunked_handback_through_host_mirror(oracle, driver, tmp_path, chunks):
     rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
     assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
     assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
+
+
+@pytest.mark.parametrize("n,chunks", [(4, 3), (2, 40)])
+def test_second_handback_through_host_mirror(oracle, driver, tmp_path, n, chunks):
+    """model->assemble() twice on one system: the second chunked hand-back runs on the arrays the first one pinned (the mirror pins
+    once per system, as the libMesh adapter does) and delivers the same rows.  K(2) has 27 nodes, so 40 chunks include empty ones."""
+    conn, xyz = synth.kuhn_tet_mesh(n, order="random")
+    from rdcfes_amd.params import PIHNA_DEFAULTS
+    d = {**PIHNA_DEFAULTS, **synth.pihna_param_dict("shipped"), "rdc/handback_chunks": chunks}
+    u = synth.pihna_fields(xyz)
+    _write_case(tmp_path, conn, xyz, u, d)
+    r = subprocess.run([str(driver), str(tmp_path), "pihna", "4", "twice"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    log = np.fromfile(tmp_path / "handback_log.bin", dtype=np.int64).reshape(-1, 2)
+    nn = xyz.shape[0]
+    assert nn == (n + 1) ** 3
+    assert log.shape[0] == chunks and log[0, 0] == 0 and log[-1, 1] == nn                 # the second call's ranges, empty ones included
+    assert np.array_equal(log[1:, 0], log[:-1, 1]) and np.all(log[:, 1] >= log[:, 0])      # a partition of [0, n_nodes), in order
+    assert (nn >= chunks) or np.any(log[:, 1] == log[:, 0])
+    val, rhs = np.fromfile(tmp_path / "val.bin"), np.fromfile(tmp_path / "rhs.bin")
+    p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))
+    rp0, col0, val0, rhs0 = oracle.assemble(0, 4, conn, xyz, 5, p, u_old=u)
+    assert rel(val, val0) < 1e-10 and rel(rhs, rhs0) < 1e-10
+    assert_csr_close(rp0, col0, val, val0, rhs, rhs0, 5)
