@@ -280,6 +280,30 @@ int rdc_assemble_pihna_part(rdc_ctx* ctx, const rdc_pihna_params* p, int part, v
 int rdc_assemble_hcc_part(rdc_ctx* ctx, const rdc_hcc_params* p, int part, void* hip_stream);
 int rdc_solid_assemble_part(rdc_ctx* ctx, const rdc_solid_params* p, int request_jacobian, int part, void* hip_stream);
 
+/* ---- TET4 cluster kernel: the element loops src/pihna.C:383-756, src/ripf.C:410-671, src/coupled_hcc.C:463-646,
+ * src/adpm.C:370-528 and src/proteas.C:338-705 on UNSTRUCTURED tetrahedral meshes (Gmsh, Delaunay: nodes with more than 16
+ * node blocks in their row, for which neither the pair lists nor the element-visit lists exist).  A workgroup owns a cluster
+ * of owned nodes grown over the mesh graph, gathers every element touching it once into LDS and assembles the cluster's
+ * CSR rows there.  Additive: RDC_ABI_VERSION stays 3.
+ *   mode 0  off (the default): nothing changes anywhere;
+ *   mode 1  on where the mesh has neither element-visit lists nor pair lists, i.e. where the row-gather kernels on runs of
+ *           consecutive node ids would run;
+ *   mode 2  on for every TET4 mesh whose cluster lists can be built (tests, A/B against the established kernels, which
+ *           are faster where they exist: DESIGN.md section 4.6).
+ * Measured on a 1.17 M-tet Delaunay mesh, mode 1 against mode 0: PIHNA 1.2x, HCC 1.3x, ADPM and PROTEAS 1.9-2.0x faster, RIPF
+ * equal; all five models take the kernel in mode 1.
+ * Any other value: RDC_ERR_INVALID.  May be called before or after rdc_mesh_upload; on a HEX8 mesh it has no effect.  The
+ * lists are built on the first assembly that wants them, honour "interior_nodes" (two-part assembly: the interior
+ * clusters run in part 1) and ghosted contexts.  The kernel runs only when the scatter resolves to RDC_SCATTER_ROWGATHER
+ * and the variant is not RDC_VARIANT_GENERIC; a mesh the lists cannot describe (a row of more than 255 node blocks), or an
+ * image beyond the device's LDS, keeps the path it had -- rdc_last_error then carries the list builder's reason. */
+int rdc_tet4_cluster_mode(rdc_ctx* ctx, int mode);
+/* *active = 1 exactly if the last assembly call on this context launched the cluster kernel; the counts describe the lists
+ * (0 before they exist): clusters, (owned node, element) pairs, elements gathered over all clusters; *lds_bytes = dynamic
+ * LDS of that launch (0 when not active).  Any output pointer may be NULL. */
+int rdc_tet4_cluster_info(rdc_ctx* ctx, int32_t* mode, int32_t* active, int64_t* n_clusters, int64_t* n_pairs,
+                          int64_t* n_elem_visits, int64_t* lds_bytes);
+
 /* ---- results ---- */
 int rdc_csr_values_device_ptr(rdc_ctx* ctx, double** d_val, double** d_rhs);
 int rdc_csr_download(rdc_ctx* ctx, double* val, double* rhs);

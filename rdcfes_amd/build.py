@@ -31,6 +31,7 @@ SOURCES = [
     "rdc_tet4_fast.hip",
     "rdc_tet4_ev.hip",
     "rdc_tet4_evc.hip",
+    "rdc_tet4_cl.hip",
     "rdc_prep_ev.cpp",
     "rdc_solid.hip",
     "rdc_solid_cl.hip",
@@ -138,7 +139,7 @@ def build(force: bool = False, jobs: int = 4, verbose: bool = True) -> Path:
     # spills / scratch are performance bugs on this path: always say so.  The kernels every default configuration runs
     # are listed by name; the experimental / diagnostic instantiations are counted (full list: lib/kernel_resources.json,
     # RDC_BUILD_VERBOSE=1).  RDC_BUILD_STRICT=1 turns scratch in a default-path kernel into an error.
-    default_path = ("k_tet4_ev", "k_tet4_evm", "k_tet4_evc", "k_tet4_rg5", "k_hex8_cl", "k_solid_cl", "k_pack_nodes",
+    default_path = ("k_tet4_ev", "k_tet4_evm", "k_tet4_evc", "k_tet4_rg5", "k_tet4_cl", "k_hex8_cl", "k_solid_cl", "k_pack_nodes",
                     "k_spmv", "k_spmv_f32", "k_scale_f32", "k_precond_setup", "k_residual", "k_finalize", "k_update_p", "k_update_s", "k_update_xr",
                     "k_galerkin", "k_restrict", "k_prolong", "k_smooth", "k_reduce", "k_advance", "k_halo_pack")
     bad = {k: v for k, v in resources.items() if v.get("scratch_bytes_per_lane", 0) or v.get("vgpr_spills", 0)}

@@ -81,6 +81,21 @@ class AssemblyContext:
     def set_option(self, key, value):
         self._ck(self._lib.rdc_set_option(self._h, key.encode(), int(value)))
 
+    def set_tet4_cluster(self, mode):
+        """rdc_tet4_cluster_mode: 0 = off (default), 1 = the TET4 cluster kernel where the mesh has no pair lists (Gmsh and
+        Delaunay meshes), 2 = on every TET4 mesh whose cluster lists can be built"""
+        self._ck(self._lib.rdc_tet4_cluster_mode(self._h, int(mode)))
+
+    def tet4_cluster_info(self):
+        """rdc_tet4_cluster_info: mode, active (the last assembly call launched the cluster kernel), the lists' clusters,
+        pairs and element visits, the dynamic LDS of that launch; last_error = rdc_last_error (after a refused list build:
+        the builder's reason)"""
+        mode, active = C.c_int32(), C.c_int32()
+        n = [C.c_int64() for _ in range(4)]
+        self._ck(self._lib.rdc_tet4_cluster_info(self._h, C.byref(mode), C.byref(active), *(C.byref(x) for x in n)))
+        return {"mode": mode.value, "active": active.value, "n_clusters": n[0].value, "n_pairs": n[1].value,
+                "n_elem_visits": n[2].value, "lds_bytes": n[3].value, "last_error": self._lib.rdc_last_error(self._h).decode()}
+
     def get_scatter(self):
         s = C.c_int()
         self._ck(self._lib.rdc_get_scatter(self._h, C.byref(s)))

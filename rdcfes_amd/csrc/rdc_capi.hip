@@ -13,6 +13,7 @@
 #include "rdc_parts.h"
 #include "rdc_tet4_pihna_moments.h"
 #include "rdc_tet4_ev.h"
+#include "rdc_tet4_cl.h"
 #include "rdc_solid.h"
 #include "rdc_solve.h"
 
@@ -64,12 +65,13 @@ struct MeshState {
   bool ev_tried = false;           // the element-visit lists of this mesh have been built (or found impossible)
   int64_t ev_perm_interior = -2;   // "interior_nodes" value the uploaded workgroup order was built for
   PartSplit ev_part1;              // the split of that order: its leading interior workgroups, the rows complete after them
-  struct ClusterLists {            // cluster lists of the HEX8 producer / consumer kernels (ensure_cluster_lists)
-    int state = 0;                 // 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass is used)
+  struct ClusterLists {            // cluster lists of the HEX8 producer / consumer kernels or of k_tet4_cl (ensure_cluster_lists)
+    int state = 0;                 // 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass / the pair kernels are used)
     int waves = 31, order = 1, interior = -1;   // the options "solid_cl_waves", pair order and "interior_nodes" they were built with
     int n_wg = 0;                  // all clusters
     PartSplit part1;               // their leading clusters of interior nodes, the rows complete after those
     size_t max_row_doubles = 0;
+    int64_t n_pairs = 0, n_elem_visits = 0;   // statistics (rdc_tet4_cluster_info)
   } cl;
   bool solid_gather_ready = false, rg5_eid_ready = false;   // buf.two_pass, buf.rg2.eid hold this mesh's lists
   SolveState solve;
@@ -93,6 +95,9 @@ struct rdc_ctx {
   char err[512] = "";
   int strategy = RDC_SCATTER_AUTO;
   int variant = RDC_VARIANT_AUTO;
+  int tet4_cl_mode = 0;         // rdc_tet4_cluster_mode
+  int tet4_cl_active = 0;       // the last assembly call launched k_tet4_cl
+  size_t tet4_cl_lds = 0;       // dynamic LDS of that launch
   Options opt;
   MeshState ms;
   Buffers buf;
@@ -359,17 +364,19 @@ int build_ev_lists(rdc_ctx* c, const uint32_t* conn) {
 }
 
 // cluster lists of the producer / consumer HEX8 kernels (three unknowns: solid system and reaction-diffusion models share
-// them), built on first use.  ms.cl.state: 1 = ready, -1 = not available for this mesh (c->err says why).
+// them) or, on a TET4 mesh, of k_tet4_cl (cll::tet4_limits), built on first use.  ms.cl.state: 1 = ready, -1 = not available
+// for this mesh (c->err says why).
 int ensure_cluster_lists(rdc_ctx* c, int order_of_caller) {
   int rc;
   MeshState::ClusterLists& L = c->ms.cl;
   const int want_order = c->opt.solid_cl_order < 0 ? (L.state == 1 ? L.order : order_of_caller) : c->opt.solid_cl_order;
   if (L.state != 0 && (L.waves != c->opt.solid_cl_waves || L.order != want_order || L.interior != c->opt.interior_nodes)) L.state = 0;
   if (L.state != 0) return RDC_OK;
-  HostPrepCl::Limits lim = cll::limits(c->opt.solid_cl_waves / 10, c->opt.solid_cl_waves % 10, c->ms.prep.nvar);
+  const int nen = c->ms.prep.nen;   // 4: the lists of k_tet4_cl (rdc_tet4_cluster_mode)
+  HostPrepCl::Limits lim = nen == 4 ? cll::tet4_limits(c->ms.prep.nvar) : cll::limits(c->opt.solid_cl_waves / 10, c->opt.solid_cl_waves % 10, c->ms.prep.nvar);
   lim.pair_order = want_order;
   HostPrepCl cl;
-  std::vector<uint32_t> conn_h((size_t)c->ms.prep.n_elem * 8);      // the context keeps the connectivity on the device only
+  std::vector<uint32_t> conn_h((size_t)c->ms.prep.n_elem * nen);      // the context keeps the connectivity on the device only
   RDC_HIP(c, hipMemcpyAsync(conn_h.data(), c->buf.mesh.conn.p, conn_h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   RDC_HIP(c, hipStreamSynchronize(c->stream));
   const std::string err = prep_build_cl(c->ms.prep, conn_h.data(), lim, cl, c->opt.interior_nodes);
@@ -388,6 +395,7 @@ int ensure_cluster_lists(rdc_ctx* c, int order_of_caller) {
   RDC_HIP(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
   L.max_row_doubles = cl.max_row_doubles;
   L.n_wg = (int)cl.desc.size();
+  L.n_pairs = cl.n_pairs; L.n_elem_visits = cl.n_elem_visits;
   if (L.interior >= 0) L.part1 = PartSplit{(int)cl.n_wg_interior, cl.part1_nodes};
   L.state = 1;
   return RDC_OK;
@@ -400,7 +408,7 @@ ClDev cluster_view(const rdc_ctx* c, int part = 0) {
   v.cw = L.waves / 10; v.pw = L.waves % 10;
   const size_t b = part == 2 ? (size_t)L.part1.wg : 0;
   v.n_wg = part == 1 ? L.part1.wg : (part == 2 ? L.n_wg - L.part1.wg : L.n_wg);
-  const cll::Strides S = cll::strides(v.cw, v.pw, c->ms.prep.nen);
+  const cll::Strides S = c->ms.prep.nen == 4 ? cll::strides(cll::tet4_limits(c->ms.prep.nvar), 4) : cll::strides(v.cw, v.pw, c->ms.prep.nen);
   v.desc = (const HostPrepCl::Desc*)c->buf.cl.desc.p + b;
   v.ntab = (const HostPrepCl::Node*)c->buf.cl.ntab.p + b * S.node;
   v.eid = (const uint32_t*)c->buf.cl.eid.p + b * S.elem;
@@ -413,6 +421,7 @@ ClDev cluster_view(const rdc_ctx* c, int part = 0) {
 template <class M, class P>
 int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   if (!c) return RDC_ERR_INVALID;
+  c->tet4_cl_active = 0;
   if (!p) return fail(c, RDC_ERR_INVALID, "null parameter struct");
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "assemble called before rdc_mesh_upload");
   if (c->ms.prep.nvar != nvar_expected)
@@ -462,7 +471,15 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   }
   // element-visit kernel: default for the shipped-pattern PIHNA / TET4 ("kernel" = 0 or 7); the diagnostic knobs of the
   // pair kernels (ablate, stamps, coefficient form, occupancy 1) and "kernel" = 5 select k_tet4_rg5 instead
-  a.use_ev = c->ms.prep_ev.ok && (c->opt.kernel == 0 || c->opt.kernel == 7) && c->opt.moments && (!c->opt.ablate || c->opt.kernel == 7) &&
+  // TET4 cluster kernel (rdc_tet4_cluster_mode): mode 1 where the mesh has neither pair lists nor element-visit lists (the latter
+  // need the former), mode 2 wherever its lists can be built.  A refused build (c->err says why) or an image beyond the device's
+  // LDS leaves the call on the path it would have taken
+  if (a.nen == 4 && Tet4ClWanted<M>::in_mode(c->tet4_cl_mode) && (c->tet4_cl_mode == 2 || !c->ms.prep.rg2_ok)) {
+    if ((rc = ensure_cluster_lists(c, 1))) return rc;
+    a.tet4_cl = c->ms.cl.state == 1 && a.strategy == RDC_SCATTER_ROWGATHER && a.variant != RDC_VARIANT_GENERIC &&
+                tet4_cl_lds_bytes<M>(c->ms.cl.max_row_doubles) <= c->max_lds;
+  }
+  a.use_ev = !a.tet4_cl && c->ms.prep_ev.ok && (c->opt.kernel == 0 || c->opt.kernel == 7) && c->opt.moments && (!c->opt.ablate || c->opt.kernel == 7) &&
              (!c->buf.scratch.stamps.p || (c->opt.kernel == 7 && c->opt.ablate == 4)) && c->opt.occupancy != 1 && c->opt.lds_pad == 0;
   if (c->opt.ev_resident) {   // cluster counter of the resident kernel
     if ((rc = dev_alloc(c, c->buf.ev.ticket, 256))) return rc;   // [0]: whole launches and part 1, [16]: part 2
@@ -504,8 +521,8 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
       c->ms.part1_packed = false;
     }
   } else
-  if (c->opt.part != 0 && hex_cl) {
-    // HEX8 cluster kernels: the cluster lists respect "interior_nodes" (interior clusters first)
+  if (c->opt.part != 0 && (hex_cl || a.tet4_cl)) {
+    // HEX8 cluster kernels, k_tet4_cl: the cluster lists respect "interior_nodes" (interior clusters first)
     c->ms.part1_packed = false;
     if (c->opt.part == 1) {
       c->ms.part1_nodes = c->ms.cl.part1.wg > 0 ? c->ms.cl.part1.nodes : 0;
@@ -541,9 +558,13 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   } else {
     c->ms.part1_packed = false;
   }
-  if (hex_cl && c->opt.part == 0) {
+  if ((hex_cl || a.tet4_cl) && c->opt.part == 0) {
     a.cl = cluster_view(c);
-    a.cl.grid = c->opt.hex_kernel == 2 ? 2 * c->n_cu : 0;   // persistent form: the workgroups resident at once
+    a.cl.grid = hex_cl && c->opt.hex_kernel == 2 ? 2 * c->n_cu : 0;   // persistent form: the workgroups resident at once
+  }
+  if (a.tet4_cl) {   // what rdc_tet4_cluster_info reports (a part without clusters has returned above)
+    c->tet4_cl_active = 1;
+    c->tet4_cl_lds = tet4_cl_lds_bytes<M>(a.cl.max_row_doubles);
   }
   a.val = (double*)c->buf.out.val.p;
   a.rhs = (double*)c->buf.out.rhs.p;
@@ -615,6 +636,7 @@ int rdc_ctx_create(int device_ordinal, rdc_ctx** out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) {
     if (prop.sharedMemPerBlock > 0) c->max_lds = prop.sharedMemPerBlock;
+    if (prop.sharedMemPerBlockOptin > c->max_lds) c->max_lds = prop.sharedMemPerBlockOptin;   // what hipFuncSetAttribute may raise a kernel to
     if (prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
   }
   *out = c;
@@ -931,6 +953,7 @@ int rdc_solid_assemble(rdc_ctx* c, const rdc_solid_params* p, int request_jacobi
   if (!c) return RDC_ERR_INVALID;
   if (!p) return fail(c, RDC_ERR_INVALID, "null parameter struct");
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "assemble called before rdc_mesh_upload");
+  c->tet4_cl_active = 0;
   if (c->ms.prep.nvar != 3) return fail(c, RDC_ERR_INVALID, "solid system needs nvar=3");
   if (!c->buf.field[RDC_FIELD_UNDEFORMED_XYZ].p) return fail(c, RDC_ERR_STATE, "undeformed coordinates not set");
   if (!c->buf.field[RDC_FIELD_ELEM_FIBRE].p) return fail(c, RDC_ERR_STATE, "fibre field not set");
@@ -1125,6 +1148,27 @@ int rdc_part1_nodes(const rdc_ctx* c, int64_t* n_nodes) {
   }
   if (c->opt.interior_nodes < 0 || !c->ms.prep.rg2_ok || c->ms.prep.nen != 4) return RDC_OK;
   *n_nodes = part1_pairs(c).nodes;
+  return RDC_OK;
+}
+
+int rdc_tet4_cluster_mode(rdc_ctx* c, int mode) {
+  if (!c) return RDC_ERR_INVALID;
+  if (mode < 0 || mode > 2) return fail(c, RDC_ERR_INVALID, "tet4 cluster mode must be 0 (off), 1 (meshes without pair lists) or 2 (every TET4 mesh), not %d", mode);
+  c->tet4_cl_mode = mode;
+  return RDC_OK;
+}
+
+int rdc_tet4_cluster_info(rdc_ctx* c, int32_t* mode, int32_t* active, int64_t* n_clusters, int64_t* n_pairs,
+                          int64_t* n_elem_visits, int64_t* lds_bytes) {
+  if (!c) return RDC_ERR_INVALID;
+  const MeshState::ClusterLists& L = c->ms.cl;
+  const bool lists = c->ms.have_mesh && c->ms.prep.nen == 4 && L.state == 1;
+  if (mode) *mode = c->tet4_cl_mode;
+  if (active) *active = c->tet4_cl_active;
+  if (n_clusters) *n_clusters = lists ? L.n_wg : 0;
+  if (n_pairs) *n_pairs = lists ? L.n_pairs : 0;
+  if (n_elem_visits) *n_elem_visits = lists ? L.n_elem_visits : 0;
+  if (lds_bytes) *lds_bytes = c->tet4_cl_active ? (int64_t)c->tet4_cl_lds : 0;
   return RDC_OK;
 }
 

@@ -93,7 +93,8 @@ struct LaunchArgs {
   int kernel = 0;  // opt.kernel as the pair-kernel launchers read it: 5 and 7 (their choice is made before the launcher) count as 0
   Rg2Dev rg2;
   EvDev ev;
-  ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted)
+  ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted); TET4: those of k_tet4_cl
+  bool tet4_cl = false;  // TET4: this call runs the cluster kernel (rdc_tet4_cl.hip) on `cl` instead of the pair / row-gather kernels
   bool use_ev = false;   // element-visit kernel allowed for this call
   int ev_grid = 0;           // 2 x CUs: the resident element-visit kernel launches 3/2 of it (22 moments: all of it)
   int* ev_ticket = nullptr;  // k_tet4_evq: cluster counter (one int, zeroed by the launch)
@@ -114,6 +115,9 @@ hipError_t launch_rd(const LaunchArgs& a, const typename M::K& k);
 // TET4-specialised factored kernels (rdc_tet4_fast.hip)
 template <class M>
 hipError_t launch_tet4_fast(const LaunchArgs& a, const typename M::K& k);
+// TET4 cluster kernel (rdc_tet4_cl.hip): reads the mesh and the nodal fields directly, no record pack
+template <class M>
+hipError_t launch_tet4_cl(const LaunchArgs& a, const typename M::K& k);
 // node records of the PIHNA kernels (xyz | u, 64 bytes per node), honouring the two-part pack rules (rdc_tet4_fast.hip)
 hipError_t pack_nodes_pihna(const LaunchArgs& a);
 // element-visit / moment kernel of the shipped-pattern PIHNA TET4 assembly (rdc_tet4_ev.hip)

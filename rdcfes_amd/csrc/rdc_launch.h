@@ -54,6 +54,7 @@ static hipError_t launch_rd_impl(const LaunchArgs& a, const typename M::K& k) {
 
 template <class M>
 hipError_t launch_rd(const LaunchArgs& a, const typename M::K& k) {
+  if (a.nen == 4 && a.tet4_cl) return launch_tet4_cl<M>(a, k);   // rdc_tet4_cluster_mode: the context decided (assemble_rd)
   if (a.nen == 4 && a.variant != RDC_VARIANT_GENERIC) {
     // per-element inputs (M::NELEM > 0) and the local-node aux mask (Proteas) travel only in k_tet4_rg5 (needs the pair -> element list) and k_tet4_coloured
     const bool rg5 = a.rg2.n_wg > 0 && a.rg2.pair_aux && a.rg2.nlist && a.rg2.block == 256 && a.rg2.pair_eid;

@@ -260,6 +260,15 @@ RDC_EVL constexpr HostPrepCl::Limits limits(int cw, int pw, int nvar) {
   if (nvar == 5) { lim.img_per_block = 5; lim.max_row_doubles = 5 * 27 * lim.max_nodes + 5 * lim.max_nodes; }
   return lim;
 }
+// The limits of the TET4 cluster kernel (rdc_tet4_cl.h; nen = 4, whole-row images): a 256-thread workgroup with a lane per pair,
+// a lane per element among its first 128, a half-wave per node in the copy-out.  max_row_doubles bounds the image: rows of
+// unstructured meshes hold 30 .. 50 node blocks, and image + element records must stay below the 160 KB of a CU
+RDC_EVL constexpr HostPrepCl::Limits tet4_limits(int nvar) {
+  HostPrepCl::Limits lim;
+  lim.max_nodes = 16; lim.max_pairs = 256; lim.max_elems = 128;
+  lim.max_row_doubles = nvar == 5 ? 7000 : 5000;
+  return lim;
+}
 }  // namespace cll
 
 // returns empty string on success, else an error message

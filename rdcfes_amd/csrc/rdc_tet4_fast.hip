@@ -734,6 +734,7 @@ static hipError_t launch_fast_impl(const LaunchArgs& a, const typename M::K& k) 
 
 template <class M>
 hipError_t launch_tet4_fast(const LaunchArgs& a, const typename M::K& k) {
+  if (a.tet4_cl) return launch_tet4_cl<M>(a, k);   // rdc_tet4_cluster_mode: the context decided (assemble_rd)
   if (a.exp_mode == M::FAST_EXP_MODE) return launch_fast_impl<M, M::FAST_EXP_MODE>(a, k);
   return launch_fast_impl<M, 0>(a, k);
 }
