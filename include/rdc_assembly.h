@@ -467,12 +467,47 @@ int rdc_solve_dist_plan(rdc_ctx* ctx, int64_t n_send, const int32_t* send_nodes)
  * owned rows hold the solution and the ghost rows the owners' values of it (the last true residual has just exchanged them),
  * whatever info->reason is; b = 0 gives x = 0 in 0 iterations, ghost rows included; RDC_SOLVE_BAD_DIAGONAL and a first
  * residual that is not finite leave the owned rows untouched.  precond: RDC_PRECOND_NONE, _JACOBI, _BLOCK_JACOBI;
- * RDC_PRECOND_MULTIGRID gives RDC_ERR_UNSUPPORTED (aggregates across ranks are not built).  RDC_ERR_STATE on a context with
+ * RDC_PRECOND_MULTIGRID gives RDC_ERR_UNSUPPORTED here (its coarse exchanges need sizes: rdc_solve_dist_mg below).  RDC_ERR_STATE on a context with
  * ghost nodes that has no plan.  A context without ghosts, with an empty or no plan and a communicator of world size 1 (an
  * exchange that does nothing, an all-reduce that leaves d_vals as they are) is legal and returns, bit for bit, what
  * rdc_solve / rdc_solve_mixed return.  Blocks the host until done.  Never modifies the CSR values or the rhs. */
 int rdc_solve_dist(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed,
                    double* d_x, rdc_solve_info* info);
+
+/* ---- multigrid across ranks (additive: RDC_ABI_VERSION stays 3): rdc_solve_dist with the V(1,1) cycle of RDC_PRECOND_MULTIGRID.
+ * Aggregates never cross a partition: every rank aggregates the nodes it owns over the edges whose two ends it owns, so a
+ * rank owns whole coarse rows and builds them without communication.  What every level needs is a ghost layer: the coarse
+ * ghosts of a rank are the aggregates its peers made of its fine ghosts, learnt once per level by one exchange of aggregate
+ * numbers (width 1, as doubles) when the hierarchy is built -- collectively, at the first such solve after a plan; a new plan
+ * or mesh upload drops it.  Levels are added until the level has at most 40 nodes over all ranks, 10 levels exist or no rank
+ * merged anything; every rank ends with the same number of levels, and with one rank the hierarchy is that of rdc_solve.
+ * Inside a cycle every operator application exchanges its argument first: level 0 through exchange_begin / exchange_end with
+ * the rows below "interior_nodes" in between, every level below through the sized pair, then one launch over the owned rows.
+ * With L levels an iteration makes 6 exchanges of the plan's size and 2 (2 (L - 2) + 7) sized ones (L >= 2); the three
+ * all-reduces per iteration are unchanged, since the cycle has no inner product. */
+/* Per-peer segment lengths, in nodes, of the send list and of the ghost tail of the plan: peer k is the k-th peer of this call
+ * (rank ids stay with the caller), the order is that of the send list and of the ghost tail, zeros are allowed.
+ * RDC_ERR_STATE before rdc_solve_dist_plan; RDC_ERR_INVALID if a count is negative or the sums are not n_send and n_ghost. */
+int rdc_solve_dist_plan_peers(rdc_ctx* ctx, int32_t n_peers, const int64_t* send_count, const int64_t* ghost_count);
+/* The communicator of rdc_solve_dist and an exchange whose sizes come with the call, for the levels below the matrix.  d_send and
+ * d_recv are as in exchange_begin; send_off and recv_off are HOST arrays of n_peers + 1 offsets in doubles: peer k gets
+ * d_send[send_off[k] .. send_off[k + 1]) and delivers d_recv[recv_off[k] .. recv_off[k + 1]); an empty segment on one side is
+ * empty on the peer's side too.  The callee only slices by what it is given.  The stream contract is that of exchange_begin /
+ * exchange_end; nothing is enqueued between a sized begin and its end. */
+typedef struct rdc_solve_comm_sized {
+  rdc_solve_comm base;
+  int (*exchange_sized_begin)(void* user, const double* d_send, double* d_recv, int32_t n_peers, const int64_t* send_off,
+                              const int64_t* recv_off, void* hip_stream);
+  int (*exchange_sized_end)(void* user, void* hip_stream);
+} rdc_solve_comm_sized;
+/* The contract of rdc_solve_dist with p->precond = RDC_PRECOND_MULTIGRID; any other preconditioner is RDC_ERR_INVALID.
+ * RDC_ERR_STATE on a context with ghost nodes that lacks the plan or the peer counts.  A singular diagonal block on any level
+ * of any rank gives RDC_SOLVE_BAD_DIAGONAL on every rank, x untouched.  A callback that returns non-zero (while the hierarchy
+ * is built included) gives RDC_ERR_COMM and no further callback.  A context without ghosts and a communicator of world size
+ * 1 returns, bit for bit, what rdc_solve / rdc_solve_mixed return with RDC_PRECOND_MULTIGRID.  rdc_solve_mg_levels and
+ * rdc_solve_mg_stats then report this rank's levels: the nodes it owns and the node blocks of its rows. */
+int rdc_solve_dist_mg(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed,
+                      double* d_x, rdc_solve_info* info);
 
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */

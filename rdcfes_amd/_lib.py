@@ -4,7 +4,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveCommStruct, SolveInfo, SolveParams
+from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveCommSizedStruct, SolveCommStruct, SolveInfo, SolveParams
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "librdc_assembly.so"
 
@@ -68,6 +68,8 @@ SIGNATURES = {
     "rdc_solve_mg_stats": (C.c_int, [ctx_p, P(C.c_float), P(C.c_int64)]),
     "rdc_solve_dist_plan": (C.c_int, [ctx_p, i64, P(i32)]),
     "rdc_solve_dist": (C.c_int, [ctx_p, P(SolveParams), P(SolveCommStruct), C.c_int, C.c_void_p, P(SolveInfo)]),
+    "rdc_solve_dist_plan_peers": (C.c_int, [ctx_p, i32, P(i64), P(i64)]),
+    "rdc_solve_dist_mg": (C.c_int, [ctx_p, P(SolveParams), P(SolveCommSizedStruct), C.c_int, C.c_void_p, P(SolveInfo)]),
     "rdc_clamp_nonnegative": (C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_ripf_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),

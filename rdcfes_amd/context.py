@@ -358,18 +358,28 @@ class AssemblyContext:
         """rdc_solve_dist: the solve of `solve`, across the ranks of comm (halo.SolveComm), every rank calling with its own
         context.  x: device address of n_node*nvar doubles in local numbering (owned rows: initial guess in, solution out; ghost
         rows: ignored in, the owners' values out), or field=FIELD_*.  The returned SolveInfo is the same on every rank.  The send
-        list of comm is uploaded once per mesh.  An exception raised inside a callback of comm is re-raised here."""
+        list of comm is uploaded once per mesh.  An exception raised inside a callback of comm is re-raised here.
+        precond=PRECOND_MULTIGRID needs a communicator with the sized exchange (SolveComm(..., sized=True)) and goes to
+        rdc_solve_dist_mg; its peer counts are uploaded with the plan."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
             x = self.field_device_ptr(int(field), self.n_node * self.nvar)
+        sized = getattr(comm, "sized_struct", None)
         if self._dist_plan is not comm:
             self.solve_dist_plan(comm.send_nodes)
+            if sized is not None:
+                sc, gc = (np.ascontiguousarray(a, dtype=np.int64) for a in comm.peer_counts)
+                i64p = C.POINTER(C.c_int64)
+                self._ck(self._lib.rdc_solve_dist_plan_peers(self._h, sc.size, sc.ctypes.data_as(i64p), gc.ctypes.data_as(i64p)))
             self._dist_plan = comm
         p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
         info = SolveInfo()
         comm.error = None
-        rc = self._lib.rdc_solve_dist(self._h, C.byref(p), C.byref(comm.struct), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
+        if sized is not None and int(precond) == PRECOND_MULTIGRID:
+            rc = self._lib.rdc_solve_dist_mg(self._h, C.byref(p), C.byref(sized), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
+        else:
+            rc = self._lib.rdc_solve_dist(self._h, C.byref(p), C.byref(comm.struct), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
         if comm.error is not None:
             err, comm.error = comm.error, None
             raise err

@@ -39,7 +39,7 @@ struct Buffers {
   // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
   // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
   // send: the send list of a partitioned solve (rdc_solve_dist_plan)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send; } solve;
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -52,9 +52,14 @@ struct SolveState {
   bool voff_ready = false;   // voff / val32 are laid out for this mesh
   bool f32_copy = false;     // val32 holds a usable fp32 copy (of the values at the time it was built)
   bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
+  bool mg_dist = false;      // ... and it is the one of rdc_solve_dist_mg (ghost layers; mg_off holds the offsets of its exchanges)
   MgDev mg;
   bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
   DistDims dist;
+  bool peers_ready = false;  // halo0 is the plan with its per-peer segments (rdc_solve_dist_plan_peers)
+  std::vector<int32_t> send_nodes;   // host copy of the plan's send list
+  MgHalo halo0;
+  std::vector<std::vector<int64_t>> mg_off;   // per level >= 1: send and ghost offsets in doubles, what MgLevelDev::send_off / ghost_off point at
 };
 
 // What is only meaningful for the uploaded mesh; rdc_mesh_upload starts from MeshState().
@@ -1211,27 +1216,37 @@ static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
 // The multigrid hierarchy of the mesh: built on the host and uploaded at the first multigrid solve (rdc_solve.h, mg_build),
 // two allocations that mg_place (rdc_solve.h) measures and then carves into the arrays of every level.  d must come from
 // solve_view(want_work).
+// measures and allocates the two arenas of a hierarchy, places it (mg_place) and uploads its lists
+static int mg_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps, const std::vector<MgHalo>* halos) {
+  const HostPrep& P = c->ms.prep;
+  MgDev& g = c->ms.solve.mg;
+  const int64_t blocks = P.bptr[(size_t)P.n_owned];
+  MgArena idx, val;
+  mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {}, halos);   // no bases: measures
+  int rc;
+  if ((rc = dev_alloc(c, c->buf.solve.mg_idx, idx.used))) return rc;
+  if ((rc = dev_alloc(c, c->buf.solve.mg_val, val.used))) return rc;
+  idx = MgArena{(char*)c->buf.solve.mg_idx.p};
+  val = MgArena{(char*)c->buf.solve.mg_val.p};
+  hipError_t e = hipSuccess;
+  mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [&](void* at, const void* list, size_t bytes) {
+    if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
+  }, halos);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host lists go out of scope
+  if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the multigrid lists failed: %s", hipGetErrorString(e));
+  return RDC_OK;
+}
+
 static int mg_view(rdc_ctx* c, SolveDev* d) {
   const HostPrep& P = c->ms.prep;
   MgDev& g = c->ms.solve.mg;
+  if (c->ms.solve.mg_dist) c->ms.solve.mg_ready = c->ms.solve.mg_dist = false;
   if (!c->ms.solve.mg_ready) {
     std::vector<MgLevelHost> steps;
     if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
       return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
-    const int64_t blocks = P.bptr[(size_t)P.n_owned];
-    MgArena idx, val;
-    mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {});   // no bases: measures
-    int rc;
-    if ((rc = dev_alloc(c, c->buf.solve.mg_idx, idx.used))) return rc;
-    if ((rc = dev_alloc(c, c->buf.solve.mg_val, val.used))) return rc;
-    idx = MgArena{(char*)c->buf.solve.mg_idx.p};
-    val = MgArena{(char*)c->buf.solve.mg_val.p};
-    hipError_t e = hipSuccess;
-    mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [&](void* at, const void* list, size_t bytes) {
-      if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
-    });
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host lists go out of scope
-    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the multigrid lists failed: %s", hipGetErrorString(e));
+    int rc = mg_upload(c, steps, nullptr);
+    if (rc) return rc;
     c->ms.solve.mg_ready = true;
   }
   g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
@@ -1339,7 +1354,9 @@ int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (n_send < 0 || (n_send > 0 && !send_nodes)) return fail(c, RDC_ERR_INVALID, "bad send list");
   const HostPrep& P = c->ms.prep;
-  c->ms.solve.plan_ready = false;
+  c->ms.solve.plan_ready = c->ms.solve.peers_ready = false;
+  if (c->ms.solve.mg_dist) c->ms.solve.mg_ready = c->ms.solve.mg_dist = false;   // a new plan drops the hierarchy built on the old one
+  c->ms.solve.halo0 = MgHalo();
   const int64_t n_int = c->opt.interior_nodes > 0 ? c->opt.interior_nodes : 0;
   int64_t where = 0;
   switch (dist_plan_check(P.n_owned, P.bptr.data(), P.bcol.data(), n_int, n_send, send_nodes, &where)) {
@@ -1351,49 +1368,173 @@ int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
   }
   int rc = set_device(c);
   if (rc) return rc;
-  if ((rc = dev_upload(c, c->buf.solve.send, std::vector<int32_t>(send_nodes, send_nodes + n_send)))) return rc;
-  RDC_HIP(c, hipStreamSynchronize(c->stream));   // the host copy goes out of scope
+  c->ms.solve.send_nodes.assign(send_nodes, send_nodes + n_send);
+  if ((rc = dev_upload(c, c->buf.solve.send, c->ms.solve.send_nodes))) return rc;
+  RDC_HIP(c, hipStreamSynchronize(c->stream));
   c->ms.solve.dist.n_nodes = P.n_node; c->ms.solve.dist.n_int = n_int; c->ms.solve.dist.n_send = n_send;
   c->ms.solve.plan_ready = true;
   return RDC_OK;
 }
 
-int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) {
+int rdc_solve_dist_plan_peers(rdc_ctx* c, int32_t n_peers, const int64_t* send_count, const int64_t* ghost_count) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  if (!c->ms.solve.plan_ready) return fail(c, RDC_ERR_STATE, "no send list: call rdc_solve_dist_plan first");
+  if (n_peers < 0 || (n_peers > 0 && (!send_count || !ghost_count))) return fail(c, RDC_ERR_INVALID, "bad peer counts");
+  const HostPrep& P = c->ms.prep;
+  SolveState& S = c->ms.solve;
+  MgHalo plan;
+  switch (mg_halo_plan(P.n_owned, P.n_node - P.n_owned, S.dist.n_send, S.send_nodes.data(), n_peers, send_count, ghost_count, plan)) {
+    case 0: break;
+    case 1: return fail(c, RDC_ERR_INVALID, "a peer count is negative");
+    case 2: return fail(c, RDC_ERR_INVALID, "the send counts of the %d peers do not add up to the %lld entries of the send list", (int)n_peers, (long long)S.dist.n_send);
+    case 3: return fail(c, RDC_ERR_INVALID, "the ghost counts of the %d peers do not add up to the %lld ghost nodes", (int)n_peers, (long long)(P.n_node - P.n_owned));
+    default: return fail(c, RDC_ERR_INVALID, "bad send list");
+  }
+  if (S.mg_dist) S.mg_ready = S.mg_dist = false;   // new peers drop the hierarchy built on the old ones
+  S.halo0 = std::move(plan);
+  S.peers_ready = true;
+  return RDC_OK;
+}
+
+// The hierarchy of rdc_solve_dist_mg: built collectively at the first such solve after a plan (rdc_solve.h: mg_dist_aggregate, the
+// exchange of aggregate numbers, mg_dist_coarsen; mg_dist_goes_on decides on all-reduced sums) and placed by mg_place with its
+// ghost layers.  The two collective calls of a step go through the communicator on a small device buffer.  *comm_rc: a callback's
+// non-zero return (the caller reports RDC_ERR_COMM).  d must carry the work buffer.
+static int mg_view_dist(rdc_ctx* c, SolveDev* d, const rdc_solve_comm_sized* comm, int* comm_rc) {
+  const HostPrep& P = c->ms.prep;
+  SolveState& S = c->ms.solve;
+  MgDev& g = S.mg;
+  if (S.mg_ready && !S.mg_dist) S.mg_ready = false;
+  if (!S.mg_ready) {
+    if (P.bptr[(size_t)P.n_owned] >= ((int64_t)1 << 31)) return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
+    std::vector<MgLevelHost> steps;
+    std::vector<MgHalo> halos(1, S.halo0);
+    const int peers = halos[0].peers();
+    // staging: [send ids | received ids | 2 sums], sized for level 0 (no level below has more to send or receive)
+    const int64_t ns0 = halos[0].n_send(), ng0 = halos[0].n_ghost;
+    int rc = dev_alloc(c, c->buf.solve.mg_stage, (size_t)(ns0 + ng0 + 8) * sizeof(double));
+    if (rc) return rc;
+    double* d_send = (double*)c->buf.solve.mg_stage.p; double* d_recv = d_send + ns0; double* d_sum = d_recv + ng0;
+    std::vector<double> ids_out, ids_in;
+    hipError_t e = hipSuccess;
+    const int64_t* bptr = P.bptr.data();
+    const int32_t* bcol = P.bcol.data();
+    const char* refused = nullptr;
+    for (;;) {
+      const MgHalo& F = halos.back();
+      MgLevelHost L;
+      ids_out.assign((size_t)F.n_send() + 1, 0.0);
+      mg_dist_aggregate(F, bptr, bcol, L, ids_out.data());
+      double sums[2] = {(double)F.n_owned, L.n < F.n_owned ? 1.0 : 0.0};
+      if ((e = hipMemcpyAsync(d_sum, sums, sizeof(sums), hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
+      if ((*comm_rc = comm->base.allreduce_sum(comm->base.user, d_sum, 2, (void*)c->stream))) break;
+      if ((e = hipMemcpyAsync(sums, d_sum, sizeof(sums), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+      if (!mg_dist_goes_on((int)halos.size(), sums[0], sums[1])) break;
+      // the owners' aggregate numbers of this rank's ghosts: one exchange of width 1
+      std::vector<int64_t> so(F.send_off), go(F.ghost_off);
+      ids_in.assign((size_t)F.n_ghost + 1, -1.0);
+      if (F.n_send() && (e = hipMemcpyAsync(d_send, ids_out.data(), (size_t)F.n_send() * sizeof(double), hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
+      if ((*comm_rc = comm->exchange_sized_begin(comm->base.user, d_send, d_recv, peers, so.data(), go.data(), (void*)c->stream))) break;
+      if ((*comm_rc = comm->exchange_sized_end(comm->base.user, (void*)c->stream))) break;
+      if (F.n_ghost && (e = hipMemcpyAsync(ids_in.data(), d_recv, (size_t)F.n_ghost * sizeof(double), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+      MgHalo C;
+      if (!mg_dist_coarsen(F, bptr, bcol, ids_in.data(), L, C)) { refused = "a multigrid level would have 2^31 node blocks or more, or a peer sent no aggregate number"; break; }
+      steps.push_back(std::move(L));
+      halos.push_back(std::move(C));
+      bptr = steps.back().bptr.data();
+      bcol = steps.back().bcol.data();
+    }
+    (void)hipStreamSynchronize(c->stream);
+    if (*comm_rc) return RDC_ERR_COMM;
+    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "building the multigrid levels failed: %s", hipGetErrorString(e));
+    if (refused) return fail(c, RDC_ERR_UNSUPPORTED, "%s", refused);
+    S.mg_off.assign(halos.size(), std::vector<int64_t>());
+    for (size_t l = 1; l < halos.size(); l++) {
+      for (int64_t o : halos[l].send_off) S.mg_off[l].push_back(o * P.nvar);
+      for (int64_t o : halos[l].ghost_off) S.mg_off[l].push_back(o * P.nvar);
+    }
+    if ((rc = mg_upload(c, steps, &halos))) return rc;
+    for (size_t l = 1; l < halos.size(); l++) {
+      g.lv[l].send_off = S.mg_off[l].data();
+      g.lv[l].ghost_off = S.mg_off[l].data() + peers + 1;
+    }
+    S.mg_ready = S.mg_dist = true;
+  }
+  g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
+  g.omega = 1e-3 * c->mg_omega_permille;
+  d->mg = &g;
+  d->peers = S.halo0.peers();
+  return RDC_OK;
+}
+
+// the two partitioned entries.  sized: rdc_solve_dist_mg, the multigrid preconditioner and nothing else; without it rdc_solve_dist
+static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, const rdc_solve_comm_sized* sized, int mixed,
+                           double* d_x, rdc_solve_info* info) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
-  if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
+  if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum || (sized && (!sized->exchange_sized_begin || !sized->exchange_sized_end)))
+    return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
   if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
   if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
-  if (p->precond == RDC_PRECOND_MULTIGRID)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner is not available across partitions (its aggregates would cross ranks)");
+  if (sized && p->precond != RDC_PRECOND_MULTIGRID)
+    return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
+                (int)RDC_PRECOND_MULTIGRID, (int)p->precond);
+  if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
   const HostPrep& P = c->ms.prep;
-  if (P.n_owned < P.n_node && !c->ms.solve.plan_ready)
+  SolveState& S = c->ms.solve;
+  if (P.n_owned < P.n_node && !S.plan_ready)
     return fail(c, RDC_ERR_STATE, "the context has ghost nodes (%lld owned of %lld) and no send list: call rdc_solve_dist_plan first",
                 (long long)P.n_owned, (long long)P.n_node);
+  if (sized && P.n_owned < P.n_node && !S.peers_ready)
+    return fail(c, RDC_ERR_STATE, "the context has ghost nodes (%lld owned of %lld) and no peer counts: call rdc_solve_dist_plan_peers first",
+                (long long)P.n_owned, (long long)P.n_node);
+  if (sized && !S.peers_ready && S.halo0.send_off.empty()) {   // no ghosts and no peer counts: no peers
+    if (S.mg_dist) S.mg_ready = S.mg_dist = false;
+    S.halo0 = MgHalo();
+    S.halo0.n_owned = P.n_owned; S.halo0.send_off.assign(1, 0); S.halo0.ghost_off.assign(1, 0);
+    mg_halo_slots(S.halo0);
+  }
   SolveDev d;
-  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
+  if (mixed) S.f32_copy = false;   // rebuilt from the current values by this call
   int rc = solve_view(c, false, mixed != 0, &d);
   if (rc) return rc;
-  d.dist = c->ms.solve.plan_ready ? c->ms.solve.dist : DistDims{P.n_node, 0, 0};
+  d.dist = S.plan_ready ? S.dist : DistDims{P.n_node, 0, 0};
   d.send_nodes = (const int32_t*)c->buf.solve.send.p;
   if ((rc = dev_alloc(c, c->buf.solve.work, solve_work_bytes(P.nvar, P.n_owned, &d.dist)))) return rc;
   if (!c->solve_rec) RDC_HIP(c, hipHostMalloc((void**)&c->solve_rec, sizeof(SolveScal), hipHostMallocDefault));
   d.work = (double*)c->buf.solve.work.p;
   d.host_rec = c->solve_rec;
   int comm_rc = 0;
-  d.comm = comm; d.comm_rc = &comm_rc;
+  d.comm = comm; d.sized = sized; d.comm_rc = &comm_rc;
+  if (sized) {
+    rc = mg_view_dist(c, &d, sized, &comm_rc);
+    if (comm_rc) return fail(c, RDC_ERR_COMM, "a communication callback returned %d while the multigrid levels were built", comm_rc);
+    if (rc) return rc;
+  }
   const hipError_t e = solve_run(d, *p, d_x, info, mixed != 0);
   if (comm_rc) {
     (void)hipStreamSynchronize(c->stream);   // x holds the last iterate
     return fail(c, RDC_ERR_COMM, "a communication callback returned %d; the solve was abandoned", comm_rc);
   }
   RDC_HIP(c, e);
-  if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
+  if (mixed) S.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   return RDC_OK;
+}
+
+int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) {
+  return solve_dist_call(c, p, comm, nullptr, mixed, d_x, info);
+}
+
+int rdc_solve_dist_mg(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed, double* d_x, rdc_solve_info* info) {
+  return solve_dist_call(c, p, comm ? &comm->base : nullptr, comm, mixed, d_x, info);
 }
 
 int rdc_clamp_nonnegative(rdc_ctx* c, int field) {

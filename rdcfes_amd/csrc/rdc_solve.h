@@ -2,7 +2,8 @@
 // rdc_solve.hip use them.  Host+device like rdc_row.h, so that a CPU build can test exactly this code
 // (tests/host_solve_shim.cpp); free of other headers of the library on purpose.  Further down: the host side of the
 // aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp) and
-// the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp).
+// the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp), and the hierarchy of a
+// ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -207,6 +208,7 @@ RDC_SOLVE_HD void scaled_block(const double (&dinv)[NV][NV], const double (&a)[N
 }  // namespace rdc
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 namespace rdc {
 
@@ -252,13 +254,11 @@ struct MgLevelHost {
   std::vector<int32_t> cnode;    // [fine blocks] ... and the fine node of each (the value layout needs the node's row length)
 };
 
-// false: the coarse level would have 2^31 blocks or more
-inline bool mg_coarsen(int64_t n_fine, const int64_t* bptr, const int32_t* bcol, MgLevelHost& L) {
-  L = MgLevelHost();
-  L.n_fine = n_fine;
-  L.agg.resize((size_t)n_fine);
-  L.n = mg_aggregate(n_fine, bptr, bcol, L.agg.data(), &L.n_pass1);
-  const int64_t na = L.n, nblk = bptr[n_fine];
+// The lists of a coarsening step from its aggregates: L.n_fine, L.n and L.agg are given, and L.agg has an entry for every column
+// of the pattern (behind the n_fine rows: the coarse number of a ghost column, mg_halo_coarsen).  Rows, members and
+// contributions are those of the n_fine row nodes only.  false: the coarse level would have 2^31 blocks or more
+inline bool mg_coarsen_lists(const int64_t* bptr, const int32_t* bcol, MgLevelHost& L) {
+  const int64_t n_fine = L.n_fine, na = L.n, nblk = bptr[n_fine];
   L.mptr.assign((size_t)na + 1, 0);
   for (int64_t i = 0; i < n_fine; i++) L.mptr[(size_t)L.agg[i] + 1]++;
   for (int64_t I = 0; I < na; I++) L.mptr[(size_t)I + 1] += L.mptr[(size_t)I];
@@ -308,6 +308,15 @@ inline bool mg_coarsen(int64_t n_fine, const int64_t* bptr, const int32_t* bcol,
   return true;
 }
 
+// false: as mg_coarsen_lists
+inline bool mg_coarsen(int64_t n_fine, const int64_t* bptr, const int32_t* bcol, MgLevelHost& L) {
+  L = MgLevelHost();
+  L.n_fine = n_fine;
+  L.agg.resize((size_t)n_fine);
+  L.n = mg_aggregate(n_fine, bptr, bcol, L.agg.data(), &L.n_pass1);
+  return mg_coarsen_lists(bptr, bcol, L);
+}
+
 // The whole hierarchy below a matrix of n nodes: steps[l] takes level l to level l + 1.  Stops at a level of at most
 // MG_COARSEST_NODES nodes, at MG_MAX_LEVELS levels, or when a coarsening would merge nothing.  false: as mg_coarsen.
 inline bool mg_build(int64_t n, const int64_t* bptr, const int32_t* bcol, std::vector<MgLevelHost>& steps) {
@@ -325,6 +334,122 @@ inline bool mg_build(int64_t n, const int64_t* bptr, const int32_t* bcol, std::v
   return true;
 }
 
+// ---- the hierarchy on a ghosted context (rdc_solve_dist_mg).  Aggregates never cross a partition, so a rank owns
+// whole coarse rows and builds them alone; what every level needs is its ghost layer.  The steps below are what one rank does
+// between the two collective calls of a coarsening step (an all-reduce that decides, an exchange of aggregate numbers); the caller
+// supplies those, so that a CPU build can drive several ranks in one process (tests/host_solve_mg_dist_shim.cpp). ----
+
+// The ghost layer of one level of one rank.  Peers in the caller's order; the send list and the ghost tail are both grouped by
+// peer in that order, and the send segment for peer q names this rank's nodes in the order of q's ghost segment from this rank.
+struct MgHalo {
+  int64_t n_owned = 0, n_ghost = 0;
+  std::vector<int64_t> send_off, ghost_off;   // [peers + 1] segment bounds, in nodes
+  std::vector<int32_t> send_nodes;            // [send_off.back()] owned nodes, send order
+  std::vector<int64_t> send_ptr;              // [n_owned + 1] the slots of the send buffer that hold node n: send_slot[send_ptr[n] ..
+  std::vector<int32_t> send_slot;             // [send_off.back()] ... send_ptr[n + 1]), ascending (a node has one per peer that sees it)
+  int64_t n_send() const { return (int64_t)send_nodes.size(); }
+  int peers() const { return (int)send_off.size() - 1; }
+};
+
+// send_ptr / send_slot from send_nodes (counting sort: the slots of a node ascend)
+inline void mg_halo_slots(MgHalo& H) {
+  H.send_ptr.assign((size_t)H.n_owned + 1, 0);
+  for (int32_t n : H.send_nodes) H.send_ptr[(size_t)n + 1]++;
+  for (int64_t n = 0; n < H.n_owned; n++) H.send_ptr[(size_t)n + 1] += H.send_ptr[(size_t)n];
+  H.send_slot.resize(H.send_nodes.size());
+  std::vector<int64_t> fill(H.send_ptr.begin(), H.send_ptr.end() - 1);
+  for (size_t i = 0; i < H.send_nodes.size(); i++) H.send_slot[(size_t)fill[(size_t)H.send_nodes[i]]++] = (int32_t)i;
+}
+
+// Level 0 from the plan (send list) and the per-peer counts.  0 = fine; 1 = a count is negative; 2 = the send counts do not add up to
+// the send list; 3 = the ghost counts do not add up to the ghost tail; 4 = a send id is not an owned node
+inline int mg_halo_plan(int64_t n_owned, int64_t n_ghost, int64_t n_send, const int32_t* send_nodes, int n_peers,
+                        const int64_t* send_count, const int64_t* ghost_count, MgHalo& H) {
+  H = MgHalo();
+  H.n_owned = n_owned; H.n_ghost = n_ghost;
+  H.send_off.assign((size_t)n_peers + 1, 0); H.ghost_off.assign((size_t)n_peers + 1, 0);
+  for (int q = 0; q < n_peers; q++) {
+    if (send_count[q] < 0 || ghost_count[q] < 0) return 1;
+    H.send_off[(size_t)q + 1] = H.send_off[(size_t)q] + send_count[q];
+    H.ghost_off[(size_t)q + 1] = H.ghost_off[(size_t)q] + ghost_count[q];
+  }
+  if (H.send_off.back() != n_send) return 2;
+  if (H.ghost_off.back() != n_ghost) return 3;
+  for (int64_t i = 0; i < n_send; i++)
+    if (send_nodes[i] < 0 || send_nodes[i] >= n_owned) return 4;
+  H.send_nodes.assign(send_nodes, send_nodes + n_send);
+  mg_halo_slots(H);
+  return 0;
+}
+
+// Step 1 of a coarsening: mg_aggregate on the edges whose two ends this rank owns (ghost columns ignored; the same passes, constants
+// and ascending order).  Sizes L.agg for every column and fills its owned part; a rank that can merge nothing gets the identity.
+// ids_out [F.n_send()]: what the exchange of width 1 sends, the aggregate of every send node as a double (exact below 2^53).
+inline void mg_dist_aggregate(const MgHalo& F, const int64_t* bptr, const int32_t* bcol, MgLevelHost& L, double* ids_out) {
+  const int64_t n = F.n_owned;
+  std::vector<int64_t> optr((size_t)n + 1, 0);
+  std::vector<int32_t> ocol;
+  for (int64_t i = 0; i < n; i++) {
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++)
+      if (bcol[k] < n) ocol.push_back(bcol[k]);
+    optr[(size_t)i + 1] = (int64_t)ocol.size();
+  }
+  L = MgLevelHost();
+  L.n_fine = n;
+  L.agg.assign((size_t)(n + F.n_ghost), -1);
+  L.n = mg_aggregate(n, optr.data(), ocol.data(), L.agg.data(), &L.n_pass1);
+  for (int64_t i = 0; i < F.n_send(); i++) ids_out[i] = (double)L.agg[(size_t)F.send_nodes[(size_t)i]];
+}
+
+// Step 2, behind the exchange: ids_in [F.n_ghost] = the owner's aggregate number of every ghost node.  The coarse ghosts from peer q
+// are the distinct ids of q's ghost segment in order of first appearance, numbered behind the owned aggregates in peer order; the
+// coarse send segment for q is the distinct own aggregates of the fine send segment for q, in order of first appearance.  The two
+// sequences are the same list on the two sides, so the coarse level needs no message of its own.  Fills the ghost part of L.agg,
+// the lists of L and the coarse ghost layer C.  false: an id is not a count below 2^31, or as mg_coarsen_lists.
+inline bool mg_dist_coarsen(const MgHalo& F, const int64_t* bptr, const int32_t* bcol, const double* ids_in, MgLevelHost& L, MgHalo& C) {
+  const int peers = F.peers();
+  C = MgHalo();
+  C.n_owned = L.n;
+  C.send_off.assign((size_t)peers + 1, 0); C.ghost_off.assign((size_t)peers + 1, 0);
+  std::vector<std::pair<int64_t, int32_t>> known;   // (id, coarse number) of the segment at hand, sorted by id
+  int64_t next = L.n;
+  for (int q = 0; q < peers; q++) {
+    known.clear();
+    for (int64_t g = F.ghost_off[(size_t)q]; g < F.ghost_off[(size_t)q + 1]; g++) {
+      const double idd = ids_in[g];
+      if (!(idd >= 0.0) || !(idd < 2147483648.0) || idd != (double)(int64_t)idd) return false;
+      const int64_t id = (int64_t)idd;
+      auto at = std::lower_bound(known.begin(), known.end(), std::make_pair(id, (int32_t)-1));
+      if (at == known.end() || at->first != id) {
+        if (next >= ((int64_t)1 << 31) - 1) return false;
+        at = known.insert(at, std::make_pair(id, (int32_t)next++));
+      }
+      L.agg[(size_t)(F.n_owned + g)] = at->second;
+    }
+    C.ghost_off[(size_t)q + 1] = next - L.n;
+    known.clear();
+    for (int64_t i = F.send_off[(size_t)q]; i < F.send_off[(size_t)q + 1]; i++) {
+      const int64_t id = L.agg[(size_t)F.send_nodes[(size_t)i]];
+      auto at = std::lower_bound(known.begin(), known.end(), std::make_pair(id, (int32_t)-1));
+      if (at == known.end() || at->first != id) {
+        known.insert(at, std::make_pair(id, (int32_t)0));
+        C.send_nodes.push_back((int32_t)id);
+      }
+    }
+    C.send_off[(size_t)q + 1] = (int64_t)C.send_nodes.size();
+  }
+  C.n_ghost = next - L.n;
+  mg_halo_slots(C);
+  return mg_coarsen_lists(bptr, bcol, L);
+}
+
+// The collective stopping rule, on the two sums every rank holds after the all-reduce of a step: the nodes of the level at hand over
+// all ranks, and the number of ranks whose aggregation merged something.  `levels` exist so far, the matrix included.  With one
+// rank this is the rule of mg_build.
+inline bool mg_dist_goes_on(int levels, double global_nodes, double ranks_that_merged) {
+  return global_nodes > (double)MG_COARSEST_NODES && levels < MG_MAX_LEVELS && ranks_that_merged > 0.0;
+}
+
 // One level of the multigrid hierarchy on the device.  Level 0 is the matrix itself (bptr / bcol only: its values are the
 // context's, its D^-1 the solver's).  A level l >= 1 owns a matrix in the node-block layout, its D_l^-1, three vectors, and
 // the lists that take level l - 1 to it (MgLevelHost of that step).
@@ -335,6 +460,14 @@ struct MgLevelDev {
   double *val = nullptr, *dinv = nullptr, *x = nullptr, *r = nullptr, *t = nullptr;
   const int32_t *agg = nullptr, *member = nullptr, *brow = nullptr, *cidx = nullptr, *cnode = nullptr;
   const int64_t *mptr = nullptr, *cptr = nullptr;
+  // across ranks (level >= 1): x has a ghost tail of n_ghost nodes behind its n owned ones; `send` (n_send nodes) is filled by the
+  // kernel that last writes x, through the slots of every node (MgHalo::send_ptr / send_slot).  send_off / ghost_off: HOST arrays
+  // of peers + 1 offsets in doubles, what the sized exchange callback gets.
+  int64_t n_ghost = 0, n_send = 0;
+  double* send = nullptr;
+  const int64_t* send_ptr = nullptr;
+  const int32_t* send_slot = nullptr;
+  const int64_t *send_off = nullptr, *ghost_off = nullptr;
 };
 
 struct MgDev {
@@ -362,9 +495,12 @@ struct MgArena {
   }
 };
 
+// halos (across ranks only): halos[l] is the ghost layer of level l, level 0 = the plan.  M p and M s then get the ghost tail the
+// outer operator receives into, and every level below its tail of x, its send buffer and its slot lists; without halos the
+// layout is that of rdc_solve, byte for byte.
 template <class Upload>
 inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_owned, int64_t blocks, MgArena& idx, MgArena& val,
-                     MgDev& g, Upload&& upload) {
+                     MgDev& g, Upload&& upload, const std::vector<MgHalo>* halos = nullptr) {
   auto list = [&](const auto& v) {
     const size_t bytes = v.size() * sizeof(v[0]);
     void* at = idx.take(bytes);
@@ -376,7 +512,9 @@ inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_
   g.n_levels = (int)steps.size() + 1;
   g.lv[0].n = n_owned; g.lv[0].blocks = blocks;
   const int64_t n0 = std::max<int64_t>(n_owned * nvar, 1);
-  g.ph = vec(n0); g.sh = vec(n0); g.t0 = vec(n0);
+  const int64_t n0g = halos ? std::max<int64_t>((n_owned + (*halos)[0].n_ghost) * nvar, 1) : n0;
+  g.lv[0].n_ghost = halos ? (*halos)[0].n_ghost : 0;
+  g.ph = vec(n0g); g.sh = vec(n0g); g.t0 = vec(n0);
   for (size_t l = 0; l < steps.size(); l++) {
     const MgLevelHost& L = steps[l];
     MgLevelDev& D = g.lv[l + 1];
@@ -385,7 +523,13 @@ inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_
     D.bptr = list(L.bptr); D.bcol = list(L.bcol); D.brow = list(L.brow);
     D.cptr = list(L.cptr); D.cidx = list(L.cidx); D.cnode = list(L.cnode);
     D.val = vec(D.blocks * nvar * nvar); D.dinv = vec(L.n * nvar * nvar);
-    D.x = vec(L.n * nvar); D.r = vec(L.n * nvar); D.t = vec(L.n * nvar);
+    if (halos) {
+      const MgHalo& H = (*halos)[l + 1];
+      D.n_ghost = H.n_ghost; D.n_send = H.n_send();
+      D.send_ptr = list(H.send_ptr); D.send_slot = list(H.send_slot);
+      D.send = vec(std::max<int64_t>(D.n_send * nvar, 1));
+    }
+    D.x = vec((L.n + D.n_ghost) * nvar); D.r = vec(L.n * nvar); D.t = vec(L.n * nvar);
   }
 }
 
@@ -490,6 +634,8 @@ struct SolveDev {
   MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
   // partitioned solve (rdc_solve_dist) only.  comm == nullptr is the single-partition path.
   const rdc_solve_comm* comm = nullptr;
+  int peers = 0;                                 // rdc_solve_dist_plan_peers
+  const rdc_solve_comm_sized* sized = nullptr;   // rdc_solve_dist_mg: comm = &sized->base, and the exchange of the levels below the matrix
   DistDims dist;                       // n_nodes, interior nodes, length of the send list
   const int32_t* send_nodes = nullptr; // device copy of the send list (owned local node ids, send order)
   int* comm_rc = nullptr;              // out: the first non-zero return of a callback; nothing is called after it

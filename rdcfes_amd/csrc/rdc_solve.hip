@@ -29,7 +29,10 @@
 // Across partitions (rdc_solve_dist): the same driver with a communicator.  apply_halo wraps an operator application
 // into pack / exchange_begin / rows without ghost columns / exchange_end / the other rows, and k_finalize becomes k_reduce, the
 // all-reduce callback and k_advance, so that every scalar the host reads and every branch it takes is global.  Without a
-// communicator the launches are those of the single-partition path, in the same order.
+// communicator the launches are those of the single-partition path, in the same order.  Multigrid across ranks (rdc_solve_dist_mg):
+// aggregates stay inside a partition, every level has a ghost layer (rdc_solve.h, MgHalo), mg_apply exchanges the argument of every
+// operator application inside the cycle, and on the levels below the matrix the kernel that last writes a vector also fills the
+// level's send buffer (k_restrict_pack, k_prolong_pack, k_smooth_pack), so that a coarse exchange costs no launch.
 //
 // Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy, multigrid cycle and communicator are
 // arguments), `apply` the one entry to y = A_l x on any level in any form; `carve` (rdc_solve.h) is the one statement of the work
@@ -474,13 +477,29 @@ __global__ __launch_bounds__(256) void k_galerkin(const int64_t* __restrict__ cp
   cval[(int64_t)NV * NV * cb0 + ((int64_t)a * clen + (c - cb0)) * NV + b] = s;
 }
 
+// Across ranks (PACK, levels below the matrix): the kernel that last writes a vector which is exchanged next also writes that
+// node's entries of the level's send buffer, so that a coarse exchange costs no launch of its own.  send_slot[send_ptr[n] ..
+// send_ptr[n + 1]) are the slots of node n (one per peer that holds it as a ghost, usually none): entry (slot, a) gets the value
+// the thread has just stored to x, from its register -- no thread reads what another wrote.
+struct SendList {
+  const int64_t* ptr;
+  const int32_t* slot;
+  double* buf;
+};
+
+template <int NV>
+__device__ __forceinline__ void pack_entry(const SendList& s, int64_t node, int a, double value) {
+  const int64_t s1 = s.ptr[node + 1];
+  for (int64_t i = s.ptr[node]; i < s1; i++) s.buf[(int64_t)s.slot[i] * NV + a] = value;
+}
+
 // r_c = P^T (r - t) and the first smoothing sweep of the coarse level, x_c = w D_c^-1 r_c: one thread per aggregate, its
 // members in ascending order
-template <int NV>
-__global__ __launch_bounds__(256) void k_restrict(const int64_t* __restrict__ mptr, const int32_t* __restrict__ member,
-                                                  const double* __restrict__ r, const double* __restrict__ t,
-                                                  const double* __restrict__ cdinv, double omega, int64_t n_coarse,
-                                                  double* __restrict__ rc, double* __restrict__ xc) {
+template <int NV, bool PACK>
+__device__ __forceinline__ void restrict_body(const int64_t* __restrict__ mptr, const int32_t* __restrict__ member,
+                                              const double* __restrict__ r, const double* __restrict__ t,
+                                              const double* __restrict__ cdinv, double omega, int64_t n_coarse,
+                                              double* __restrict__ rc, double* __restrict__ xc, const SendList& send) {
   const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (I >= n_coarse) return;
   double acc[NV];
@@ -499,31 +518,62 @@ __global__ __launch_bounds__(256) void k_restrict(const int64_t* __restrict__ mp
     for (int q = 0; q < NV; q++) z = fma(cdinv[(I * NV + a) * NV + q], acc[q], z);
     rc[I * NV + a] = acc[a];
     xc[I * NV + a] = omega * z;
+    if (PACK) pack_entry<NV>(send, I, a, omega * z);
   }
 }
 
-// x += P x_c: one thread per fine unknown, one read of agg[n]
 template <int NV>
-__global__ __launch_bounds__(256) void k_prolong(const int32_t* __restrict__ agg, const double* __restrict__ xc, double* __restrict__ x,
-                                                 int64_t n_fine) {
+__global__ __launch_bounds__(256) void k_restrict(const int64_t* __restrict__ mptr, const int32_t* __restrict__ member,
+                                                  const double* __restrict__ r, const double* __restrict__ t,
+                                                  const double* __restrict__ cdinv, double omega, int64_t n_coarse,
+                                                  double* __restrict__ rc, double* __restrict__ xc) {
+  restrict_body<NV, false>(mptr, member, r, t, cdinv, omega, n_coarse, rc, xc, SendList{});
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_restrict_pack(const int64_t* __restrict__ mptr, const int32_t* __restrict__ member,
+                                                       const double* __restrict__ r, const double* __restrict__ t,
+                                                       const double* __restrict__ cdinv, double omega, int64_t n_coarse,
+                                                       double* __restrict__ rc, double* __restrict__ xc, SendList send) {
+  restrict_body<NV, true>(mptr, member, r, t, cdinv, omega, n_coarse, rc, xc, send);
+}
+
+// x += P x_c: one thread per fine unknown, one read of agg[n]
+template <int NV, bool PACK>
+__device__ __forceinline__ void prolong_body(const int32_t* __restrict__ agg, const double* __restrict__ xc, double* __restrict__ x,
+                                             int64_t n_fine, const SendList& send) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_fine * NV) return;
   const int64_t n = i / NV;
-  x[i] += xc[(int64_t)agg[n] * NV + (i - n * NV)];
+  const double xn = x[i] + xc[(int64_t)agg[n] * NV + (i - n * NV)];
+  x[i] = xn;
+  if (PACK) pack_entry<NV>(send, n, (int)(i - n * NV), xn);
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_prolong(const int32_t* __restrict__ agg, const double* __restrict__ xc, double* __restrict__ x,
+                                                 int64_t n_fine) {
+  prolong_body<NV, false>(agg, xc, x, n_fine, SendList{});
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_prolong_pack(const int32_t* __restrict__ agg, const double* __restrict__ xc,
+                                                      double* __restrict__ x, int64_t n_fine, SendList send) {
+  prolong_body<NV, true>(agg, xc, x, n_fine, send);
 }
 
 // damped block Jacobi, one thread per unknown: x = w D^-1 r (FIRST) or x += w D^-1 (r - t); IDENT: D = I (level 0, whose
 // operator D^-1 A has the identity on its block diagonal)
-template <int NV, bool IDENT, bool FIRST>
-__global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv, const double* __restrict__ r, const double* __restrict__ t,
-                                                double omega, int64_t n, double* __restrict__ x) {
+template <int NV, bool IDENT, bool FIRST, bool PACK>
+__device__ __forceinline__ void smooth_body(const double* __restrict__ dinv, const double* __restrict__ r, const double* __restrict__ t,
+                                            double omega, int64_t n, double* __restrict__ x, const SendList& send) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * NV) return;
+  const int64_t node = i / NV;
   double z;
   if (IDENT) {
     z = FIRST ? r[i] : r[i] - t[i];
   } else {
-    const int64_t node = i / NV;
     z = 0.0;
 #pragma unroll
     for (int q = 0; q < NV; q++) {
@@ -531,7 +581,23 @@ __global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv,
       z = fma(dinv[i * NV + q], res, z);
     }
   }
-  x[i] = FIRST ? omega * z : x[i] + omega * z;
+  const double xn = FIRST ? omega * z : x[i] + omega * z;
+  x[i] = xn;
+  if (PACK) pack_entry<NV>(send, node, (int)(i - node * NV), xn);
+}
+
+template <int NV, bool IDENT, bool FIRST>
+__global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv, const double* __restrict__ r, const double* __restrict__ t,
+                                                double omega, int64_t n, double* __restrict__ x) {
+  smooth_body<NV, IDENT, FIRST, false>(dinv, r, t, omega, n, x, SendList{});
+}
+
+// the sweeps on a level below the matrix across ranks
+template <int NV>
+__global__ __launch_bounds__(256) void k_smooth_pack(const double* __restrict__ dinv, const double* __restrict__ r,
+                                                     const double* __restrict__ t, double omega, int64_t n, double* __restrict__ x,
+                                                     SendList send) {
+  smooth_body<NV, false, false, true>(dinv, r, t, omega, n, x, send);
 }
 
 // First use of every kernel instantiation.  A code object lists template instantiations by first use; this list keeps the order
@@ -546,7 +612,9 @@ __global__ __launch_bounds__(256) void k_smooth(const double* __restrict__ dinv,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
     (const void*)k_precond_setup<3>, (const void*)k_scale_f32<3>, (const void*)k_precond_setup<5>, (const void*)k_scale_f32<5>,
     KERNELS_OF(3), (const void*)k_update_xr<true>, (const void*)k_update_xr<false>, KERNELS_OF(5),
-    (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>};
+    (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>,
+    (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
+    (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>};
 #undef KERNELS_OF
 
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
@@ -684,20 +752,42 @@ hipError_t setup(const SolveDev& d, const Work& w, int precond, bool f32) {
   return hipGetLastError();
 }
 
+// Across ranks: does the kernel that writes x on level l also fill the level's send buffer?  (Level 0 keeps k_halo_pack.)
+inline bool packs(const SolveDev& d, int l) { return d.sized && l > 0 && d.mg->lv[l].n_send > 0; }
+inline SendList send_list(const MgLevelDev& L) { return SendList{L.send_ptr, L.send_slot, L.send}; }
+
+// y = A_l x inside the cycle.  Across ranks x is exchanged first (it is written: its ghost tail receives): level 0 as apply_halo
+// does it, a level below through the sized exchange of the send buffer its last writer filled, then one launch over the owned rows.
+template <int NV>
+hipError_t mg_apply(const SolveDev& d, const Work& w, int l, Form form, double* x, double* y) {
+  if (l == 0) return apply_halo<NV>(d, w, form, x, y, nullptr);
+  if (d.sized) {
+    const MgLevelDev& L = d.mg->lv[l];
+    SOLVE_HIP(callback(d, d.sized->exchange_sized_begin(d.comm->user, L.send, x + L.n * NV, d.peers, L.send_off, L.ghost_off, (void*)d.stream)));
+    SOLVE_HIP(callback(d, d.sized->exchange_sized_end(d.comm->user, (void*)d.stream)));
+  }
+  return apply<NV>(d, &w, l, form, x, y, nullptr);
+}
+
 // x += w D_l^-1 (r - A_l x)
 template <int NV>
 hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, double* t) {
   const MgDev& g = *d.mg;
   const int64_t n = g.lv[l].n;
-  SOLVE_HIP(apply<NV>(d, &w, l, form, x, t, nullptr));
+  SOLVE_HIP(mg_apply<NV>(d, w, l, form, x, t));
+  if (!n) return hipSuccess;   // a rank may own no node of a level
   if (l == 0)
     hipLaunchKernelGGL((k_smooth<NV, true, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
+  else if (packs(d, l))
+    hipLaunchKernelGGL((k_smooth_pack<NV>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x,
+                       send_list(g.lv[l]));
   else
     hipLaunchKernelGGL((k_smooth<NV, false, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
   return hipGetLastError();
 }
 
-// out = M in: one V(1,1) cycle from a zero start.  Enqueues only; a fixed linear operator for fixed values.
+// out = M in: one V(1,1) cycle from a zero start.  Enqueues only; a fixed linear operator for fixed values.  Across ranks `out`
+// has a ghost tail, and with L >= 2 levels the cycle makes 2 exchanges of the plan's size and 2 (L - 2) + 7 sized ones.
 template <int NV>
 hipError_t mg_cycle(const SolveDev& d, const Work& w, Form form, const double* in, double* out) {
   const MgDev& g = *d.mg;
@@ -705,18 +795,30 @@ hipError_t mg_cycle(const SolveDev& d, const Work& w, Form form, const double* i
   auto R = [&](int l) { return l == 0 ? in : (const double*)g.lv[l].r; };
   auto X = [&](int l) { return l == 0 ? out : g.lv[l].x; };
   auto T = [&](int l) { return l == 0 ? g.t0 : g.lv[l].t; };
-  hipLaunchKernelGGL((k_smooth<NV, true, true>), per_thread(w.n), dim3(256), 0, d.stream, (const double*)nullptr, in,
-                     (const double*)nullptr, g.omega, d.n_owned, out);
+  if (w.n)
+    hipLaunchKernelGGL((k_smooth<NV, true, true>), per_thread(w.n), dim3(256), 0, d.stream, (const double*)nullptr, in,
+                       (const double*)nullptr, g.omega, d.n_owned, out);
   for (int l = 0; l < last; l++) {   // down: residual of the first sweep, restricted; the coarse level's first sweep rides along
     const MgLevelDev& C = g.lv[l + 1];
-    SOLVE_HIP(apply<NV>(d, &w, l, form, X(l), T(l), nullptr));
-    hipLaunchKernelGGL((k_restrict<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
-                       (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x);
+    SOLVE_HIP(mg_apply<NV>(d, w, l, form, X(l), T(l)));
+    if (!C.n) continue;
+    if (packs(d, l + 1))
+      hipLaunchKernelGGL((k_restrict_pack<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
+                         (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x, send_list(C));
+    else
+      hipLaunchKernelGGL((k_restrict<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
+                         (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x);
   }
   for (int sweep = 1; sweep < MG_COARSEST_SWEEPS; sweep++) SOLVE_HIP(mg_smooth<NV>(d, w, last, form, R(last), X(last), T(last)));
   for (int l = last - 1; l >= 0; l--) {   // up: correction, then the second sweep
     const int64_t n = g.lv[l].n;
-    hipLaunchKernelGGL((k_prolong<NV>), per_thread(n * NV), dim3(256), 0, d.stream, g.lv[l + 1].agg, (const double*)g.lv[l + 1].x, X(l), n);
+    if (n) {
+      if (packs(d, l))
+        hipLaunchKernelGGL((k_prolong_pack<NV>), per_thread(n * NV), dim3(256), 0, d.stream, g.lv[l + 1].agg, (const double*)g.lv[l + 1].x, X(l), n,
+                           send_list(g.lv[l]));
+      else
+        hipLaunchKernelGGL((k_prolong<NV>), per_thread(n * NV), dim3(256), 0, d.stream, g.lv[l + 1].agg, (const double*)g.lv[l + 1].x, X(l), n);
+    }
     SOLVE_HIP(mg_smooth<NV>(d, w, l, form, R(l), X(l), T(l)));
   }
   return hipGetLastError();
@@ -731,6 +833,7 @@ hipError_t mg_setup(const SolveDev& d, const Work& w) {
     const int64_t* fbptr = l == 1 ? d.bptr : g.lv[l - 1].bptr;
     const double* fval = l == 1 ? d.val : (const double*)g.lv[l - 1].val;
     const dim3 grid = per_thread(C.blocks * NV * NV);
+    if (!C.n) continue;   // across ranks: a rank may own no node of a level
     if (l == 1)
       hipLaunchKernelGGL((k_galerkin<NV, true>), grid, dim3(256), 0, d.stream, C.cptr, C.cidx, C.cnode, C.brow, C.blocks, fbptr, fval,
                          (const double*)w.dinv, C.bptr, C.val);
@@ -749,7 +852,7 @@ template <int NV>
 hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, bool mg) {
   const dim3 vg((unsigned)w.vec_blocks), vb(256);
   const int64_t parts = op_parts(d.n_owned, d.comm ? d.dist.n_int : 0, form);
-  double* px = mg ? d.mg->ph : w.p;   // across partitions (never with mg): p and s themselves, whose ghost tails receive
+  double* px = mg ? d.mg->ph : w.p;   // across partitions: the ghost tails of these receive (mg_place gives M p and M s one too)
   double* sx = mg ? d.mg->sh : w.s;
   if (vg.x) hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
   if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.p, d.mg->ph));

@@ -10,7 +10,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .params import ALLREDUCE_SUM_FN, EXCHANGE_BEGIN_FN, EXCHANGE_END_FN, SolveCommStruct
+from .params import (ALLREDUCE_SUM_FN, EXCHANGE_BEGIN_FN, EXCHANGE_END_FN, EXCHANGE_SIZED_BEGIN_FN, SolveCommSizedStruct,
+                     SolveCommStruct)
 
 
 class HaloExchange:
@@ -119,9 +120,15 @@ class SolveComm:
 
     send_nodes is the send list for rdc_solve_dist_plan (peer order, per peer the order of lp.send_ids, which is the order of
     the peer's lp.recv_ids: ascending global id on both sides).  An exception inside a callback is kept in .error and the
-    callback returns 1; solve_dist re-raises it.  Subclasses may override begin / end / allreduce (tests do)."""
+    callback returns 1; solve_dist re-raises it.  Subclasses may override begin / end / allreduce (tests do).
 
-    def __init__(self, lp, nvar: int, device, group=None):
+    sized=True adds what the multigrid solve across ranks needs (rdc_solve_comm_sized, rdc_solve_dist_mg): sized_begin / sized_end
+    move the ghost values of a level below the matrix, whose per-peer slices come with the call, over ONE peer list (`peers`: every
+    rank this one sends to or receives from, ascending); peer_counts are the plan's segment lengths over that list for
+    rdc_solve_dist_plan_peers.  The gloo staging buffers serve them too: no level has more to move than the plan.  Without it
+    solve_dist(precond=PRECOND_MULTIGRID) stays RDC_ERR_UNSUPPORTED."""
+
+    def __init__(self, lp, nvar: int, device, group=None, sized=False):
         self.group, self.nvar, self.rank = group, int(nvar), lp.rank
         self.dev = torch.device(device)
         peers = sorted(set(lp.send_ids) | set(lp.recv_ids))
@@ -148,13 +155,26 @@ class SolveComm:
             mk = lambda rows: torch.empty((rows, self.nvar), dtype=torch.float64, pin_memory=pin)
             self.send_host, self.recv_host = mk(self.n_send), mk(self.n_ghost)
             self.vals_host = torch.empty(8, dtype=torch.float64, pin_memory=pin)
-        self.exchanges = self.allreduces = 0
+        self.exchanges = self.allreduces = self.sized_exchanges = 0
+        self.peers = peers
+        self.peer_counts = (np.array([len(lp.send_ids.get(q, ())) for q in peers], dtype=np.int64),
+                            np.array([len(lp.recv_ids.get(q, ())) for q in peers], dtype=np.int64))
+        # the plan's send list and the ghost tail are grouped by peer in this order, or the counts would not describe them
+        o = 0
+        for q in peers:
+            if q in self.recv_slice and self.recv_slice[q][0] != o:
+                raise ValueError("the ghost tail is not grouped by owner in ascending rank order")
+            o += len(lp.recv_ids.get(q, ()))
         self.error = None
-        self._views, self._streams, self._pending, self._recv = {}, {}, [], None
+        self._views, self._streams, self._pending, self._recv, self._recv_sized = {}, {}, [], None, None
         # the ctypes function objects must outlive every call that uses the struct
         self._cb = (EXCHANGE_BEGIN_FN(self._guard(self._c_begin)), EXCHANGE_END_FN(self._guard(self._c_end)),
                     ALLREDUCE_SUM_FN(self._guard(self._c_allreduce)))
         self.struct = SolveCommStruct(None, *self._cb)
+        self.sized_struct = None
+        if sized:
+            self._cb_sized = (EXCHANGE_SIZED_BEGIN_FN(self._guard(self._c_sized_begin)), EXCHANGE_END_FN(self._guard(self._c_sized_end)))
+            self.sized_struct = SolveCommSizedStruct(self.struct, *self._cb_sized)
 
     # -- raw addresses -> torch
     def _view(self, addr, rows):
@@ -201,6 +221,61 @@ class SolveComm:
             v.__cuda_array_interface__ = {"shape": (8,), "typestr": "<f8", "data": (d_vals, False), "version": 2, "strides": None}
             self._views[key] = torch.as_tensor(v, device=self.dev)
         return self.allreduce(self._views[key][:n], self._stream(stream))
+
+    def _flat(self, addr, count):
+        """zero-copy [count] view of device memory at addr"""
+        if count == 0 or not addr:
+            return torch.empty(0, dtype=torch.float64, device=self.dev)
+        key = ("flat", addr, count)
+        if key not in self._views:
+            class _V:
+                pass
+            v = _V()
+            v.__cuda_array_interface__ = {"shape": (count,), "typestr": "<f8", "data": (addr, False), "version": 2, "strides": None}
+            self._views[key] = torch.as_tensor(v, device=self.dev)
+        return self._views[key]
+
+    def _c_sized_begin(self, user, d_send, d_recv, n_peers, send_off, recv_off, stream):
+        if n_peers != len(self.peers):
+            raise ValueError(f"the library names {n_peers} peers, this communicator has {len(self.peers)}")
+        so, ro = [int(send_off[k]) for k in range(n_peers + 1)], [int(recv_off[k]) for k in range(n_peers + 1)]
+        return self.sized_begin(self._flat(d_send, so[-1]), self._flat(d_recv, ro[-1]), so, ro, self._stream(stream))
+
+    def _c_sized_end(self, user, stream):
+        return self.sized_end(self._stream(stream))
+
+    # -- the sized exchange on tensors.  send / recv: flat, send_off[-1] and recv_off[-1] doubles; peer k of self.peers owns
+    #    send[send_off[k]:send_off[k + 1]] and fills recv[recv_off[k]:recv_off[k + 1]]
+    def sized_begin(self, send, recv, send_off, recv_off, stream):
+        self.sized_exchanges += 1
+        if self.world == 1 or not self.peers:
+            return 0
+        with torch.cuda.stream(stream):
+            if self.host_staged:
+                sb, rb = self.send_host.view(-1)[:send.numel()], self.recv_host.view(-1)[:recv.numel()]
+                if send.numel():
+                    sb.copy_(send, non_blocking=True)
+                stream.synchronize()
+                self._recv_sized = (recv, rb)
+            else:
+                sb, rb, self._recv_sized = send, recv, None
+            ops = [dist.P2POp(dist.irecv, rb[recv_off[k]:recv_off[k + 1]], q, group=self.group)
+                   for k, q in enumerate(self.peers) if recv_off[k + 1] > recv_off[k]]
+            ops += [dist.P2POp(dist.isend, sb[send_off[k]:send_off[k + 1]], q, group=self.group)
+                    for k, q in enumerate(self.peers) if send_off[k + 1] > send_off[k]]
+            self._pending = dist.batch_isend_irecv(ops) if ops else []
+        return 0
+
+    def sized_end(self, stream):
+        if self.world == 1 or not self.peers:
+            return 0
+        with torch.cuda.stream(stream):
+            for w in self._pending:
+                w.wait()
+            self._pending = []
+            if self._recv_sized is not None and self._recv_sized[0].numel():
+                self._recv_sized[0].copy_(self._recv_sized[1], non_blocking=True)
+        return 0
 
     # -- the three callbacks on tensors.  send: [n_send][nvar], packed; recv: [n_ghost][nvar], the ghost tail; stream: the library's
     def begin(self, send, recv, stream):

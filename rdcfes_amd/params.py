@@ -115,6 +115,16 @@ class SolveCommStruct(C.Structure):
                 ("allreduce_sum", ALLREDUCE_SUM_FN)]
 
 
+# user, d_send, d_recv, n_peers, send_off, recv_off (host arrays of n_peers + 1 offsets in doubles), hip_stream
+EXCHANGE_SIZED_BEGIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.c_void_p)
+
+
+class SolveCommSizedStruct(C.Structure):
+    """rdc_solve_comm_sized: rdc_solve_comm and the exchange whose sizes come with the call (rdc_solve_dist_mg)."""
+    _fields_ = [("base", SolveCommStruct), ("exchange_sized_begin", EXCHANGE_SIZED_BEGIN_FN), ("exchange_sized_end", EXCHANGE_END_FN)]
+
+
 # reference parameter key -> struct field
 PIHNA_KEYS = {
     "time_step": "time_step",

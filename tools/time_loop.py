@@ -13,11 +13,12 @@ holds.  --ab runs the loop four times from the same initial state on one upload,
 process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, multigrid, block Jacobi (all four fp64, or all
 four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
 rdc_solve_dist, rdc_solve_dist, rdc_solve, the partitioned entry at world size 1 (its exchange moves nothing and its all-reduce
-leaves the values alone: what is timed is the pack launches, the k_reduce / k_advance split and the callbacks).  --dump writes
+leaves the values alone: what is timed is the pack launches, the k_reduce / k_advance split and the callbacks; with --precond 3
+the partitioned entry is rdc_solve_dist_mg, whose cycle adds the sized callbacks of the levels below the matrix).  --dump writes
 the state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
-rdc_solve_dist -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
+rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
 no halo update of its own.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
 iterations and the global true residual.  Rank r uses GPU r modulo the number of GPUs: on a one-GPU machine the ranks share it,
 and with --backend gloo every message is staged through the host -- such a run checks correctness and measures nothing."""
@@ -106,7 +107,7 @@ def rank_main(rank, world, port, a):
             ctx.set_option("interior_nodes", int(lp.n_interior))
             ctx.mesh_upload(4, lp.conn, lp.xyz, 5, n_owned=lp.n_owned)
             ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
-            comm = SolveComm(lp, 5, torch.device("cuda", gpu))
+            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=a.precond == 3)   # multigrid: rdc_solve_dist_mg
             shared = world > torch.cuda.device_count()
             head = dict(rank=rank, gpu=gpu, owned_nodes=int(lp.n_owned), interior_nodes=int(lp.n_interior),
                         ghost_nodes=int(lp.xyz.shape[0] - lp.n_owned), halo_bytes_per_exchange=comm.bytes_per_exchange,
@@ -119,6 +120,7 @@ def rank_main(rank, world, port, a):
             for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, a.precond, a.max_its, mixed=a.mixed, comm=comm):
                 if rank == 0:          # every figure of the solve is global and the same on every rank
                     keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
+                    keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if a.precond == 3 else ()     # rank 0's own levels
                     print(json.dumps({k: rec[k] for k in keep}), flush=True)
         dist.barrier()
     finally:
@@ -167,11 +169,11 @@ def main():
             from rdcfes_amd import SolveComm, partition
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
-            comm = SolveComm(lp, 5, torch.device("cuda", 0))
+            comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3)
         for precond, mixed, dist_entry in runs:
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
-                                  entry="rdc_solve_dist, world size 1" if dist_entry else "rdc_solve")))
+                                  entry=("rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") + ", world size 1" if dist_entry else "rdc_solve")))
             for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None):
                 print(json.dumps(rec), flush=True)
         if a.dump:
