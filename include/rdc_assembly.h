@@ -325,7 +325,9 @@ int rdc_host_unpin(rdc_ctx* ctx, void* host_ptr);
 /* two-part assembly: the rows of nodes [0, *n_nodes) are complete after "part" = 1 (whole workgroups inside the
  * interior; 0 when the active kernel path cannot launch sub-ranges).  After a part-1 assemble call the value is what
  * THAT call completed -- the kernel path, and with it the split, depends on the model, the parameter values and the
- * tuning options; before any part-1 call since the upload it is the prediction for the default path. */
+ * tuning options; before any part-1 call since the upload it is the prediction for a shipped-pattern PIHNA call with the
+ * current scatter strategy, kernel variant, cluster mode and tuning options, on the lists the mesh has at that moment (the
+ * call's own decision; it builds nothing, so lists that only the first assembly builds are not counted on). */
 int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 
 /* ---- device-resident linear solve: what the reference does in model.solve() (src/pihna.C:80) and in the Newton /

@@ -11,7 +11,6 @@
 
 #include "rdc_internal.h"
 #include "rdc_parts.h"
-#include "rdc_tet4_pihna_moments.h"
 #include "rdc_tet4_ev.h"
 #include "rdc_tet4_cl.h"
 #include "rdc_solid.h"
@@ -264,14 +263,35 @@ int64_t field_expected(const rdc_ctx* c, int field) {
   return rows * field_width(c, field);
 }
 
+bool rowgather_available(const rdc_ctx* c) {
+  return c->ms.prep.rowgather_ok || (c->ms.prep.rg2_ok && c->ms.prep.nen == 4 && c->variant != RDC_VARIANT_GENERIC);
+}
+
+// the scatter strategy with AUTO resolved
+int strategy_of(const rdc_ctx* c) {
+  if (c->strategy != RDC_SCATTER_AUTO) return c->strategy;
+  return rowgather_available(c) ? RDC_SCATTER_ROWGATHER : RDC_SCATTER_COLOURED;
+}
+
 int resolve_strategy(rdc_ctx* c, int* out) {
-  int s = c->strategy;
-  const bool rg = c->ms.prep.rowgather_ok || (c->ms.prep.rg2_ok && c->ms.prep.nen == 4 && c->variant != RDC_VARIANT_GENERIC);
-  if (s == RDC_SCATTER_AUTO) s = rg ? RDC_SCATTER_ROWGATHER : RDC_SCATTER_COLOURED;
-  if (s == RDC_SCATTER_ROWGATHER && !rg)
+  *out = strategy_of(c);
+  if (*out == RDC_SCATTER_ROWGATHER && !rowgather_available(c))
     return fail(c, RDC_ERR_UNSUPPORTED, "row-gather scatter unavailable: a node row exceeds the LDS budget");
-  *out = s;
   return RDC_OK;
+}
+
+// What the kernel-path decision (rdc_path.h) reads of the context and the lists its mesh has at this moment.  The two facts that
+// depend on the model are the caller's: pattern, and cl_fits (the LDS image of k_tet4_cl)
+Facts path_facts(const rdc_ctx* c, int strategy) {
+  const MeshState::ClusterLists& L = c->ms.cl;
+  Facts f;
+  f.strategy = strategy; f.variant = c->variant; f.opt = c->opt; f.tet4_cl_mode = c->tet4_cl_mode;
+  f.stamps = c->buf.scratch.stamps.p != nullptr;
+  list_facts(c->ms.prep, c->ms.prep_ev, f);
+  f.ev_tried = c->ms.ev_tried;
+  f.cl_ready = L.state == 1 && L.waves == c->opt.solid_cl_waves && L.interior == c->opt.interior_nodes &&
+               (c->opt.solid_cl_order < 0 || L.order == c->opt.solid_cl_order);   // what ensure_cluster_lists would keep
+  return f;
 }
 
 // hands out the next (start, stop) event pair of the timing pool, growing it on demand
@@ -289,47 +309,34 @@ int next_event_pair(rdc_ctx* c, hipEvent_t* start, hipEvent_t* stop) {
   return RDC_OK;
 }
 
-// parameter-sparsity specialisation: models may offer a variant with smaller structural masks that is
-// exact for the given parameter values (PIHNA with the cell transport terms off)
-template <class M, class P>
-hipError_t launch_specialised(const LaunchArgs& a, const typename M::K& k, const P&) { return launch_rd<M>(a, k); }
-template <>
-hipError_t launch_specialised<Pihna, rdc_pihna_params>(const LaunchArgs& a, const Pihna::K& k, const rdc_pihna_params& p) {
-  // any parameter values: the element-visit kernel with all 22 moments ("ev_general", rdc_tet4_ev.h GEN)
-  if (a.nen == 4 && a.variant != RDC_VARIANT_GENERIC && a.ev_general && a.use_ev && a.ev.n_wg > 0 && a.strategy == RDC_SCATTER_ROWGATHER) return launch_tet4_ev(a, k);
-  if (a.nen == 4 && a.variant != RDC_VARIANT_GENERIC && a.opt.specialise && PihnaNoCellTransport::applies(p)) {
-    // default: one thread per element visit, moments accumulated per node block (rdc_tet4_ev.hip)
-    if (a.use_ev && a.ev.n_wg > 0 && a.strategy == RDC_SCATTER_ROWGATHER) return launch_tet4_ev(a, k);
-    if (a.opt.moments) return launch_tet4_fast<PihnaNoCellTransportMoments>(a, k);  // same sums, moment form
-    return launch_tet4_fast<PihnaNoCellTransport>(a, k);
+// instantiation I of model M on the path of the plan
+template <class M, class I>
+hipError_t launch_path(const LaunchArgs& a, const typename M::K& k) {
+  switch (a.plan.path) {
+    case Path::TET4_CL: return launch_tet4_cl<I>(a, k);
+    case Path::TET4_EV:
+      if constexpr (std::is_same<M, Pihna>::value) return launch_tet4_ev(a, k);
+      break;
+    case Path::TET4_EVC: case Path::TET4_RG5: case Path::TET4_RG3: case Path::TET4_RG2: case Path::TET4_ROWGATHER: case Path::TET4_COLOURED:
+      return launch_tet4_fast<I>(a, k);
+    case Path::HEX8_CL: case Path::HEX8_CL_ROWS: case Path::GENERIC_ROWGATHER: case Path::GENERIC_COLOURED:
+      if constexpr (std::is_same<M, I>::value || !Forms<M>::TET4_ONLY) return launch_rd<I>(a, k);
+      break;
   }
-  return launch_rd<Pihna>(a, k);
+  return hipErrorInvalidValue;   // a path this instantiation does not have
 }
 
-template <>
-hipError_t launch_specialised<Ripf, rdc_ripf_params>(const LaunchArgs& a, const Ripf::K& k, const rdc_ripf_params& p) {
-  if (a.nen == 4 && a.variant != RDC_VARIANT_GENERIC && a.opt.specialise && RipfReduced::applies(p)) return launch_tet4_fast<RipfReduced>(a, k);
-  return launch_rd<Ripf>(a, k);
+template <class M>
+hipError_t launch_specialised(const LaunchArgs& a, const typename M::K& k) {
+  switch (a.plan.inst) {
+    case Inst::SPARSE: return launch_path<M, typename Forms<M>::Sparse>(a, k);
+    case Inst::MOMENTS:
+      if constexpr (std::is_same<M, Pihna>::value) return launch_path<M, PihnaNoCellTransportMoments>(a, k);
+      return hipErrorInvalidValue;
+    case Inst::FULL: break;
+  }
+  return launch_path<M, M>(a, k);
 }
-
-// the all-rates-zero HCC of run/Coupled/HCC and the decay-only ADPM of run/HCP102513: any element type and kernel
-template <>
-hipError_t launch_specialised<Hcc, rdc_hcc_params>(const LaunchArgs& a, const Hcc::K& k, const rdc_hcc_params& p) {
-  if (a.variant != RDC_VARIANT_GENERIC && a.opt.specialise && HccMassOnly::applies(p)) return launch_rd<HccMassOnly>(a, k);
-  return launch_rd<Hcc>(a, k);
-}
-template <>
-hipError_t launch_specialised<Adpm, rdc_adpm_params>(const LaunchArgs& a, const Adpm::K& k, const rdc_adpm_params& p) {
-  if (a.variant != RDC_VARIANT_GENERIC && a.opt.specialise && AdpmDecayOnly::applies(p)) return launch_rd<AdpmDecayOnly>(a, k);
-  return launch_rd<Adpm>(a, k);
-}
-
-// k_tet4_evc serves the all-terms Ripf instantiation: not when the reduced one will be chosen (launch_specialised<Ripf>)
-template <class P> bool evc_wanted(const P*, bool) { return false; }
-template <> bool evc_wanted<rdc_ripf_params>(const rdc_ripf_params* p, bool special) { return !(special && RipfReduced::applies(*p)); }
-
-template <class P> bool pihna_pattern_applies(const P*) { return false; }
-template <> bool pihna_pattern_applies<rdc_pihna_params>(const rdc_pihna_params* p) { return PihnaNoCellTransport::applies(*p); }
 
 // two-part assembly on the element-visit lists: (re)builds the workgroup order for the current "interior_nodes":
 // clusters all of whose nodes are below it first (the split itself: rdc_parts.h)
@@ -346,6 +353,14 @@ int ev_order_for_interior(rdc_ctx* c) {
 
 // two-part assembly: the leading row-gather workgroups that part 1 launches and the rows complete after them
 PartSplit part1_pairs(const rdc_ctx* c) { return split_pairs(c->ms.prep.wg2, c->opt.interior_nodes); }
+
+// the context keeps the connectivity on the device only: the list builders of the first assembly read a host copy
+int download_conn(rdc_ctx* c, std::vector<uint32_t>& conn_h) {
+  conn_h.resize((size_t)c->ms.prep.n_elem * c->ms.prep.nen);
+  RDC_HIP(c, hipMemcpyAsync(conn_h.data(), c->buf.mesh.conn.p, conn_h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  RDC_HIP(c, hipStreamSynchronize(c->stream));
+  return RDC_OK;
+}
 
 // element-visit lists (rdc_prep_ev.cpp) of the current mesh: at the upload for five unknowns (PIHNA), on the first
 // assembly for three (RIPF / HCC).  A mesh they cannot describe simply keeps the pair kernels (prep_ev.ok stays false).
@@ -381,9 +396,8 @@ int ensure_cluster_lists(rdc_ctx* c, int order_of_caller) {
   HostPrepCl::Limits lim = nen == 4 ? cll::tet4_limits(c->ms.prep.nvar) : cll::limits(c->opt.solid_cl_waves / 10, c->opt.solid_cl_waves % 10, c->ms.prep.nvar);
   lim.pair_order = want_order;
   HostPrepCl cl;
-  std::vector<uint32_t> conn_h((size_t)c->ms.prep.n_elem * nen);      // the context keeps the connectivity on the device only
-  RDC_HIP(c, hipMemcpyAsync(conn_h.data(), c->buf.mesh.conn.p, conn_h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  RDC_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<uint32_t> conn_h;
+  if ((rc = download_conn(c, conn_h))) return rc;
   const std::string err = prep_build_cl(c->ms.prep, conn_h.data(), lim, cl, c->opt.interior_nodes);
   L = MeshState::ClusterLists();
   L.interior = c->opt.interior_nodes; L.waves = c->opt.solid_cl_waves; L.order = want_order;
@@ -442,7 +456,8 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   a.m = mesh_view(c);
   a.nen = c->ms.prep.nen;
   a.exp_mode = exp_mode_of(M::exponent(k)) == M::FAST_EXP_MODE ? M::FAST_EXP_MODE : 0;
-  rc = resolve_strategy(c, &a.strategy);
+  int strategy;
+  rc = resolve_strategy(c, &strategy);
   if (rc) return rc;
   a.u = (const double*)c->buf.field[RDC_FIELD_OLD_SOLUTION].p;
   a.aux = (const double*)c->buf.field[RDC_FIELD_AUX_NODAL].p;
@@ -454,120 +469,91 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     a.hx_max_nodes = c->ms.prep.hx_max_nodes;
   }
   a.packed = (double*)c->buf.out.packed.p;
-  a.variant = c->variant;
   a.opt = c->opt;
-  a.kernel = (c->opt.kernel == 5 || c->opt.kernel == 7) ? 0 : c->opt.kernel;
   a.stamps = (long long*)c->buf.scratch.stamps.p;
   a.rg2 = rg2_view(c);
-  if (a.rg2.nl_stride > 0 && (M::NELEM > 0 || M::AUX_LOCAL_NODE >= 0) && !c->ms.prep.pair_eid.empty()) {
+  // Which kernel runs (rdc_path.h; DESIGN.md, "Which kernel runs"): the lists the call builds on first use, then the plan.  A refused
+  // list build (c->err says why) leaves the call on the path it would have taken without the lists
+  constexpr PathModel model = describe<M>();
+  Facts f = path_facts(c, strategy);
+  f.pattern = Forms<M>::pattern(*p);
+  const Builds b = path_builds(model, f);
+  if (b.pair_eid) {
     if (!c->ms.rg5_eid_ready) {
       if ((rc = dev_upload(c, c->buf.rg2.eid, c->ms.prep.pair_eid))) return rc;
       c->ms.rg5_eid_ready = true;
     }
     a.rg2.pair_eid = (const uint32_t*)c->buf.rg2.eid.p;
   }
-  // RIPF with all terms on (k_tet4_evc): the element-visit lists are built on the first assembly
-  const bool evc_model = EvcEligible<M>::value && evc_wanted(p, c->opt.specialise != 0);
-  if (evc_model && a.nen == 4 && !c->ms.ev_tried && c->ms.prep.rg2_ok && c->opt.kernel == 0 && a.strategy == RDC_SCATTER_ROWGATHER && a.variant != RDC_VARIANT_GENERIC) {
-    std::vector<uint32_t> conn_h((size_t)c->ms.prep.n_elem * 4);      // the context keeps the connectivity on the device only
-    RDC_HIP(c, hipMemcpyAsync(conn_h.data(), c->buf.mesh.conn.p, conn_h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    RDC_HIP(c, hipStreamSynchronize(c->stream));
+  if (b.ev) {
+    std::vector<uint32_t> conn_h;
+    if ((rc = download_conn(c, conn_h))) return rc;
     if ((rc = build_ev_lists(c, conn_h.data()))) return rc;
+    f.ev_ok = c->ms.prep_ev.ok;
   }
-  // element-visit kernel: default for the shipped-pattern PIHNA / TET4 ("kernel" = 0 or 7); the diagnostic knobs of the
-  // pair kernels (ablate, stamps, coefficient form, occupancy 1) and "kernel" = 5 select k_tet4_rg5 instead
-  // TET4 cluster kernel (rdc_tet4_cluster_mode): mode 1 where the mesh has neither pair lists nor element-visit lists (the latter
-  // need the former), mode 2 wherever its lists can be built.  A refused build (c->err says why) or an image beyond the device's
-  // LDS leaves the call on the path it would have taken
-  if (a.nen == 4 && Tet4ClWanted<M>::in_mode(c->tet4_cl_mode) && (c->tet4_cl_mode == 2 || !c->ms.prep.rg2_ok)) {
-    if ((rc = ensure_cluster_lists(c, 1))) return rc;
-    a.tet4_cl = c->ms.cl.state == 1 && a.strategy == RDC_SCATTER_ROWGATHER && a.variant != RDC_VARIANT_GENERIC &&
-                tet4_cl_lds_bytes<M>(c->ms.cl.max_row_doubles) <= c->max_lds;
+  if (b.tet4_cl || b.hex8_cl) {
+    if ((rc = ensure_cluster_lists(c, b.tet4_cl ? 1 : 0))) return rc;
+    f.cl_ready = c->ms.cl.state == 1;
+    f.cl_fits = tet4_cl_lds_bytes<M>(c->ms.cl.max_row_doubles) <= c->max_lds;
   }
-  a.use_ev = !a.tet4_cl && c->ms.prep_ev.ok && (c->opt.kernel == 0 || c->opt.kernel == 7) && c->opt.moments && (!c->opt.ablate || c->opt.kernel == 7) &&
-             (!c->buf.scratch.stamps.p || (c->opt.kernel == 7 && c->opt.ablate == 4)) && c->opt.occupancy != 1 && c->opt.lds_pad == 0;
+  const Plan plan = a.plan = path_decide(model, f);
   if (c->opt.ev_resident) {   // cluster counter of the resident kernel
     if ((rc = dev_alloc(c, c->buf.ev.ticket, 256))) return rc;   // [0]: whole launches and part 1, [16]: part 2
     a.ev_ticket = (int*)c->buf.ev.ticket.p;
   }
   a.ev_grid = c->opt.grid > 0 ? c->opt.grid : 2 * c->n_cu;
-  if (a.use_ev) a.ev = ev_view(c);
-  // HEX8, three (five) unknowns: producer / consumer cluster kernel; a two-part call launches the interior clusters / the rest
-  // (the persistent form, "hex_kernel" = 2, assembles whole meshes only)
-  bool hex_cl = false;
-  if (a.nen == 8 && (M::NV == 3 || M::NV == 5) && c->opt.hex_kernel != 1 && (c->opt.part == 0 || c->opt.hex_kernel == 0) &&
-      a.strategy == RDC_SCATTER_ROWGATHER && c->opt.solid_cl_waves == 31) {
-    if ((rc = ensure_cluster_lists(c, 0))) return rc;
-    hex_cl = c->ms.cl.state == 1;
+  if (plan.path == Path::TET4_EV || plan.path == Path::TET4_EVC || plan.two_part == TwoPart::EV_SPLIT) a.ev = ev_view(c);
+  // Two-part assembly (halo overlap): part 1 = the leading work items of the path's lists whose nodes are all interior, part 2 = the
+  // rest.  A path that launches no sub-ranges assembles nothing in part 1 and everything in part 2
+  const int part = c->opt.part;
+  PartSplit split;   // the work items of part 1 and the rows complete after them
+  switch (plan.two_part) {
+    case TwoPart::WHOLE: c->ms.part1_packed = false; break;
+    case TwoPart::CL_SPLIT:   // the cluster lists respect "interior_nodes" (interior clusters first)
+      c->ms.part1_packed = false;
+      if (part == 1) {
+        c->ms.part1_nodes = c->ms.cl.part1.wg > 0 ? c->ms.cl.part1.nodes : 0;
+        if (c->ms.cl.part1.wg == 0) return RDC_OK;
+      }
+      a.cl = cluster_view(c, c->ms.cl.interior >= 0 ? part : (part == 2 ? 0 : 1));
+      if (a.cl.n_wg == 0) return RDC_OK;
+      break;
+    case TwoPart::EV_SPLIT:
+      if (c->opt.interior_nodes < 0) return fail(c, RDC_ERR_STATE, "\"part\" needs \"interior_nodes\"");
+      if ((rc = ev_order_for_interior(c))) return rc;
+      a.ev.wg_perm = (const uint32_t*)c->buf.ev.perm.p;
+      split = c->ms.ev_part1;
+      break;
+    case TwoPart::PAIR_SPLIT: split = part1_pairs(c); break;
+    case TwoPart::ALL_IN_PART2: break;
   }
-  bool pattern_ok = evc_model;
-  if constexpr (std::is_same<M, Pihna>::value) pattern_ok = pihna_pattern_applies(p) || c->opt.ev_general;
-  const bool ev_path = a.use_ev && (std::is_same<M, Pihna>::value || evc_model) && a.nen == 4 && a.variant != RDC_VARIANT_GENERIC &&
-                       (c->opt.specialise || c->opt.ev_general || !std::is_same<M, Pihna>::value) && a.strategy == RDC_SCATTER_ROWGATHER && pattern_ok;
-  if constexpr (std::is_same<M, Pihna>::value) a.ev_general = ev_path && c->opt.ev_general && !(c->opt.specialise && pihna_pattern_applies(p));
-  if (!std::is_same<M, Pihna>::value) a.use_ev = ev_path && c->opt.kernel == 0;   // k_tet4_evc (rdc_tet4_fast.hip dispatches on it)
-  if (c->opt.part != 0 && ev_path) {
-    // two-part assembly on the element-visit lists: the clusters all of whose nodes are interior run in part 1
-    if (c->opt.interior_nodes < 0) return fail(c, RDC_ERR_STATE, "\"part\" needs \"interior_nodes\"");
-    if ((rc = ev_order_for_interior(c))) return rc;
-    a.ev.wg_perm = (const uint32_t*)c->buf.ev.perm.p;
-    if (c->opt.part == 1) {
+  if (plan.two_part == TwoPart::EV_SPLIT || plan.two_part == TwoPart::PAIR_SPLIT || plan.two_part == TwoPart::ALL_IN_PART2) {
+    const bool ev = plan.two_part == TwoPart::EV_SPLIT;
+    int& wg_begin = ev ? a.ev.wg_begin : a.rg2.wg_begin;
+    int& wg_count = ev ? a.ev.wg_count : a.rg2.wg_count;
+    if (part == 1) {
       c->ms.part1_packed = false;
       c->ms.part1_nodes = 0;
-      if (c->ms.ev_part1.wg == 0) return RDC_OK;
-      c->ms.part1_nodes = c->ms.ev_part1.nodes;
-      a.ev.wg_begin = 0; a.ev.wg_count = c->ms.ev_part1.wg;
-      if (!c->pack_event) RDC_HIP(c, hipEventCreateWithFlags(&c->pack_event, hipEventDisableTiming));
-      a.pack_part = 1; a.pack_event = c->pack_event;
-      c->ms.part1_packed = true;
-    } else {
-      a.ev.wg_begin = c->ms.ev_part1.wg; a.ev.wg_count = -1;
-      if (c->ms.part1_packed) { a.pack_part = 2; a.pack_event = c->pack_event; }
-      c->ms.part1_packed = false;
-    }
-  } else
-  if (c->opt.part != 0 && (hex_cl || a.tet4_cl)) {
-    // HEX8 cluster kernels, k_tet4_cl: the cluster lists respect "interior_nodes" (interior clusters first)
-    c->ms.part1_packed = false;
-    if (c->opt.part == 1) {
-      c->ms.part1_nodes = c->ms.cl.part1.wg > 0 ? c->ms.cl.part1.nodes : 0;
-      if (c->ms.cl.part1.wg == 0) return RDC_OK;
-    }
-    a.cl = cluster_view(c, c->ms.cl.interior >= 0 ? c->opt.part : (c->opt.part == 2 ? 0 : 1));
-    if (a.cl.n_wg == 0) return RDC_OK;
-  } else
-  if (c->opt.part != 0) {
-    // two-part assembly (halo overlap): part 1 = the leading workgroups whose nodes are all interior, part 2 = the
-    // rest.  Only the default TET4 row-gather kernel launches sub-ranges; every other path assembles everything in
-    // part 2 and nothing in part 1.
-    const bool sub = a.nen == 4 && a.strategy == RDC_SCATTER_ROWGATHER && a.variant != RDC_VARIANT_GENERIC && a.rg2.n_wg > 0 &&
-                     a.rg2.pair_aux && a.rg2.nlist && a.rg2.block == 256 && a.kernel == 0 && c->opt.interior_nodes >= 0 &&
-                     ((M::NELEM == 0 && M::AUX_LOCAL_NODE < 0) || a.rg2.pair_eid);
-    const PartSplit pairs = sub ? part1_pairs(c) : PartSplit();
-    if (c->opt.part == 1) {
-      c->ms.part1_packed = false;
-      c->ms.part1_nodes = 0;
-      if (!sub || pairs.wg == 0) return RDC_OK;
-      c->ms.part1_nodes = pairs.nodes;
-      a.rg2.wg_begin = 0; a.rg2.wg_count = pairs.wg;
+      if (split.wg == 0) return RDC_OK;
+      c->ms.part1_nodes = split.nodes;
+      wg_begin = 0; wg_count = split.wg;
       // part 1 packs the records of the owned nodes only and part 2 those of the ghosts, ordered by an event: the two
       // parts may run on different streams (rdc_assembly.h, stream contract of the two-part assembly)
       if (!c->pack_event) RDC_HIP(c, hipEventCreateWithFlags(&c->pack_event, hipEventDisableTiming));
       a.pack_part = 1; a.pack_event = c->pack_event;
       c->ms.part1_packed = true;
     } else {
-      a.rg2.wg_begin = pairs.wg; a.rg2.wg_count = -1;
-      if (sub && c->ms.part1_packed) { a.pack_part = 2; a.pack_event = c->pack_event; }
+      wg_begin = split.wg; wg_count = -1;
+      if (plan.two_part != TwoPart::ALL_IN_PART2 && c->ms.part1_packed) { a.pack_part = 2; a.pack_event = c->pack_event; }
       c->ms.part1_packed = false;
     }
-  } else {
-    c->ms.part1_packed = false;
   }
-  if ((hex_cl || a.tet4_cl) && c->opt.part == 0) {
+  const bool hex8_cl = plan.path == Path::HEX8_CL || plan.path == Path::HEX8_CL_ROWS;
+  if ((hex8_cl || plan.path == Path::TET4_CL) && part == 0) {
     a.cl = cluster_view(c);
-    a.cl.grid = hex_cl && c->opt.hex_kernel == 2 ? 2 * c->n_cu : 0;   // persistent form: the workgroups resident at once
+    a.cl.grid = hex8_cl && c->opt.hex_kernel == 2 ? 2 * c->n_cu : 0;   // persistent form: the workgroups resident at once
   }
-  if (a.tet4_cl) {   // what rdc_tet4_cluster_info reports (a part without clusters has returned above)
+  if (plan.path == Path::TET4_CL) {   // what rdc_tet4_cluster_info reports (a part without clusters has returned above)
     c->tet4_cl_active = 1;
     c->tet4_cl_lds = tet4_cl_lds_bytes<M>(a.cl.max_row_doubles);
   }
@@ -583,7 +569,7 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   if (c->timing) {
     if ((rc = next_event_pair(c, &a.ev_start, &ev_stop))) return rc;
   }
-  hipError_t e = launch_specialised<M>(a, k, *p);
+  hipError_t e = launch_specialised<M>(a, k);
   if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
   if (c->timing) RDC_HIP(c, hipEventRecord(ev_stop, c->stream));
   return RDC_OK;
@@ -1146,13 +1132,21 @@ int rdc_part1_nodes(const rdc_ctx* c, int64_t* n_nodes) {
   // after a part-1 call: what THAT call completed (the kernel path depends on the model, the parameter values and the
   // tuning options, and the paths split the rows differently)
   if (c->ms.part1_nodes >= 0) { *n_nodes = c->ms.part1_nodes; return RDC_OK; }
-  // before any part-1 call: the prediction for the default path of the shipped-pattern PIHNA (element-visit clusters)
-  if (c->opt.interior_nodes >= 0 && c->ms.prep_ev.ok && (c->opt.kernel == 0 || c->opt.kernel == 7)) {
-    *n_nodes = split_ev(c->ms.prep_ev.desc, c->opt.interior_nodes).nodes;
-    return RDC_OK;
+  // before any part-1 call: what part 1 of a shipped-pattern PIHNA call would complete with the current options and the lists
+  // that exist now (nothing is built here): the same decision as the call's
+  if (c->opt.interior_nodes < 0) return RDC_OK;
+  Facts f = path_facts(c, strategy_of(c));
+  f.opt.part = 1;
+  f.pattern = true;
+  f.cl_fits = tet4_cl_lds_bytes<Pihna>(c->ms.cl.max_row_doubles) <= c->max_lds;
+  PartSplit s;
+  switch (path_decide(describe<Pihna>(), f).two_part) {
+    case TwoPart::EV_SPLIT: s = split_ev(c->ms.prep_ev.desc, c->opt.interior_nodes); break;
+    case TwoPart::CL_SPLIT: s = c->ms.cl.part1; break;
+    case TwoPart::PAIR_SPLIT: s = part1_pairs(c); break;
+    case TwoPart::WHOLE: case TwoPart::ALL_IN_PART2: break;
   }
-  if (c->opt.interior_nodes < 0 || !c->ms.prep.rg2_ok || c->ms.prep.nen != 4) return RDC_OK;
-  *n_nodes = part1_pairs(c).nodes;
+  *n_nodes = s.wg > 0 ? s.nodes : 0;
   return RDC_OK;
 }
 

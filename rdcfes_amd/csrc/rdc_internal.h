@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rdc_kernels.h"
+#include "rdc_models.h"
 #include "rdc_options.h"
 #include "rdc_prep.h"
 
@@ -76,7 +77,7 @@ struct ClDev {
 // ---- kernel launch plumbing -----------------------------------------------------------------
 struct LaunchArgs {
   MeshDev m;
-  int nen, exp_mode, strategy;
+  int nen, exp_mode;
   const double* u;
   const double* aux;
   // node-staged generic row gather (HEX8)
@@ -88,17 +89,13 @@ struct LaunchArgs {
   double* packed;  // scratch for the per-node records of the TET4 fast path
   int pack_part = 0;               // 0 = pack every record; 1 = owned nodes only, then record pack_event; 2 = wait for pack_event, ghosts only
   hipEvent_t pack_event = nullptr;
-  int variant;     // RDC_VARIANT_*
-  Options opt;     // the context's tuning knobs (rdc_set_option) as they were at the call; what the call derives from them has fields of its own
-  int kernel = 0;  // opt.kernel as the pair-kernel launchers read it: 5 and 7 (their choice is made before the launcher) count as 0
+  Options opt;     // the context's tuning knobs (rdc_set_option) as they were at the call: tuning inside a kernel family
+  Plan plan;       // the kernel family, the model instantiation and the two-part mode of this call (rdc_path.h): the launchers obey it
   Rg2Dev rg2;
   EvDev ev;
   ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted); TET4: those of k_tet4_cl
-  bool tet4_cl = false;  // TET4: this call runs the cluster kernel (rdc_tet4_cl.hip) on `cl` instead of the pair / row-gather kernels
-  bool use_ev = false;   // element-visit kernel allowed for this call
   int ev_grid = 0;           // 2 x CUs: the resident element-visit kernel launches 3/2 of it (22 moments: all of it)
   int* ev_ticket = nullptr;  // k_tet4_evq: cluster counter (one int, zeroed by the launch)
-  bool ev_general = false;   // k_tet4_ev with every PIHNA term on (22 moments) instead of the shipped parameter pattern (16)
   long long* stamps = nullptr;  // diagnostic phase stamps (rdc_debug_stamps)
   double* val;
   double* rhs;
@@ -110,9 +107,10 @@ struct LaunchArgs {
   size_t lds_bytes;
 };
 
+// the generic kernels and the HEX8 cluster kernels (rdc_launch.h)
 template <class M>
 hipError_t launch_rd(const LaunchArgs& a, const typename M::K& k);
-// TET4-specialised factored kernels (rdc_tet4_fast.hip)
+// TET4-specialised factored kernels (rdc_tet4_fast.hip): k_tet4_evc, the pair kernels, k_tet4_rowgather, k_tet4_coloured
 template <class M>
 hipError_t launch_tet4_fast(const LaunchArgs& a, const typename M::K& k);
 // TET4 cluster kernel (rdc_tet4_cl.hip): reads the mesh and the nodal fields directly, no record pack
@@ -126,11 +124,6 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k);
 // the node records must have been packed
 template <class M>
 hipError_t launch_tet4_evc(const LaunchArgs& a, const typename M::K& k);
-// which models run it: measured on K(94) against k_tet4_rg5 (tools/ab.py): Ripf with all terms on 1.41 vs 1.79 ms (the per-element
-// part -- two exp, sqrt, the unit gradient -- dominates); RipfReduced 0.87 vs 0.78, Hcc 0.90 vs 0.65: the pair kernel packs the
-// row atomics of a wave densely, an element visit executes a row position for as few as 10 of 64 lanes
-// (Pihna with all terms on, five unknowns, was tried in round 3: tet4_visit<Pihna> needs 3.9 KB of scratch per lane -- profiles/r03_ev_ab_log.md)
-template <class M> struct EvcEligible { static constexpr bool value = std::is_same<M, Ripf>::value; };
 
 }  // namespace rdc
 #endif

@@ -3,6 +3,7 @@
 #ifndef RDC_PARTS_H
 #define RDC_PARTS_H
 #include <algorithm>
+#include "rdc_path.h"
 #include "rdc_prep.h"
 
 namespace rdc {
@@ -36,6 +37,19 @@ inline PartSplit split_ev(const std::vector<HostPrepEv::Desc>& desc, int64_t int
   }
   if (perm) perm->insert(perm->end(), rest.begin(), rest.end());
   return s;
+}
+
+// What the kernel-path decision (rdc_path.h) reads of a mesh's lists as they stand: the element type and the pair, row-gather and
+// element-visit lists.  The cluster-list facts are the caller's: they depend on the options the lists were built with
+inline void list_facts(const HostPrep& P, const HostPrepEv& E, Facts& f) {
+  f.nen = P.nen;
+  f.rowgather_ok = P.rowgather_ok && P.wg_node_ptr.size() > 1;
+  f.rg2_ok = P.rg2_ok && P.nen == 4;
+  f.rg2_block = P.rg2_block;
+  f.pair_aux = f.rg2_ok;
+  f.nlist = f.rg2_ok && P.nl_stride > 0;
+  f.pair_eid = !P.pair_eid.empty();
+  f.ev_ok = E.ok;
 }
 
 }  // namespace rdc

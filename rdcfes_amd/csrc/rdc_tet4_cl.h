@@ -39,17 +39,6 @@ constexpr size_t tet4_cl_lds_bytes(size_t max_row_doubles) {
   return sizeof(double) * (tet4_cl_rec_offset<M>(max_row_doubles) + (size_t)cll::tet4_limits(M::NV).max_elems * Tet4ClRec<M>::STRIDE);
 }
 
-// Which models (the model of the assemble call: Pihna, Ripf, Hcc, Adpm, Proteas) take the cluster kernel in mode 1 of
-// rdc_tet4_cluster_mode; mode 2 forces every model.  The measurements behind MODE1 (meshes.delaunay(56),
-// 1.17 M tets, against k_tet4_rowgather / k_rowgather<M, 4>): PIHNA 1.20 - 1.25 x, HCC 1.27 x, ADPM 1.90 x, PROTEAS 1.97 x faster;
-// RIPF 1.00 - 1.01 x (a tie just outside the run's noise floor, and no record pack pass): every model stays in.  On a Kuhn mesh
-// the established kernels are 1.1 - 2.8 x faster than this one: mode 2 is for tests and A/B
-template <class M>
-struct Tet4ClWanted {
-  static constexpr bool MODE1 = true;
-  static constexpr bool in_mode(int mode) { return mode == 2 || (mode == 1 && MODE1); }
-};
-
 // block (a, b) of the model is structurally non-zero: the others stay the zeros of the image
 template <class M>
 RDC_HD constexpr bool tet4_cl_block(int a, int b) {

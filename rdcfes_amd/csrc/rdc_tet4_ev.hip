@@ -452,7 +452,7 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   const int wg_count = E.wg_count < 0 ? E.n_wg - E.wg_begin : E.wg_count;
   if (wg_count <= 0) return hipSuccess;
   // LDS (doubles): [moment slice | rhs | node records]; k_tet4_ev lays the CSR image over them, k_tet4_evq (image halves inside the slice) puts its lists behind
-  const size_t acc = (size_t)(a.ev_general ? ev::NMG : ev::NM) * ev::NBP + 5 * ev::MAXN + (size_t)4 * E.nls * 2;
+  const size_t acc = (size_t)(a.plan.ev_general ? ev::NMG : ev::NM) * ev::NBP + 5 * ev::MAXN + (size_t)4 * E.nls * 2;
   const bool cube = a.exp_mode == 3;   // the dedicated-exponent instantiations
   // default: pipelined resident workgroups, clusters handed out by a counter (the two parts of a two-part assembly, which may run
   // concurrently on two streams, have a counter each: ev_ticket[0] and ev_ticket[16]).  Not when a diagnostic knob of k_tet4_ev is set
@@ -460,18 +460,18 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   // ids -> fetch: three round trips) and the tail of the launch are not hidden and cost ~20 us whatever the size -- K(55) = 10,700
   // clusters runs 0.184 vs 0.167 ms, K(75) 0.388 vs 0.370, K(85) = 40,000 clusters 0.577 vs 0.575, K(94) 0.713 vs 0.737, K(119)
   // 1.38 vs 1.50 ("grid" > 0 or "ev_resident" = 2 force it: tests)
-  const int evq_grid = a.opt.grid > 0 ? a.opt.grid : (a.ev_grid > 0 ? (a.ev_general ? a.ev_grid : a.ev_grid / 2 * 3) : 768);   // three per CU (22 moments: two)
-  if (a.opt.ev_resident && (!a.opt.ablate || (a.opt.ablate == 4 && !a.ev_general)) && a.opt.ev_occupancy == 3 && !a.opt.xcd && a.opt.stagger == 0 &&
+  const int evq_grid = a.opt.grid > 0 ? a.opt.grid : (a.ev_grid > 0 ? (a.plan.ev_general ? a.ev_grid : a.ev_grid / 2 * 3) : 768);   // three per CU (22 moments: two)
+  if (a.opt.ev_resident && (!a.opt.ablate || (a.opt.ablate == 4 && !a.plan.ev_general)) && a.opt.ev_occupancy == 3 && !a.opt.xcd && a.opt.stagger == 0 &&
       (a.opt.grid > 0 || a.opt.ev_resident == 2 || (int64_t)wg_count >= 56 * (int64_t)evq_grid)) {
     const int grid = evq_grid > wg_count ? wg_count : evq_grid;
     const size_t bytes = acc * sizeof(double) + EvqLists::bytes(E.nls);
     if (!a.ev_ticket) return hipErrorInvalidValue;   // the cluster counter: zeroed by the record pack kernel in front of this launch
-    if (a.ev_general) return cube ? launch_evq<3, false, true>(a, k, wg_count, grid, bytes) : launch_evq<0, false, true>(a, k, wg_count, grid, bytes);
+    if (a.plan.ev_general) return cube ? launch_evq<3, false, true>(a, k, wg_count, grid, bytes) : launch_evq<0, false, true>(a, k, wg_count, grid, bytes);
     else if (a.opt.ablate == 4) return cube ? launch_evq<3, true, false>(a, k, wg_count, grid, bytes) : launch_evq<0, true, false>(a, k, wg_count, grid, bytes);
     else return cube ? launch_evq<3, false, false>(a, k, wg_count, grid, bytes) : launch_evq<0, false, false>(a, k, wg_count, grid, bytes);
   }
   const size_t lds_bytes = (acc > E.max_out_doubles ? acc : E.max_out_doubles) * sizeof(double);
-  if (cube && a.opt.ablate >= 1 && a.opt.ablate <= 4 && !a.ev_general) {   // diagnostic builds (1-3: timing only)
+  if (cube && a.opt.ablate >= 1 && a.opt.ablate <= 4 && !a.plan.ev_general) {   // diagnostic builds (1-3: timing only)
     if (a.opt.ablate == 1) return launch_ev<3, 3, 1, false>(a, k, wg_count, lds_bytes);
     else if (a.opt.ablate == 2) return launch_ev<3, 3, 2, false>(a, k, wg_count, lds_bytes);
     else if (a.opt.ablate == 3) return launch_ev<3, 3, 3, false>(a, k, wg_count, lds_bytes);
@@ -479,7 +479,7 @@ hipError_t launch_tet4_ev(const LaunchArgs& a, const PihnaK& k) {
   }
   // every term on: 22 moments, 54 KB of LDS.  Register budget of TWO workgroups per CU (244 registers, no scratch): at three the visit
   // spills 79 registers (304 B of scratch per lane) and runs 8.8 instead of 3.0 ms on K(119) (profiles/r03_ev_ab_log.md, r03q)
-  if (a.ev_general) return cube ? launch_ev<3, 2, 0, true>(a, k, wg_count, lds_bytes) : launch_ev<0, 2, 0, true>(a, k, wg_count, lds_bytes);
+  if (a.plan.ev_general) return cube ? launch_ev<3, 2, 0, true>(a, k, wg_count, lds_bytes) : launch_ev<0, 2, 0, true>(a, k, wg_count, lds_bytes);
   if (cube) return a.opt.ev_occupancy == 2 ? launch_ev<3, 2, 0, false>(a, k, wg_count, lds_bytes) : launch_ev<3, 3, 0, false>(a, k, wg_count, lds_bytes);
   else return a.opt.ev_occupancy == 2 ? launch_ev<0, 2, 0, false>(a, k, wg_count, lds_bytes) : launch_ev<0, 3, 0, false>(a, k, wg_count, lds_bytes);
 }

@@ -1,5 +1,5 @@
 // rdc_tet4_evc.hip — element-visit kernel in coefficient form for three-unknown TET4 models; instantiated for Ripf (all terms
-// on), the one model whose per-element part is heavy enough to win against the pair kernel (EvcEligible, rdc_internal.h).  Formulation: rdc_tet4_evc.h; lists: rdc_prep_ev.cpp (the lists of k_tet4_ev).
+// on), the one model whose per-element part is heavy enough to win against the pair kernel (EvcEligible, rdc_models.h).  Formulation: rdc_tet4_evc.h; lists: rdc_prep_ev.cpp (the lists of k_tet4_ev).
 //
 // One workgroup = one CLUSTER of <= 16 owned nodes and the <= 256 elements touching it.
 //   phase 0  zero the entry slice, load the lists, LDS-DMA the node records of the cluster's closure

@@ -614,127 +614,134 @@ static hipError_t launch_fast_impl(const LaunchArgs& a, const typename M::K& k) 
   }
   // the timed region starts after the (tiny) record pack: it brackets the dominant kernel only
   if (a.ev_start) (void)hipEventRecord(a.ev_start, a.stream);
-  // element visits in coefficient form (rdc_tet4_evc.hip) for the models that profit, when the context has the lists
-  if constexpr (EvcEligible<M>::value)
-  if (a.use_ev && a.ev.n_wg > 0 && a.strategy == RDC_SCATTER_ROWGATHER) return launch_tet4_evc<M>(a, k);
   // models with per-element inputs (M::NELEM > 0) or a local-node aux mask exist only as k_tet4_rg5 and k_tet4_coloured
-  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.rg2.pair_aux && a.rg2.nlist && a.rg2.block == 256 &&
-      (a.kernel == 0 || M::NELEM > 0 || M::AUX_LOCAL_NODE >= 0)) {
-    constexpr int BLOCK = 256;
-    const int nl = a.rg2.nl_stride;
-    const int acc_doubles = (int)((a.rg2.lds_bytes / sizeof(double) + 3) & ~(size_t)1);  // + slice phase shift + diagonal alignment
-    // + "lds_pad" KB of unused LDS: diagnostic, lowers the number of co-resident workgroups (one per CU from ~55 KB)
-    const size_t lds_bytes = sizeof(double) * ((size_t)acc_doubles + (size_t)(Rec<M>::N / 2) * nl * 2) + (size_t)a.opt.lds_pad * 1024;
-    const int wg_begin = a.rg2.wg_begin, wg_count = a.rg2.wg_count < 0 ? a.rg2.n_wg - a.rg2.wg_begin : a.rg2.wg_count;
-    if (wg_count <= 0) return hipSuccess;
+  constexpr bool PLAIN = M::NELEM == 0 && M::AUX_LOCAL_NODE < 0;
+  switch (a.plan.path) {
+    case Path::TET4_EVC:   // element visits in coefficient form (rdc_tet4_evc.hip)
+      if constexpr (EvcEligible<M>::value) return launch_tet4_evc<M>(a, k);
+      break;
+    case Path::TET4_RG5: {
+      constexpr int BLOCK = 256;
+      const int nl = a.rg2.nl_stride;
+      const int acc_doubles = (int)((a.rg2.lds_bytes / sizeof(double) + 3) & ~(size_t)1);  // + slice phase shift + diagonal alignment
+      // + "lds_pad" KB of unused LDS: diagnostic, lowers the number of co-resident workgroups (one per CU from ~55 KB)
+      const size_t lds_bytes = sizeof(double) * ((size_t)acc_doubles + (size_t)(Rec<M>::N / 2) * nl * 2) + (size_t)a.opt.lds_pad * 1024;
+      const int wg_begin = a.rg2.wg_begin, wg_count = a.rg2.wg_count < 0 ? a.rg2.n_wg - a.rg2.wg_begin : a.rg2.wg_count;
+      if (wg_count <= 0) return hipSuccess;
 #define RDC_RG5(MINW, ST)                                                                                          \
-  hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, MINW, ST>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,     \
-                     a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
-                     nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
-    if constexpr ((std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) {
-      // diagnostic builds (timing only, results are wrong): LDS atomics replaced by plain stores / removed
-      if (a.opt.ablate >= 1 && a.opt.ablate <= 6) {
+    hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, MINW, ST>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,     \
+                       a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
+                       nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
+      if constexpr ((std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) {
+        // diagnostic builds (timing only, results are wrong): LDS atomics replaced by plain stores / removed
+        if (a.opt.ablate >= 1 && a.opt.ablate <= 6) {
 #define RDC_ABL(X)                                                                                                        \
-  hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, 2, false, X>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,      \
-                     a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
-                     nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
-        switch (a.opt.ablate) {
-          case 1: RDC_ABL(1); break;   // plain LDS stores instead of atomics
-          case 2: RDC_ABL(2); break;   // no LDS accumulation traffic
-          case 3: RDC_ABL(3); break;   // no compute phase
-          case 4: RDC_ABL(4); break;   // no compute, no fold
-          case 5: RDC_ABL(5); break;   // loads + zero + barriers only
-          default: RDC_ABL(6); break;  // everything but the store phase
-        }
+    hipLaunchKernelGGL((k_tet4_rg5<M, EXP_MODE, BLOCK, 2, false, X>), dim3(wg_count), dim3(BLOCK), lds_bytes, a.stream,      \
+                       a.rg2.desc, a.rg2.pair_loc, a.rg2.pair_aux, a.rg2.nlist, a.rg2.node_tab, k, a.packed, a.val, a.rhs, \
+                       nl, acc_doubles, a.stamps, a.opt.prefetch, a.opt.xcd, a.rg2.pair_eid, a.elem, wg_begin, a.opt.stagger)
+          switch (a.opt.ablate) {
+            case 1: RDC_ABL(1); break;   // plain LDS stores instead of atomics
+            case 2: RDC_ABL(2); break;   // no LDS accumulation traffic
+            case 3: RDC_ABL(3); break;   // no compute phase
+            case 4: RDC_ABL(4); break;   // no compute, no fold
+            case 5: RDC_ABL(5); break;   // loads + zero + barriers only
+            default: RDC_ABL(6); break;  // everything but the store phase
+          }
 #undef RDC_ABL
-        return hipGetLastError();
+          return hipGetLastError();
+        }
       }
-    }
-    if constexpr (std::is_same<M, PihnaNoCellTransportMoments>::value) {
-      if (a.opt.occupancy == 3) { RDC_RG5(3, false); return hipGetLastError(); }
-    }
-    if (a.stamps && (std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) RDC_RG5(2, true);
-    else if (a.opt.occupancy == 1) RDC_RG5(1, false);
-    else RDC_RG5(2, false);
+      if constexpr (std::is_same<M, PihnaNoCellTransportMoments>::value) {
+        if (a.opt.occupancy == 3) { RDC_RG5(3, false); return hipGetLastError(); }
+      }
+      if (a.stamps && (std::is_same<M, PihnaNoCellTransport>::value || std::is_same<M, PihnaNoCellTransportMoments>::value) && EXP_MODE == 3) RDC_RG5(2, true);
+      else if (a.opt.occupancy == 1) RDC_RG5(1, false);
+      else RDC_RG5(2, false);
 #undef RDC_RG5
-    return hipGetLastError();
-  }
-  if constexpr (M::NELEM == 0 && M::AUX_LOCAL_NODE < 0)
-  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.rg2.pair_aux && (a.kernel == 0 || a.kernel == 3)) {
-#define RDC_RG3(BLOCK, MINW)                                                                                       \
-  hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), a.rg2.lds_bytes, a.stream, \
-                     a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,  \
-                     (long long*)nullptr)
-    if (a.stamps && a.rg2.block == 256 && std::is_same<M, PihnaNoCellTransport>::value && EXP_MODE == 3) {
-      // diagnostic build with s_memtime stamps per phase (tools/stamp_report.py); never the timed kernel
-      hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, 256, 2, true>), dim3(a.rg2.n_wg), dim3(256), a.rg2.lds_bytes, a.stream,
-                         a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,
-                         a.stamps);
       return hipGetLastError();
     }
-    if (a.rg2.block == 128) {  // MINW counts waves per SIMD: 2 means four 128-thread workgroups per CU
-      if (a.opt.occupancy == 1) RDC_RG3(128, 1); else RDC_RG3(128, 2);
-    } else {
-      if (a.opt.occupancy == 1) RDC_RG3(256, 1);
-      else if (a.opt.occupancy == 3) RDC_RG3(256, 3);
-      else RDC_RG3(256, 2);
-    }
-#undef RDC_RG3
-    return hipGetLastError();
-  }
-  if constexpr (M::NELEM == 0 && M::AUX_LOCAL_NODE < 0)
-  if (a.strategy == RDC_SCATTER_ROWGATHER && a.rg2.n_wg > 0 && a.kernel == 2 && a.rg2.block == 256) {
-    constexpr int BLOCK = 256;
-#define RDC_RG2(MINW)                                                                                              \
-  hipLaunchKernelGGL((k_tet4_rg2<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), 0, a.stream, a.rg2.desc, \
-                     a.rg2.pair_rec, a.rg2.chunk, a.rg2.sdesc, a.rg2.contrib, k, a.packed, a.val, a.rhs, a.opt.ablate)
-    if (a.opt.occupancy == 1) RDC_RG2(1);
-    else if (a.opt.occupancy == 3) RDC_RG2(3);
-    else RDC_RG2(2);
-#undef RDC_RG2
-    return hipGetLastError();
-  }
-  if constexpr (M::NELEM == 0 && M::AUX_LOCAL_NODE < 0)
-  if (a.strategy == RDC_SCATTER_ROWGATHER) {
-    constexpr int BLOCK = 256;
-    if (a.n_wg > 0) {
-#define RDC_RG(MINW, ABL)                                                                                          \
-  hipLaunchKernelGGL((k_tet4_rowgather<M, EXP_MODE, BLOCK, MINW, ABL>), dim3(a.n_wg), dim3(BLOCK), a.lds_bytes, a.stream, \
-                     a.m, k, a.packed, a.val, a.rhs)
-      // tuning variants exist for the PIHNA / cubic-exponent instantiation only
-      const bool lab = (std::is_same<M, Pihna>::value || std::is_same<M, PihnaNoCellTransport>::value) && EXP_MODE == 3;
-      const int key = lab ? a.opt.occupancy * 10 + a.opt.ablate : 20;
-      if (lab) {
-        switch (key) {
-          case 10: RDC_RG(1, 0); break;
-          case 11: RDC_RG(1, 1); break;
-          case 12: RDC_RG(1, 2); break;
-          case 21: RDC_RG(2, 1); break;
-          case 22: RDC_RG(2, 2); break;
-          case 30: RDC_RG(3, 0); break;
-          case 31: RDC_RG(3, 1); break;
-          default: RDC_RG(2, 0); break;
+    case Path::TET4_RG3:
+      if constexpr (PLAIN) {
+#define RDC_RG3(BLOCK, MINW)                                                                                       \
+      hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), a.rg2.lds_bytes, a.stream, \
+                         a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,  \
+                         (long long*)nullptr)
+        if (a.stamps && a.rg2.block == 256 && std::is_same<M, PihnaNoCellTransport>::value && EXP_MODE == 3) {
+          // diagnostic build with s_memtime stamps per phase (tools/stamp_report.py); never the timed kernel
+          hipLaunchKernelGGL((k_tet4_rg3<M, EXP_MODE, 256, 2, true>), dim3(a.rg2.n_wg), dim3(256), a.rg2.lds_bytes, a.stream,
+                             a.rg2.desc, a.rg2.pair_rec, a.rg2.pair_aux, a.rg2.node_tab, k, a.packed, a.val, a.rhs, a.opt.xcd,
+                             a.stamps);
+          return hipGetLastError();
         }
-      } else {
-        RDC_RG(2, 0);
+        if (a.rg2.block == 128) {  // MINW counts waves per SIMD: 2 means four 128-thread workgroups per CU
+          if (a.opt.occupancy == 1) RDC_RG3(128, 1); else RDC_RG3(128, 2);
+        } else {
+          if (a.opt.occupancy == 1) RDC_RG3(256, 1);
+          else if (a.opt.occupancy == 3) RDC_RG3(256, 3);
+          else RDC_RG3(256, 2);
+        }
+#undef RDC_RG3
+        return hipGetLastError();
       }
+      break;
+    case Path::TET4_RG2:
+      if constexpr (PLAIN) {
+        constexpr int BLOCK = 256;
+#define RDC_RG2(MINW)                                                                                              \
+      hipLaunchKernelGGL((k_tet4_rg2<M, EXP_MODE, BLOCK, MINW>), dim3(a.rg2.n_wg), dim3(BLOCK), 0, a.stream, a.rg2.desc, \
+                         a.rg2.pair_rec, a.rg2.chunk, a.rg2.sdesc, a.rg2.contrib, k, a.packed, a.val, a.rhs, a.opt.ablate)
+        if (a.opt.occupancy == 1) RDC_RG2(1);
+        else if (a.opt.occupancy == 3) RDC_RG2(3);
+        else RDC_RG2(2);
+#undef RDC_RG2
+        return hipGetLastError();
+      }
+      break;
+    case Path::TET4_ROWGATHER:
+      if constexpr (PLAIN) {
+        constexpr int BLOCK = 256;
+        if (a.n_wg > 0) {
+#define RDC_RG(MINW, ABL)                                                                                          \
+      hipLaunchKernelGGL((k_tet4_rowgather<M, EXP_MODE, BLOCK, MINW, ABL>), dim3(a.n_wg), dim3(BLOCK), a.lds_bytes, a.stream, \
+                         a.m, k, a.packed, a.val, a.rhs)
+          // tuning variants exist for the PIHNA / cubic-exponent instantiation only
+          const bool lab = (std::is_same<M, Pihna>::value || std::is_same<M, PihnaNoCellTransport>::value) && EXP_MODE == 3;
+          const int key = lab ? a.opt.occupancy * 10 + a.opt.ablate : 20;
+          if (lab) {
+            switch (key) {
+              case 10: RDC_RG(1, 0); break;
+              case 11: RDC_RG(1, 1); break;
+              case 12: RDC_RG(1, 2); break;
+              case 21: RDC_RG(2, 1); break;
+              case 22: RDC_RG(2, 2); break;
+              case 30: RDC_RG(3, 0); break;
+              case 31: RDC_RG(3, 1); break;
+              default: RDC_RG(2, 0); break;
+            }
+          } else {
+            RDC_RG(2, 0);
+          }
 #undef RDC_RG
-    }
-    return hipGetLastError();
+        }
+        return hipGetLastError();
+      }
+      break;
+    case Path::TET4_COLOURED:
+      for (int c = 0; c < a.n_colours; c++) {
+        const int64_t first = a.colour_ptr[c], count = a.colour_ptr[c + 1] - first;
+        if (count <= 0) continue;
+        const int64_t grid = (count + 255) / 256;
+        hipLaunchKernelGGL((k_tet4_coloured<M, EXP_MODE>), dim3((unsigned)grid), dim3(256), 0, a.stream, a.m, k, first, count,
+                           a.packed, a.elem, a.val, a.rhs);
+      }
+      return hipGetLastError();
+    default: break;
   }
-  for (int c = 0; c < a.n_colours; c++) {
-    const int64_t first = a.colour_ptr[c], count = a.colour_ptr[c + 1] - first;
-    if (count <= 0) continue;
-    const int64_t grid = (count + 255) / 256;
-    hipLaunchKernelGGL((k_tet4_coloured<M, EXP_MODE>), dim3((unsigned)grid), dim3(256), 0, a.stream, a.m, k, first, count,
-                       a.packed, a.elem, a.val, a.rhs);
-  }
-  return hipGetLastError();
+  return hipErrorInvalidValue;   // a path this instantiation does not have
 }
 
 template <class M>
 hipError_t launch_tet4_fast(const LaunchArgs& a, const typename M::K& k) {
-  if (a.tet4_cl) return launch_tet4_cl<M>(a, k);   // rdc_tet4_cluster_mode: the context decided (assemble_rd)
   if (a.exp_mode == M::FAST_EXP_MODE) return launch_fast_impl<M, M::FAST_EXP_MODE>(a, k);
   return launch_fast_impl<M, 0>(a, k);
 }

@@ -13,6 +13,8 @@
 #include "../rdcfes_amd/csrc/rdc_tet4_ev.h"
 #include "../rdcfes_amd/csrc/rdc_hex8_cl.h"
 #include "../rdcfes_amd/csrc/rdc_tet4_evc.h"
+#include "../rdcfes_amd/csrc/rdc_tet4_cl.h"
+#include "../rdcfes_amd/csrc/rdc_models.h"
 
 using namespace rdc;
 
@@ -343,6 +345,60 @@ int64_t shim_split_ev(int64_t interior, int64_t* out, uint32_t* perm, int64_t ca
   out[0] = s.wg; out[1] = s.nodes;
   if (perm) std::memcpy(perm, order.data(), std::min<size_t>(order.size(), (size_t)cap) * sizeof(uint32_t));
   return (int64_t)order.size();
+}
+
+}  // extern "C"
+
+// ---- which kernel runs (rdc_path.h, rdc_models.h) ------------------------------------------
+// facts[16]: nen, strategy, variant, tet4_cl_mode, pattern, stamps, rowgather_ok, rg2_ok, rg2_block, pair_aux, nlist, pair_eid,
+// ev_ok, ev_tried, cl_ready, cl_fits.  out[8]: path, instantiation, two-part mode, ev_general, then the builds: ev, tet4_cl,
+// hex8_cl, pair_eid
+template <class M>
+static void path_run(const Facts& f, int* out) {
+  constexpr PathModel m = describe<M>();
+  const Plan p = path_decide(m, f);
+  const Builds b = path_builds(m, f);
+  out[0] = (int)p.path; out[1] = (int)p.inst; out[2] = (int)p.two_part; out[3] = p.ev_general;
+  out[4] = b.ev; out[5] = b.tet4_cl; out[6] = b.hex8_cl; out[7] = b.pair_eid;
+}
+
+extern "C" {
+// model: 0 PIHNA, 1 RIPF, 2 HCC, 4 ADPM, 5 PROTEAS (as shim_row); the options are set through the table of rdc_set_option
+int shim_path_decide(int model, const int* facts, int n_opts, const char* const* keys, const int* values, int* out) {
+  Facts f;
+  char err[128];
+  for (int i = 0; i < n_opts; i++)
+    if (options_set(f.opt, keys[i], values[i], err, sizeof(err))) return 1;
+  f.nen = facts[0]; f.strategy = facts[1]; f.variant = facts[2]; f.tet4_cl_mode = facts[3]; f.pattern = facts[4]; f.stamps = facts[5];
+  f.rowgather_ok = facts[6]; f.rg2_ok = facts[7]; f.rg2_block = facts[8]; f.pair_aux = facts[9]; f.nlist = facts[10];
+  f.pair_eid = facts[11]; f.ev_ok = facts[12]; f.ev_tried = facts[13]; f.cl_ready = facts[14]; f.cl_fits = facts[15];
+  switch (model) {
+    case 0: path_run<Pihna>(f, out); return 0;
+    case 1: path_run<Ripf>(f, out); return 0;
+    case 2: path_run<Hcc>(f, out); return 0;
+    case 4: path_run<Adpm>(f, out); return 0;
+    case 5: path_run<Proteas>(f, out); return 0;
+  }
+  return 2;
+}
+
+// the list facts (facts[0] and facts[6..12]) of the last shim_prep_build; ev: with the element-visit lists of the last
+// shim_ev_build on that mesh, else as a mesh without them
+void shim_path_list_facts(int ev, int* facts) {
+  Facts f;
+  list_facts(g_prep, ev ? g_ev : HostPrepEv(), f);
+  facts[0] = f.nen; facts[6] = f.rowgather_ok; facts[7] = f.rg2_ok; facts[8] = f.rg2_block; facts[9] = f.pair_aux; facts[10] = f.nlist;
+  facts[11] = f.pair_eid; facts[12] = f.ev_ok;
+}
+
+// the lists of k_tet4_cl on the last shim_prep_build, as the context builds them: out[2] = ready, LDS bytes of the PIHNA image
+int shim_path_build_tet4_cl(int64_t* out) {
+  HostPrepCl::Limits lim = cll::tet4_limits(g_prep.nvar);
+  lim.pair_order = 1;
+  g_err = prep_build_cl(g_prep, g_conn.data(), lim, g_cl, -1);
+  out[0] = g_err.empty();
+  out[1] = g_err.empty() ? (int64_t)tet4_cl_lds_bytes<Pihna>(g_cl.max_row_doubles) : 0;
+  return 0;
 }
 
 // cluster lists of the producer / consumer kernels (rdc_prep_cl.cpp) of the mesh of the last shim_prep_build, and a

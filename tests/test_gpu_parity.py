@@ -982,11 +982,12 @@ def test_chunked_handback_follows_the_part1_bound(params, opts):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("opts", [{}, {"kernel": 5}])
+@pytest.mark.parametrize("opts", [{}, {"kernel": 5}, {"moments": 0}, {"occupancy": 1}])
 def test_part1_bound_is_predicted_before_the_first_part1_call(opts):
     """rdc_part1_nodes BEFORE any part-1 call since the upload (the pipelined hand-back of the benchmark sizes its first chunk
     with it) is what the part-1 call then reports to have completed: the prediction and the call take the split from the same
-    lists (element-visit clusters by default, pair workgroups for "kernel" = 5), and both split the mesh."""
+    decision (rdc_path.h) and so from the same lists (element-visit clusters by default; pair workgroups for "kernel" = 5 and for
+    the knobs that leave the element-visit kernel, "moments" = 0 and "occupancy" = 1), and both split the mesh."""
     conn, xyz = synth.kuhn_tet_mesh(12, order="lex")
     u = synth.pihna_fields(xyz)
     p = pihna_params_from_dict(synth.pihna_param_dict("shipped"))

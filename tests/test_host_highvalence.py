@@ -46,6 +46,23 @@ def test_high_valence_mesh_is_rejected_gracefully(shim, make_prep):
         assert P.pair_rec.size == P.wg2.size * P.rg2_block * 4
 
 
+@pytest.mark.parametrize("model,pattern,cl_mode,path,inst", [
+    ("pihna", True, 0, "TET4_ROWGATHER", "MOMENTS"), ("pihna", False, 0, "TET4_ROWGATHER", "FULL"),
+    ("ripf", False, 0, "TET4_ROWGATHER", "FULL"), ("hcc", True, 0, "TET4_ROWGATHER", "SPARSE"),
+    ("adpm", False, 0, "GENERIC_ROWGATHER", "FULL"), ("proteas", False, 0, "GENERIC_ROWGATHER", "FULL"),
+    ("pihna", True, 1, "TET4_CL", "MOMENTS"), ("adpm", False, 1, "TET4_CL", "FULL")])
+def test_the_fallback_that_runs_after_the_rejection(shim, make_prep, model, pattern, cl_mode, path, inst):
+    """The rejected lists are not the end of it: on this mesh the decision (rdc_path.h) lands where the hydrogel mesh, whose lists
+    are rejected in the same way, was traced (the hydrogel rows of the table of tests/test_host_path.py): k_tet4_rowgather, the
+    generic row gather for the models that exist as k_tet4_rg5 only, k_tet4_cl in mode 1; never the coloured kernels, and a two-part step assembles everything in part 2 unless the cluster kernel runs."""
+    from test_host_path import plan_on_mesh
+    plan, facts = plan_on_mesh(shim, make_prep, "delaunay", model, pattern, cl_mode=cl_mode)
+    assert not facts["rg2_ok"] and not facts["ev_ok"] and facts["rowgather_ok"]
+    assert (plan["path"], plan["inst"]) == (path, inst)
+    plan, _ = plan_on_mesh(shim, make_prep, "delaunay", model, pattern, {"part": 1}, cl_mode=cl_mode)
+    assert plan["two_part"] == ("CL_SPLIT" if cl_mode else "ALL_IN_PART2")
+
+
 @pytest.mark.parametrize("nvar", [5, 3])
 def test_kuhn_mesh_still_builds(shim, make_prep, nvar):
     from rdcfes_amd import synth
