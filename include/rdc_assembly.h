@@ -418,7 +418,18 @@ int rdc_csr_matvec_f32(rdc_ctx* ctx, const double* d_x, double* d_y);
  * and, with 8 sweeps, on the last level.  The damping is the option "mg_omega" of rdc_set_option, in thousandths
  * (default 600 = 0.6; accepted 1 .. 1999).  A singular or non-finite diagonal block on ANY level counts into bad_blocks
  * and gives RDC_SOLVE_BAD_DIAGONAL with x untouched.  RDC_ERR_UNSUPPORTED with ghost nodes, and if a level would have
- * 2^31 node blocks or more.  rdc_solve_mixed streams the fp32 copy on level 0 inside the cycle as well. */
+ * 2^31 node blocks or more.  rdc_solve_mixed streams the fp32 copy on level 0 inside the cycle as well.
+ * Smoother: the option "mg_smoother" (0 or 1, default 0; anything else is RDC_ERR_INVALID and changes nothing).  With 1 the
+ * first sweep from zero on every level stays x = w D_l^-1 r, and every other sweep -- the post-smoothing of every level and
+ * the 7 further sweeps of the last one -- is one forward Gauss-Seidel sweep x_n += D_l^-1 (r_n - (A_l x)_n) in a
+ * multicolour order, undamped.  The colours are greedy (nodes ascending, the smallest colour no coloured row neighbour
+ * holds; as many colours as it takes), built on the host at the first such solve on a mesh and kept with it: 4 bytes per
+ * node and level in an allocation of their own, which rdc_solve_mg_stats does not count.  A sweep reads the matrix once,
+ * as a Jacobi sweep does, and takes one launch per colour; a level of at most 512 nodes sweeps in one launch of one
+ * workgroup (option "mg_gs_fuse", default 1; 0 = one launch per colour on every level; the results are bitwise equal).
+ * Deterministic: two solves return the same bytes.  RDC_ERR_UNSUPPORTED, with nothing launched, if the block pattern of a
+ * level is not structurally symmetric (two coupled nodes would share a colour), on a context with ghost nodes, and in
+ * rdc_solve_dist_mg.  With "mg_smoother" = 0 every call launches what it launched before the option existed. */
 /* The hierarchy of the last multigrid solve on this mesh: *n_levels = its levels (the matrix itself is level 0), and for
  * the first min(*n_levels, cap) of them nodes[l] and blocks[l] (node blocks of the level's matrix).  nodes / blocks may
  * be NULL with cap = 0.  RDC_ERR_STATE if no multigrid solve has run on this mesh. */
@@ -427,6 +438,10 @@ int rdc_solve_mg_levels(rdc_ctx* ctx, int32_t* n_levels, int64_t* nodes, int64_t
  * (part of its rdc_solve_info.device_ms); *level_bytes = device memory the levels hold for this mesh (matrices, lists and
  * vectors).  Either pointer may be NULL.  RDC_ERR_STATE as above. */
 int rdc_solve_mg_stats(rdc_ctx* ctx, float* setup_ms, int64_t* level_bytes);
+/* The colours of the Gauss-Seidel smoother: n_colours[l] for the first min(levels, cap) levels of the hierarchy
+ * (rdc_solve_mg_levels tells how many there are).  RDC_ERR_STATE if no multigrid solve with "mg_smoother" = 1 has run on
+ * this mesh. */
+int rdc_solve_mg_colours(rdc_ctx* ctx, int32_t* n_colours, int cap);
 
 /* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
  * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own

@@ -335,7 +335,10 @@ class AssemblyContext:
         (initial guess in, solution out); or field=FIELD_*: the device storage of that field is used in place.
         mixed=True: rdc_solve_mixed, the iteration streams an fp32 copy of D^-1 A (info.matrix_bits tells).
         precond=PRECOND_MULTIGRID: block Jacobi's system with an aggregation-multigrid cycle applied from the right: same
-        stopping test and norms, fewer iterations (mg_levels(), mg_stats(); damping: set_option("mg_omega", thousandths))."""
+        stopping test and norms, fewer iterations (mg_levels(), mg_stats(); damping: set_option("mg_omega", thousandths)).
+        set_option("mg_smoother", 1): every sweep of the cycle but the first on each level is a forward multicolour Gauss-Seidel
+        sweep, undamped (mg_colours(); default 0 = damped block Jacobi; not on a ghosted context, not in solve_dist;
+        set_option("mg_gs_fuse", 0): one launch per colour on the small levels too, same bytes)."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -399,6 +402,14 @@ class AssemblyContext:
         ms, nbytes = C.c_float(), C.c_int64()
         self._ck(self._lib.rdc_solve_mg_stats(self._h, C.byref(ms), C.byref(nbytes)))
         return ms.value, nbytes.value
+
+    def mg_colours(self):
+        """[colours] of every level of that hierarchy, as the Gauss-Seidel smoother (set_option("mg_smoother", 1)) sweeps them"""
+        n = C.c_int32()
+        self._ck(self._lib.rdc_solve_mg_levels(self._h, C.byref(n), None, None, 0))
+        colours = (C.c_int32 * n.value)()
+        self._ck(self._lib.rdc_solve_mg_colours(self._h, colours, n.value))
+        return [int(k) for k in colours]
 
     def part1_nodes(self):
         n = C.c_int64()

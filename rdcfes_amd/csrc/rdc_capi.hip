@@ -38,7 +38,8 @@ struct Buffers {
   // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
   // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
   // send: the send list of a partitioned solve (rdc_solve_dist_plan)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
+  // mg_gs: the colour lists of every level (first multigrid solve with the Gauss-Seidel smoother)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -53,6 +54,9 @@ struct SolveState {
   bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
   bool mg_dist = false;      // ... and it is the one of rdc_solve_dist_mg (ghost layers; mg_off holds the offsets of its exchanges)
   MgDev mg;
+  bool gs_ready = false;     // mg_gs holds the colour lists of this mesh's (single-partition) hierarchy, gs describes them
+  MgGsDev gs;
+  std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
   bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
   DistDims dist;
   bool peers_ready = false;  // halo0 is the plan with its per-peer segments (rdc_solve_dist_plan_peers)
@@ -115,6 +119,8 @@ struct rdc_ctx {
   hipEvent_t solid_part1_event = nullptr;   // recorded behind part 1 of a two-part solid assembly (the sides of part 2 wait for it)
   SolveScal* solve_rec = nullptr;   // pinned: the one record the host reads per iteration of the linear solve
   int mg_omega_permille = MG_OMEGA_PERMILLE;   // option "mg_omega": damping of the multigrid smoother, in thousandths
+  int mg_smoother = 0;                         // option "mg_smoother": 0 = damped block Jacobi, 1 = multicolour Gauss-Seidel
+  int mg_gs_fuse = 1;                          // option "mg_gs_fuse": small levels sweep in one launch (0: one launch per colour everywhere)
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call
@@ -686,6 +692,12 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
     c->mg_omega_permille = value;
     return RDC_OK;
   }
+  const bool smoother = !std::strcmp(key, "mg_smoother");
+  if (smoother || !std::strcmp(key, "mg_gs_fuse")) {   // solver settings as well
+    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "%s is 0 or 1, not %d", key, value);
+    (smoother ? c->mg_smoother : c->mg_gs_fuse) = value;
+    return RDC_OK;
+  }
   return options_set(c->opt, key, value, c->err, sizeof(c->err));
 }
 
@@ -1231,21 +1243,58 @@ static int mg_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps, const st
   return RDC_OK;
 }
 
+// The colour lists of the Gauss-Seidel smoother, one per level of the hierarchy `steps` describes: coloured on the host, validated,
+// and uploaded into one allocation that mg_gs_place measures and then carves (first solve with "mg_smoother" = 1 on a mesh).
+static int gs_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps) {
+  const HostPrep& P = c->ms.prep;
+  SolveState& S = c->ms.solve;
+  std::vector<MgColours> cols(steps.size() + 1);
+  for (size_t l = 0; l < cols.size(); l++) {
+    const bool ok = l == 0 ? mg_colour(P.n_owned, P.bptr.data(), P.bcol.data(), cols[0])
+                           : mg_colour(steps[l - 1].n, steps[l - 1].bptr.data(), steps[l - 1].bcol.data(), cols[l]);
+    if (!ok)
+      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern of multigrid level %d is not structurally symmetric: two coupled nodes share "
+                  "a colour, and a Gauss-Seidel sweep (\"mg_smoother\" = 1) over such colours would race", (int)l);
+  }
+  MgArena arena;
+  MgGsDev g;
+  mg_gs_place(cols, arena, g, [](void*, const void*, size_t) {});   // no base: measures
+  int rc = dev_alloc(c, c->buf.solve.mg_gs, arena.used);
+  if (rc) return rc;
+  arena = MgArena{(char*)c->buf.solve.mg_gs.p};
+  S.gs_cols = std::move(cols);
+  hipError_t e = hipSuccess;
+  mg_gs_place(S.gs_cols, arena, S.gs, [&](void* at, const void* list, size_t bytes) {
+    if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
+  });
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the colour lists failed: %s", hipGetErrorString(e));
+  S.gs_ready = true;
+  return RDC_OK;
+}
+
 static int mg_view(rdc_ctx* c, SolveDev* d) {
   const HostPrep& P = c->ms.prep;
-  MgDev& g = c->ms.solve.mg;
-  if (c->ms.solve.mg_dist) c->ms.solve.mg_ready = c->ms.solve.mg_dist = false;
-  if (!c->ms.solve.mg_ready) {
+  SolveState& S = c->ms.solve;
+  MgDev& g = S.mg;
+  if (S.mg_dist) S.mg_ready = S.mg_dist = false;
+  const bool want_gs = c->mg_smoother == 1 && !S.gs_ready;   // the hierarchy of a mesh is always the same: its colours outlive a rebuild
+  if (!S.mg_ready || want_gs) {
     std::vector<MgLevelHost> steps;
     if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
       return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
-    int rc = mg_upload(c, steps, nullptr);
-    if (rc) return rc;
-    c->ms.solve.mg_ready = true;
+    int rc;
+    if (want_gs && (rc = gs_upload(c, steps))) return rc;   // first: a refusal leaves the context as it was
+    if (!S.mg_ready && (rc = mg_upload(c, steps, nullptr))) return rc;
+    S.mg_ready = true;
   }
   g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
   g.omega = 1e-3 * c->mg_omega_permille;
   d->mg = &g;
+  if (c->mg_smoother == 1) {
+    S.gs.fuse = c->mg_gs_fuse != 0;
+    d->gs = &S.gs;
+  }
   return RDC_OK;
 }
 
@@ -1262,6 +1311,13 @@ int rdc_solve_mg_stats(rdc_ctx* c, float* setup_ms, int64_t* level_bytes) {
   if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
   if (setup_ms) *setup_ms = c->ms.solve.mg.setup_ms;
   if (level_bytes) *level_bytes = (int64_t)(c->buf.solve.mg_idx.bytes + c->buf.solve.mg_val.bytes);
+  return RDC_OK;
+}
+
+int rdc_solve_mg_colours(rdc_ctx* c, int32_t* n_colours, int cap) {
+  if (!c || cap < 0 || (cap > 0 && !n_colours)) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.solve.gs_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve with the Gauss-Seidel smoother has run on this mesh");
+  for (int l = 0; l < c->ms.solve.gs.n_levels && l < cap; l++) n_colours[l] = c->ms.solve.gs.lv[l].n_colours;
   return RDC_OK;
 }
 
@@ -1320,6 +1376,9 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (c->ms.prep.n_owned < c->ms.prep.n_node && p->precond == RDC_PRECOND_MULTIGRID && c->mg_smoother == 1)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
+                "partitions needs a rule for the ghost values and is not implemented", (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
   if (c->ms.prep.n_owned < c->ms.prep.n_node)
     return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
                 "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
@@ -1482,6 +1541,9 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
                 (int)RDC_PRECOND_MULTIGRID, (int)p->precond);
   if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
+  if (sized && c->mg_smoother == 1)
+    return fail(c, RDC_ERR_UNSUPPORTED, "rdc_solve_dist_mg smooths with damped Jacobi only: a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
+                "partitions needs a rule for the ghost values and is not implemented");
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   if (P.n_owned < P.n_node && !S.plan_ready)

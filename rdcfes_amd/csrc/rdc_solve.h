@@ -2,7 +2,8 @@
 // rdc_solve.hip use them.  Host+device like rdc_row.h, so that a CPU build can test exactly this code
 // (tests/host_solve_shim.cpp); free of other headers of the library on purpose.  Further down: the host side of the
 // aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp) and
-// the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp), and the hierarchy of a
+// the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp), the colour lists of the
+// Gauss-Seidel smoother (mg_colour, mg_gs_place; tests/host_solve_mg_gs_shim.cpp, tests/host_solve_mg_gs_main.cpp), and the hierarchy of a
 // ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
@@ -178,6 +179,11 @@ constexpr int MG_COARSEST_NODES = 40;   // no further level below a level of at 
 constexpr int MG_MAX_LEVELS = 10;       // levels, the matrix itself (level 0) included
 constexpr int MG_COARSEST_SWEEPS = 8;   // damped block-Jacobi sweeps that stand for the solve on the last level
 constexpr int MG_OMEGA_PERMILLE = 600;  // default damping of the smoother, in thousandths (option "mg_omega")
+// Gauss-Seidel smoother (option "mg_smoother" = 1): a level of at most this many nodes runs a whole sweep -- on the last level all
+// its sweeps -- in one launch of one workgroup (option "mg_gs_fuse" = 0: one launch per colour on every level).
+// Measured at K(119) on an MI355X: 54 launches per cycle against 94, and 233.7 / 155.9 ms per solve (first / fifth
+// step, FP64) against 233.9 / 156.0 ms -- worth 0.1 to 0.4 ms of a solve, inside the spread of two runs; kept, since it costs nothing.
+constexpr int MG_GS_FUSED_NODES = 512;
 
 // out = dinv * a in FP64: the summand of the level-1 Galerkin sum.  Every sum in ascending index order from 0.0, separate
 // multiply and add (scaled_block_f32 without its rounding).  scaled_entry is one entry: row `drow` of dinv, column `acol` of a.
@@ -533,6 +539,80 @@ inline void mg_place(const std::vector<MgLevelHost>& steps, int nvar, int64_t n_
   }
 }
 
+// ---- multicolour Gauss-Seidel smoother (option "mg_smoother" = 1): the colours of one level ----
+
+// Colour lists of the node-block graph of one level: the nodes of colour c are nodes[cptr[c] .. cptr[c + 1]), ascending.
+struct MgColours {
+  std::vector<int32_t> colour;   // [n] colour of a node
+  std::vector<int64_t> cptr;     // [colours + 1]
+  std::vector<int32_t> nodes;    // [n]
+  int n_colours() const { return (int)cptr.size() - 1; }
+};
+
+// Greedy colouring (n nodes, pattern bptr / bcol): nodes in ascending order, each takes the smallest colour that no row neighbour
+// with a colour already holds; self and columns >= n are ignored; no cap on the number of colours.  Then one pass over every block
+// (i, j), i != j: false if its two nodes share a colour, which only a structurally asymmetric pattern brings about -- a sweep
+// over such lists would race, so the caller must not run one.
+inline bool mg_colour(int64_t n, const int64_t* bptr, const int32_t* bcol, MgColours& C) {
+  C = MgColours();
+  C.colour.assign((size_t)n, -1);
+  std::vector<int64_t> held;   // held[c] == i + 1: a neighbour of node i has colour c
+  for (int64_t i = 0; i < n; i++) {
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
+      const int64_t j = bcol[k];
+      if (j != i && j < n && C.colour[(size_t)j] >= 0) held[(size_t)C.colour[(size_t)j]] = i + 1;
+    }
+    size_t c = 0;
+    while (c < held.size() && held[c] == i + 1) c++;
+    if (c == held.size()) held.push_back(0);
+    C.colour[(size_t)i] = (int32_t)c;
+  }
+  C.cptr.assign(held.size() + 1, 0);
+  for (int64_t i = 0; i < n; i++) C.cptr[(size_t)C.colour[(size_t)i] + 1]++;
+  for (size_t c = 0; c < held.size(); c++) C.cptr[c + 1] += C.cptr[c];
+  C.nodes.resize((size_t)n);
+  std::vector<int64_t> fill(C.cptr.begin(), C.cptr.end() - 1);
+  for (int64_t i = 0; i < n; i++) C.nodes[(size_t)fill[(size_t)C.colour[(size_t)i]]++] = (int32_t)i;
+  for (int64_t i = 0; i < n; i++)
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++)
+      if (bcol[k] != i && bcol[k] < n && C.colour[(size_t)bcol[k]] == C.colour[(size_t)i]) return false;
+  return true;
+}
+
+// The colour lists of every level on the device: one allocation, measured and placed like the arenas of mg_place (MgArena:
+// no base measures).  cptr_host: the same pointer array on the host, what the per-colour launches take their bounds from; it
+// points into `cols` and lives as long as they do.
+struct MgGsLevel {
+  int n_colours = 0;
+  const int32_t* nodes = nullptr;
+  const int64_t* cptr = nullptr;
+  const int64_t* cptr_host = nullptr;
+};
+
+struct MgGsDev {
+  int n_levels = 0;
+  MgGsLevel lv[MG_MAX_LEVELS];
+  bool fuse = true;   // option "mg_gs_fuse"
+};
+
+template <class Upload>
+inline void mg_gs_place(const std::vector<MgColours>& cols, MgArena& arena, MgGsDev& g, Upload&& upload) {
+  auto list = [&](const auto& v) {
+    const size_t bytes = v.size() * sizeof(v[0]);
+    void* at = arena.take(bytes);
+    if (at && bytes) upload(at, (const void*)v.data(), bytes);
+    return (decltype(v.data()))at;
+  };
+  g = MgGsDev();
+  g.n_levels = (int)cols.size();
+  for (size_t l = 0; l < cols.size(); l++) {
+    g.lv[l].n_colours = cols[l].n_colours();
+    g.lv[l].nodes = list(cols[l].nodes);
+    g.lv[l].cptr = list(cols[l].cptr);
+    g.lv[l].cptr_host = cols[l].cptr.data();
+  }
+}
+
 // ---- the iteration's scalars, its launch shapes and the layout of its work buffer: host code without HIP, so that a CPU build
 // can test the layout (tests/host_solve_dist_shim.cpp) ----
 
@@ -632,6 +712,7 @@ struct SolveDev {
   SolveScal* host_rec = nullptr;   // pinned
   hipStream_t stream = nullptr;
   MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
+  const MgGsDev* gs = nullptr;     // its colour lists: the smoother is Gauss-Seidel (option "mg_smoother" = 1); null: damped Jacobi
   // partitioned solve (rdc_solve_dist) only.  comm == nullptr is the single-partition path.
   const rdc_solve_comm* comm = nullptr;
   int peers = 0;                                 // rdc_solve_dist_plan_peers

@@ -20,7 +20,8 @@
 // x += alpha M p + omega M s), so the recurrence residual and everything that decides stay what they are above.  Coarse
 // matrices live in the same node-block layout and go through k_spmv and k_precond_setup as they are; k_galerkin rebuilds
 // their values per solve (a gather in a fixed order: no atomics), k_restrict / k_prolong / k_smooth are the rest of the cycle.
-// The cycle has no inner product and no host round trip.
+// The cycle has no inner product and no host round trip.  Its smoother is an argument (SolveDev::gs): damped block Jacobi, or,
+// opt-in, forward Gauss-Seidel in a multicolour order (k_gs and its kin, further down) for every sweep but the first of a level.
 //
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
@@ -600,13 +601,210 @@ __global__ __launch_bounds__(256) void k_smooth_pack(const double* __restrict__ 
   smooth_body<NV, false, false, true>(dinv, r, t, omega, n, x, send);
 }
 
-// First use of every kernel instantiation.  A code object lists template instantiations by first use; this list keeps the order
+// ---- multicolour Gauss-Seidel smoother (option "mg_smoother" = 1): x_n += D_l^-1 (r_n - (A_l x)_n), colour after colour ----
+//
+// A sweep visits the colour lists of the level in order (rdc_solve.h, mg_colour).  No two nodes of a colour are coupled, so the
+// nodes of a colour neither read nor write each other's entries of x and can run in any order: what orders the sweep is the
+// boundary between two colours -- a launch boundary (k_gs, k_gs_f32: one launch per colour), or, on a level small enough for
+// one workgroup, the barrier between two colours of one launch (k_gs_fused, k_gs_f32_fused).  x is read and written in place
+// and therefore neither const nor __restrict__ here; a node reads its own entries (its diagonal block) before it writes them:
+// the write of a lane depends on the sums of all lanes of the node through the butterfly.  The arithmetic of a node is
+// row_product followed by that of k_smooth with a damping of 1, in both kinds of launch: their results are bitwise equal.
+
+// The row product of k_spmv for one node: acc[a] = row a of `node` times x, a = 0 .. NV-1, in all 16 lanes of the node -- a lane's
+// own entries in ascending order, then the xor butterfly over the 16 lanes.  Every lane of the node calls, live or not (the
+// butterfly).  Stated a second time, for an x that is written in place: k_spmv keeps its own text, so that its device assembly
+// stays what it was.
+template <int NV>
+__device__ __forceinline__ void row_product(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                            const double* __restrict__ val, const double* x, int64_t node, bool live, int lane,
+                                            double (&acc)[NV]) {
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  if (live) {
+    const int64_t b0 = bptr[node];
+    const int L = (int)(bptr[node + 1] - b0) * NV;      // entries of one row of the node
+    const double* __restrict__ vrow = val + (int64_t)NV * NV * b0;
+    for (int j = lane; j < L; j += 16) {
+      const int k = j / NV, b = j - k * NV;
+      const double xv = x[(int64_t)bcol[b0 + k] * NV + b];
+#pragma unroll
+      for (int a = 0; a < NV; a++) acc[a] = fma(__builtin_nontemporal_load(vrow + (int64_t)a * L + j), xv, acc[a]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, 16);
+}
+
+// ... and that of k_spmv_f32: 8 lanes per node, 16 bytes per lane, row and step; x and the sums are FP64
+template <int NV>
+__device__ __forceinline__ void row_product_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                const int64_t* __restrict__ voff, const float* __restrict__ val32, const double* x,
+                                                int64_t node, bool live, int lane, double (&acc)[NV]) {
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  const int64_t b0 = live ? bptr[node] : 0;
+  const int len = live ? (int)(bptr[node + 1] - b0) : 0;
+  if (len > 0) {
+    const int L = len * NV, Lp = (int)f32_row_stride(NV, len);   // entries of one row of the node, and its padded stride
+    const float* __restrict__ vrow = val32 + voff[node];
+    // x indices of the 4 entries at j .. j + 3.  Every load of the loop is unconditional -- a position past the row's end
+    // (padding, or the look-ahead behind the last step) re-reads the row's last entry and is zeroed or dropped afterwards:
+    // a load behind a per-element condition would be branched around and waited for one by one.
+    auto columns = [&](int j, int32_t (&cn)[4], int (&cb)[4]) {   // column node and unknown of the entries j .. j + 3
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const int jj = min(j + e, L - 1), k = jj / NV;
+        cb[e] = jj - k * NV;
+        cn[e] = bcol[b0 + k];
+      }
+    };
+    int32_t cn[4], nn[4];
+    int cb[4], nb[4];
+    columns(4 * lane, cn, cb);
+    for (int j = 4 * lane; j < Lp; j += 4 * F32_LANES) {
+      // the next step's column nodes are requested together with this step's values and x entries and used a step later:
+      // the bcol -> x chain then costs one memory latency per step, not two
+      columns(j + 4 * F32_LANES, nn, nb);
+      f32x4 v[NV];
+#pragma unroll
+      for (int a = 0; a < NV; a++) v[a] = __builtin_nontemporal_load((const f32x4*)(vrow + (int64_t)a * Lp + j));
+      double xv[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) xv[e] = x[(int64_t)cn[e] * NV + cb[e]];
+      __builtin_amdgcn_sched_barrier(0);   // keep the three groups of loads ahead of the arithmetic
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        xv[e] = j + e < L ? xv[e] : 0.0;
+        cn[e] = nn[e];
+        cb[e] = nb[e];
+      }
+#pragma unroll
+      for (int a = 0; a < NV; a++) {
+        acc[a] = fma((double)v[a].x, xv[0], acc[a]);
+        acc[a] = fma((double)v[a].y, xv[1], acc[a]);
+        acc[a] = fma((double)v[a].z, xv[2], acc[a]);
+        acc[a] = fma((double)v[a].w, xv[3], acc[a]);
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = F32_LANES / 2; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, F32_LANES);
+}
+
+// one node on the FP64 values.  IDENT (level 0): the operator is D^-1 A, whose block diagonal is the identity, and dinv is the
+// D^-1 of the operator (k_spmv, EPI 2); otherwise dinv is the D_l^-1 of the smoother (k_smooth)
+template <int NV, bool IDENT>
+__device__ __forceinline__ void gs_node(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                        const double* __restrict__ val, const double* __restrict__ dinv, const double* __restrict__ r,
+                                        double* x, int64_t node, bool live, int lane) {
+  double acc[NV];
+  row_product<NV>(bptr, bcol, val, x, node, live, lane, acc);
+  if (live && lane < NV) {
+    const int64_t i = node * NV + lane;
+    const double* __restrict__ drow = dinv + i * NV;
+    double z = 0.0;
+    if (IDENT) {
+#pragma unroll
+      for (int a = 0; a < NV; a++) z = fma(drow[a], acc[a], z);
+      z = r[i] - z;
+    } else {
+#pragma unroll
+      for (int q = 0; q < NV; q++) z = fma(drow[q], r[node * NV + q] - acc[q], z);
+    }
+    x[i] = x[i] + z;
+  }
+}
+
+// one node on the fp32 copy of D^-1 A (level 0 of rdc_solve_mixed): no epilogue, the copy is scaled
+template <int NV>
+__device__ __forceinline__ void gs_node_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                            const int64_t* __restrict__ voff, const float* __restrict__ val32,
+                                            const double* __restrict__ r, double* x, int64_t node, bool live, int lane) {
+  double acc[NV];
+  row_product_f32<NV>(bptr, bcol, voff, val32, x, node, live, lane, acc);
+  double t = acc[0];
+#pragma unroll
+  for (int a = 1; a < NV; a++) t = lane == a ? acc[a] : t;
+  if (live && lane < NV) {
+    const int64_t i = node * NV + lane;
+    x[i] = x[i] + (r[i] - t);
+  }
+}
+
+// the nodes list[0 .. count) of one colour: 16 lanes per node as k_spmv
+template <int NV, bool IDENT>
+__global__ __launch_bounds__(256) void k_gs(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                            const double* __restrict__ val, const double* __restrict__ dinv,
+                                            const double* __restrict__ r, double* x, const int32_t* __restrict__ list, int64_t count) {
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  const bool live = at < count;
+  gs_node<NV, IDENT>(bptr, bcol, val, dinv, r, x, live ? list[at] : 0, live, threadIdx.x & 15);
+}
+
+// ... 8 lanes per node as k_spmv_f32
+template <int NV>
+__global__ __launch_bounds__(256) void k_gs_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                const int64_t* __restrict__ voff, const float* __restrict__ val32,
+                                                const double* __restrict__ r, double* x, const int32_t* __restrict__ list, int64_t count) {
+  const int64_t at = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  const bool live = at < count;
+  gs_node_f32<NV>(bptr, bcol, voff, val32, r, x, live ? list[at] : 0, live, threadIdx.x & (F32_LANES - 1));
+}
+
+// `sweeps` whole sweeps over a level of at most MG_GS_FUSED_NODES nodes in one workgroup: the colours in order, a barrier behind
+// each (it also makes the stores to x visible to the other waves of the workgroup).  The trip counts are uniform over the
+// lanes of a node and the barriers over the workgroup.
+constexpr int GS_FUSED_THREADS = 1024;
+
+template <int NV, bool IDENT>
+__global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_fused(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                               const double* __restrict__ val, const double* __restrict__ dinv,
+                                                               const double* __restrict__ r, double* x, const int32_t* __restrict__ list,
+                                                               const int64_t* __restrict__ cptr, int n_colours, int sweeps) {
+  for (int s = 0; s < sweeps; s++)
+    for (int c = 0; c < n_colours; c++) {
+      const int64_t c1 = cptr[c + 1];
+      for (int64_t at0 = cptr[c]; at0 < c1; at0 += GS_FUSED_THREADS / 16) {
+        const int64_t at = at0 + (threadIdx.x >> 4);
+        const bool live = at < c1;
+        gs_node<NV, IDENT>(bptr, bcol, val, dinv, r, x, live ? list[at] : 0, live, threadIdx.x & 15);
+      }
+      __syncthreads();
+    }
+}
+
+template <int NV>
+__global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_f32_fused(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                                   const int64_t* __restrict__ voff, const float* __restrict__ val32,
+                                                                   const double* __restrict__ r, double* x, const int32_t* __restrict__ list,
+                                                                   const int64_t* __restrict__ cptr, int n_colours, int sweeps) {
+  for (int s = 0; s < sweeps; s++)
+    for (int c = 0; c < n_colours; c++) {
+      const int64_t c1 = cptr[c + 1];
+      for (int64_t at0 = cptr[c]; at0 < c1; at0 += GS_FUSED_THREADS / F32_LANES) {
+        const int64_t at = at0 + (threadIdx.x / F32_LANES);
+        const bool live = at < c1;
+        gs_node_f32<NV>(bptr, bcol, voff, val32, r, x, live ? list[at] : 0, live, threadIdx.x & (F32_LANES - 1));
+      }
+      __syncthreads();
+    }
+}
+
+// First use of every kernel instantiation. A code object lists template instantiations by first use; this list keeps the order
 // they have had since each was added, whatever order the launch code below uses them in, so that the device assembly of two
 // revisions can be compared byte for byte.
 #define KERNELS_OF(NV)                                                                                                          \
   (const void*)k_galerkin<NV, true>, (const void*)k_galerkin<NV, false>, (const void*)k_residual<NV>,                            \
   (const void*)k_smooth<NV, true, true>, (const void*)k_spmv<NV, 2>, (const void*)k_restrict<NV>,                                \
   (const void*)k_smooth<NV, true, false>, (const void*)k_smooth<NV, false, false>, (const void*)k_prolong<NV>
+#define GS_KERNELS_OF(NV)                                                                                                       \
+  (const void*)k_gs<NV, true>, (const void*)k_gs<NV, false>, (const void*)k_gs_f32<NV>, (const void*)k_gs_fused<NV, true>,     \
+  (const void*)k_gs_fused<NV, false>, (const void*)k_gs_f32_fused<NV>
 [[maybe_unused]] const void* const KERNEL_ORDER[] = {
     (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
@@ -614,8 +812,10 @@ __global__ __launch_bounds__(256) void k_smooth_pack(const double* __restrict__ 
     KERNELS_OF(3), (const void*)k_update_xr<true>, (const void*)k_update_xr<false>, KERNELS_OF(5),
     (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>,
     (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
-    (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>};
+    (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>,
+    GS_KERNELS_OF(3), GS_KERNELS_OF(5)};
 #undef KERNELS_OF
+#undef GS_KERNELS_OF
 
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
@@ -769,21 +969,58 @@ hipError_t mg_apply(const SolveDev& d, const Work& w, int l, Form form, double* 
   return apply<NV>(d, &w, l, form, x, y, nullptr);
 }
 
-// x += w D_l^-1 (r - A_l x)
+// `sweeps` forward Gauss-Seidel sweeps on level l over its colour lists (d.gs): x_n += D_l^-1 (r_n - (A_l x)_n) in place.  A level
+// of at most MG_GS_FUSED_NODES nodes takes one launch of one workgroup for all of them, any other one launch per colour and sweep.
 template <int NV>
-hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, double* t) {
+hipError_t gs_sweeps(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, int sweeps) {
+  const MgLevelDev& L = d.mg->lv[l];
+  const MgGsLevel& C = d.gs->lv[l];
+  if (!L.n) return hipSuccess;
+  const bool f32 = l == 0 && form == F32, fused = d.gs->fuse && L.n <= MG_GS_FUSED_NODES;
+  const double* val = l ? (const double*)L.val : d.val;
+  const double* dinv = l ? (const double*)L.dinv : (const double*)w.dinv;
+  if (fused) {
+    const dim3 one(1), block(GS_FUSED_THREADS);
+    if (f32)
+      hipLaunchKernelGGL((k_gs_f32_fused<NV>), one, block, 0, d.stream, L.bptr, L.bcol, d.voff, (const float*)d.val32, r, x, C.nodes, C.cptr,
+                         C.n_colours, sweeps);
+    else
+      hipLaunchKernelGGL((l ? k_gs_fused<NV, false> : k_gs_fused<NV, true>), one, block, 0, d.stream, L.bptr, L.bcol, val, dinv, r, x, C.nodes,
+                         C.cptr, C.n_colours, sweeps);
+    return hipGetLastError();
+  }
+  for (int s = 0; s < sweeps; s++)
+    for (int c = 0; c < C.n_colours; c++) {
+      const int64_t c0 = C.cptr_host[c], count = C.cptr_host[c + 1] - c0;
+      const dim3 grid((unsigned)op_blocks(count, f32 ? F32 : SCALED)), block(256);
+      if (f32)
+        hipLaunchKernelGGL((k_gs_f32<NV>), grid, block, 0, d.stream, L.bptr, L.bcol, d.voff, (const float*)d.val32, r, x, C.nodes + c0, count);
+      else
+        hipLaunchKernelGGL((l ? k_gs<NV, false> : k_gs<NV, true>), grid, block, 0, d.stream, L.bptr, L.bcol, val, dinv, r, x, C.nodes + c0, count);
+    }
+  return hipGetLastError();
+}
+
+// `sweeps` sweeps of the smoother on level l from the x at hand: damped Jacobi, x += w D_l^-1 (r - A_l x), or, with colour lists
+// (d.gs), forward Gauss-Seidel, which needs neither t nor a launch of the operator
+template <int NV>
+hipError_t mg_smooth(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, double* t, int sweeps = 1) {
+  if (d.gs) return gs_sweeps<NV>(d, w, l, form, r, x, sweeps);
   const MgDev& g = *d.mg;
   const int64_t n = g.lv[l].n;
-  SOLVE_HIP(mg_apply<NV>(d, w, l, form, x, t));
-  if (!n) return hipSuccess;   // a rank may own no node of a level
-  if (l == 0)
-    hipLaunchKernelGGL((k_smooth<NV, true, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
-  else if (packs(d, l))
-    hipLaunchKernelGGL((k_smooth_pack<NV>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x,
-                       send_list(g.lv[l]));
-  else
-    hipLaunchKernelGGL((k_smooth<NV, false, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
-  return hipGetLastError();
+  for (int s = 0; s < sweeps; s++) {
+    SOLVE_HIP(mg_apply<NV>(d, w, l, form, x, t));
+    if (!n) continue;   // a rank may own no node of a level
+    if (l == 0)
+      hipLaunchKernelGGL((k_smooth<NV, true, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)nullptr, r, (const double*)t, g.omega, n, x);
+    else if (packs(d, l))
+      hipLaunchKernelGGL((k_smooth_pack<NV>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x,
+                         send_list(g.lv[l]));
+    else
+      hipLaunchKernelGGL((k_smooth<NV, false, false>), per_thread(n * NV), dim3(256), 0, d.stream, (const double*)g.lv[l].dinv, r, (const double*)t, g.omega, n, x);
+    SOLVE_HIP(hipGetLastError());
+  }
+  return hipSuccess;
 }
 
 // out = M in: one V(1,1) cycle from a zero start.  Enqueues only; a fixed linear operator for fixed values.  Across ranks `out`
@@ -809,7 +1046,7 @@ hipError_t mg_cycle(const SolveDev& d, const Work& w, Form form, const double* i
       hipLaunchKernelGGL((k_restrict<NV>), per_thread(C.n), dim3(256), 0, d.stream, C.mptr, C.member, R(l),
                          (const double*)T(l), (const double*)C.dinv, g.omega, C.n, C.r, C.x);
   }
-  for (int sweep = 1; sweep < MG_COARSEST_SWEEPS; sweep++) SOLVE_HIP(mg_smooth<NV>(d, w, last, form, R(last), X(last), T(last)));
+  SOLVE_HIP(mg_smooth<NV>(d, w, last, form, R(last), X(last), T(last), MG_COARSEST_SWEEPS - 1));
   for (int l = last - 1; l >= 0; l--) {   // up: correction, then the second sweep
     const int64_t n = g.lv[l].n;
     if (n) {

@@ -1,7 +1,8 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--ab [precond|precision|dist]] [--dump DIR]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
+                              [--ab [precond|precision|dist|smoother]] [--dump DIR]
     python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
@@ -14,8 +15,12 @@ process on one device: --ab (= --ab precond) in the order block Jacobi, multigri
 four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
 rdc_solve_dist, rdc_solve_dist, rdc_solve, the partitioned entry at world size 1 (its exchange moves nothing and its all-reduce
 leaves the values alone: what is timed is the pack launches, the k_reduce / k_advance split and the callbacks; with --precond 3
-the partitioned entry is rdc_solve_dist_mg, whose cycle adds the sized callbacks of the levels below the matrix).  --dump writes
-the state after the last step as DIR/state.npy (+ conn, xyz).
+the partitioned entry is rdc_solve_dist_mg, whose cycle adds the sized callbacks of the levels below the matrix); --ab smoother
+(multigrid) in the order damped Jacobi, Gauss-Seidel, Gauss-Seidel, damped Jacobi.  --smoother 1 is the multicolour Gauss-Seidel
+smoother of the cycle (option "mg_smoother"; single partition, --precond 3), --gs-fuse 0 gives every level one launch per colour
+(option "mg_gs_fuse"); every record of a multigrid solve has the smoother, with Gauss-Seidel the colours per level, and the
+kernel launches of one cycle (counted from the level sizes and colours: tools/time_loop.py, cycle_launches).  --dump writes the
+state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
@@ -52,7 +57,22 @@ def background_share(u, conn_dev):
     return float(bg.double().mean()), float(bg[conn_dev].all(dim=1).double().mean())
 
 
-def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None):
+def cycle_launches(levels, colours=None, fuse=True, fused_nodes=512):
+    """kernel launches of one V(1,1) cycle on one partition.  Both smoothers: the first sweep of level 0, an operator application and
+    a restriction per step down, a prolongation per step up.  Damped Jacobi: 2 more (operator, update) for each of the 7 further sweeps
+    of the last level and for the post-smoothing of every other level.  Gauss-Seidel (colours = [colours per level]): a sweep is one
+    launch per colour, or one launch for all sweeps on a level of at most fused_nodes (rdc_solve.h, MG_GS_FUSED_NODES) nodes"""
+    last = len(levels) - 1
+    sweeps = [1] * last + [7]
+
+    def smooth(l):
+        if colours is None:
+            return 2 * sweeps[l]
+        return 1 if fuse and levels[l][0] <= fused_nodes else colours[l] * sweeps[l]
+    return 1 + 3 * last + sum(smooth(l) for l in range(last + 1))
+
+
+def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None, smoother=0, gs_fuse=1):
     """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
     on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there).
     comm: a halo.SolveComm -- the solve is solve_dist across its ranks (the background shares are then those of the local nodes)."""
@@ -61,6 +81,9 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
     u = state_tensor(ctx)
     conn_dev = torch.from_numpy(np.ascontiguousarray(conn, dtype=np.int64)).to(dev)
     ctx.timing_enable(True)
+    if precond == 3 and comm is None:   # across partitions the smoother is damped Jacobi, and the option would be refused
+        ctx.set_option("mg_smoother", smoother)
+        ctx.set_option("mg_gs_fuse", gs_fuse)
     out = []
     for k in range(steps):
         ctx.assemble_pihna(params)
@@ -83,6 +106,11 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         if precond == 3:
             setup_ms, level_bytes = ctx.mg_stats()
             out[-1].update(mg_setup_ms=setup_ms, mg_level_bytes=level_bytes, mg_levels=ctx.mg_levels())
+            if comm is None:
+                colours = ctx.mg_colours() if smoother else None
+                out[-1].update(mg_smoother=smoother, cycle_launches=cycle_launches(out[-1]["mg_levels"], colours, bool(gs_fuse)))
+                if smoother:
+                    out[-1].update(mg_colours=colours, mg_gs_fuse=gs_fuse)
     return out
 
 
@@ -135,11 +163,17 @@ def main():
     ap.add_argument("--precond", type=int, default=2)
     ap.add_argument("--max-its", type=int, default=20000)
     ap.add_argument("--mixed", action="store_true")
-    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist"), default=None)
+    ap.add_argument("--smoother", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--gs-fuse", type=int, choices=(0, 1), default=1)
+    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist", "smoother"), default=None)
     ap.add_argument("--dump", default=None)
     ap.add_argument("--ranks", type=int, default=1)
     ap.add_argument("--backend", choices=("gloo", "nccl"), default="gloo")
     a = ap.parse_args()
+    if a.ab == "smoother":
+        a.precond = 3
+    if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or a.ab == "dist"):
+        ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
     if a.ranks > 1:
         import socket
         import torch.multiprocessing as mp
@@ -157,24 +191,28 @@ def main():
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
-        runs = [(a.precond, a.mixed, False)]
+        runs = [(a.precond, a.mixed, False, a.smoother)]
         if a.ab == "precond":
-            runs = [(pc, a.mixed, False) for pc in (2, 3, 3, 2)]
+            runs = [(pc, a.mixed, False, a.smoother) for pc in (2, 3, 3, 2)]
         elif a.ab == "precision":
-            runs = [(a.precond, mixed, False) for mixed in (False, True, True, False)]
+            runs = [(a.precond, mixed, False, a.smoother) for mixed in (False, True, True, False)]
         elif a.ab == "dist":
-            runs = [(a.precond, a.mixed, d) for d in (False, True, True, False)]
+            runs = [(a.precond, a.mixed, d, 0) for d in (False, True, True, False)]
+        elif a.ab == "smoother":
+            runs = [(3, a.mixed, False, sm) for sm in (0, 1, 1, 0)]
         comm = None
         if a.ab == "dist":      # world size 1: no peers, no process group
             from rdcfes_amd import SolveComm, partition
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
             comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3)
-        for precond, mixed, dist_entry in runs:
+        for precond, mixed, dist_entry, smoother in runs:
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
+                                  smoother=smoother if precond == 3 else None,
                                   entry=("rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") + ", world size 1" if dist_entry else "rdc_solve")))
-            for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None):
+            for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None,
+                           smoother=smoother, gs_fuse=a.gs_fuse):
                 print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
