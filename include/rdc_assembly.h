@@ -442,6 +442,28 @@ int rdc_solve_mg_stats(rdc_ctx* ctx, float* setup_ms, int64_t* level_bytes);
  * (rdc_solve_mg_levels tells how many there are).  RDC_ERR_STATE if no multigrid solve with "mg_smoother" = 1 has run on
  * this mesh. */
 int rdc_solve_mg_colours(rdc_ctx* ctx, int32_t* n_colours, int cap);
+/* ---- two read-only observation points of the cycle (additive: RDC_ABI_VERSION stays 3).  TEST HOOKS: they exist so that a
+ * test can hold the cycle M and the coarse matrices to a reference; no solver path needs them, and nothing is claimed about
+ * their speed.
+ * rdc_solve_mg_apply: d_out = M d_in, ONE cycle, as the next rdc_solve (mixed == 0) or rdc_solve_mixed (mixed != 0) with
+ * RDC_PRECOND_MULTIGRID would apply it: the call first does what such a solve does before its first iteration (D^-1, the
+ * fp32 copy if mixed, the values and D_l^-1 of every level from the current CSR values -- the same host function, so the
+ * hierarchy and the colours are built at first use here too), then applies the cycle in the form that solve would iterate
+ * in: on the fp32 copy of level 0 if mixed and every entry of D^-1 A is finite in FP32, on the FP64 values otherwise.
+ * "mg_omega", "mg_smoother" and "mg_gs_fuse" are honoured; it launches no kernel a solve does not launch.  d_in, d_out:
+ * DEVICE pointers, n_owned*nvar doubles each, not overlapping.  Blocks the host until done; never modifies the CSR values
+ * or the rhs.  RDC_ERR_STATE without a mesh, RDC_ERR_INVALID for a null pointer, RDC_ERR_UNSUPPORTED on a context with
+ * ghost nodes (the message of rdc_solve); RDC_ERR_INVALID, with the count in the message and d_out untouched, if a
+ * diagonal block of any level is not invertible. */
+int rdc_solve_mg_apply(rdc_ctx* ctx, int mixed, const double* d_in, double* d_out);
+/* What the last rdc_solve_mg_apply, or the last rdc_solve / rdc_solve_mixed with RDC_PRECOND_MULTIGRID, built for `level`
+ * (0 .. levels - 1, rdc_solve_mg_levels), into HOST arrays: val = the level's matrix, blocks[level] * nvar^2 doubles in the
+ * node-block layout of the CSR values ([var a][block k][var b] per node, over the level's own pattern); dinv = its D_l^-1,
+ * nodes[level] * nvar^2 doubles, row-major per node.  Level 0 is the matrix itself: val must be NULL there, and dinv
+ * receives the solver's D^-1.  Either pointer may be NULL to skip that array.  RDC_ERR_STATE if neither producer has run
+ * on this mesh, or if a call that runs or plans a solve (any other rdc_solve* entry but the three queries above) or
+ * rdc_csr_scale_f32 has come after it: those write over the D^-1 this call reads.  RDC_ERR_INVALID for a level out of range. */
+int rdc_solve_mg_level_download(rdc_ctx* ctx, int level, double* val, double* dinv);
 
 /* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
  * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own

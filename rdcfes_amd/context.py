@@ -411,6 +411,38 @@ class AssemblyContext:
         self._ck(self._lib.rdc_solve_mg_colours(self._h, colours, n.value))
         return [int(k) for k in colours]
 
+    def mg_apply_device(self, in_ptr, out_ptr, mixed=False):
+        """rdc_solve_mg_apply on device addresses (n_owned*nvar doubles each): out = M in, one multigrid cycle as the next
+        solve(precond=PRECOND_MULTIGRID, mixed=mixed) would apply it.  A test hook."""
+        self._ck(self._lib.rdc_solve_mg_apply(self._h, 1 if mixed else 0, C.c_void_p(int(in_ptr)), C.c_void_p(int(out_ptr))))
+
+    def mg_apply(self, x, mixed=False):
+        """numpy in, numpy out (tests): M x"""
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.n_owned * self.nvar:
+            raise ValueError("x must have n_owned * nvar entries")
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(x).to(dev)
+        yd = torch.empty_like(xd)
+        torch.cuda.synchronize(dev)
+        self.mg_apply_device(xd.data_ptr(), yd.data_ptr(), mixed)
+        return yd.cpu().numpy()
+
+    def mg_level(self, level):
+        """rdc_solve_mg_level_download -> (val, dinv) of a level as the last mg_apply or multigrid solve built them: val
+        [blocks * nvar^2] in the node-block layout over the level's pattern (None for level 0, the matrix itself), dinv
+        [nodes][nvar][nvar].  A test hook."""
+        levels = self.mg_levels()
+        if not 0 <= int(level) < len(levels):
+            self._ck(self._lib.rdc_solve_mg_level_download(self._h, int(level), None, None))
+        n, blocks = levels[int(level)]
+        nv = self.nvar
+        val = np.empty(blocks * nv * nv, dtype=np.float64) if level else None
+        dinv = np.empty((n, nv, nv), dtype=np.float64)
+        self._ck(self._lib.rdc_solve_mg_level_download(self._h, int(level), _dp(val) if level else None, _dp(dinv)))
+        return val, dinv
+
     def part1_nodes(self):
         n = C.c_int64()
         self._ck(self._lib.rdc_part1_nodes(self._h, C.byref(n)))

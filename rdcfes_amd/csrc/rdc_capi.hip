@@ -54,6 +54,10 @@ struct SolveState {
   bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
   bool mg_dist = false;      // ... and it is the one of rdc_solve_dist_mg (ghost layers; mg_off holds the offsets of its exchanges)
   MgDev mg;
+  // mg_val and the D^-1 of the work buffer hold what the last rdc_solve_mg_apply or multigrid solve built, and nothing has run
+  // over them since (rdc_solve_mg_level_download).  Set by those two; cleared on entry to every other call that runs or plans a
+  // solve (rdc_solve*, rdc_solve_dist*) and to rdc_csr_scale_f32; the queries (rdc_solve_mg_levels / _stats / _colours) leave it.
+  bool mg_values = false;
   bool gs_ready = false;     // mg_gs holds the colour lists of this mesh's (single-partition) hierarchy, gs describes them
   MgGsDev gs;
   std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
@@ -1343,6 +1347,7 @@ int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (!known_precond(precond, false)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
   c->ms.solve.f32_copy = false;
+  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt, for `precond`
   SolveDev d;
   int rc = solve_view(c, true, true, &d);
   if (rc) return rc;
@@ -1367,22 +1372,27 @@ int rdc_csr_matvec_f32(rdc_ctx* c, const double* d_x, double* d_y) {
   return RDC_OK;
 }
 
+// the single-partition entries on a context with ghost nodes (multigrid: the cycle is asked for)
+static int refuse_ghosted(rdc_ctx* c, bool multigrid) {
+  if (multigrid && c->mg_smoother == 1)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
+                "partitions needs a rule for the ghost values and is not implemented", (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
+  return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
+              "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
+              (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
+}
+
 static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info, bool mixed) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;
   if (!p || !d_x || !info) return fail(c, RDC_ERR_INVALID, "null argument");
   if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
   if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
-  if (c->ms.prep.n_owned < c->ms.prep.n_node && p->precond == RDC_PRECOND_MULTIGRID && c->mg_smoother == 1)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
-                "partitions needs a rule for the ghost values and is not implemented", (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
-  if (c->ms.prep.n_owned < c->ms.prep.n_node)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
-                "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
-                (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
+  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, p->precond == RDC_PRECOND_MULTIGRID);
   if (c->ms.prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
     *info = rdc_solve_info();
     info->matrix_bits = 64;
@@ -1395,6 +1405,7 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
   RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
   if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
+  c->ms.solve.mg_values = p->precond == RDC_PRECOND_MULTIGRID;
   return RDC_OK;
 }
 
@@ -1402,12 +1413,56 @@ int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info
 
 int rdc_solve_mixed(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, true); }
 
+int rdc_solve_mg_apply(rdc_ctx* c, int mixed, const double* d_in, double* d_out) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;
+  if (!d_in || !d_out) return fail(c, RDC_ERR_INVALID, "null vector");
+  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, true);
+  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
+  SolveDev d;
+  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
+  int rc = solve_view(c, true, mixed != 0, &d);
+  if (rc) return rc;
+  if ((rc = mg_view(c, &d))) return rc;
+  int bad = 0, bits = 64;
+  RDC_HIP(c, solve_mg_apply(d, mixed != 0, d_in, d_out, &bad, &bits));
+  if (mixed) c->ms.solve.f32_copy = bits == 32 && bad == 0;
+  c->ms.solve.mg_values = true;
+  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks of the multigrid levels are not invertible: no cycle was applied", bad);
+  return RDC_OK;
+}
+
+int rdc_solve_mg_level_download(rdc_ctx* c, int level, double* val, double* dinv) {
+  if (!c) return RDC_ERR_INVALID;
+  const SolveState& S = c->ms.solve;
+  if (!c->ms.have_mesh || !S.mg_ready || !S.mg_values)
+    return fail(c, RDC_ERR_STATE, "no rdc_solve_mg_apply or multigrid solve has run on this mesh, or a later call has overwritten what it built");
+  if (level < 0 || level >= S.mg.n_levels) return fail(c, RDC_ERR_INVALID, "level %d: the hierarchy has the levels 0 .. %d", level, S.mg.n_levels - 1);
+  if (level == 0 && val) return fail(c, RDC_ERR_INVALID, "level 0 is the matrix itself (rdc_csr_download): val must be NULL");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const MgLevelDev& L = S.mg.lv[level];
+  const size_t nv2 = (size_t)c->ms.prep.nvar * c->ms.prep.nvar;
+  const double* d_dinv = L.dinv;
+  if (level == 0) {
+    SolveDev d;
+    if ((rc = solve_view(c, true, false, &d))) return rc;
+    d_dinv = solve_dinv(d);
+  }
+  if (val && L.blocks) RDC_HIP(c, hipMemcpyAsync(val, L.val, (size_t)L.blocks * nv2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (dinv && L.n) RDC_HIP(c, hipMemcpyAsync(dinv, d_dinv, (size_t)L.n * nv2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  RDC_HIP(c, hipStreamSynchronize(c->stream));
+  return RDC_OK;
+}
+
 int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   if (n_send < 0 || (n_send > 0 && !send_nodes)) return fail(c, RDC_ERR_INVALID, "bad send list");
   const HostPrep& P = c->ms.prep;
   c->ms.solve.plan_ready = c->ms.solve.peers_ready = false;
+  c->ms.solve.mg_values = false;
   if (c->ms.solve.mg_dist) c->ms.solve.mg_ready = c->ms.solve.mg_dist = false;   // a new plan drops the hierarchy built on the old one
   c->ms.solve.halo0 = MgHalo();
   const int64_t n_int = c->opt.interior_nodes > 0 ? c->opt.interior_nodes : 0;
@@ -1432,6 +1487,7 @@ int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
 int rdc_solve_dist_plan_peers(rdc_ctx* c, int32_t n_peers, const int64_t* send_count, const int64_t* ghost_count) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;
   if (!c->ms.solve.plan_ready) return fail(c, RDC_ERR_STATE, "no send list: call rdc_solve_dist_plan first");
   if (n_peers < 0 || (n_peers > 0 && (!send_count || !ghost_count))) return fail(c, RDC_ERR_INVALID, "bad peer counts");
   const HostPrep& P = c->ms.prep;
@@ -1528,6 +1584,7 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
                            double* d_x, rdc_solve_info* info) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;   // the work buffer takes the layout of a partitioned solve
   if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
   if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum || (sized && (!sized->exchange_sized_begin || !sized->exchange_sized_end)))
     return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");

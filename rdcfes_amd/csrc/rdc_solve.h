@@ -732,6 +732,12 @@ hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rd
 // D^-1 and the fp32 copy from the current values; synchronises to return the two counters
 hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int* overflow);
 hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y);
+// Test hook (rdc_solve_mg_apply): out = M in, one multigrid cycle behind the prologue of a multigrid solve (the same host function),
+// in the form that solve would iterate in; in and out hold n_owned * nvar doubles and do not overlap; d.mg is set, d.comm is not.
+// *bad_blocks > 0: a diagonal block of some level is not invertible, nothing was applied.  Synchronises.
+hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, double* out, int* bad_blocks, int* matrix_bits);
+// where the D^-1 of the last single-partition set-up lies in d.work (n_owned * nvar * nvar doubles)
+const double* solve_dinv(const SolveDev& d);
 
 }  // namespace rdc
 #endif

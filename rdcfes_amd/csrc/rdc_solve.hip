@@ -1108,6 +1108,27 @@ hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, boo
   return read_record(d, w);
 }
 
+// What a solve does before its first iteration, stated once for run() and for the probe of the cycle (solve_mg_apply): the scalars
+// cleared, D^-1 and (mixed) the fp32 copy, with RDC_PRECOND_MULTIGRID the values and D_l^-1 of every coarse level, then `read`,
+// which brings the scalar record to the host -- the first residual of a solve, the bare copy of the probe -- and what the record
+// decides: the blocks that could not be inverted, and the form the operator applications stream.
+struct Start {
+  Form form = SCALED;
+  int bad_blocks = 0;
+};
+
+template <int NV, class Read>
+hipError_t prologue(const SolveDev& d, const Work& w, int precond, bool mixed, Read&& read, Start* s) {
+  SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
+  const bool mg = precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
+  SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : precond, mixed));
+  if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
+  SOLVE_HIP(read());
+  s->bad_blocks = d.host_rec->bad_blocks;
+  s->form = mixed && d.host_rec->f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
+  return hipSuccess;
+}
+
 template <int NV>
 hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   const Work w = carve(d.nvar, d.n_owned, d.work, d.comm ? &d.dist : nullptr);
@@ -1117,15 +1138,13 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
     info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
   };
-  SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
-  const bool mg = p.precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
-  SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : (int)p.precond, mixed));
-  if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
-  SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale, true));
-  info->bad_blocks = rec.bad_blocks;
-  const Form form = mixed && rec.f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
+  const bool mg = p.precond == RDC_PRECOND_MULTIGRID;
+  Start start;
+  SOLVE_HIP(prologue<NV>(d, w, (int)p.precond, mixed, [&] { return residual<NV>(d, w, x, p.rhs_scale, true); }, &start));
+  info->bad_blocks = start.bad_blocks;
+  const Form form = start.form;
   info->matrix_bits = form == F32 ? 32 : 64;
-  if (rec.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
+  if (start.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
   if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
   if (rec.bn2 == 0.0) {   // b = 0: x = 0
     SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)(d.comm ? d.dist.n_nodes * NV : w.n) * sizeof(double), d.stream));
@@ -1181,6 +1200,22 @@ hipError_t solve_scale_f32(const SolveDev& d, int precond, int* bad_blocks, int*
   *overflow = d.host_rec->f32_overflow;
   return hipSuccess;
 }
+
+hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, double* out, int* bad_blocks, int* matrix_bits) {
+  return by_nvar(d.nvar, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    const Work w = carve(d.nvar, d.n_owned, d.work);
+    Start start;
+    SOLVE_HIP(prologue<NV>(d, w, (int)RDC_PRECOND_MULTIGRID, mixed, [&] { return read_record(d, w); }, &start));
+    *bad_blocks = start.bad_blocks;
+    *matrix_bits = start.form == F32 ? 32 : 64;
+    if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is applied, `out` stays what it was
+    SOLVE_HIP(mg_cycle<NV>(d, w, start.form, in, out));
+    return hipStreamSynchronize(d.stream);
+  });
+}
+
+const double* solve_dinv(const SolveDev& d) { return carve(d.nvar, d.n_owned, d.work).dinv; }
 
 hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   *info = rdc_solve_info();
