@@ -341,6 +341,7 @@ int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 #define RDC_PRECOND_JACOBI 1
 #define RDC_PRECOND_BLOCK_JACOBI 2      /* default choice of the Python wrapper */
 #define RDC_PRECOND_MULTIGRID 3         /* block Jacobi's system, with an aggregation-multigrid cycle applied from the right (below) */
+#define RDC_PRECOND_ILU0 4              /* block Jacobi's system, with a multicolour block ILU(0) applied from the right (below); rdc_solve only */
 
 #define RDC_SOLVE_CONVERGED     0
 #define RDC_SOLVE_MAX_ITS       1       /* x holds the last iterate */
@@ -464,6 +465,44 @@ int rdc_solve_mg_apply(rdc_ctx* ctx, int mixed, const double* d_in, double* d_ou
  * on this mesh, or if a call that runs or plans a solve (any other rdc_solve* entry but the three queries above) or
  * rdc_csr_scale_f32 has come after it: those write over the D^-1 this call reads.  RDC_ERR_INVALID for a level out of range. */
 int rdc_solve_mg_level_download(rdc_ctx* ctx, int level, double* val, double* dinv);
+
+/* ---- RDC_PRECOND_ILU0 (rdc_solve; additive: RDC_ABI_VERSION stays 3) ----
+ * The iteration runs on the system of RDC_PRECOND_BLOCK_JACOBI, D^-1 A x = D^-1 b, and M = (LU)^-1 is applied from the RIGHT,
+ * exactly as the multigrid cycle is: LU is the block ILU(0) factorisation of A^ = D^-1 A on the node-block pattern.  The
+ * stopping test, the confirmation of a claim on the true residual, the restarts and every field of rdc_solve_info mean what
+ * they mean for RDC_PRECOND_BLOCK_JACOBI; only the number of iterations differs.
+ * Elimination order: (colour, node id), the colours being the greedy ones of the Gauss-Seidel smoother on the matrix itself
+ * (nodes ascending, the smallest colour no coloured row neighbour holds), built on the host at the first such solve on a mesh
+ * and kept with it.  L has identity diagonal blocks, U carries the diagonal blocks, and U_ii^-1 is kept per node.  A node of
+ * colour c depends on nodes of other colours only, so the factorisation is one launch per colour and each triangular sweep
+ * one launch per colour: forward z_i = y_i - sum_{colour(k) < c} L_ik z_k over the colours ascending, backward
+ * z_i = U_ii^-1 (z_i - sum_{colour(j) > c} U_ij z_j) descending.  The factor is rebuilt from the current values by every
+ * solve; it lives in a copy of A^ (8 bytes per non-zero, 4 bytes per node block of index, in a layout private to the library,
+ * allocated at the first such solve on a mesh and freed with it: rdc_solve_ilu_stats), which the two sweeps of an apply
+ * together read once.  Deterministic: the order of every sum is fixed, there are no atomics, two solves return the same bytes.
+ * A diagonal block of A, or a pivot U_ii, that is singular or not finite counts into bad_blocks and gives
+ * RDC_SOLVE_BAD_DIAGONAL with x untouched and no iteration run.  RDC_ERR_UNSUPPORTED, with nothing launched: on a context with
+ * ghost nodes, for a block pattern that is not structurally symmetric or lacks a diagonal block, and for this value of
+ * precond in rdc_solve_mixed, rdc_solve_dist and rdc_solve_dist_mg.  Every other call launches what it launched before the
+ * value existed. */
+/* What the factor costs: *setup_ms = device time the last solve (or rdc_solve_ilu_apply) spent on the copy of A^ and the
+ * factorisation (part of its rdc_solve_info.device_ms); *bytes = device memory the factor holds for this mesh (values, U_ii^-1,
+ * index lists, colour lists and the two vectors M p and M s); *n_colours = the colours.  Any pointer may be NULL.
+ * RDC_ERR_STATE if no such solve has run on this mesh. */
+int rdc_solve_ilu_stats(rdc_ctx* ctx, float* setup_ms, int64_t* bytes, int32_t* n_colours);
+/* ---- two read-only observation points (additive: RDC_ABI_VERSION stays 3).  TEST HOOKS, as the multigrid pair above.
+ * rdc_solve_ilu_apply: d_out = M d_in, ONE application, as the next rdc_solve with RDC_PRECOND_ILU0 would apply it: the call
+ * first does what such a solve does before its first iteration (D^-1, the copy of A^, the factorisation from the current CSR
+ * values -- the same host function, so colours and lists are built at first use here too).  d_in, d_out: DEVICE pointers,
+ * n_owned*nvar doubles each, not overlapping.  Blocks the host until done; never modifies the CSR values or the rhs.
+ * RDC_ERR_STATE without a mesh, RDC_ERR_INVALID for a null pointer, RDC_ERR_UNSUPPORTED as the solve; RDC_ERR_INVALID, with
+ * the count in the message and d_out untouched, if a diagonal block or a pivot is not invertible. */
+int rdc_solve_ilu_apply(rdc_ctx* ctx, const double* d_in, double* d_out);
+/* The factor the last rdc_solve_ilu_apply or solve with RDC_PRECOND_ILU0 built, into HOST arrays, in the PUBLIC node-block
+ * layout of the CSR values whatever the private layout is: val = nnz doubles, the L blocks and the U blocks (diagonal blocks
+ * included) in the positions of the blocks they replace, the identity of L not stored; uinv = U_ii^-1, n_owned * nvar^2
+ * doubles, row-major per node.  Either pointer may be NULL.  RDC_ERR_STATE if neither producer has run on this mesh. */
+int rdc_solve_ilu_download(rdc_ctx* ctx, double* val, double* uinv);
 
 /* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
  * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own

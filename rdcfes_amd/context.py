@@ -14,7 +14,7 @@ FIELD_OLD_SOLUTION, FIELD_AUX_NODAL, FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE = 0,
 FIELD_PREV_SOLUTION, FIELD_TIME_DERIV, FIELD_RT_DOSE = 4, 5, 6
 FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1, 2, 3
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0 = 0, 1, 2, 3, 4
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 1, 2, 3, 4, 5, 6
 
@@ -338,7 +338,9 @@ class AssemblyContext:
         stopping test and norms, fewer iterations (mg_levels(), mg_stats(); damping: set_option("mg_omega", thousandths)).
         set_option("mg_smoother", 1): every sweep of the cycle but the first on each level is a forward multicolour Gauss-Seidel
         sweep, undamped (mg_colours(); default 0 = damped block Jacobi; not on a ghosted context, not in solve_dist;
-        set_option("mg_gs_fuse", 0): one launch per colour on the small levels too, same bytes)."""
+        set_option("mg_gs_fuse", 0): one launch per colour on the small levels too, same bytes).
+        precond=PRECOND_ILU0: block Jacobi's system with a multicolour block ILU(0) of D^-1 A applied from the right, factored
+        anew by every solve (ilu_stats(); FP64 only: not with mixed=True, not on a ghosted context, not in solve_dist)."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -442,6 +444,40 @@ class AssemblyContext:
         dinv = np.empty((n, nv, nv), dtype=np.float64)
         self._ck(self._lib.rdc_solve_mg_level_download(self._h, int(level), _dp(val) if level else None, _dp(dinv)))
         return val, dinv
+
+    def ilu_stats(self):
+        """(device ms the last ILU(0) solve spent on the copy of D^-1 A and its factorisation, device bytes the factor holds, colours)"""
+        ms, nbytes, ncol = C.c_float(), C.c_int64(), C.c_int32()
+        self._ck(self._lib.rdc_solve_ilu_stats(self._h, C.byref(ms), C.byref(nbytes), C.byref(ncol)))
+        return ms.value, nbytes.value, ncol.value
+
+    def ilu_apply_device(self, in_ptr, out_ptr):
+        """rdc_solve_ilu_apply on device addresses (n_owned*nvar doubles each): out = (LU)^-1 in, as the next
+        solve(precond=PRECOND_ILU0) would apply it.  A test hook."""
+        self._ck(self._lib.rdc_solve_ilu_apply(self._h, C.c_void_p(int(in_ptr)), C.c_void_p(int(out_ptr))))
+
+    def ilu_apply(self, x):
+        """numpy in, numpy out (tests): M x"""
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.n_owned * self.nvar:
+            raise ValueError("x must have n_owned * nvar entries")
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(x).to(dev)
+        yd = torch.empty_like(xd)
+        torch.cuda.synchronize(dev)
+        self.ilu_apply_device(xd.data_ptr(), yd.data_ptr())
+        return yd.cpu().numpy()
+
+    def ilu_factor(self):
+        """rdc_solve_ilu_download -> (val, uinv) as the last ilu_apply or ILU(0) solve built them: val [nnz] in the node-block layout
+        of the CSR values, L and U blocks in the positions of the blocks they replace (L's identity not stored); uinv
+        [n_owned][nvar][nvar] = U_ii^-1.  A test hook."""
+        nv = self.nvar
+        val = np.empty(self.csr_dims()[1], dtype=np.float64)
+        uinv = np.empty((self.n_owned, nv, nv), dtype=np.float64)
+        self._ck(self._lib.rdc_solve_ilu_download(self._h, _dp(val), _dp(uinv)))
+        return val, uinv
 
     def part1_nodes(self):
         n = C.c_int64()

@@ -39,7 +39,8 @@ struct Buffers {
   // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
   // send: the send list of a partitioned solve (rdc_solve_dist_plan)
   // mg_gs: the colour lists of every level (first multigrid solve with the Gauss-Seidel smoother)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
+  // ilu_idx / ilu_val: the lists, and the factor / U_ii^-1 / vectors, of the block ILU(0) (first solve with RDC_PRECOND_ILU0; rdc_solve.h, ilu_place)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -61,6 +62,10 @@ struct SolveState {
   bool gs_ready = false;     // mg_gs holds the colour lists of this mesh's (single-partition) hierarchy, gs describes them
   MgGsDev gs;
   std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
+  bool ilu_ready = false;    // ilu_idx / ilu_val hold this mesh's lists, ilu describes them, ilu_host is their host copy
+  bool ilu_factored = false; // ... and ilu_val holds the factor of the last rdc_solve_ilu_apply or solve with RDC_PRECOND_ILU0
+  IluDev ilu;
+  IluHost ilu_host;          // (IluDev::cptr_host points into it; rdc_solve_ilu_download permutes with it)
   bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
   DistDims dist;
   bool peers_ready = false;  // halo0 is the plan with its per-peer segments (rdc_solve_dist_plan_peers)
@@ -1302,6 +1307,52 @@ static int mg_view(rdc_ctx* c, SolveDev* d) {
   return RDC_OK;
 }
 
+// The lists of the block ILU(0) of the mesh (rdc_solve.h, ilu_build: colours, rows in elimination order), built on the host and
+// uploaded at the first solve with RDC_PRECOND_ILU0, and the two allocations ilu_place measures and then carves.  d must come
+// from solve_view(want_work) on a context without ghost nodes.
+static int ilu_view(rdc_ctx* c, SolveDev* d) {
+  const HostPrep& P = c->ms.prep;
+  SolveState& S = c->ms.solve;
+  if (!S.ilu_ready) {
+    IluHost H;
+    int64_t where = -1;
+    const int bad = ilu_build(P.n_owned, P.bptr.data(), P.bcol.data(), H, &where);
+    if (bad == 1)
+      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern is not structurally symmetric: two coupled nodes share a colour, and the "
+                  "block ILU(0) (precond %d) eliminates colour by colour", (int)RDC_PRECOND_ILU0);
+    if (bad) return fail(c, RDC_ERR_UNSUPPORTED, "node %lld has no diagonal block in the pattern: no block ILU(0)", (long long)where);
+    const int64_t blocks = P.bptr[(size_t)P.n_owned];
+    MgArena idx, val;
+    IluDev g;
+    ilu_place(H, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {});   // no bases: measures
+    int rc;
+    if ((rc = dev_alloc(c, c->buf.solve.ilu_idx, idx.used))) return rc;
+    if ((rc = dev_alloc(c, c->buf.solve.ilu_val, val.used))) return rc;
+    idx = MgArena{(char*)c->buf.solve.ilu_idx.p};
+    val = MgArena{(char*)c->buf.solve.ilu_val.p};
+    S.ilu_host = std::move(H);
+    hipError_t e = hipSuccess;
+    ilu_place(S.ilu_host, P.nvar, P.n_owned, blocks, idx, val, S.ilu, [&](void* at, const void* list, size_t bytes) {
+      if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
+    });
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the ILU(0) lists failed: %s", hipGetErrorString(e));
+    S.ilu_ready = true;
+    S.ilu_factored = false;
+  }
+  d->ilu = &S.ilu;
+  return RDC_OK;
+}
+
+int rdc_solve_ilu_stats(rdc_ctx* c, float* setup_ms, int64_t* bytes, int32_t* n_colours) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.solve.ilu_ready) return fail(c, RDC_ERR_STATE, "no solve with the block ILU(0) preconditioner has run on this mesh");
+  if (setup_ms) *setup_ms = c->ms.solve.ilu.setup_ms;
+  if (bytes) *bytes = (int64_t)(c->buf.solve.ilu_idx.bytes + c->buf.solve.ilu_val.bytes);
+  if (n_colours) *n_colours = c->ms.solve.ilu.n_colours;
+  return RDC_OK;
+}
+
 int rdc_solve_mg_levels(rdc_ctx* c, int32_t* n_levels, int64_t* nodes, int64_t* blocks, int cap) {
   if (!c || !n_levels || cap < 0 || (cap > 0 && (!nodes || !blocks))) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
@@ -1337,9 +1388,10 @@ int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
   return RDC_OK;
 }
 
-static bool known_precond(int precond, bool with_multigrid) {
+// with_right: the preconditioners applied from the right on top of block Jacobi's system count (the solve entries)
+static bool known_precond(int precond, bool with_right) {
   return precond == RDC_PRECOND_NONE || precond == RDC_PRECOND_JACOBI || precond == RDC_PRECOND_BLOCK_JACOBI ||
-         (with_multigrid && precond == RDC_PRECOND_MULTIGRID);
+         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0));
 }
 
 int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
@@ -1392,6 +1444,8 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (mixed && p->precond == RDC_PRECOND_ILU0)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve, not rdc_solve_mixed", (int)RDC_PRECOND_ILU0);
   if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, p->precond == RDC_PRECOND_MULTIGRID);
   if (c->ms.prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
     *info = rdc_solve_info();
@@ -1403,7 +1457,12 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   int rc = solve_view(c, true, mixed, &d);
   if (rc) return rc;
   if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
+  if (p->precond == RDC_PRECOND_ILU0) {
+    if ((rc = ilu_view(c, &d))) return rc;
+    c->ms.solve.ilu_factored = false;
+  }
   RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
+  if (p->precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
   if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   c->ms.solve.mg_values = p->precond == RDC_PRECOND_MULTIGRID;
   return RDC_OK;
@@ -1430,6 +1489,52 @@ int rdc_solve_mg_apply(rdc_ctx* c, int mixed, const double* d_in, double* d_out)
   if (mixed) c->ms.solve.f32_copy = bits == 32 && bad == 0;
   c->ms.solve.mg_values = true;
   if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks of the multigrid levels are not invertible: no cycle was applied", bad);
+  return RDC_OK;
+}
+
+int rdc_solve_ilu_apply(rdc_ctx* c, const double* d_in, double* d_out) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt
+  if (!d_in || !d_out) return fail(c, RDC_ERR_INVALID, "null vector");
+  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, false);
+  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
+  SolveDev d;
+  int rc = solve_view(c, true, false, &d);
+  if (rc) return rc;
+  if ((rc = ilu_view(c, &d))) return rc;
+  c->ms.solve.ilu_factored = false;
+  int bad = 0;
+  RDC_HIP(c, solve_ilu_apply(d, d_in, d_out, &bad));
+  c->ms.solve.ilu_factored = true;
+  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks or ILU(0) pivots are not invertible: nothing was applied", bad);
+  return RDC_OK;
+}
+
+int rdc_solve_ilu_download(rdc_ctx* c, double* val, double* uinv) {
+  if (!c) return RDC_ERR_INVALID;
+  const SolveState& S = c->ms.solve;
+  if (!c->ms.have_mesh || !S.ilu_ready || !S.ilu_factored)
+    return fail(c, RDC_ERR_STATE, "no rdc_solve_ilu_apply or solve with the block ILU(0) preconditioner has run on this mesh");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const HostPrep& P = c->ms.prep;
+  const int nv = P.nvar;
+  const int64_t n = P.n_owned, blocks = P.bptr[(size_t)n];
+  std::vector<double> priv(val ? (size_t)blocks * nv * nv : 0);
+  if (val && blocks) RDC_HIP(c, hipMemcpyAsync(priv.data(), S.ilu.val, priv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (uinv && n) RDC_HIP(c, hipMemcpyAsync(uinv, S.ilu.uinv, (size_t)n * nv * nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  RDC_HIP(c, hipStreamSynchronize(c->stream));
+  if (val)   // private position p of a node -> the block of the same column in the CSR row (bcol ascends)
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t b0 = P.bptr[(size_t)i], len = P.bptr[(size_t)i + 1] - b0, nl = S.ilu_host.nlow[(size_t)i];
+      for (int64_t p = 0; p < len; p++) {
+        const int64_t k = std::lower_bound(P.bcol.begin() + b0, P.bcol.begin() + b0 + len, S.ilu_host.pcol[(size_t)(b0 + p)]) - (P.bcol.begin() + b0);
+        for (int a = 0; a < nv; a++)
+          for (int b = 0; b < nv; b++)
+            val[csr_value_offset(P.bptr.data(), nv, i, a, k, b)] = priv[(size_t)ilu_value_offset(b0, nv, len, nl, a, p, b)];
+      }
+    }
   return RDC_OK;
 }
 
@@ -1593,6 +1698,9 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
+  if (p->precond == RDC_PRECOND_ILU0)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour, or a "
+                "rank-local factor, and is not implemented: rdc_solve on a context without ghost nodes", (int)RDC_PRECOND_ILU0);
   if (sized && p->precond != RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
                 (int)RDC_PRECOND_MULTIGRID, (int)p->precond);

@@ -4,7 +4,9 @@
 // aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp) and
 // the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp), the colour lists of the
 // Gauss-Seidel smoother (mg_colour, mg_gs_place; tests/host_solve_mg_gs_shim.cpp, tests/host_solve_mg_gs_main.cpp), and the hierarchy of a
-// ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).
+// ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).  The multicolour
+// block ILU(0) has its private layout and the factor step of a node among the host+device functions (ilu_value_offset, ilu_find,
+// ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -209,6 +211,111 @@ RDC_SOLVE_HD void scaled_block(const double (&dinv)[NV][NV], const double (&a)[N
       for (int q = 0; q < NV; q++) col[q] = a[q][j];
       out[i][j] = scaled_entry<NV>(dinv[i], col);
     }
+}
+
+// ---- multicolour block ILU(0) (precond 4): the factor's private layout and the factor step of one node ----
+//
+// The factor of A^ = D^-1 A lives in a copy of the node-block values, 8 bytes per non-zero, whose layout is private to the library and
+// stated here once.  Node i keeps its blocks [bptr[i], bptr[i + 1]) of the pattern, but in ELIMINATION order, (colour, node id)
+// ascending: position p of the node couples it to node pcol[bptr[i] + p]; the first nlow[i] positions are the lower blocks (a
+// column of a lower colour: L_ip, the identity on L's diagonal is not stored), position nlow[i] is the diagonal block (U_ii), the
+// rest are the upper blocks (U_ip).  The values of a node lie as three runs, each [var a][block][var b] like the CSR values:
+//   lower  nvar x (nlow * nvar)   at nvar^2 * bptr[i]                      what the forward sweep reads, contiguous
+//   diag   nvar x nvar            behind it                                (the sweeps read U_ii^-1 from an array of its own)
+//   upper  nvar x (nup * nvar)    behind that, nup = len - nlow - 1        what the backward sweep reads, contiguous
+// so that forward and backward together cross the factor once: 8 nnz + 4 blocks bytes.
+// b0 = bptr[i], len = bptr[i + 1] - b0, nl = nlow[i]
+RDC_SOLVE_HD int64_t ilu_value_offset(int64_t b0, int nvar, int64_t len, int64_t nl, int a, int64_t p, int b) {
+  const int64_t base = (int64_t)nvar * nvar * b0;
+  if (p < nl) return base + ((int64_t)a * nl + p) * nvar + b;
+  if (p == nl) return base + (int64_t)nvar * nvar * nl + (int64_t)a * nvar + b;
+  return base + (int64_t)nvar * nvar * (nl + 1) + ((int64_t)a * (len - nl - 1) + (p - nl - 1)) * nvar + b;
+}
+
+// position of column node j in the private row `row` (len entries, ascending in (colour, node id)); -1 if the row has none
+RDC_SOLVE_HD int64_t ilu_find(const int32_t* row, int64_t len, const int32_t* colour, int32_t j) {
+  const int32_t cj = colour[j];
+  int64_t lo = 0, hi = len - 1;
+  while (lo <= hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    const int32_t m = row[mid], cm = colour[m];
+    if (m == j) return mid;
+    if (cm < cj || (cm == cj && m < j)) lo = mid + 1; else hi = mid - 1;
+  }
+  return -1;
+}
+
+// The factor of node i, all of whose row neighbours of a lower colour are factored: for its lower positions p in order (node
+// k = pcol[p]) L_ip = F_ip U_kk^-1, then F_ij -= L_ip U_kj for every upper block j of row k that row i has as well (at a position
+// behind p); at the end U_ii^-1 (block_inverse).  `lanes` callers share the node: each computes L_ip for itself, lane 0 stores it,
+// and the upper blocks of row k are dealt out lane, lane + lanes, ... -- their targets in row i are distinct.  sync(): what makes
+// the stores of all lanes visible to all lanes before the next position is read (one lane: nothing).  Every sum is a chain of fma
+// in ascending index order, the updates of a block come in the order of p: no atomics, the same bits whatever `lanes` is.
+// Returns (lane 0; the others true) whether U_ii could be inverted; if not, uinv of the node is the identity.
+template <int NV, class Sync>
+RDC_SOLVE_HD bool ilu_factor_node(const int64_t* bptr, const int32_t* pcol, const int32_t* nlow, const int32_t* colour,
+                                  double* val, double* uinv, int64_t i, int lane, int lanes, Sync&& sync) {
+  const int64_t b0 = bptr[i], len = bptr[i + 1] - b0, nl = nlow[i];
+  for (int64_t p = 0; p < nl; p++) {
+    const int64_t k = pcol[b0 + p];
+    double l[NV][NV];
+    {
+      double f[NV][NV];
+#pragma unroll
+      for (int a = 0; a < NV; a++)
+#pragma unroll
+        for (int b = 0; b < NV; b++) f[a][b] = val[ilu_value_offset(b0, NV, len, nl, a, p, b)];
+#pragma unroll
+      for (int a = 0; a < NV; a++)
+#pragma unroll
+        for (int b = 0; b < NV; b++) {
+          double s = 0.0;
+#pragma unroll
+          for (int q = 0; q < NV; q++) s = fma(f[a][q], uinv[(k * NV + q) * NV + b], s);
+          l[a][b] = s;
+        }
+    }
+    if (lane == 0)
+#pragma unroll
+      for (int a = 0; a < NV; a++)
+#pragma unroll
+        for (int b = 0; b < NV; b++) val[ilu_value_offset(b0, NV, len, nl, a, p, b)] = l[a][b];
+    const int64_t k0 = bptr[k], klen = bptr[k + 1] - k0, knl = nlow[k];
+    for (int64_t q = knl + 1 + lane; q < klen; q += lanes) {
+      const int64_t at = ilu_find(pcol + b0, len, colour, pcol[k0 + q]);
+      if (at < 0) continue;
+      double u[NV][NV];
+#pragma unroll
+      for (int a = 0; a < NV; a++)
+#pragma unroll
+        for (int b = 0; b < NV; b++) u[a][b] = val[ilu_value_offset(k0, NV, klen, knl, a, q, b)];
+#pragma unroll
+      for (int a = 0; a < NV; a++)
+#pragma unroll
+        for (int b = 0; b < NV; b++) {
+          const int64_t o = ilu_value_offset(b0, NV, len, nl, a, at, b);
+          double t = val[o];
+#pragma unroll
+          for (int c = 0; c < NV; c++) t = fma(-l[a][c], u[c][b], t);
+          val[o] = t;
+        }
+    }
+    sync();
+  }
+  bool ok = true;
+  if (lane == 0) {
+    double d[NV][NV];
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) d[a][b] = val[ilu_value_offset(b0, NV, len, nl, a, nl, b)];
+    ok = precond_block<NV>(d, 2);
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) uinv[(i * NV + a) * NV + b] = d[a][b];
+  }
+  return ok;
 }
 
 }  // namespace rdc
@@ -613,6 +720,82 @@ inline void mg_gs_place(const std::vector<MgColours>& cols, MgArena& arena, MgGs
   }
 }
 
+// ---- multicolour block ILU(0) (precond 4): the lists of a mesh, and where the factor lies on the device ----
+
+// What the private layout (ilu_value_offset, above) needs beside bptr: the colours of level 0 (mg_colour) and every row in
+// elimination order.  Built on the host once per mesh.
+struct IluHost {
+  MgColours col;
+  std::vector<int32_t> pcol;   // [blocks] column node of every position, per node ascending in (colour, node id)
+  std::vector<int32_t> nlow;   // [n] lower blocks of a node = position of its diagonal block
+};
+
+// 0 = fine; 1 = the pattern is not structurally symmetric (mg_colour refuses it: a colour would not be independent);
+// 2 = node *where has no diagonal block, or a column that is no row (a ghost)
+inline int ilu_build(int64_t n, const int64_t* bptr, const int32_t* bcol, IluHost& H, int64_t* where) {
+  H = IluHost();
+  for (int64_t i = 0; i < n; i++) {
+    bool diag = false;
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
+      if (bcol[k] < 0 || bcol[k] >= n) { *where = i; return 2; }
+      diag = diag || bcol[k] == i;
+    }
+    if (!diag) { *where = i; return 2; }
+  }
+  if (!mg_colour(n, bptr, bcol, H.col)) return 1;
+  const std::vector<int32_t>& colour = H.col.colour;
+  H.pcol.assign(bcol, bcol + bptr[n]);
+  H.nlow.assign((size_t)n, 0);
+  for (int64_t i = 0; i < n; i++) {
+    std::sort(H.pcol.begin() + bptr[i], H.pcol.begin() + bptr[i + 1], [&](int32_t x, int32_t y) {
+      return colour[(size_t)x] != colour[(size_t)y] ? colour[(size_t)x] < colour[(size_t)y] : x < y;
+    });
+    int32_t nl = 0;
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) nl += colour[(size_t)bcol[k]] < colour[(size_t)i];
+    H.nlow[(size_t)i] = nl;
+  }
+  return 0;
+}
+
+// The factorisation of one whole matrix on the host, node after node in elimination order with one lane (tests, and the yardstick
+// of what the per-colour launches compute): val holds A^ in the private layout on entry and the factor on exit, uinv [n][NV][NV]
+// the U_ii^-1.  Returns the number of nodes whose U_ii could not be inverted.
+template <int NV>
+inline int64_t ilu_factor_host(int64_t n, const int64_t* bptr, const IluHost& H, double* val, double* uinv) {
+  int64_t bad = 0;
+  for (int64_t at = 0; at < n; at++)
+    bad += !ilu_factor_node<NV>(bptr, H.pcol.data(), H.nlow.data(), H.col.colour.data(), val, uinv, H.col.nodes[(size_t)at], 0, 1, [] {});
+  return bad;
+}
+
+// The factor on the device.  Two allocations, measured and placed like the arenas of mg_place (MgArena: no base measures):
+// `idx` holds pcol, nlow, the colours and the colour lists, `val` the factor, the U_ii^-1 and the two vectors M p and M s of the
+// right-preconditioned iteration.  cptr_host: the bounds of the colour lists on the host (it points into H).
+struct IluDev {
+  int n_colours = 0;
+  const int32_t *pcol = nullptr, *nlow = nullptr, *colour = nullptr, *nodes = nullptr;
+  const int64_t* cptr_host = nullptr;
+  double *val = nullptr, *uinv = nullptr, *ph = nullptr, *sh = nullptr;
+  float setup_ms = 0.0f;   // out: device time of the copy of A^ and the factorisation of the last solve
+};
+
+template <class Upload>
+inline void ilu_place(const IluHost& H, int nvar, int64_t n, int64_t blocks, MgArena& idx, MgArena& val, IluDev& g, Upload&& upload) {
+  auto list = [&](const auto& v) {
+    const size_t bytes = v.size() * sizeof(v[0]);
+    void* at = idx.take(bytes);
+    if (at && bytes) upload(at, (const void*)v.data(), bytes);
+    return (decltype(v.data()))at;
+  };
+  auto vec = [&](int64_t doubles) { return (double*)val.take((size_t)doubles * sizeof(double)); };
+  g = IluDev();
+  g.n_colours = H.col.n_colours();
+  g.pcol = list(H.pcol); g.nlow = list(H.nlow); g.colour = list(H.col.colour); g.nodes = list(H.col.nodes);
+  g.cptr_host = H.col.cptr.data();
+  g.val = vec(blocks * nvar * nvar); g.uinv = vec(n * nvar * nvar);
+  g.ph = vec(std::max<int64_t>(n * nvar, 1)); g.sh = vec(std::max<int64_t>(n * nvar, 1));
+}
+
 // ---- the iteration's scalars, its launch shapes and the layout of its work buffer: host code without HIP, so that a CPU build
 // can test the layout (tests/host_solve_dist_shim.cpp) ----
 
@@ -713,6 +896,7 @@ struct SolveDev {
   hipStream_t stream = nullptr;
   MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
   const MgGsDev* gs = nullptr;     // its colour lists: the smoother is Gauss-Seidel (option "mg_smoother" = 1); null: damped Jacobi
+  IluDev* ilu = nullptr;           // the factor (RDC_PRECOND_ILU0 only)
   // partitioned solve (rdc_solve_dist) only.  comm == nullptr is the single-partition path.
   const rdc_solve_comm* comm = nullptr;
   int peers = 0;                                 // rdc_solve_dist_plan_peers
@@ -736,6 +920,10 @@ hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y);
 // in the form that solve would iterate in; in and out hold n_owned * nvar doubles and do not overlap; d.mg is set, d.comm is not.
 // *bad_blocks > 0: a diagonal block of some level is not invertible, nothing was applied.  Synchronises.
 hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, double* out, int* bad_blocks, int* matrix_bits);
+// Test hook (rdc_solve_ilu_apply): out = (LU)^-1 in behind the prologue of a solve with RDC_PRECOND_ILU0 (the same host function);
+// in and out hold n_owned * nvar doubles and do not overlap; d.ilu is set, d.comm is not.  *bad_blocks > 0: a diagonal block or a
+// pivot U_ii is not invertible, nothing was applied.  Synchronises.
+hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int* bad_blocks);
 // where the D^-1 of the last single-partition set-up lies in d.work (n_owned * nvar * nvar doubles)
 const double* solve_dinv(const SolveDev& d);
 

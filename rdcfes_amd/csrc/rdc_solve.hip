@@ -23,6 +23,10 @@
 // The cycle has no inner product and no host round trip.  Its smoother is an argument (SolveDev::gs): damped block Jacobi, or,
 // opt-in, forward Gauss-Seidel in a multicolour order (k_gs and its kin, further down) for every sweep but the first of a level.
 //
+// Block ILU(0) (precond 4): the other right preconditioner of `iteration`, M = (LU)^-1 with LU the block ILU(0) of
+// D^-1 A in the multicolour order of the Gauss-Seidel smoother; factorisation, forward and backward sweep are one launch per colour
+// each (k_ilu_copy, k_ilu_factor, k_ilu_fwd, k_ilu_bwd, further down), on a copy of D^-1 A in a layout of its own (rdc_solve.h).
+//
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
 // device memory.  No floating-point atomics anywhere.
@@ -795,6 +799,129 @@ __global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_f32_fused(const int64_t
     }
 }
 
+// ---- multicolour block ILU(0) (precond 4): M = (LU)^-1 from the right, LU the block ILU(0) of A^ = D^-1 A ----
+//
+// The factor lives in a copy of A^ in a layout of its own (rdc_solve.h, ilu_value_offset: per node the lower blocks in elimination
+// order, the diagonal block, the upper blocks).  Nodes are eliminated by (colour, node id); no two nodes of a colour are coupled, so
+// a colour is one launch: of the factorisation (k_ilu_factor), of the forward sweep (k_ilu_fwd) and of the backward sweep
+// (k_ilu_bwd).  16 lanes per node throughout, as k_spmv.
+
+// A^ = D^-1 A into the private layout: a lane takes the positions p = lane, lane + 16, ... of its node, finds the block of the same
+// column in the CSR row (bcol ascends: binary search), reads it once (non-temporal) and multiplies it by D^-1 from the left
+// (scaled_block: ascending, no contraction).  Runs after k_precond_setup.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_copy(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                  const int32_t* __restrict__ pcol, const int32_t* __restrict__ nlow,
+                                                  const double* __restrict__ val, const double* __restrict__ dinv, int64_t n_owned,
+                                                  double* __restrict__ fval) {
+  const int lane = threadIdx.x & 15;
+  const int64_t node = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  if (node >= n_owned) return;
+  const int64_t b0 = bptr[node], len = bptr[node + 1] - b0, nl = nlow[node];
+  const double* __restrict__ vrow = val + (int64_t)NV * NV * b0;
+  double di[NV][NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int b = 0; b < NV; b++) di[a][b] = dinv[(node * NV + a) * NV + b];
+  for (int64_t p = lane; p < len; p += 16) {
+    const int32_t j = pcol[b0 + p];
+    int64_t lo = 0, hi = len - 1, k = 0;
+    while (lo <= hi) {   // the row has the column: pcol is a permutation of bcol within the node
+      k = lo + (hi - lo) / 2;
+      const int32_t c = bcol[b0 + k];
+      if (c == j) break;
+      if (c < j) lo = k + 1; else hi = k - 1;
+    }
+    double blk[NV][NV], out[NV][NV];
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) blk[a][b] = __builtin_nontemporal_load(vrow + ((int64_t)a * len + k) * NV + b);
+    scaled_block<NV>(di, blk, out);
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) fval[ilu_value_offset(b0, NV, len, nl, a, p, b)] = out[a][b];
+  }
+}
+
+// The nodes list[0 .. count) of one colour, one 16-lane group each (rdc_solve.h, ilu_factor_node: the lanes run over the upper
+// blocks of the row of a lower neighbour, whose targets in the node's own row are distinct).  The row is read and written in
+// global memory whatever its length; between two lower neighbours a workgroup-scope fence makes the blocks the 16 lanes have
+// just written visible to all of them (they are lanes of one wave, so they reach it together).  fval and uinv are read (rows and
+// pivots of lower colours, final since an earlier launch) and written (the node's own): neither const nor __restrict__.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_factor(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                    const int32_t* __restrict__ nlow, const int32_t* __restrict__ colour, double* fval,
+                                                    double* uinv, const int32_t* __restrict__ list, int64_t count,
+                                                    SolveScal* __restrict__ scal) {
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  if (at >= count) return;
+  const bool ok = ilu_factor_node<NV>(bptr, pcol, nlow, colour, fval, uinv, list[at], threadIdx.x & 15, 16,
+                                      [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); });
+  if (!ok) atomicAdd(&scal->bad_blocks, 1);
+}
+
+// acc[a] = sum over the run `vrow` (NV rows of L entries: the lower or the upper blocks of a node, columns cols[0 .. L / NV)) of
+// value times x, in all 16 lanes: row_product on a run of the private layout
+template <int NV>
+__device__ __forceinline__ void ilu_run_product(const double* __restrict__ vrow, int L, const int32_t* __restrict__ cols, const double* x,
+                                                int lane, double (&acc)[NV]) {
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  for (int j = lane; j < L; j += 16) {
+    const int k = j / NV, b = j - k * NV;
+    const double xv = x[(int64_t)cols[k] * NV + b];
+#pragma unroll
+    for (int a = 0; a < NV; a++) acc[a] = fma(__builtin_nontemporal_load(vrow + (int64_t)a * L + j), xv, acc[a]);
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, 16);
+}
+
+// forward sweep over one colour: z_i = y_i - sum_{colour(k) < c} L_ik z_k.  z is read (lower colours) and written (this one);
+// y is the argument of the apply and does not overlap z.  Colour 0 has no lower blocks: its launch copies y.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_fwd(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                 const int32_t* __restrict__ nlow, const double* __restrict__ fval,
+                                                 const double* __restrict__ y, double* z, const int32_t* __restrict__ list, int64_t count) {
+  const int lane = threadIdx.x & 15;
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  const bool live = at < count;
+  const int64_t node = live ? list[at] : 0;
+  const int64_t b0 = bptr[node];
+  double acc[NV];
+  ilu_run_product<NV>(fval + (int64_t)NV * NV * b0, live ? nlow[node] * NV : 0, pcol + b0, z, lane, acc);
+  double t = acc[0];
+#pragma unroll
+  for (int a = 1; a < NV; a++) t = lane == a ? acc[a] : t;
+  if (live && lane < NV) z[node * NV + lane] = y[node * NV + lane] - t;
+}
+
+// backward sweep over one colour: z_i = U_ii^-1 (z_i - sum_{colour(j) > c} U_ij z_j), in place
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                 const int32_t* __restrict__ nlow, const double* __restrict__ fval,
+                                                 const double* __restrict__ uinv, double* z, const int32_t* __restrict__ list, int64_t count) {
+  const int lane = threadIdx.x & 15;
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  const bool live = at < count;
+  const int64_t node = live ? list[at] : 0;
+  const int64_t b0 = bptr[node], len = bptr[node + 1] - b0, nl = nlow[node];
+  double acc[NV];
+  ilu_run_product<NV>(fval + (int64_t)NV * NV * (b0 + nl + 1), live ? (int)(len - nl - 1) * NV : 0, pcol + b0 + nl + 1, z, lane, acc);
+  if (live && lane < NV) {
+    const double* __restrict__ urow = uinv + (node * NV + lane) * NV;
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) t = fma(urow[q], z[node * NV + q] - acc[q], t);
+    z[node * NV + lane] = t;
+  }
+}
+
 // First use of every kernel instantiation. A code object lists template instantiations by first use; this list keeps the order
 // they have had since each was added, whatever order the launch code below uses them in, so that the device assembly of two
 // revisions can be compared byte for byte.
@@ -805,6 +932,7 @@ __global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_f32_fused(const int64_t
 #define GS_KERNELS_OF(NV)                                                                                                       \
   (const void*)k_gs<NV, true>, (const void*)k_gs<NV, false>, (const void*)k_gs_f32<NV>, (const void*)k_gs_fused<NV, true>,     \
   (const void*)k_gs_fused<NV, false>, (const void*)k_gs_f32_fused<NV>
+#define ILU_KERNELS_OF(NV) (const void*)k_ilu_copy<NV>, (const void*)k_ilu_factor<NV>, (const void*)k_ilu_fwd<NV>, (const void*)k_ilu_bwd<NV>
 [[maybe_unused]] const void* const KERNEL_ORDER[] = {
     (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
@@ -813,9 +941,10 @@ __global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_f32_fused(const int64_t
     (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>,
     (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
     (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>,
-    GS_KERNELS_OF(3), GS_KERNELS_OF(5)};
+    GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5)};
 #undef KERNELS_OF
 #undef GS_KERNELS_OF
+#undef ILU_KERNELS_OF
 
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
@@ -1083,20 +1212,62 @@ hipError_t mg_setup(const SolveDev& d, const Work& w) {
   return hipGetLastError();
 }
 
-// One BiCGStab iteration.  form: what the operator applications stream (F32: the copy, which needs no D^-1 epilogue).
-// mg: the multigrid cycle is applied from the right, so the operator sees M p and M s and x advances along them.
+// the factor from the current values (behind setup(): the copy reads D^-1): A^ into the private layout, then one launch per colour
+// in ascending order; a pivot U_ii that cannot be inverted counts into bad_blocks
 template <int NV>
-hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, bool mg) {
+hipError_t ilu_setup(const SolveDev& d, const Work& w) {
+  const IluDev& g = *d.ilu;
+  hipLaunchKernelGGL((k_ilu_copy<NV>), dim3((unsigned)op_blocks(d.n_owned, SCALED)), dim3(256), 0, d.stream, d.bptr, d.bcol, g.pcol, g.nlow, d.val,
+                     (const double*)w.dinv, d.n_owned, g.val);
+  for (int c = 0; c < g.n_colours; c++) {
+    const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
+    hipLaunchKernelGGL((k_ilu_factor<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.colour,
+                       g.val, g.uinv, g.nodes + c0, count, w.scal);
+  }
+  return hipGetLastError();
+}
+
+// out = (LU)^-1 in: forward over the colours ascending, backward descending, one launch per colour each way (colour 0 forward is the
+// copy of `in`, since out is another vector).  Enqueues only; a fixed linear operator for fixed values.
+template <int NV>
+hipError_t ilu_apply(const SolveDev& d, const double* in, double* out) {
+  const IluDev& g = *d.ilu;
+  for (int c = 0; c < g.n_colours; c++) {
+    const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
+    hipLaunchKernelGGL((k_ilu_fwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
+                       (const double*)g.val, in, out, g.nodes + c0, count);
+  }
+  for (int c = g.n_colours - 1; c >= 0; c--) {
+    const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
+    hipLaunchKernelGGL((k_ilu_bwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
+                       (const double*)g.val, (const double*)g.uinv, out, g.nodes + c0, count);
+  }
+  return hipGetLastError();
+}
+
+// One BiCGStab iteration.  form: what the operator applications stream (F32: the copy, which needs no D^-1 epilogue).
+// right: a preconditioner M is applied from the right (the multigrid cycle, or the ILU(0) sweeps), so the operator sees M p and
+// M s and x advances along them.
+enum Right { RIGHT_NONE, RIGHT_MG, RIGHT_ILU };
+
+template <int NV>
+hipError_t right_apply(const SolveDev& d, const Work& w, Form form, Right right, const double* in, double* out) {
+  return right == RIGHT_MG ? mg_cycle<NV>(d, w, form, in, out) : ilu_apply<NV>(d, in, out);
+}
+
+template <int NV>
+hipError_t iteration(const SolveDev& d, const Work& w, double* x, Form form, Right right) {
+  const bool mg = right != RIGHT_NONE;
   const dim3 vg((unsigned)w.vec_blocks), vb(256);
   const int64_t parts = op_parts(d.n_owned, d.comm ? d.dist.n_int : 0, form);
-  double* px = mg ? d.mg->ph : w.p;   // across partitions: the ghost tails of these receive (mg_place gives M p and M s one too)
-  double* sx = mg ? d.mg->sh : w.s;
+  double* px = right == RIGHT_MG ? d.mg->ph : right == RIGHT_ILU ? d.ilu->ph : w.p;   // across partitions: the ghost tails of these receive (mg_place gives M p and M s one too)
+  double* sx = right == RIGHT_MG ? d.mg->sh : right == RIGHT_ILU ? d.ilu->sh : w.s;
   if (vg.x) hipLaunchKernelGGL(k_update_p, vg, vb, 0, d.stream, (const double*)w.r, w.p, (const double*)w.v, (const SolveScal*)w.scal, w.n);
-  if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.p, d.mg->ph));
+  if (mg) SOLVE_HIP(right_apply<NV>(d, w, form, right, w.p, px));
   SOLVE_HIP(apply_halo<NV>(d, w, form, px, w.v, w.rh));   // v = D^-1 A [M] p, (r_hat, v)
   SOLVE_HIP(finalize(d, w, parts, 2, STAGE_ALPHA));
   if (vg.x) hipLaunchKernelGGL(k_update_s, vg, vb, 0, d.stream, (const double*)w.r, (const double*)w.v, w.s, (const SolveScal*)w.scal, w.n);
-  if (mg) SOLVE_HIP(mg_cycle<NV>(d, w, form, w.s, d.mg->sh));
+  if (mg) SOLVE_HIP(right_apply<NV>(d, w, form, right, w.s, sx));
   SOLVE_HIP(apply_halo<NV>(d, w, form, sx, w.t, w.s));    // t = D^-1 A [M] s, (t, s), (t, t)
   SOLVE_HIP(finalize(d, w, parts, 2, STAGE_OMEGA));
   if (vg.x)
@@ -1121,8 +1292,10 @@ template <int NV, class Read>
 hipError_t prologue(const SolveDev& d, const Work& w, int precond, bool mixed, Read&& read, Start* s) {
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
   const bool mg = precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
-  SOLVE_HIP(setup<NV>(d, w, mg ? (int)RDC_PRECOND_BLOCK_JACOBI : precond, mixed));
+  const bool ilu = precond == RDC_PRECOND_ILU0;       // ... or the ILU(0) sweeps
+  SOLVE_HIP(setup<NV>(d, w, mg || ilu ? (int)RDC_PRECOND_BLOCK_JACOBI : precond, mixed));
   if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
+  if (ilu) SOLVE_HIP(timed(d.stream, &d.ilu->setup_ms, [&] { return ilu_setup<NV>(d, w); }));
   SOLVE_HIP(read());
   s->bad_blocks = d.host_rec->bad_blocks;
   s->form = mixed && d.host_rec->f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
@@ -1138,7 +1311,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
     info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
   };
-  const bool mg = p.precond == RDC_PRECOND_MULTIGRID;
+  const Right right = p.precond == RDC_PRECOND_MULTIGRID ? RIGHT_MG : p.precond == RDC_PRECOND_ILU0 ? RIGHT_ILU : RIGHT_NONE;
   Start start;
   SOLVE_HIP(prologue<NV>(d, w, (int)p.precond, mixed, [&] { return residual<NV>(d, w, x, p.rhs_scale, true); }, &start));
   info->bad_blocks = start.bad_blocks;
@@ -1162,7 +1335,7 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
       report(rec.flag ? RDC_SOLVE_NOT_FINITE : (std::sqrt(rec.rn2) <= tol ? RDC_SOLVE_CONVERGED : RDC_SOLVE_MAX_ITS));
       return hipSuccess;
     }
-    SOLVE_HIP(iteration<NV>(d, w, x, form, mg));
+    SOLVE_HIP(iteration<NV>(d, w, x, form, right));
     info->iterations++;
     const bool claims = !(rec.flag & 1) && std::sqrt(rec.rn2) <= tol;
     if (!claims && !rec.flag) continue;
@@ -1211,6 +1384,19 @@ hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, doubl
     *matrix_bits = start.form == F32 ? 32 : 64;
     if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is applied, `out` stays what it was
     SOLVE_HIP(mg_cycle<NV>(d, w, start.form, in, out));
+    return hipStreamSynchronize(d.stream);
+  });
+}
+
+hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int* bad_blocks) {
+  return by_nvar(d.nvar, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    const Work w = carve(d.nvar, d.n_owned, d.work);
+    Start start;
+    SOLVE_HIP(prologue<NV>(d, w, (int)RDC_PRECOND_ILU0, false, [&] { return read_record(d, w); }, &start));
+    *bad_blocks = start.bad_blocks;
+    if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is applied, `out` stays what it was
+    SOLVE_HIP(ilu_apply<NV>(d, in, out));
     return hipStreamSynchronize(d.stream);
   });
 }

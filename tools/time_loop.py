@@ -1,7 +1,7 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
                               [--ab [precond|precision|dist|smoother]] [--dump DIR]
     python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl]
 
@@ -10,9 +10,11 @@ preconditioned residual, and the share of nodes / elements still in the exact ba
 counted on the device after the clamp.  --mixed solves with rdc_solve_mixed (the iteration streams an fp32 copy of D^-1 A;
 matrix_bits in every record says what ran).  --precond 3 is the aggregation-multigrid preconditioner: every record then also has
 the device ms the solve spent building the hierarchy (mg_setup_ms, part of solve_ms), its level sizes and the device bytes it
-holds.  --ab runs the loop four times from the same initial state on one upload, so that two kinds of solve are timed in one
-process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, multigrid, block Jacobi (all four fp64, or all
-four mixed with --mixed); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
+holds.  --precond 4 is the multicolour block ILU(0): every record then has the device ms the solve spent on the copy of D^-1 A and
+its factorisation (ilu_setup_ms, part of solve_ms), the device bytes the factor holds and the colours; FP64 and one partition only.
+--ab runs the loop several times from the same initial state on one upload, so that the kinds of solve are timed in one
+process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, ILU(0), ILU(0), multigrid, block Jacobi (fp64; with
+--mixed, which has no ILU(0), block Jacobi, multigrid, multigrid, block Jacobi); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
 rdc_solve_dist, rdc_solve_dist, rdc_solve, the partitioned entry at world size 1 (its exchange moves nothing and its all-reduce
 leaves the values alone: what is timed is the pack launches, the k_reduce / k_advance split and the callbacks; with --precond 3
 the partitioned entry is rdc_solve_dist_mg, whose cycle adds the sized callbacks of the levels below the matrix); --ab smoother
@@ -111,6 +113,9 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
                 out[-1].update(mg_smoother=smoother, cycle_launches=cycle_launches(out[-1]["mg_levels"], colours, bool(gs_fuse)))
                 if smoother:
                     out[-1].update(mg_colours=colours, mg_gs_fuse=gs_fuse)
+        if precond == 4:
+            setup_ms, nbytes, colours = ctx.ilu_stats()
+            out[-1].update(ilu_setup_ms=setup_ms, ilu_bytes=nbytes, ilu_colours=colours)
     return out
 
 
@@ -174,6 +179,8 @@ def main():
         a.precond = 3
     if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or a.ab == "dist"):
         ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
+    if a.precond == 4 and (a.mixed or a.ranks > 1 or a.ab in ("precision", "dist")):
+        ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only")
     if a.ranks > 1:
         import socket
         import torch.multiprocessing as mp
@@ -193,7 +200,7 @@ def main():
         u0 = synth.pihna_fields(xyz)
         runs = [(a.precond, a.mixed, False, a.smoother)]
         if a.ab == "precond":
-            runs = [(pc, a.mixed, False, a.smoother) for pc in (2, 3, 3, 2)]
+            runs = [(pc, a.mixed, False, a.smoother) for pc in ((2, 3, 3, 2) if a.mixed else (2, 3, 4, 4, 3, 2))]
         elif a.ab == "precision":
             runs = [(a.precond, mixed, False, a.smoother) for mixed in (False, True, True, False)]
         elif a.ab == "dist":
