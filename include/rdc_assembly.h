@@ -342,6 +342,7 @@ int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 #define RDC_PRECOND_BLOCK_JACOBI 2      /* default choice of the Python wrapper */
 #define RDC_PRECOND_MULTIGRID 3         /* block Jacobi's system, with an aggregation-multigrid cycle applied from the right (below) */
 #define RDC_PRECOND_ILU0 4              /* block Jacobi's system, with a multicolour block ILU(0) applied from the right (below); rdc_solve only */
+#define RDC_PRECOND_ILU0_LOCAL 5        /* the same with the ILU(0) of the rank's owned square: block Jacobi between the ranks, ILU(0) inside each (below); rdc_solve_dist, and rdc_solve without ghosts */
 
 #define RDC_SOLVE_CONVERGED     0
 #define RDC_SOLVE_MAX_ITS       1       /* x holds the last iterate */
@@ -483,8 +484,8 @@ int rdc_solve_mg_level_download(rdc_ctx* ctx, int level, double* val, double* di
  * A diagonal block of A, or a pivot U_ii, that is singular or not finite counts into bad_blocks and gives
  * RDC_SOLVE_BAD_DIAGONAL with x untouched and no iteration run.  RDC_ERR_UNSUPPORTED, with nothing launched: on a context with
  * ghost nodes, for a block pattern that is not structurally symmetric or lacks a diagonal block, and for this value of
- * precond in rdc_solve_mixed, rdc_solve_dist and rdc_solve_dist_mg.  Every other call launches what it launched before the
- * value existed. */
+ * precond in rdc_solve_mixed, rdc_solve_dist and rdc_solve_dist_mg (across ranks: RDC_PRECOND_ILU0_LOCAL below, the rank-local
+ * factor; an ILU coupled across ranks is not implemented).  Every other call launches what it launched before the value existed. */
 /* What the factor costs: *setup_ms = device time the last solve (or rdc_solve_ilu_apply) spent on the copy of A^ and the
  * factorisation (part of its rdc_solve_info.device_ms); *bytes = device memory the factor holds for this mesh (values, U_ii^-1,
  * index lists, colour lists and the two vectors M p and M s); *n_colours = the colours.  Any pointer may be NULL.
@@ -503,6 +504,51 @@ int rdc_solve_ilu_apply(rdc_ctx* ctx, const double* d_in, double* d_out);
  * included) in the positions of the blocks they replace, the identity of L not stored; uinv = U_ii^-1, n_owned * nvar^2
  * doubles, row-major per node.  Either pointer may be NULL.  RDC_ERR_STATE if neither producer has run on this mesh. */
 int rdc_solve_ilu_download(rdc_ctx* ctx, double* val, double* uinv);
+
+/* ---- RDC_PRECOND_ILU0_LOCAL (rdc_solve_dist, FP64; additive: RDC_ABI_VERSION stays 3) ----
+ * The rank-local form of RDC_PRECOND_ILU0, a preconditioner of its own: what PETSc runs by default under mpirun, block Jacobi
+ * between the ranks with ILU(0) inside each.  System, stopping test and rdc_solve_info are those of RDC_PRECOND_BLOCK_JACOBI,
+ * M = (LU)^-1 is applied from the right, and LU is the multicolour block ILU(0) described above of the OWNED SQUARE of A^ = D^-1 A:
+ * the rows and columns below n_owned, the blocks in ghost columns left out.  The greedy colours are taken over the owned nodes in
+ * local order.  With more than one rank this is another operator than that of RDC_PRECOND_ILU0 (the couplings across partitions
+ * are dropped from the factor, not from the system), which is why it has a value of its own; RDC_PRECOND_ILU0 keeps its refusals.
+ *   rdc_solve_dist, mixed == 0   accepted on a context with or without ghosts, with the plain rdc_solve_comm.  An apply needs no
+ *                                communication: per iteration the call makes the two exchanges (of M p and M s, where block Jacobi
+ *                                exchanges p and s; the rows below "interior_nodes" still run before the ghosts arrive) and the three
+ *                                all-reduces of RDC_PRECOND_BLOCK_JACOBI, plus one of each per true residual -- no more.  The pivots
+ *                                U_ii that could not be inverted count into bad_blocks, which rides over the ranks in the all-reduce
+ *                                of the first true residual as it always has: on a bad pivot on any rank every rank returns
+ *                                RDC_SOLVE_BAD_DIAGONAL with the same bad_blocks, the owned rows of x untouched and no iteration run.
+ *                                On return the ghost rows of x hold the owners' values; two solves return the same bytes; a context
+ *                                without ghosts and a communicator of world size 1 returns, bit for bit, what rdc_solve returns
+ *                                with RDC_PRECOND_ILU0.
+ *   rdc_solve, no ghosts         accepted: the owned square is the matrix, and the call returns the bytes (x and every field of
+ *                                rdc_solve_info) of RDC_PRECOND_ILU0.  With ghosts it refuses as it does for every value.
+ *   rdc_solve_mixed, and rdc_solve_dist with mixed != 0   RDC_ERR_UNSUPPORTED: the factor is FP64 only.
+ *   rdc_solve_dist_mg            RDC_ERR_INVALID, as for anything but RDC_PRECOND_MULTIGRID.
+ * The factor shares the lists and the two allocations of RDC_PRECOND_ILU0 (rdc_solve_ilu_stats serves both).  On a context with
+ * ghost nodes every node block in a ghost column keeps an unused slot of nvar^2 doubles in the value buffer, the lists grow by 4
+ * bytes per owned node, and M p and M s by a ghost tail; on a context without ghosts the allocations are byte for byte those of
+ * RDC_PRECOND_ILU0.  RDC_ERR_UNSUPPORTED, as there, for an owned square that is not structurally symmetric or lacks a diagonal
+ * block; that refusal is taken by the rank alone, before its first callback.  Out of scope: a mixed-precision factor, an ILU coupled
+ * across ranks, overlapping partitions. */
+/* ---- two read-only observation points that accept a context with ghost nodes (TEST HOOKS, as the pair above, which keep refusing one).
+ * rdc_solve_ilu_local_apply: d_out = M d_in, ONE application of this rank's M, as the next rdc_solve_dist with
+ * RDC_PRECOND_ILU0_LOCAL would apply it (the same host function: D^-1, the copy of the owned square of A^, its factorisation from
+ * the current CSR values; lists built at first use).  d_in, d_out: DEVICE pointers, n_owned*nvar doubles each, not overlapping.
+ * No communication.  Blocks the host until done; never modifies the CSR values or the rhs.  RDC_ERR_STATE without a mesh,
+ * RDC_ERR_INVALID for a null pointer; RDC_ERR_INVALID, with the count in the message and d_out untouched, if a diagonal block or a
+ * pivot of THIS rank is not invertible. */
+int rdc_solve_ilu_local_apply(rdc_ctx* ctx, const double* d_in, double* d_out);
+/* The factor the last rdc_solve_ilu_local_apply or solve with RDC_PRECOND_ILU0_LOCAL (or, without ghosts, RDC_PRECOND_ILU0) built,
+ * into HOST arrays.  val: the layout of a node-block CSR RESTRICTED TO THE OWNED COLUMNS.  Node n has own[n] = the blocks of its row
+ * whose column is below n_owned -- the leading own[n] blocks of the row, since ghost ids lie above every owned id and the columns
+ * ascend; its values start at nvar^2 * (own[0] + .. + own[n - 1]) and lie as [var a][block k][var b], k = 0 .. own[n) - 1: the L
+ * and U blocks (diagonal blocks included) in the positions of the blocks they replace, the identity of L not stored.  The buffer
+ * is compact, nvar^2 * sum(own) doubles: it has no position for a ghost block.  Without ghosts this is the layout and content of
+ * rdc_solve_ilu_download.  uinv = U_ii^-1, n_owned * nvar^2 doubles, row-major per node.  Either pointer may be NULL.
+ * RDC_ERR_STATE if no producer has run on this mesh. */
+int rdc_solve_ilu_local_download(rdc_ctx* ctx, double* val, double* uinv);
 
 /* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
  * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own
@@ -544,7 +590,8 @@ int rdc_solve_dist_plan(rdc_ctx* ctx, int64_t n_send, const int32_t* send_nodes)
  * doubles in local numbering.  On entry the owned rows hold the initial guess, the ghost rows are ignored.  On exit the
  * owned rows hold the solution and the ghost rows the owners' values of it (the last true residual has just exchanged them),
  * whatever info->reason is; b = 0 gives x = 0 in 0 iterations, ghost rows included; RDC_SOLVE_BAD_DIAGONAL and a first
- * residual that is not finite leave the owned rows untouched.  precond: RDC_PRECOND_NONE, _JACOBI, _BLOCK_JACOBI;
+ * residual that is not finite leave the owned rows untouched.  precond: RDC_PRECOND_NONE, _JACOBI, _BLOCK_JACOBI, and with
+ * mixed == 0 RDC_PRECOND_ILU0_LOCAL (above);
  * RDC_PRECOND_MULTIGRID gives RDC_ERR_UNSUPPORTED here (its coarse exchanges need sizes: rdc_solve_dist_mg below).  RDC_ERR_STATE on a context with
  * ghost nodes that has no plan.  A context without ghosts, with an empty or no plan and a communicator of world size 1 (an
  * exchange that does nothing, an all-reduce that leaves d_vals as they are) is legal and returns, bit for bit, what

@@ -14,7 +14,7 @@ FIELD_OLD_SOLUTION, FIELD_AUX_NODAL, FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE = 0,
 FIELD_PREV_SOLUTION, FIELD_TIME_DERIV, FIELD_RT_DOSE = 4, 5, 6
 FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0 = 0, 1, 2, 3, 4
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL = 0, 1, 2, 3, 4, 5
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 1, 2, 3, 4, 5, 6
 
@@ -340,7 +340,8 @@ class AssemblyContext:
         sweep, undamped (mg_colours(); default 0 = damped block Jacobi; not on a ghosted context, not in solve_dist;
         set_option("mg_gs_fuse", 0): one launch per colour on the small levels too, same bytes).
         precond=PRECOND_ILU0: block Jacobi's system with a multicolour block ILU(0) of D^-1 A applied from the right, factored
-        anew by every solve (ilu_stats(); FP64 only: not with mixed=True, not on a ghosted context, not in solve_dist)."""
+        anew by every solve (ilu_stats(); FP64 only: not with mixed=True, not on a ghosted context, not in solve_dist).
+        precond=PRECOND_ILU0_LOCAL: the rank-local form of solve_dist; without ghosts it returns the bytes of PRECOND_ILU0."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -365,7 +366,9 @@ class AssemblyContext:
         rows: ignored in, the owners' values out), or field=FIELD_*.  The returned SolveInfo is the same on every rank.  The send
         list of comm is uploaded once per mesh.  An exception raised inside a callback of comm is re-raised here.
         precond=PRECOND_MULTIGRID needs a communicator with the sized exchange (SolveComm(..., sized=True)) and goes to
-        rdc_solve_dist_mg; its peer counts are uploaded with the plan."""
+        rdc_solve_dist_mg; its peer counts are uploaded with the plan.
+        precond=PRECOND_ILU0_LOCAL: block Jacobi between the ranks, the block ILU(0) of every rank's owned square inside it, applied
+        from the right; the exchanges and all-reduces of block Jacobi, fewer iterations (FP64 only: not with mixed=True)."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -477,6 +480,35 @@ class AssemblyContext:
         val = np.empty(self.csr_dims()[1], dtype=np.float64)
         uinv = np.empty((self.n_owned, nv, nv), dtype=np.float64)
         self._ck(self._lib.rdc_solve_ilu_download(self._h, _dp(val), _dp(uinv)))
+        return val, uinv
+
+    def ilu_local_apply_device(self, in_ptr, out_ptr):
+        """rdc_solve_ilu_local_apply on device addresses (n_owned*nvar doubles each): out = (LU)^-1 in with the ILU(0) of this
+        rank's owned square, as the next solve_dist(precond=PRECOND_ILU0_LOCAL) would apply it; takes a ghosted context.  A test hook."""
+        self._ck(self._lib.rdc_solve_ilu_local_apply(self._h, C.c_void_p(int(in_ptr)), C.c_void_p(int(out_ptr))))
+
+    def ilu_local_apply(self, x):
+        """numpy in, numpy out (tests): M x, n_owned*nvar entries each"""
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.n_owned * self.nvar:
+            raise ValueError("x must have n_owned * nvar entries")
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(x).to(dev)
+        yd = torch.empty_like(xd)
+        torch.cuda.synchronize(dev)
+        self.ilu_local_apply_device(xd.data_ptr(), yd.data_ptr())
+        return yd.cpu().numpy()
+
+    def ilu_local_factor(self):
+        """rdc_solve_ilu_local_download -> (val, uinv) as the last ilu_local_apply or solve with PRECOND_ILU0_LOCAL built them: val
+        in the layout of a node-block CSR restricted to the owned columns (per node [var a][owned block k][var b], the nodes one
+        behind the other; no position for a ghost block), uinv [n_owned][nvar][nvar] = U_ii^-1.  A test hook."""
+        nv = self.nvar
+        rp, col = self.csr_pattern()
+        val = np.empty(int(np.count_nonzero(col[:rp[self.n_owned * nv]] < self.n_owned * nv)), dtype=np.float64)
+        uinv = np.empty((self.n_owned, nv, nv), dtype=np.float64)
+        self._ck(self._lib.rdc_solve_ilu_local_download(self._h, _dp(val), _dp(uinv)))
         return val, uinv
 
     def part1_nodes(self):

@@ -63,7 +63,7 @@ struct SolveState {
   MgGsDev gs;
   std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
   bool ilu_ready = false;    // ilu_idx / ilu_val hold this mesh's lists, ilu describes them, ilu_host is their host copy
-  bool ilu_factored = false; // ... and ilu_val holds the factor of the last rdc_solve_ilu_apply or solve with RDC_PRECOND_ILU0
+  bool ilu_factored = false; // ... and ilu_val holds the factor of the last rdc_solve_ilu_apply / _local_apply or solve with RDC_PRECOND_ILU0 / _ILU0_LOCAL
   IluDev ilu;
   IluHost ilu_host;          // (IluDev::cptr_host points into it; rdc_solve_ilu_download permutes with it)
   bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
@@ -1308,15 +1308,17 @@ static int mg_view(rdc_ctx* c, SolveDev* d) {
 }
 
 // The lists of the block ILU(0) of the mesh (rdc_solve.h, ilu_build: colours, rows in elimination order), built on the host and
-// uploaded at the first solve with RDC_PRECOND_ILU0, and the two allocations ilu_place measures and then carves.  d must come
-// from solve_view(want_work) on a context without ghost nodes.
+// uploaded at the first solve with RDC_PRECOND_ILU0 or RDC_PRECOND_ILU0_LOCAL, and the two allocations ilu_place measures and then
+// carves.  One set per mesh serves both values: on a context with ghost nodes -- only the callers of the rank-local factor get here
+// with one -- the lists are those of the owned square and M p and M s have a ghost tail; without ghosts they are what they always
+// were.  d must come from solve_view.
 static int ilu_view(rdc_ctx* c, SolveDev* d) {
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   if (!S.ilu_ready) {
     IluHost H;
     int64_t where = -1;
-    const int bad = ilu_build(P.n_owned, P.bptr.data(), P.bcol.data(), H, &where);
+    const int bad = ilu_build(P.n_owned, P.bptr.data(), P.bcol.data(), H, &where, P.n_owned < P.n_node);
     if (bad == 1)
       return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern is not structurally symmetric: two coupled nodes share a colour, and the "
                   "block ILU(0) (precond %d) eliminates colour by colour", (int)RDC_PRECOND_ILU0);
@@ -1324,7 +1326,7 @@ static int ilu_view(rdc_ctx* c, SolveDev* d) {
     const int64_t blocks = P.bptr[(size_t)P.n_owned];
     MgArena idx, val;
     IluDev g;
-    ilu_place(H, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {});   // no bases: measures
+    ilu_place(H, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {}, P.n_node);   // no bases: measures
     int rc;
     if ((rc = dev_alloc(c, c->buf.solve.ilu_idx, idx.used))) return rc;
     if ((rc = dev_alloc(c, c->buf.solve.ilu_val, val.used))) return rc;
@@ -1334,7 +1336,7 @@ static int ilu_view(rdc_ctx* c, SolveDev* d) {
     hipError_t e = hipSuccess;
     ilu_place(S.ilu_host, P.nvar, P.n_owned, blocks, idx, val, S.ilu, [&](void* at, const void* list, size_t bytes) {
       if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
-    });
+    }, P.n_node);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the ILU(0) lists failed: %s", hipGetErrorString(e));
     S.ilu_ready = true;
@@ -1391,7 +1393,7 @@ int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
 // with_right: the preconditioners applied from the right on top of block Jacobi's system count (the solve entries)
 static bool known_precond(int precond, bool with_right) {
   return precond == RDC_PRECOND_NONE || precond == RDC_PRECOND_JACOBI || precond == RDC_PRECOND_BLOCK_JACOBI ||
-         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0));
+         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL));
 }
 
 int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
@@ -1446,6 +1448,9 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
   if (mixed && p->precond == RDC_PRECOND_ILU0)
     return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve, not rdc_solve_mixed", (int)RDC_PRECOND_ILU0);
+  if (mixed && p->precond == RDC_PRECOND_ILU0_LOCAL)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve or rdc_solve_dist, "
+                "not rdc_solve_mixed", (int)RDC_PRECOND_ILU0_LOCAL);
   if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, p->precond == RDC_PRECOND_MULTIGRID);
   if (c->ms.prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
     *info = rdc_solve_info();
@@ -1457,12 +1462,14 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
   int rc = solve_view(c, true, mixed, &d);
   if (rc) return rc;
   if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
-  if (p->precond == RDC_PRECOND_ILU0) {
+  rdc_solve_params q = *p;
+  if (q.precond == RDC_PRECOND_ILU0_LOCAL) q.precond = RDC_PRECOND_ILU0;   // no ghosts: the owned square is the matrix
+  if (q.precond == RDC_PRECOND_ILU0) {
     if ((rc = ilu_view(c, &d))) return rc;
     c->ms.solve.ilu_factored = false;
   }
-  RDC_HIP(c, solve_run(d, *p, d_x, info, mixed));
-  if (p->precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
+  RDC_HIP(c, solve_run(d, q, d_x, info, mixed));
+  if (q.precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
   if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   c->ms.solve.mg_values = p->precond == RDC_PRECOND_MULTIGRID;
   return RDC_OK;
@@ -1492,12 +1499,13 @@ int rdc_solve_mg_apply(rdc_ctx* c, int mixed, const double* d_in, double* d_out)
   return RDC_OK;
 }
 
-int rdc_solve_ilu_apply(rdc_ctx* c, const double* d_in, double* d_out) {
+// the two hooks of one application; local: rdc_solve_ilu_local_apply, which takes a context with ghost nodes (the factor of its owned square)
+static int ilu_apply_call(rdc_ctx* c, const double* d_in, double* d_out, bool local) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt
   if (!d_in || !d_out) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, false);
+  if (!local && c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, false);
   if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
   SolveDev d;
   int rc = solve_view(c, true, false, &d);
@@ -1511,32 +1519,48 @@ int rdc_solve_ilu_apply(rdc_ctx* c, const double* d_in, double* d_out) {
   return RDC_OK;
 }
 
-int rdc_solve_ilu_download(rdc_ctx* c, double* val, double* uinv) {
+int rdc_solve_ilu_apply(rdc_ctx* c, const double* d_in, double* d_out) { return ilu_apply_call(c, d_in, d_out, false); }
+
+int rdc_solve_ilu_local_apply(rdc_ctx* c, const double* d_in, double* d_out) { return ilu_apply_call(c, d_in, d_out, true); }
+
+// the two downloads.  Both write a node-block CSR over the columns the factor has: private position p of a node goes to the block of the
+// same column in the CSR row (bcol ascends, and the owned columns of a row are its leading ones), rows of own = the node's owned
+// blocks, nodes one behind the other.  Without ghosts own is the whole row, and this is the layout of the CSR values.
+static int ilu_download_call(rdc_ctx* c, double* val, double* uinv, bool local) {
   if (!c) return RDC_ERR_INVALID;
   const SolveState& S = c->ms.solve;
   if (!c->ms.have_mesh || !S.ilu_ready || !S.ilu_factored)
     return fail(c, RDC_ERR_STATE, "no rdc_solve_ilu_apply or solve with the block ILU(0) preconditioner has run on this mesh");
+  const HostPrep& P = c->ms.prep;
+  if (!local && P.n_owned < P.n_node) return refuse_ghosted(c, false);
   int rc = set_device(c);
   if (rc) return rc;
-  const HostPrep& P = c->ms.prep;
   const int nv = P.nvar;
   const int64_t n = P.n_owned, blocks = P.bptr[(size_t)n];
   std::vector<double> priv(val ? (size_t)blocks * nv * nv : 0);
   if (val && blocks) RDC_HIP(c, hipMemcpyAsync(priv.data(), S.ilu.val, priv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (uinv && n) RDC_HIP(c, hipMemcpyAsync(uinv, S.ilu.uinv, (size_t)n * nv * nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   RDC_HIP(c, hipStreamSynchronize(c->stream));
-  if (val)   // private position p of a node -> the block of the same column in the CSR row (bcol ascends)
+  if (val) {
+    int64_t o0 = 0;   // owned blocks of the nodes before i
     for (int64_t i = 0; i < n; i++) {
-      const int64_t b0 = P.bptr[(size_t)i], len = P.bptr[(size_t)i + 1] - b0, nl = S.ilu_host.nlow[(size_t)i];
-      for (int64_t p = 0; p < len; p++) {
-        const int64_t k = std::lower_bound(P.bcol.begin() + b0, P.bcol.begin() + b0 + len, S.ilu_host.pcol[(size_t)(b0 + p)]) - (P.bcol.begin() + b0);
+      const int64_t b0 = P.bptr[(size_t)i], nl = S.ilu_host.nlow[(size_t)i];
+      const int64_t own = S.ilu_host.nown.empty() ? P.bptr[(size_t)i + 1] - b0 : S.ilu_host.nown[(size_t)i];
+      for (int64_t p = 0; p < own; p++) {
+        const int64_t k = std::lower_bound(P.bcol.begin() + b0, P.bcol.begin() + b0 + own, S.ilu_host.pcol[(size_t)(b0 + p)]) - (P.bcol.begin() + b0);
         for (int a = 0; a < nv; a++)
           for (int b = 0; b < nv; b++)
-            val[csr_value_offset(P.bptr.data(), nv, i, a, k, b)] = priv[(size_t)ilu_value_offset(b0, nv, len, nl, a, p, b)];
+            val[(int64_t)nv * nv * o0 + ((int64_t)a * own + k) * nv + b] = priv[(size_t)ilu_value_offset(b0, nv, own, nl, a, p, b)];
       }
+      o0 += own;
     }
+  }
   return RDC_OK;
 }
+
+int rdc_solve_ilu_download(rdc_ctx* c, double* val, double* uinv) { return ilu_download_call(c, val, uinv, false); }
+
+int rdc_solve_ilu_local_download(rdc_ctx* c, double* val, double* uinv) { return ilu_download_call(c, val, uinv, true); }
 
 int rdc_solve_mg_level_download(rdc_ctx* c, int level, double* val, double* dinv) {
   if (!c) return RDC_ERR_INVALID;
@@ -1699,13 +1723,18 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
   if (p->precond == RDC_PRECOND_ILU0)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour, or a "
-                "rank-local factor, and is not implemented: rdc_solve on a context without ghost nodes", (int)RDC_PRECOND_ILU0);
+    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour and is "
+                "not implemented: rdc_solve on a context without ghost nodes, or the rank-local factor (precond %d)", (int)RDC_PRECOND_ILU0,
+                (int)RDC_PRECOND_ILU0_LOCAL);
   if (sized && p->precond != RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
                 (int)RDC_PRECOND_MULTIGRID, (int)p->precond);
   if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
+  const bool ilu_local = p->precond == RDC_PRECOND_ILU0_LOCAL;
+  if (ilu_local && mixed)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve_dist with mixed = 0",
+                (int)RDC_PRECOND_ILU0_LOCAL);
   if (sized && c->mg_smoother == 1)
     return fail(c, RDC_ERR_UNSUPPORTED, "rdc_solve_dist_mg smooths with damped Jacobi only: a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
                 "partitions needs a rule for the ghost values and is not implemented");
@@ -1740,7 +1769,12 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
     if (comm_rc) return fail(c, RDC_ERR_COMM, "a communication callback returned %d while the multigrid levels were built", comm_rc);
     if (rc) return rc;
   }
+  if (ilu_local) {
+    if ((rc = ilu_view(c, &d))) return rc;
+    S.ilu_factored = false;
+  }
   const hipError_t e = solve_run(d, *p, d_x, info, mixed != 0);
+  if (ilu_local && !comm_rc && e == hipSuccess) S.ilu_factored = true;
   if (comm_rc) {
     (void)hipStreamSynchronize(c->stream);   // x holds the last iterate
     return fail(c, RDC_ERR_COMM, "a communication callback returned %d; the solve was abandoned", comm_rc);

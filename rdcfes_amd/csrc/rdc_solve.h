@@ -6,7 +6,8 @@
 // Gauss-Seidel smoother (mg_colour, mg_gs_place; tests/host_solve_mg_gs_shim.cpp, tests/host_solve_mg_gs_main.cpp), and the hierarchy of a
 // ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).  The multicolour
 // block ILU(0) has its private layout and the factor step of a node among the host+device functions (ilu_value_offset, ilu_find,
-// ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp).
+// ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp); on a
+// pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -224,7 +225,12 @@ RDC_SOLVE_HD void scaled_block(const double (&dinv)[NV][NV], const double (&a)[N
 //   diag   nvar x nvar            behind it                                (the sweeps read U_ii^-1 from an array of its own)
 //   upper  nvar x (nup * nvar)    behind that, nup = len - nlow - 1        what the backward sweep reads, contiguous
 // so that forward and backward together cross the factor once: 8 nnz + 4 blocks bytes.
-// b0 = bptr[i], len = bptr[i + 1] - b0, nl = nlow[i]
+// On a pattern with ghost columns (precond 5, the rank-local factor: the ILU(0) of the OWNED SQUARE, rows and columns below
+// n_owned) the ghost columns of a node stand last in its private row, in ascending id, behind its nown[i] owned positions, and
+// nothing else changes: elimination order, nlow and the three runs are those of the nown[i] owned positions, nup = nown - nlow - 1.
+// The node keeps its nvar^2 * len values at nvar^2 * bptr[i]; the nvar^2 * (len - nown) behind the upper run are the slots of the
+// ghost blocks, which nothing writes or reads.  No node has a ghost column: nown is not kept, and everything is as stated above.
+// b0 = bptr[i], len = the positions the runs cover: bptr[i + 1] - b0, or nown[i] on a pattern with ghost columns; nl = nlow[i]
 RDC_SOLVE_HD int64_t ilu_value_offset(int64_t b0, int nvar, int64_t len, int64_t nl, int a, int64_t p, int b) {
   const int64_t base = (int64_t)nvar * nvar * b0;
   if (p < nl) return base + ((int64_t)a * nl + p) * nvar + b;
@@ -232,7 +238,8 @@ RDC_SOLVE_HD int64_t ilu_value_offset(int64_t b0, int nvar, int64_t len, int64_t
   return base + (int64_t)nvar * nvar * (nl + 1) + ((int64_t)a * (len - nl - 1) + (p - nl - 1)) * nvar + b;
 }
 
-// position of column node j in the private row `row` (len entries, ascending in (colour, node id)); -1 if the row has none
+// position of column node j in the private row `row` (len entries, ascending in (colour, node id); with ghost columns: the owned
+// positions only, since `colour` has no entry for a ghost); -1 if the row has none
 RDC_SOLVE_HD int64_t ilu_find(const int32_t* row, int64_t len, const int32_t* colour, int32_t j) {
   const int32_t cj = colour[j];
   int64_t lo = 0, hi = len - 1;
@@ -252,10 +259,11 @@ RDC_SOLVE_HD int64_t ilu_find(const int32_t* row, int64_t len, const int32_t* co
 // the stores of all lanes visible to all lanes before the next position is read (one lane: nothing).  Every sum is a chain of fma
 // in ascending index order, the updates of a block come in the order of p: no atomics, the same bits whatever `lanes` is.
 // Returns (lane 0; the others true) whether U_ii could be inverted; if not, uinv of the node is the identity.
-template <int NV, class Sync>
+// OWNED (a pattern with ghost columns): the rows end at their owned positions, nown[i] and nown[k]; no ghost block is touched.
+template <int NV, bool OWNED = false, class Sync>
 RDC_SOLVE_HD bool ilu_factor_node(const int64_t* bptr, const int32_t* pcol, const int32_t* nlow, const int32_t* colour,
-                                  double* val, double* uinv, int64_t i, int lane, int lanes, Sync&& sync) {
-  const int64_t b0 = bptr[i], len = bptr[i + 1] - b0, nl = nlow[i];
+                                  double* val, double* uinv, int64_t i, int lane, int lanes, Sync&& sync, const int32_t* nown = nullptr) {
+  const int64_t b0 = bptr[i], len = OWNED ? (int64_t)nown[i] : bptr[i + 1] - b0, nl = nlow[i];
   for (int64_t p = 0; p < nl; p++) {
     const int64_t k = pcol[b0 + p];
     double l[NV][NV];
@@ -280,7 +288,7 @@ RDC_SOLVE_HD bool ilu_factor_node(const int64_t* bptr, const int32_t* pcol, cons
       for (int a = 0; a < NV; a++)
 #pragma unroll
         for (int b = 0; b < NV; b++) val[ilu_value_offset(b0, NV, len, nl, a, p, b)] = l[a][b];
-    const int64_t k0 = bptr[k], klen = bptr[k + 1] - k0, knl = nlow[k];
+    const int64_t k0 = bptr[k], klen = OWNED ? (int64_t)nown[k] : bptr[k + 1] - k0, knl = nlow[k];
     for (int64_t q = knl + 1 + lane; q < klen; q += lanes) {
       const int64_t at = ilu_find(pcol + b0, len, colour, pcol[k0 + q]);
       if (at < 0) continue;
@@ -720,24 +728,29 @@ inline void mg_gs_place(const std::vector<MgColours>& cols, MgArena& arena, MgGs
   }
 }
 
-// ---- multicolour block ILU(0) (precond 4): the lists of a mesh, and where the factor lies on the device ----
+// ---- multicolour block ILU(0) (precond 4, and 5: the rank-local factor): the lists of a mesh, and where the factor lies on the device ----
 
 // What the private layout (ilu_value_offset, above) needs beside bptr: the colours of level 0 (mg_colour) and every row in
 // elimination order.  Built on the host once per mesh.
 struct IluHost {
   MgColours col;
-  std::vector<int32_t> pcol;   // [blocks] column node of every position, per node ascending in (colour, node id)
+  std::vector<int32_t> pcol;   // [blocks] column node of every position, per node ascending in (colour, node id), ghost columns last
   std::vector<int32_t> nlow;   // [n] lower blocks of a node = position of its diagonal block
+  std::vector<int32_t> nown;   // [n] owned positions of a node; EMPTY if no node has a ghost column (they are bptr[i + 1] - bptr[i])
 };
 
 // 0 = fine; 1 = the pattern is not structurally symmetric (mg_colour refuses it: a colour would not be independent);
-// 2 = node *where has no diagonal block, or a column that is no row (a ghost)
-inline int ilu_build(int64_t n, const int64_t* bptr, const int32_t* bcol, IluHost& H, int64_t* where) {
+// 2 = node *where has no diagonal block, or a column that is no row (a ghost).
+// ghosts: columns >= n are ghost columns and legal (2 then: no diagonal block, or a negative column).  The lists are those of the
+// owned square: mg_colour ignores the ghost columns, they stand last in every private row and count into neither nlow nor nown.
+inline int ilu_build(int64_t n, const int64_t* bptr, const int32_t* bcol, IluHost& H, int64_t* where, bool ghosts = false) {
   H = IluHost();
+  bool any_ghost = false;
   for (int64_t i = 0; i < n; i++) {
     bool diag = false;
     for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
-      if (bcol[k] < 0 || bcol[k] >= n) { *where = i; return 2; }
+      if (bcol[k] < 0 || (bcol[k] >= n && !ghosts)) { *where = i; return 2; }
+      any_ghost = any_ghost || bcol[k] >= n;
       diag = diag || bcol[k] == i;
     }
     if (!diag) { *where = i; return 2; }
@@ -746,41 +759,56 @@ inline int ilu_build(int64_t n, const int64_t* bptr, const int32_t* bcol, IluHos
   const std::vector<int32_t>& colour = H.col.colour;
   H.pcol.assign(bcol, bcol + bptr[n]);
   H.nlow.assign((size_t)n, 0);
+  if (any_ghost) H.nown.assign((size_t)n, 0);
   for (int64_t i = 0; i < n; i++) {
     std::sort(H.pcol.begin() + bptr[i], H.pcol.begin() + bptr[i + 1], [&](int32_t x, int32_t y) {
+      if (x >= n || y >= n) return x < y;   // a ghost behind every owned column, ghosts by id
       return colour[(size_t)x] != colour[(size_t)y] ? colour[(size_t)x] < colour[(size_t)y] : x < y;
     });
-    int32_t nl = 0;
-    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) nl += colour[(size_t)bcol[k]] < colour[(size_t)i];
+    int32_t nl = 0, no = 0;
+    for (int64_t k = bptr[i]; k < bptr[i + 1]; k++) {
+      if (bcol[k] >= n) continue;
+      no++;
+      nl += colour[(size_t)bcol[k]] < colour[(size_t)i];
+    }
     H.nlow[(size_t)i] = nl;
+    if (any_ghost) H.nown[(size_t)i] = no;
   }
   return 0;
 }
 
 // The factorisation of one whole matrix on the host, node after node in elimination order with one lane (tests, and the yardstick
 // of what the per-colour launches compute): val holds A^ in the private layout on entry and the factor on exit, uinv [n][NV][NV]
-// the U_ii^-1.  Returns the number of nodes whose U_ii could not be inverted.
+// the U_ii^-1.  Returns the number of nodes whose U_ii could not be inverted.  On lists with ghost columns: the factor of the owned
+// square; the slots of the ghost blocks are neither read nor written.
 template <int NV>
 inline int64_t ilu_factor_host(int64_t n, const int64_t* bptr, const IluHost& H, double* val, double* uinv) {
   int64_t bad = 0;
-  for (int64_t at = 0; at < n; at++)
-    bad += !ilu_factor_node<NV>(bptr, H.pcol.data(), H.nlow.data(), H.col.colour.data(), val, uinv, H.col.nodes[(size_t)at], 0, 1, [] {});
+  for (int64_t at = 0; at < n; at++) {
+    const int64_t i = H.col.nodes[(size_t)at];
+    bad += H.nown.empty() ? !ilu_factor_node<NV>(bptr, H.pcol.data(), H.nlow.data(), H.col.colour.data(), val, uinv, i, 0, 1, [] {})
+                          : !ilu_factor_node<NV, true>(bptr, H.pcol.data(), H.nlow.data(), H.col.colour.data(), val, uinv, i, 0, 1, [] {}, H.nown.data());
+  }
   return bad;
 }
 
 // The factor on the device.  Two allocations, measured and placed like the arenas of mg_place (MgArena: no base measures):
 // `idx` holds pcol, nlow, the colours and the colour lists, `val` the factor, the U_ii^-1 and the two vectors M p and M s of the
 // right-preconditioned iteration.  cptr_host: the bounds of the colour lists on the host (it points into H).
+// nown: the owned positions per node, behind the other lists; null on a mesh without ghost columns (IluHost::nown is empty), whose
+// two allocations are then byte for byte what they were before ghost columns were taken.  n_nodes (>= n): M p and M s get the ghost
+// tail the operator of a partitioned solve receives into.
 struct IluDev {
   int n_colours = 0;
-  const int32_t *pcol = nullptr, *nlow = nullptr, *colour = nullptr, *nodes = nullptr;
+  const int32_t *pcol = nullptr, *nlow = nullptr, *colour = nullptr, *nodes = nullptr, *nown = nullptr;
   const int64_t* cptr_host = nullptr;
   double *val = nullptr, *uinv = nullptr, *ph = nullptr, *sh = nullptr;
   float setup_ms = 0.0f;   // out: device time of the copy of A^ and the factorisation of the last solve
 };
 
 template <class Upload>
-inline void ilu_place(const IluHost& H, int nvar, int64_t n, int64_t blocks, MgArena& idx, MgArena& val, IluDev& g, Upload&& upload) {
+inline void ilu_place(const IluHost& H, int nvar, int64_t n, int64_t blocks, MgArena& idx, MgArena& val, IluDev& g, Upload&& upload,
+                      int64_t n_nodes = -1) {
   auto list = [&](const auto& v) {
     const size_t bytes = v.size() * sizeof(v[0]);
     void* at = idx.take(bytes);
@@ -791,9 +819,11 @@ inline void ilu_place(const IluHost& H, int nvar, int64_t n, int64_t blocks, MgA
   g = IluDev();
   g.n_colours = H.col.n_colours();
   g.pcol = list(H.pcol); g.nlow = list(H.nlow); g.colour = list(H.col.colour); g.nodes = list(H.col.nodes);
+  if (!H.nown.empty()) g.nown = list(H.nown);
   g.cptr_host = H.col.cptr.data();
   g.val = vec(blocks * nvar * nvar); g.uinv = vec(n * nvar * nvar);
-  g.ph = vec(std::max<int64_t>(n * nvar, 1)); g.sh = vec(std::max<int64_t>(n * nvar, 1));
+  const int64_t tail = std::max<int64_t>(std::max(n_nodes, n) * nvar, 1);
+  g.ph = vec(tail); g.sh = vec(tail);
 }
 
 // ---- the iteration's scalars, its launch shapes and the layout of its work buffer: host code without HIP, so that a CPU build
@@ -896,7 +926,7 @@ struct SolveDev {
   hipStream_t stream = nullptr;
   MgDev* mg = nullptr;             // the hierarchy (RDC_PRECOND_MULTIGRID only)
   const MgGsDev* gs = nullptr;     // its colour lists: the smoother is Gauss-Seidel (option "mg_smoother" = 1); null: damped Jacobi
-  IluDev* ilu = nullptr;           // the factor (RDC_PRECOND_ILU0 only)
+  IluDev* ilu = nullptr;           // the factor (RDC_PRECOND_ILU0 and RDC_PRECOND_ILU0_LOCAL only)
   // partitioned solve (rdc_solve_dist) only.  comm == nullptr is the single-partition path.
   const rdc_solve_comm* comm = nullptr;
   int peers = 0;                                 // rdc_solve_dist_plan_peers
@@ -920,7 +950,8 @@ hipError_t solve_matvec_f32(const SolveDev& d, const double* x, double* y);
 // in the form that solve would iterate in; in and out hold n_owned * nvar doubles and do not overlap; d.mg is set, d.comm is not.
 // *bad_blocks > 0: a diagonal block of some level is not invertible, nothing was applied.  Synchronises.
 hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, double* out, int* bad_blocks, int* matrix_bits);
-// Test hook (rdc_solve_ilu_apply): out = (LU)^-1 in behind the prologue of a solve with RDC_PRECOND_ILU0 (the same host function);
+// Test hook (rdc_solve_ilu_apply, rdc_solve_ilu_local_apply): out = (LU)^-1 in behind the prologue of a solve with RDC_PRECOND_ILU0
+// or, on lists with ghost columns, RDC_PRECOND_ILU0_LOCAL (the same host function);
 // in and out hold n_owned * nvar doubles and do not overlap; d.ilu is set, d.comm is not.  *bad_blocks > 0: a diagonal block or a
 // pivot U_ii is not invertible, nothing was applied.  Synchronises.
 hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int* bad_blocks);

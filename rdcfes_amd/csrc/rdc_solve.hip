@@ -26,6 +26,9 @@
 // Block ILU(0) (precond 4): the other right preconditioner of `iteration`, M = (LU)^-1 with LU the block ILU(0) of
 // D^-1 A in the multicolour order of the Gauss-Seidel smoother; factorisation, forward and backward sweep are one launch per colour
 // each (k_ilu_copy, k_ilu_factor, k_ilu_fwd, k_ilu_bwd, further down), on a copy of D^-1 A in a layout of its own (rdc_solve.h).
+// Rank-local (precond 5, rdc_solve_dist): the same of the owned square of D^-1 A, rows and columns below n_owned, through the _owned
+// forms of those kernels, which end every row at its owned positions; the apply exchanges nothing, M p and M s travel in the two
+// exchanges of the iteration.
 //
 // Dot products: per-workgroup partials (wave butterfly, then the four waves in order) into a scratch array, then one
 // small kernel that adds the partials in a fixed order AND turns them into the next scalar (alpha, omega, beta) in
@@ -846,6 +849,47 @@ __global__ __launch_bounds__(256) void k_ilu_copy(const int64_t* __restrict__ bp
   }
 }
 
+// k_ilu_copy on lists with ghost columns (rdc_solve.h): the node's owned positions only, own = nown[node] of them.  Its owned
+// columns are the first `own` of its CSR row (ghost ids lie above every owned id and bcol ascends), so the search stays among them
+// and neither the column nor the values of a ghost block are read; the CSR rows keep their stride of len blocks.  A kernel of its
+// own text and no instantiation of a shared body: through one k_ilu_copy compiles to other (equivalent) instructions than it did.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_copy_owned(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                        const int32_t* __restrict__ pcol, const int32_t* __restrict__ nlow,
+                                                        const int32_t* __restrict__ nown, const double* __restrict__ val,
+                                                        const double* __restrict__ dinv, int64_t n_owned, double* __restrict__ fval) {
+  const int lane = threadIdx.x & 15;
+  const int64_t node = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  if (node >= n_owned) return;
+  const int64_t b0 = bptr[node], len = bptr[node + 1] - b0, nl = nlow[node], own = nown[node];
+  const double* __restrict__ vrow = val + (int64_t)NV * NV * b0;
+  double di[NV][NV];
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int b = 0; b < NV; b++) di[a][b] = dinv[(node * NV + a) * NV + b];
+  for (int64_t p = lane; p < own; p += 16) {
+    const int32_t j = pcol[b0 + p];
+    int64_t lo = 0, hi = own - 1, k = 0;
+    while (lo <= hi) {   // the owned part of the row has the column
+      k = lo + (hi - lo) / 2;
+      const int32_t c = bcol[b0 + k];
+      if (c == j) break;
+      if (c < j) lo = k + 1; else hi = k - 1;
+    }
+    double blk[NV][NV], out[NV][NV];
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) blk[a][b] = __builtin_nontemporal_load(vrow + ((int64_t)a * len + k) * NV + b);
+    scaled_block<NV>(di, blk, out);
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) fval[ilu_value_offset(b0, NV, own, nl, a, p, b)] = out[a][b];
+  }
+}
+
 // The nodes list[0 .. count) of one colour, one 16-lane group each (rdc_solve.h, ilu_factor_node: the lanes run over the upper
 // blocks of the row of a lower neighbour, whose targets in the node's own row are distinct).  The row is read and written in
 // global memory whatever its length; between two lower neighbours a workgroup-scope fence makes the blocks the 16 lanes have
@@ -860,6 +904,20 @@ __global__ __launch_bounds__(256) void k_ilu_factor(const int64_t* __restrict__ 
   if (at >= count) return;
   const bool ok = ilu_factor_node<NV>(bptr, pcol, nlow, colour, fval, uinv, list[at], threadIdx.x & 15, 16,
                                       [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); });
+  if (!ok) atomicAdd(&scal->bad_blocks, 1);
+}
+
+// ... on lists with ghost columns: the rows of the node and of its lower neighbours end at their owned positions (nown), and
+// ilu_find searches the owned part of the node's row only -- `colour` has no entry for a ghost
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_factor_owned(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                          const int32_t* __restrict__ nlow, const int32_t* __restrict__ nown,
+                                                          const int32_t* __restrict__ colour, double* fval, double* uinv,
+                                                          const int32_t* __restrict__ list, int64_t count, SolveScal* __restrict__ scal) {
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  if (at >= count) return;
+  const bool ok = ilu_factor_node<NV, true>(bptr, pcol, nlow, colour, fval, uinv, list[at], threadIdx.x & 15, 16,
+                                            [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }, nown);
   if (!ok) atomicAdd(&scal->bad_blocks, 1);
 }
 
@@ -884,6 +942,8 @@ __device__ __forceinline__ void ilu_run_product(const double* __restrict__ vrow,
 
 // forward sweep over one colour: z_i = y_i - sum_{colour(k) < c} L_ik z_k.  z is read (lower colours) and written (this one);
 // y is the argument of the apply and does not overlap z.  Colour 0 has no lower blocks: its launch copies y.
+// Serves lists with ghost columns as it is: the lower run starts at nvar^2 * bptr[node] and has nlow[node] blocks whatever follows
+// it, and a lower column has a lower colour, so it is an owned node: z is read below n_owned only.
 template <int NV>
 __global__ __launch_bounds__(256) void k_ilu_fwd(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
                                                  const int32_t* __restrict__ nlow, const double* __restrict__ fval,
@@ -902,15 +962,17 @@ __global__ __launch_bounds__(256) void k_ilu_fwd(const int64_t* __restrict__ bpt
 }
 
 // backward sweep over one colour: z_i = U_ii^-1 (z_i - sum_{colour(j) > c} U_ij z_j), in place
-template <int NV>
-__global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
-                                                 const int32_t* __restrict__ nlow, const double* __restrict__ fval,
-                                                 const double* __restrict__ uinv, double* z, const int32_t* __restrict__ list, int64_t count) {
+// OWNED (lists with ghost columns): the upper run ends at the node's owned positions, so z is read below n_owned only
+template <int NV, bool OWNED>
+__device__ __forceinline__ void ilu_bwd_body(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                             const int32_t* __restrict__ nlow, const int32_t* __restrict__ nown,
+                                             const double* __restrict__ fval, const double* __restrict__ uinv, double* z,
+                                             const int32_t* __restrict__ list, int64_t count) {
   const int lane = threadIdx.x & 15;
   const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
   const bool live = at < count;
   const int64_t node = live ? list[at] : 0;
-  const int64_t b0 = bptr[node], len = bptr[node + 1] - b0, nl = nlow[node];
+  const int64_t b0 = bptr[node], len = OWNED ? (int64_t)nown[node] : bptr[node + 1] - b0, nl = nlow[node];
   double acc[NV];
   ilu_run_product<NV>(fval + (int64_t)NV * NV * (b0 + nl + 1), live ? (int)(len - nl - 1) * NV : 0, pcol + b0 + nl + 1, z, lane, acc);
   if (live && lane < NV) {
@@ -920,6 +982,21 @@ __global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bpt
     for (int q = 0; q < NV; q++) t = fma(urow[q], z[node * NV + q] - acc[q], t);
     z[node * NV + lane] = t;
   }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                 const int32_t* __restrict__ nlow, const double* __restrict__ fval,
+                                                 const double* __restrict__ uinv, double* z, const int32_t* __restrict__ list, int64_t count) {
+  ilu_bwd_body<NV, false>(bptr, pcol, nlow, nullptr, fval, uinv, z, list, count);
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_bwd_owned(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                       const int32_t* __restrict__ nlow, const int32_t* __restrict__ nown,
+                                                       const double* __restrict__ fval, const double* __restrict__ uinv, double* z,
+                                                       const int32_t* __restrict__ list, int64_t count) {
+  ilu_bwd_body<NV, true>(bptr, pcol, nlow, nown, fval, uinv, z, list, count);
 }
 
 // First use of every kernel instantiation. A code object lists template instantiations by first use; this list keeps the order
@@ -933,6 +1010,7 @@ __global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bpt
   (const void*)k_gs<NV, true>, (const void*)k_gs<NV, false>, (const void*)k_gs_f32<NV>, (const void*)k_gs_fused<NV, true>,     \
   (const void*)k_gs_fused<NV, false>, (const void*)k_gs_f32_fused<NV>
 #define ILU_KERNELS_OF(NV) (const void*)k_ilu_copy<NV>, (const void*)k_ilu_factor<NV>, (const void*)k_ilu_fwd<NV>, (const void*)k_ilu_bwd<NV>
+#define ILU_OWNED_KERNELS_OF(NV) (const void*)k_ilu_copy_owned<NV>, (const void*)k_ilu_factor_owned<NV>, (const void*)k_ilu_bwd_owned<NV>
 [[maybe_unused]] const void* const KERNEL_ORDER[] = {
     (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
@@ -941,10 +1019,11 @@ __global__ __launch_bounds__(256) void k_ilu_bwd(const int64_t* __restrict__ bpt
     (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>,
     (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
     (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>,
-    GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5)};
+    GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5), ILU_OWNED_KERNELS_OF(3), ILU_OWNED_KERNELS_OF(5)};
 #undef KERNELS_OF
 #undef GS_KERNELS_OF
 #undef ILU_KERNELS_OF
+#undef ILU_OWNED_KERNELS_OF
 
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
@@ -1213,22 +1292,35 @@ hipError_t mg_setup(const SolveDev& d, const Work& w) {
 }
 
 // the factor from the current values (behind setup(): the copy reads D^-1): A^ into the private layout, then one launch per colour
-// in ascending order; a pivot U_ii that cannot be inverted counts into bad_blocks
+// in ascending order; a pivot U_ii that cannot be inverted counts into bad_blocks.  Lists with ghost columns (g.nown): the _owned
+// kernels, the factor of the owned square.  A rank that owns no node launches nothing.
 template <int NV>
 hipError_t ilu_setup(const SolveDev& d, const Work& w) {
   const IluDev& g = *d.ilu;
-  hipLaunchKernelGGL((k_ilu_copy<NV>), dim3((unsigned)op_blocks(d.n_owned, SCALED)), dim3(256), 0, d.stream, d.bptr, d.bcol, g.pcol, g.nlow, d.val,
-                     (const double*)w.dinv, d.n_owned, g.val);
+  const dim3 grid((unsigned)op_blocks(d.n_owned, SCALED)), block(256);
+  if (!grid.x) return hipSuccess;
+  if (g.nown)
+    hipLaunchKernelGGL((k_ilu_copy_owned<NV>), grid, block, 0, d.stream, d.bptr, d.bcol, g.pcol, g.nlow, g.nown, d.val, (const double*)w.dinv,
+                       d.n_owned, g.val);
+  else
+    hipLaunchKernelGGL((k_ilu_copy<NV>), grid, block, 0, d.stream, d.bptr, d.bcol, g.pcol, g.nlow, d.val, (const double*)w.dinv, d.n_owned, g.val);
   for (int c = 0; c < g.n_colours; c++) {
     const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
-    hipLaunchKernelGGL((k_ilu_factor<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.colour,
-                       g.val, g.uinv, g.nodes + c0, count, w.scal);
+    const dim3 cgrid((unsigned)op_blocks(count, SCALED));
+    if (g.nown)
+      hipLaunchKernelGGL((k_ilu_factor_owned<NV>), cgrid, block, 0, d.stream, d.bptr, g.pcol, g.nlow, g.nown, g.colour, g.val, g.uinv,
+                         g.nodes + c0, count, w.scal);
+    else
+      hipLaunchKernelGGL((k_ilu_factor<NV>), cgrid, block, 0, d.stream, d.bptr, g.pcol, g.nlow, g.colour, g.val, g.uinv, g.nodes + c0, count,
+                         w.scal);
   }
   return hipGetLastError();
 }
 
 // out = (LU)^-1 in: forward over the colours ascending, backward descending, one launch per colour each way (colour 0 forward is the
-// copy of `in`, since out is another vector).  Enqueues only; a fixed linear operator for fixed values.
+// copy of `in`, since out is another vector).  Enqueues only; a fixed linear operator for fixed values.  Writes the owned entries
+// of `out` and needs no communication: across ranks the factor is rank-local, and the ghost tail of `out` is filled by the exchange
+// of the operator application that follows.
 template <int NV>
 hipError_t ilu_apply(const SolveDev& d, const double* in, double* out) {
   const IluDev& g = *d.ilu;
@@ -1239,8 +1331,12 @@ hipError_t ilu_apply(const SolveDev& d, const double* in, double* out) {
   }
   for (int c = g.n_colours - 1; c >= 0; c--) {
     const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
-    hipLaunchKernelGGL((k_ilu_bwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
-                       (const double*)g.val, (const double*)g.uinv, out, g.nodes + c0, count);
+    if (g.nown)
+      hipLaunchKernelGGL((k_ilu_bwd_owned<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.nown,
+                         (const double*)g.val, (const double*)g.uinv, out, g.nodes + c0, count);
+    else
+      hipLaunchKernelGGL((k_ilu_bwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
+                         (const double*)g.val, (const double*)g.uinv, out, g.nodes + c0, count);
   }
   return hipGetLastError();
 }
@@ -1292,7 +1388,7 @@ template <int NV, class Read>
 hipError_t prologue(const SolveDev& d, const Work& w, int precond, bool mixed, Read&& read, Start* s) {
   SOLVE_HIP(hipMemsetAsync(w.scal, 0, sizeof(SolveScal), d.stream));
   const bool mg = precond == RDC_PRECOND_MULTIGRID;   // the system is that of block Jacobi, the cycle comes on top
-  const bool ilu = precond == RDC_PRECOND_ILU0;       // ... or the ILU(0) sweeps
+  const bool ilu = precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL;   // ... or the ILU(0) sweeps (5: of the rank's owned square)
   SOLVE_HIP(setup<NV>(d, w, mg || ilu ? (int)RDC_PRECOND_BLOCK_JACOBI : precond, mixed));
   if (mg) SOLVE_HIP(timed(d.stream, &d.mg->setup_ms, [&] { return mg_setup<NV>(d, w); }));
   if (ilu) SOLVE_HIP(timed(d.stream, &d.ilu->setup_ms, [&] { return ilu_setup<NV>(d, w); }));
@@ -1311,7 +1407,8 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
     info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
   };
-  const Right right = p.precond == RDC_PRECOND_MULTIGRID ? RIGHT_MG : p.precond == RDC_PRECOND_ILU0 ? RIGHT_ILU : RIGHT_NONE;
+  const Right right = p.precond == RDC_PRECOND_MULTIGRID ? RIGHT_MG
+                      : p.precond == RDC_PRECOND_ILU0 || p.precond == RDC_PRECOND_ILU0_LOCAL ? RIGHT_ILU : RIGHT_NONE;
   Start start;
   SOLVE_HIP(prologue<NV>(d, w, (int)p.precond, mixed, [&] { return residual<NV>(d, w, x, p.rhs_scale, true); }, &start));
   info->bad_blocks = start.bad_blocks;

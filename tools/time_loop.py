@@ -1,9 +1,9 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
                               [--ab [precond|precision|dist|smoother]] [--dump DIR]
-    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl]
+    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--ab precond]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
@@ -12,6 +12,8 @@ matrix_bits in every record says what ran).  --precond 3 is the aggregation-mult
 the device ms the solve spent building the hierarchy (mg_setup_ms, part of solve_ms), its level sizes and the device bytes it
 holds.  --precond 4 is the multicolour block ILU(0): every record then has the device ms the solve spent on the copy of D^-1 A and
 its factorisation (ilu_setup_ms, part of solve_ms), the device bytes the factor holds and the colours; FP64 and one partition only.
+--precond 5 is its rank-local form (the ILU(0) of every rank's owned square: block Jacobi between the ranks, ILU(0) inside each), the
+one --ranks takes, with the same three figures per record (rank 0's own); on one partition it runs what --precond 4 runs.
 --ab runs the loop several times from the same initial state on one upload, so that the kinds of solve are timed in one
 process on one device: --ab (= --ab precond) in the order block Jacobi, multigrid, ILU(0), ILU(0), multigrid, block Jacobi (fp64; with
 --mixed, which has no ILU(0), block Jacobi, multigrid, multigrid, block Jacobi); --ab precision in the order fp64, mixed, mixed, fp64 with --precond; --ab dist in the order rdc_solve,
@@ -26,7 +28,8 @@ state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
-no halo update of its own.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
+no halo update of its own.  --ab (= --ab precond) with --ranks runs the loop from the same initial state in the order block Jacobi,
+multigrid, rank-local ILU(0), rank-local ILU(0), multigrid, block Jacobi in the same processes.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
 iterations and the global true residual.  Rank r uses GPU r modulo the number of GPUs: on a one-GPU machine the ranks share it,
 and with --backend gloo every message is staged through the host -- such a run checks correctness and measures nothing."""
 import argparse
@@ -113,7 +116,7 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
                 out[-1].update(mg_smoother=smoother, cycle_launches=cycle_launches(out[-1]["mg_levels"], colours, bool(gs_fuse)))
                 if smoother:
                     out[-1].update(mg_colours=colours, mg_gs_fuse=gs_fuse)
-        if precond == 4:
+        if precond in (4, 5):
             setup_ms, nbytes, colours = ctx.ilu_stats()
             out[-1].update(ilu_setup_ms=setup_ms, ilu_bytes=nbytes, ilu_colours=colours)
     return out
@@ -140,7 +143,8 @@ def rank_main(rank, world, port, a):
             ctx.set_option("interior_nodes", int(lp.n_interior))
             ctx.mesh_upload(4, lp.conn, lp.xyz, 5, n_owned=lp.n_owned)
             ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
-            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=a.precond == 3)   # multigrid: rdc_solve_dist_mg
+            preconds = (2, 3, 5, 5, 3, 2) if a.ab == "precond" else (a.precond,)
+            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=3 in preconds)   # multigrid: rdc_solve_dist_mg
             shared = world > torch.cuda.device_count()
             head = dict(rank=rank, gpu=gpu, owned_nodes=int(lp.n_owned), interior_nodes=int(lp.n_interior),
                         ghost_nodes=int(lp.xyz.shape[0] - lp.n_owned), halo_bytes_per_exchange=comm.bytes_per_exchange,
@@ -150,11 +154,17 @@ def rank_main(rank, world, port, a):
                 if r == rank:
                     print(json.dumps(head), flush=True)
                 dist.barrier()
-            for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, a.precond, a.max_its, mixed=a.mixed, comm=comm):
-                if rank == 0:          # every figure of the solve is global and the same on every rank
-                    keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
-                    keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if a.precond == 3 else ()     # rank 0's own levels
-                    print(json.dumps({k: rec[k] for k in keep}), flush=True)
+            for precond in preconds:
+                if len(preconds) > 1:
+                    ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
+                    if rank == 0:
+                        print(json.dumps(dict(precond=precond)), flush=True)
+                for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=a.mixed, comm=comm):
+                    if rank == 0:          # every figure of the solve is global and the same on every rank
+                        keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
+                        keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if precond == 3 else ()     # rank 0's own levels
+                        keep += ("ilu_setup_ms", "ilu_bytes", "ilu_colours") if precond == 5 else ()        # rank 0's own factor
+                        print(json.dumps({k: rec[k] for k in keep}), flush=True)
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -180,7 +190,13 @@ def main():
     if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or a.ab == "dist"):
         ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
     if a.precond == 4 and (a.mixed or a.ranks > 1 or a.ab in ("precision", "dist")):
-        ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only")
+        ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only (across ranks: --precond 5)")
+    if a.precond == 5 and (a.mixed or a.ab == "precision"):
+        ap.error("the rank-local block ILU(0) (--precond 5) is FP64 only")
+    if a.ranks > 1 and a.ab not in (None, "precond"):
+        ap.error("--ranks takes --ab precond only")
+    if a.ranks > 1 and a.ab == "precond" and a.mixed:
+        ap.error("--ab precond with --ranks is FP64: the rank-local ILU(0) has no mixed form")
     if a.ranks > 1:
         import socket
         import torch.multiprocessing as mp
