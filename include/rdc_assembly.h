@@ -203,7 +203,15 @@ int rdc_set_kernel_variant(rdc_ctx* ctx, int variant);
  * "ev_general" 1 (default) = any parameter values through the kernel with all 22 moments, 0 = through the (node, element) pair
  * kernel as before round 3; "ev_background" 1 (default) = waves all of whose elements are in the background state of the shipped
  * field file (n = c = h = a = 0, v > 0) do not evaluate the moments and right-hand sides that are sums of exact zeros -- same
- * matrix, the kernel time then depends on the state --, 0 = everything is evaluated.  HEX8 with three unknowns: "hex_kernel" 0 =
+ * matrix, the kernel time then depends on the state --, 0 = everything is evaluated; "const_rows" 1 (default) = with
+ * uptake/a/from/v = 0 the matrix rows of the a equation (a fifth of the values) do not depend on the unknowns, and an element-visit
+ * launch that finds them in the value array from an earlier one with the same dt * secrete/a/from/c, dt * secrete/a/from/h and
+ * dt * decay/a does not write them again -- the a rows of the value array PERSIST between calls: do not write over them.  The
+ * library forgets them on rdc_mesh_upload, rdc_mesh_update_coords, a change of "interior_nodes", any assembly through another
+ * kernel or model and a failed launch, stops skipping once rdc_csr_values_device_ptr (until the next rdc_mesh_upload) or
+ * rdc_mesh_coords_device_ptr (for good) has given out a writable pointer, and always writes every row into a stream that is
+ * capturing a graph; 0 = every launch writes every row; 2 = as 1, and the caller promises not to write the value or coordinate
+ * arrays through the pointers it was given, which then do not stop the skipping.  HEX8 with three unknowns: "hex_kernel" 0 =
  * producer / consumer cluster kernel (default), 1 = (node, element) pair kernels, 2 = persistent form of the cluster
  * kernel; "solid_kernel" 0 = fused cluster kernel for HEX8 tangent requests and the two-pass form otherwise (default),
  * 1 = coloured read-modify-write, 2 = two-pass always (bitwise reproducible sums), 3 = fused (error when unavailable);
@@ -231,7 +239,8 @@ int rdc_mesh_upload(rdc_ctx* ctx, int elem_type, int64_t n_elem, int64_t n_node,
                     int64_t n_owned_nodes, const uint32_t* conn, const double* xyz, int nvar);
 /* moving mesh: new CURRENT node positions (host pointer), same numbering */
 int rdc_mesh_update_coords(rdc_ctx* ctx, const double* xyz);
-/* device pointer of the current coordinates [n_node][3] (e.g. to update them in place on the GPU) */
+/* device pointer of the current coordinates [n_node][3] (e.g. to update them in place on the GPU); ends the skipping of
+ * "const_rows" = 1 for the life of the context (the library cannot see such updates) */
 int rdc_mesh_coords_device_ptr(rdc_ctx* ctx, double** d_xyz);
 int rdc_mesh_dims(const rdc_ctx* ctx, int64_t* n_elem, int64_t* n_node, int64_t* n_owned_nodes,
                   int* elem_type, int* nvar, int* n_colours);
@@ -305,6 +314,8 @@ int rdc_tet4_cluster_info(rdc_ctx* ctx, int32_t* mode, int32_t* active, int64_t*
                           int64_t* n_elem_visits, int64_t* lds_bytes);
 
 /* ---- results ---- */
+/* device pointers of the CSR values and of the rhs (either output may be NULL).  They are writable: asking for d_val
+ * ends the skipping of "const_rows" = 1 until the next rdc_mesh_upload ("const_rows" = 2: the caller only reads). */
 int rdc_csr_values_device_ptr(rdc_ctx* ctx, double** d_val, double** d_rhs);
 int rdc_csr_download(rdc_ctx* ctx, double* val, double* rhs);
 /* Chunked hand-back: the CSR values and rhs entries of the rows of nodes [node_begin, node_end) only, written to the

@@ -226,6 +226,8 @@ static bool push_results_device(TransientLinearImplicitSystem& sys, Binding& B) 
   PetscObjectTypeCompare((PetscObject)A, MATSEQAIJHIPSPARSE, &is_seq_hip);
   if (!is_seq_hip) return false;
   double *d_val = nullptr, *d_rhs = nullptr;
+  // d_val is only read here (the copy below): a binding that keeps it that way may set rdc_set_option(ctx, "const_rows", 2) once,
+  // so that this hand-out does not stop the element-visit launches from leaving the a rows they find
   check(B.ctx, rdc_csr_values_device_ptr(B.ctx, &d_val, &d_rhs), "rdc_csr_values_device_ptr");
   PetscScalar* a = nullptr;
   MatSeqAIJHIPSPARSEGetArrayWrite(A, &a);                 // device pointer of the CSR values, write access

@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "rdc_internal.h"
+#include "rdc_const_rows.h"
 #include "rdc_parts.h"
 #include "rdc_tet4_ev.h"
 #include "rdc_tet4_cl.h"
@@ -118,6 +119,7 @@ struct rdc_ctx {
   Options opt;
   MeshState ms;
   Buffers buf;
+  ConstRows const_rows;         // the a rows of the value array that PIHNA element-visit launches may leave (rdc_const_rows.h); coords_out outlives the mesh
   hipEvent_t pack_event = nullptr;  // two-part assembly: recorded behind part 1's pack of the owned node records
   // chunked hand-back (rdc_csr_download_rows_async): a copy stream of the context's own and a small pool of completion events
   hipStream_t copy_stream = nullptr;
@@ -512,6 +514,10 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
     f.cl_fits = tet4_cl_lds_bytes<M>(c->ms.cl.max_row_doubles) <= c->max_lds;
   }
   const Plan plan = a.plan = path_decide(model, f);
+  // the a rows of the value array (rdc_const_rows.h) are kept by the PIHNA element-visit launches alone: any other assembly of the
+  // context -- another path, another model, a timing-only build ("ablate" 1-3: wrong results) -- forgets them
+  const bool const_rows_path = std::is_same<M, Pihna>::value && plan.path == Path::TET4_EV && (c->opt.ablate == 0 || c->opt.ablate == 4);
+  if (!const_rows_path) c->const_rows.other_assembly();
   if (c->opt.ev_resident) {   // cluster counter of the resident kernel
     if ((rc = dev_alloc(c, c->buf.ev.ticket, 256))) return rc;   // [0]: whole launches and part 1, [16]: part 2
     a.ev_ticket = (int*)c->buf.ev.ticket.p;
@@ -584,7 +590,21 @@ int assemble_rd(rdc_ctx* c, const P* p, int nvar_expected, bool need_aux) {
   if (c->timing) {
     if ((rc = next_event_pair(c, &a.ev_start, &ev_stop))) return rc;
   }
+  ConstRowsKey rows_key;
+  bool capturing = false;
+  if constexpr (std::is_same<M, Pihna>::value) {
+    if (const_rows_path) {
+      rows_key = const_rows_key(k);
+      // a launch recorded into a graph writes every row: a replay must not depend on what the host knew at capture time.  A
+      // query that fails (another stream of the thread is capturing) counts as capturing
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); capturing = true; }
+      else capturing = cs != hipStreamCaptureStatusNone;
+      a.ev_rows = c->const_rows.rows(c->const_rows.mode, rows_key, plan.two_part == TwoPart::WHOLE ? 0 : part, c->opt.interior_nodes, capturing);
+    }
+  }
   hipError_t e = launch_specialised<M>(a, k);
+  if (const_rows_path) c->const_rows.launched(a.ev_rows, rows_key, plan.two_part == TwoPart::WHOLE ? 0 : part, capturing, e == hipSuccess);
   if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
   if (c->timing) RDC_HIP(c, hipEventRecord(ev_stop, c->stream));
   return RDC_OK;
@@ -707,6 +727,11 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
     (smoother ? c->mg_smoother : c->mg_gs_fuse) = value;
     return RDC_OK;
   }
+  if (!std::strcmp(key, "const_rows")) {   // rdc_const_rows.h: a contract with the caller about the value array, not a tuning knob of a kernel
+    if (!const_rows_mode_ok(value)) return fail(c, RDC_ERR_INVALID, "%s", CONST_ROWS_REFUSED);
+    c->const_rows.mode = value;
+    return RDC_OK;
+  }
   return options_set(c->opt, key, value, c->err, sizeof(c->err));
 }
 
@@ -725,6 +750,7 @@ int rdc_mesh_upload(rdc_ctx* c, int elem_type, int64_t n_elem, int64_t n_node, i
   int rc = set_device(c);
   if (rc) return rc;
   c->ms.have_mesh = false;
+  c->const_rows.mesh_upload();
   // LDS budget of a row-gather workgroup: half the per-block limit keeps two workgroups per CU
   const size_t budget = c->max_lds >= 64 * 1024 ? 50 * 1024 : c->max_lds / 2;
   std::string err = prep_build(elem_type, n_elem, n_node, n_owned, conn, nvar, budget, c->opt.block, c->ms.prep, c->opt.schedule != 0);
@@ -790,6 +816,7 @@ int rdc_mesh_update_coords(rdc_ctx* c, const double* xyz) {
   if (!xyz) return fail(c, RDC_ERR_INVALID, "null coordinates");
   int rc = set_device(c);
   if (rc) return rc;
+  c->const_rows.coords_update();
   RDC_HIP(c, hipMemcpyAsync(c->buf.mesh.xyz.p, xyz, (size_t)c->ms.prep.n_node * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   RDC_HIP(c, hipStreamSynchronize(c->stream));
   return RDC_OK;
@@ -799,6 +826,7 @@ int rdc_mesh_coords_device_ptr(rdc_ctx* c, double** d) {
   if (!c || !d) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   *d = (double*)c->buf.mesh.xyz.p;
+  c->const_rows.coords_pointer();   // the caller may move nodes at any time from now on
   return RDC_OK;
 }
 
@@ -966,6 +994,7 @@ int rdc_solid_assemble(rdc_ctx* c, const rdc_solid_params* p, int request_jacobi
   if (!p) return fail(c, RDC_ERR_INVALID, "null parameter struct");
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "assemble called before rdc_mesh_upload");
   c->tet4_cl_active = 0;
+  c->const_rows.other_assembly();
   if (c->ms.prep.nvar != 3) return fail(c, RDC_ERR_INVALID, "solid system needs nvar=3");
   if (!c->buf.field[RDC_FIELD_UNDEFORMED_XYZ].p) return fail(c, RDC_ERR_STATE, "undeformed coordinates not set");
   if (!c->buf.field[RDC_FIELD_ELEM_FIBRE].p) return fail(c, RDC_ERR_STATE, "fibre field not set");
@@ -1063,7 +1092,7 @@ int rdc_solid_assemble(rdc_ctx* c, const rdc_solid_params* p, int request_jacobi
 int rdc_csr_values_device_ptr(rdc_ctx* c, double** d_val, double** d_rhs) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (d_val) *d_val = (double*)c->buf.out.val.p;
+  if (d_val) { *d_val = (double*)c->buf.out.val.p; c->const_rows.values_pointer(); }   // ... or write the values
   if (d_rhs) *d_rhs = (double*)c->buf.out.rhs.p;
   return RDC_OK;
 }

@@ -101,10 +101,13 @@ __device__ __forceinline__ void wave_nodes(const HostPrepEv::Node* snode, const 
 // doubles with them -- is issued into registers of its own and waited for once, then the stores leave.  `image` holds the image
 // from offset `base` (even) on; out[x] <-> img[x]: the image has the 16-byte phase of the segment in memory.  A lane past the end of
 // its segment reads the segment's first piece (inside the image whatever the workgroup's LDS size) and stores nothing.
-template <int NV2, int NS>
+// NVW < NV2 (a multiple of nvar: whole equation rows): only the first NVW * len values of every segment leave -- the trailing rows
+// keep what memory holds (rdc_const_rows.h); the image and the segment's place in memory are those of NV2 values per block.
+template <int NV2, int NS, int NVW = NV2>
 __device__ __forceinline__ void store_segments(const double* image, double* val, const HostPrepEv::Node (&nd)[NS], const bool (&on)[NS],
                                                const int lane, const uint32_t base = 0) {
-  constexpr int NR = seg_reads(NV2);
+  static_assert(NVW > 0 && NVW <= NV2, "the leading NVW of a block's NV2 values");
+  constexpr int NR = seg_reads(NVW);
   v2d_t r[NS][NR];
   double ends[NS][2];   // the odd head and tail doubles
   const double* img[NS];
@@ -112,7 +115,7 @@ __device__ __forceinline__ void store_segments(const double* image, double* val,
 #pragma unroll
   for (int s = 0; s < NS; s++) {
     img[s] = image + (on[s] ? nd[s].obase - base : 0u);
-    cnt[s] = on[s] ? NV2 * (int)nd[s].len : 0;
+    cnt[s] = on[s] ? NVW * (int)nd[s].len : 0;
     sh[s] = on[s] ? seg_phase(nd[s].obase) : 0;
     npair[s] = (cnt[s] - sh[s]) >> 1;
     const v2d_t* src = reinterpret_cast<const v2d_t*>(img[s] + sh[s]);

@@ -96,6 +96,7 @@ struct LaunchArgs {
   ClDev cl;              // HEX8, three unknowns: cluster lists (n_wg = 0: not available / not wanted); TET4: those of k_tet4_cl
   int ev_grid = 0;           // 2 x CUs: the resident element-visit kernel launches 3/2 of it (22 moments: all of it)
   int* ev_ticket = nullptr;  // k_tet4_evq: cluster counter (one int, zeroed by the launch)
+  int ev_rows = 5;           // k_tet4_ev / k_tet4_evq: equation rows of every node they write, 5 or 4 (rdc_const_rows.h)
   long long* stamps = nullptr;  // diagnostic phase stamps (rdc_debug_stamps)
   double* val;
   double* rhs;

@@ -8,6 +8,8 @@
 //            CSR rows of the cluster's nodes; rhs entries straight to memory
 //   phase 3  the image leaves with 16-byte non-temporal stores, one contiguous CSR segment per node
 // Every CSR value is written exactly once; no global atomics, no colours.  Sums are order-dependent in the last bits.
+// The a equation's rows do not depend on the unknowns when the uptake rate is 0 (pihna_expand, o[20..24]): a launch that finds them
+// in memory from an earlier one leaves them there (NROW = 4; rdc_const_rows.h says when).
 #include "rdc_internal.h"
 #include <type_traits>
 #include "rdc_tet4_ev.h"
@@ -61,13 +63,17 @@ __device__ __forceinline__ void ev_read_moments(const double* lds, const int blk
 }
 
 // GEN: every term on (22 moments, rdc_tet4_ev.h); otherwise the shipped parameter pattern (16)
-template <int EXP_MODE, int MINW, int ABL = 0, bool GEN = false>
+// NROW: equation rows of a node the launch writes.  4 = the a row (cytokine: the last 5 len values of every segment) keeps what an
+// earlier launch wrote, neither expanded into the image nor copied out; when that is exact is rdc_const_rows.h's decision.  A
+// template parameter: as a run-time scalar both copy-outs live in one kernel and k_tet4_evq spills 15 more scalar registers
+template <int EXP_MODE, int MINW, int ABL = 0, bool GEN = false, int NROW = 5>
 __global__ void __launch_bounds__(256, MINW)
 k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict__ nlist, const uint32_t* __restrict__ vloc,
           const uint32_t* __restrict__ vslot, const HostPrepEv::Node* __restrict__ ntab, const uint8_t* __restrict__ bpart,
           const uint32_t* __restrict__ wg_perm, const PihnaK k, const double* __restrict__ rec, double* __restrict__ val,
           double* __restrict__ rhs, const int nls, const int wg_begin, const int xcd_n, const int stagger,
           long long* __restrict__ stamps, const int bg_skip) {
+  static_assert(NROW == 4 || NROW == 5, "all five equation rows, or all but the a row");
   constexpr int BLOCK = 256, NP = 4;   // PIHNA node record: 8 doubles = 4 pieces of 16 bytes
   constexpr bool TL = ABL == 4;
   long long ts[11];
@@ -168,7 +174,7 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
     const int len = (int)snode[bn].len;
     double* dst = lds + snode[bn].obase + evl::seg_entry(5, len, 0, bs, 0);   // the block's origin first: k_tet4_evq
 #pragma unroll
-    for (int a = 0; a < 5; a++)
+    for (int a = 0; a < NROW; a++)   // NROW = 4: the a row's place in the image stays unused
 #pragma unroll
       for (int b = 0; b < 5; b++) dst[evl::seg_entry(5, len, a, 0, b)] = o[a * 5 + b];
   }
@@ -182,8 +188,8 @@ k_tet4_ev(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict_
     evl::wave_nodes(snode, wvu, nd);   // nodes wv, wv + 4, wv + 8, wv + 12: two at a time
     const HostPrepEv::Node nd01[2] = {nd[0], nd[1]}, nd23[2] = {nd[2], nd[3]};
     const bool on01[2] = {wvu < (int)d.nown, wvu + 4 < (int)d.nown}, on23[2] = {wvu + 8 < (int)d.nown, wvu + 12 < (int)d.nown};
-    if (on01[0]) evl::store_segments<25, 2>(lds, val, nd01, on01, lane);
-    if (on23[0]) evl::store_segments<25, 2>(lds, val, nd23, on23, lane);
+    if (on01[0]) evl::store_segments<25, 2, 5 * NROW>(lds, val, nd01, on01, lane);
+    if (on23[0]) evl::store_segments<25, 2, 5 * NROW>(lds, val, nd23, on23, lane);
   }
   if (TL) {
     RDC_TS(9);
@@ -229,13 +235,14 @@ struct EvqLists {   // landing area of a cluster's lists (bytes): visit position
 };
 }
 // GEN: the 22-moment instantiation (any parameter values), at the register budget of two workgroups per CU as in k_tet4_ev
-template <int EXP_MODE, bool TL, bool GEN = false>
+template <int EXP_MODE, bool TL, bool GEN = false, int NROW = 5>   // NROW: k_tet4_ev
 __global__ void __launch_bounds__(256, GEN ? 2 : 3)
 k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict__ nlist, const uint32_t* __restrict__ vloc,
            const uint32_t* __restrict__ vslot, const HostPrepEv::Node* __restrict__ ntab, const uint8_t* __restrict__ bpart,
            const PihnaK k, const double* __restrict__ rec, double* __restrict__ val, double* __restrict__ rhs, const int nls,
            const int wg_begin, const int wg_count, long long* __restrict__ stamps, const int bg_skip, int* __restrict__ ticket,
            const uint32_t* __restrict__ wg_perm) {
+  static_assert(NROW == 4 || NROW == 5, "k_tet4_ev");
   constexpr int BLOCK = 256, NP = 4;
   constexpr int NM = GEN ? ev::NMG : ev::NM, NBP = ev::NBP, MAXN = ev::MAXN;
   extern __shared__ __attribute__((aligned(16))) double lds[];   // [M: NM x NBP, later the image halves | R: 5 x MAXN | records: NP x nls x 16 B | lists]
@@ -396,7 +403,7 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
         // spill 4-8 registers instead of 2 (20-32 B of scratch per lane)
         double* dst = lds + (bn_obase - base) + evl::seg_entry(5, len, 0, bs, 0);
 #pragma unroll
-        for (int a = 0; a < 5; a++)
+        for (int a = 0; a < NROW; a++)
 #pragma unroll
           for (int b = 0; b < 5; b++) dst[evl::seg_entry(5, len, a, 0, b)] = o[a * 5 + b];
       }
@@ -409,7 +416,7 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
       lds_barrier();
       const int n1 = nown < n0 + 8 ? nown : n0 + 8;
       const bool on[2] = {n0 + wv < n1, n0 + wv + 4 < n1};
-      if (on[0]) evl::store_segments<25, 2>(lds, val, ndh, on, lane, base);
+      if (on[0]) evl::store_segments<25, 2, 5 * NROW>(lds, val, ndh, on, lane, base);
       lds_barrier();   // the half has been read (into the stores' registers)
     }
     RDC_TS(5);
@@ -427,17 +434,24 @@ k_tet4_evq(const HostPrepEv::Desc* __restrict__ desc, const uint32_t* __restrict
 
 namespace {
 // the one launch of k_tet4_ev (one workgroup per cluster) and of its resident form k_tet4_evq (`grid` workgroups walk over the clusters)
+// a.ev_rows (4 or 5: what assemble_rd took from rdc_const_rows.h) picks the instantiation; the timing-only builds (ABL 1-3: wrong
+// results) have the five-row form alone, and assemble_rd never asks them for four
 template <int MODE, int MINW, int ABL, bool GEN>
 hipError_t launch_ev(const LaunchArgs& a, const PihnaK& k, const int wg_count, const size_t lds_bytes) {
   const EvDev& E = a.ev;
-  hipLaunchKernelGGL((k_tet4_ev<MODE, MINW, ABL, GEN>), dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab,
+  auto kern = k_tet4_ev<MODE, MINW, ABL, GEN, 5>;
+  if constexpr (ABL == 0 || ABL == 4) {
+    if (a.ev_rows == 4) kern = k_tet4_ev<MODE, MINW, ABL, GEN, 4>;
+  } else if (a.ev_rows != 5) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3(wg_count), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab,
                      E.bpart, E.wg_perm, k, a.packed, a.val, a.rhs, E.nls, E.wg_begin, a.opt.xcd ? wg_count : 0, a.opt.stagger, a.stamps, a.opt.ev_background);
   return hipGetLastError();
 }
 template <int MODE, bool TL, bool GEN>
 hipError_t launch_evq(const LaunchArgs& a, const PihnaK& k, const int wg_count, const int grid, const size_t lds_bytes) {
   const EvDev& E = a.ev;
-  hipLaunchKernelGGL((k_tet4_evq<MODE, TL, GEN>), dim3(grid), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab, E.bpart, k,
+  const auto kern = a.ev_rows == 4 ? k_tet4_evq<MODE, TL, GEN, 4> : k_tet4_evq<MODE, TL, GEN, 5>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, a.stream, E.desc, E.nlist, E.vloc, E.vslot, E.ntab, E.bpart, k,
                      a.packed, a.val, a.rhs, E.nls, E.wg_begin, wg_count, a.stamps, a.opt.ev_background, a.ev_ticket + (a.pack_part == 2 ? 16 : 0), E.wg_perm);
   return hipGetLastError();
 }

@@ -19,16 +19,18 @@ for f in glob.glob(d + "/pmc*/**/*counter_collection.csv", recursive=True):
         for k, v in c.items():
             agg[name][k].append(v)
 print("## counters (mean per dispatch)\n")
-traffic = None
+traffic, traffic_n = None, 0   # of the kernel with the most dispatches: the steady-state launch (a first launch that still writes the a rows is another instantiation)
 for name, c in agg.items():
     if "pack" in name or "fill" in name.lower():
         continue
-    print(f"`{name[:100]}`\n")
+    n_disp = max(len(v) for v in c.values())
+    print(f"`{name[:100]}` ({n_disp} dispatches per pass)\n")
     print("| counter | mean per launch |\n|---|---|")
     m = {k: sum(v) / len(v) for k, v in c.items()}
     for k in sorted(m):
         print(f"| {k} | {m[k]:.6g} |")
-    if "FETCH_SIZE" in m and "WRITE_SIZE" in m and ("rg" in name or "tet4" in name):
+    if "FETCH_SIZE" in m and "WRITE_SIZE" in m and ("rg" in name or "tet4" in name) and n_disp > traffic_n:
+        traffic_n = n_disp
         # guide: FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of the bytes of wide (16 B/lane)
         # coalesced reads -> doubled.  Reads here are 16-B-per-lane loads (pair records, node records).
         traffic = {"fetch_kib_raw": m["FETCH_SIZE"], "write_kib": m["WRITE_SIZE"],
