@@ -495,13 +495,33 @@ int rdc_solve_mg_level_download(rdc_ctx* ctx, int level, double* val, double* di
  * A diagonal block of A, or a pivot U_ii, that is singular or not finite counts into bad_blocks and gives
  * RDC_SOLVE_BAD_DIAGONAL with x untouched and no iteration run.  RDC_ERR_UNSUPPORTED, with nothing launched: on a context with
  * ghost nodes, for a block pattern that is not structurally symmetric or lacks a diagonal block, and for this value of
- * precond in rdc_solve_mixed, rdc_solve_dist and rdc_solve_dist_mg (across ranks: RDC_PRECOND_ILU0_LOCAL below, the rank-local
+ * precond in rdc_solve_mixed (unless "ilu_factor_bits" is 32, below), rdc_solve_dist and rdc_solve_dist_mg (across ranks: RDC_PRECOND_ILU0_LOCAL below, the rank-local
  * factor; an ILU coupled across ranks is not implemented).  Every other call launches what it launched before the value existed. */
 /* What the factor costs: *setup_ms = device time the last solve (or rdc_solve_ilu_apply) spent on the copy of A^ and the
  * factorisation (part of its rdc_solve_info.device_ms); *bytes = device memory the factor holds for this mesh (values, U_ii^-1,
  * index lists, colour lists and the two vectors M p and M s); *n_colours = the colours.  Any pointer may be NULL.
  * RDC_ERR_STATE if no such solve has run on this mesh. */
 int rdc_solve_ilu_stats(rdc_ctx* ctx, float* setup_ms, int64_t* bytes, int32_t* n_colours);
+/* ---- the fp32 factor (option "ilu_factor_bits", rdc_set_option; additive: RDC_ABI_VERSION stays 3) ----
+ * "ilu_factor_bits" is 64 (default) or 32; any other value is RDC_ERR_INVALID and changes nothing.  With 64 every entry launches,
+ * returns and refuses what is described above and below.  With 32 the factorisation is unchanged (FP64, the private layout); a
+ * further kernel then rounds the lower and the upper blocks to fp32 into a third allocation (made at the first solve or hook
+ * with the option at 32 on a mesh, freed with the mesh, counted by rdc_solve_ilu_stats from then on: 4 bytes per off-diagonal
+ * non-zero, every row of a node's lower and upper run padded to a multiple of 16 bytes, 8 bytes per node of offsets, no slot
+ * for a diagonal or a ghost block), and the two sweeps of every apply stream that copy.  U_ii^-1, z, every sum and the epilogue
+ * stay FP64: each value is converted to double and fed to an fma.  The set-up time of rdc_solve_ilu_stats includes the rounding.
+ * Accepted with 32, beside what 64 accepts: RDC_PRECOND_ILU0 and RDC_PRECOND_ILU0_LOCAL in rdc_solve_mixed, and
+ * RDC_PRECOND_ILU0_LOCAL in rdc_solve_dist with mixed != 0 (the fp32 operator with the fp32 factor).  Every other refusal stays.
+ * Fall-back: the rounding counts the entries that are finite in FP64 and not in fp32, and the host reads the count with the
+ * record of bad_blocks before the first iteration (no further synchronisation).  If it is not zero the sweeps stream the FP64
+ * factor, and the call is bit for bit the one with the option at 64.  This is independent of the operator's fall-back
+ * (matrix_bits), and across ranks each rank decides alone: M is block-diagonal over the ranks, so a mixture is a legal
+ * preconditioner, and the exchanges and all-reduces per iteration stay what they are.  Deterministic as the FP64 sweeps.
+ * rdc_solve_ilu_apply and rdc_solve_ilu_local_apply apply what the next solve would; the two downloads return the FP64 factor
+ * the copy was rounded from.
+ * rdc_solve_ilu_factor_bits: *bits = what the sweeps of the last ILU(0) solve or apply hook on this mesh streamed, 32 or 64.
+ * RDC_ERR_STATE before any has run. */
+int rdc_solve_ilu_factor_bits(rdc_ctx* ctx, int32_t* bits);
 /* ---- two read-only observation points (additive: RDC_ABI_VERSION stays 3).  TEST HOOKS, as the multigrid pair above.
  * rdc_solve_ilu_apply: d_out = M d_in, ONE application, as the next rdc_solve with RDC_PRECOND_ILU0 would apply it: the call
  * first does what such a solve does before its first iteration (D^-1, the copy of A^, the factorisation from the current CSR
@@ -535,13 +555,14 @@ int rdc_solve_ilu_download(rdc_ctx* ctx, double* val, double* uinv);
  *                                with RDC_PRECOND_ILU0.
  *   rdc_solve, no ghosts         accepted: the owned square is the matrix, and the call returns the bytes (x and every field of
  *                                rdc_solve_info) of RDC_PRECOND_ILU0.  With ghosts it refuses as it does for every value.
- *   rdc_solve_mixed, and rdc_solve_dist with mixed != 0   RDC_ERR_UNSUPPORTED: the factor is FP64 only.
+ *   rdc_solve_mixed, and rdc_solve_dist with mixed != 0   RDC_ERR_UNSUPPORTED: the factor is FP64 only -- unless the option
+ *                                "ilu_factor_bits" is 32 (above): the sweeps then stream the fp32 copy of the factor.
  *   rdc_solve_dist_mg            RDC_ERR_INVALID, as for anything but RDC_PRECOND_MULTIGRID.
  * The factor shares the lists and the two allocations of RDC_PRECOND_ILU0 (rdc_solve_ilu_stats serves both).  On a context with
  * ghost nodes every node block in a ghost column keeps an unused slot of nvar^2 doubles in the value buffer, the lists grow by 4
  * bytes per owned node, and M p and M s by a ghost tail; on a context without ghosts the allocations are byte for byte those of
  * RDC_PRECOND_ILU0.  RDC_ERR_UNSUPPORTED, as there, for an owned square that is not structurally symmetric or lacks a diagonal
- * block; that refusal is taken by the rank alone, before its first callback.  Out of scope: a mixed-precision factor, an ILU coupled
+ * block; that refusal is taken by the rank alone, before its first callback.  Out of scope: an fp32 U_ii^-1, an ILU coupled
  * across ranks, overlapping partitions. */
 /* ---- two read-only observation points that accept a context with ghost nodes (TEST HOOKS, as the pair above, which keep refusing one).
  * rdc_solve_ilu_local_apply: d_out = M d_in, ONE application of this rank's M, as the next rdc_solve_dist with

@@ -70,6 +70,7 @@ SIGNATURES = {
     "rdc_solve_mg_apply": (C.c_int, [ctx_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rdc_solve_mg_level_download": (C.c_int, [ctx_p, C.c_int, P(dbl), P(dbl)]),
     "rdc_solve_ilu_stats": (C.c_int, [ctx_p, P(C.c_float), P(C.c_int64), P(C.c_int32)]),
+    "rdc_solve_ilu_factor_bits": (C.c_int, [ctx_p, P(C.c_int32)]),
     "rdc_solve_ilu_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
     "rdc_solve_ilu_download": (C.c_int, [ctx_p, P(dbl), P(dbl)]),
     "rdc_solve_ilu_local_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),

@@ -142,7 +142,8 @@ def build(force: bool = False, jobs: int = 4, verbose: bool = True) -> Path:
     default_path = ("k_tet4_ev", "k_tet4_evm", "k_tet4_evc", "k_tet4_rg5", "k_tet4_cl", "k_hex8_cl", "k_solid_cl", "k_pack_nodes",
                     "k_spmv", "k_spmv_f32", "k_scale_f32", "k_precond_setup", "k_residual", "k_finalize", "k_update_p", "k_update_s", "k_update_xr",
                     "k_galerkin", "k_restrict", "k_prolong", "k_smooth", "k_reduce", "k_advance", "k_halo_pack",
-                    "k_gs", "k_gs_f32", "k_gs_fused", "k_gs_f32_fused")   # opt-in ("mg_smoother" = 1), held to the same rule
+                    "k_gs", "k_gs_f32", "k_gs_fused", "k_gs_f32_fused",   # opt-in ("mg_smoother" = 1), held to the same rule
+                    "k_ilu_round_f32", "k_ilu_fwd_f32", "k_ilu_bwd_f32", "k_ilu_bwd_f32_owned")   # opt-in ("ilu_factor_bits" = 32), likewise
     bad = {k: v for k, v in resources.items() if v.get("scratch_bytes_per_lane", 0) or v.get("vgpr_spills", 0)}
     hot = {k: v for k, v in bad.items() if any(f"{len(n)}{n}I" in k or f"{len(n)}{n}E" in k for n in default_path)}
     for k, v in sorted(bad.items() if os.environ.get("RDC_BUILD_VERBOSE") else hot.items()):

@@ -340,7 +340,9 @@ class AssemblyContext:
         sweep, undamped (mg_colours(); default 0 = damped block Jacobi; not on a ghosted context, not in solve_dist;
         set_option("mg_gs_fuse", 0): one launch per colour on the small levels too, same bytes).
         precond=PRECOND_ILU0: block Jacobi's system with a multicolour block ILU(0) of D^-1 A applied from the right, factored
-        anew by every solve (ilu_stats(); FP64 only: not with mixed=True, not on a ghosted context, not in solve_dist).
+        anew by every solve (ilu_stats(); not on a ghosted context, not in solve_dist; the factor is FP64, so not with mixed=True --
+        unless set_option("ilu_factor_bits", 32): the sweeps then stream an fp32 copy of the FP64 factor, with or without
+        mixed=True, and ilu_factor_bits() tells what they streamed).
         precond=PRECOND_ILU0_LOCAL: the rank-local form of solve_dist; without ghosts it returns the bytes of PRECOND_ILU0."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
@@ -368,7 +370,8 @@ class AssemblyContext:
         precond=PRECOND_MULTIGRID needs a communicator with the sized exchange (SolveComm(..., sized=True)) and goes to
         rdc_solve_dist_mg; its peer counts are uploaded with the plan.
         precond=PRECOND_ILU0_LOCAL: block Jacobi between the ranks, the block ILU(0) of every rank's owned square inside it, applied
-        from the right; the exchanges and all-reduces of block Jacobi, fewer iterations (FP64 only: not with mixed=True)."""
+        from the right; the exchanges and all-reduces of block Jacobi, fewer iterations (not with mixed=True, unless set_option("ilu_factor_bits", 32): an fp32 copy
+        of every rank's factor)."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -453,6 +456,13 @@ class AssemblyContext:
         ms, nbytes, ncol = C.c_float(), C.c_int64(), C.c_int32()
         self._ck(self._lib.rdc_solve_ilu_stats(self._h, C.byref(ms), C.byref(nbytes), C.byref(ncol)))
         return ms.value, nbytes.value, ncol.value
+
+    def ilu_factor_bits(self):
+        """rdc_solve_ilu_factor_bits: what the sweeps of the last ILU(0) solve or apply hook streamed, 32 (the fp32 copy of the
+        factor, set_option("ilu_factor_bits", 32)) or 64 (the default, or the fall-back of a factor that does not fit fp32)"""
+        bits = C.c_int32()
+        self._ck(self._lib.rdc_solve_ilu_factor_bits(self._h, C.byref(bits)))
+        return bits.value
 
     def ilu_apply_device(self, in_ptr, out_ptr):
         """rdc_solve_ilu_apply on device addresses (n_owned*nvar doubles each): out = (LU)^-1 in, as the next

@@ -40,8 +40,9 @@ struct Buffers {
   // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
   // send: the send list of a partitioned solve (rdc_solve_dist_plan)
   // mg_gs: the colour lists of every level (first multigrid solve with the Gauss-Seidel smoother)
+  // ilu_f32: the offsets and the floats of the fp32 copy of that factor (first ILU solve or hook with "ilu_factor_bits" = 32; ilu_place_f32)
   // ilu_idx / ilu_val: the lists, and the factor / U_ii^-1 / vectors, of the block ILU(0) (first solve with RDC_PRECOND_ILU0; rdc_solve.h, ilu_place)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -132,6 +133,7 @@ struct rdc_ctx {
   int mg_omega_permille = MG_OMEGA_PERMILLE;   // option "mg_omega": damping of the multigrid smoother, in thousandths
   int mg_smoother = 0;                         // option "mg_smoother": 0 = damped block Jacobi, 1 = multicolour Gauss-Seidel
   int mg_gs_fuse = 1;                          // option "mg_gs_fuse": small levels sweep in one launch (0: one launch per colour everywhere)
+  int ilu_factor_bits = 64;                    // option "ilu_factor_bits": what the ILU(0) sweeps stream, the FP64 factor or its fp32 copy (32)
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call
@@ -725,6 +727,11 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
   if (smoother || !std::strcmp(key, "mg_gs_fuse")) {   // solver settings as well
     if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "%s is 0 or 1, not %d", key, value);
     (smoother ? c->mg_smoother : c->mg_gs_fuse) = value;
+    return RDC_OK;
+  }
+  if (!std::strcmp(key, "ilu_factor_bits")) {   // a solver setting too: every ILU(0) solve and hook reads it
+    if (value != 64 && value != 32) return fail(c, RDC_ERR_INVALID, "ilu_factor_bits is 64 or 32, not %d", value);
+    c->ilu_factor_bits = value;
     return RDC_OK;
   }
   if (!std::strcmp(key, "const_rows")) {   // rdc_const_rows.h: a contract with the caller about the value array, not a tuning knob of a kernel
@@ -1371,6 +1378,23 @@ static int ilu_view(rdc_ctx* c, SolveDev* d) {
     S.ilu_ready = true;
     S.ilu_factored = false;
   }
+  S.ilu.want32 = c->ilu_factor_bits == 32;
+  if (S.ilu.want32 && !S.ilu.val32) {   // the third allocation: the fp32 copy of the factor, from the first call that wants it
+    const std::vector<int64_t> foff = ilu_f32_offsets(P.n_owned, P.bptr.data(), S.ilu_host, P.nvar);
+    MgArena f32;
+    IluDev g;
+    ilu_place_f32(foff, f32, g, [](void*, const void*, size_t) {});   // no base: measures
+    int rc;
+    if ((rc = dev_alloc(c, c->buf.solve.ilu_f32, f32.used))) return rc;
+    f32 = MgArena{(char*)c->buf.solve.ilu_f32.p};
+    hipError_t e = hipSuccess;
+    ilu_place_f32(foff, f32, S.ilu, [&](void* at, const void* list, size_t bytes) { e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream); });
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // foff is a local
+    if (e != hipSuccess) {
+      S.ilu.foff = nullptr; S.ilu.val32 = nullptr;
+      return fail(c, RDC_ERR_HIP, "upload of the offsets of the fp32 ILU(0) factor failed: %s", hipGetErrorString(e));
+    }
+  }
   d->ilu = &S.ilu;
   return RDC_OK;
 }
@@ -1379,8 +1403,16 @@ int rdc_solve_ilu_stats(rdc_ctx* c, float* setup_ms, int64_t* bytes, int32_t* n_
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh || !c->ms.solve.ilu_ready) return fail(c, RDC_ERR_STATE, "no solve with the block ILU(0) preconditioner has run on this mesh");
   if (setup_ms) *setup_ms = c->ms.solve.ilu.setup_ms;
-  if (bytes) *bytes = (int64_t)(c->buf.solve.ilu_idx.bytes + c->buf.solve.ilu_val.bytes);
+  if (bytes) *bytes = (int64_t)(c->buf.solve.ilu_idx.bytes + c->buf.solve.ilu_val.bytes + c->buf.solve.ilu_f32.bytes);
   if (n_colours) *n_colours = c->ms.solve.ilu.n_colours;
+  return RDC_OK;
+}
+
+int rdc_solve_ilu_factor_bits(rdc_ctx* c, int32_t* bits) {
+  if (!c || !bits) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.solve.ilu_ready || !c->ms.solve.ilu.bits)
+    return fail(c, RDC_ERR_STATE, "no solve or apply hook with the block ILU(0) preconditioner has run on this mesh");
+  *bits = c->ms.solve.ilu.bits;
   return RDC_OK;
 }
 
@@ -1475,9 +1507,9 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
     return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
   if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
   if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
-  if (mixed && p->precond == RDC_PRECOND_ILU0)
+  if (mixed && p->precond == RDC_PRECOND_ILU0 && c->ilu_factor_bits != 32)
     return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve, not rdc_solve_mixed", (int)RDC_PRECOND_ILU0);
-  if (mixed && p->precond == RDC_PRECOND_ILU0_LOCAL)
+  if (mixed && p->precond == RDC_PRECOND_ILU0_LOCAL && c->ilu_factor_bits != 32)
     return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve or rdc_solve_dist, "
                 "not rdc_solve_mixed", (int)RDC_PRECOND_ILU0_LOCAL);
   if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, p->precond == RDC_PRECOND_MULTIGRID);
@@ -1761,7 +1793,7 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
   if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
   const bool ilu_local = p->precond == RDC_PRECOND_ILU0_LOCAL;
-  if (ilu_local && mixed)
+  if (ilu_local && mixed && c->ilu_factor_bits != 32)
     return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve_dist with mixed = 0",
                 (int)RDC_PRECOND_ILU0_LOCAL);
   if (sized && c->mg_smoother == 1)

@@ -7,7 +7,8 @@
 // ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).  The multicolour
 // block ILU(0) has its private layout and the factor step of a node among the host+device functions (ilu_value_offset, ilu_find,
 // ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp); on a
-// pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).
+// pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).  The fp32 copy of
+// the factor has a layout of its own beside them (ilu_f32_offset, ilu_f32_offsets, ilu_place_f32; tests/host_solve_ilu_f32_shim.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -236,6 +237,20 @@ RDC_SOLVE_HD int64_t ilu_value_offset(int64_t b0, int nvar, int64_t len, int64_t
   if (p < nl) return base + ((int64_t)a * nl + p) * nvar + b;
   if (p == nl) return base + (int64_t)nvar * nvar * nl + (int64_t)a * nvar + b;
   return base + (int64_t)nvar * nvar * (nl + 1) + ((int64_t)a * (len - nl - 1) + (p - nl - 1)) * nvar + b;
+}
+
+// The fp32 copy of the factor (option "ilu_factor_bits" = 32; DESIGN.md 7.4, "fp32 factor"): what the sweeps stream instead of the
+// FP64 runs above.  It is rounded from them after the factorisation and has a layout and offsets of its own: node i starts at
+// float offset foff[i] and keeps its lower run and, behind it, its upper run, each [var a][block][var b] as above, with every one
+// of the nvar rows of a run padded with zeros to a multiple of 4 floats (f32_row_stride: a row starts 16-byte aligned).  There is
+// no diagonal block (the sweeps read the FP64 U_ii^-1), and on lists with ghost columns the upper run ends at the owned positions:
+// a ghost block has no slot at all.  len and nl as for ilu_value_offset; p != nl.
+RDC_SOLVE_HD int64_t ilu_f32_node_floats(int nvar, int64_t len, int64_t nl) {
+  return (int64_t)nvar * (f32_row_stride(nvar, nl) + f32_row_stride(nvar, len - nl - 1));
+}
+RDC_SOLVE_HD int64_t ilu_f32_offset(int64_t f0, int nvar, int64_t len, int64_t nl, int a, int64_t p, int b) {
+  if (p < nl) return f0 + (int64_t)a * f32_row_stride(nvar, nl) + p * nvar + b;
+  return f0 + (int64_t)nvar * f32_row_stride(nvar, nl) + (int64_t)a * f32_row_stride(nvar, len - nl - 1) + (p - nl - 1) * nvar + b;
 }
 
 // position of column node j in the private row `row` (len entries, ascending in (colour, node id); with ghost columns: the owned
@@ -803,7 +818,12 @@ struct IluDev {
   const int32_t *pcol = nullptr, *nlow = nullptr, *colour = nullptr, *nodes = nullptr, *nown = nullptr;
   const int64_t* cptr_host = nullptr;
   double *val = nullptr, *uinv = nullptr, *ph = nullptr, *sh = nullptr;
-  float setup_ms = 0.0f;   // out: device time of the copy of A^ and the factorisation of the last solve
+  float setup_ms = 0.0f;   // out: device time of the copy of A^ and the factorisation (and the rounding) of the last solve
+  // the fp32 copy of the factor (ilu_place_f32; a third allocation, made at the first solve with "ilu_factor_bits" = 32)
+  const int64_t* foff = nullptr;   // float offset of every node, and the total: n + 1 entries
+  float* val32 = nullptr;
+  bool want32 = false;             // in: the set-up rounds the factor into val32, and the sweeps stream it unless an entry overflowed
+  int bits = 0;                    // out: what the sweeps of the last solve or apply hook streamed, 32 or 64 (0: none has run)
 };
 
 template <class Upload>
@@ -826,6 +846,26 @@ inline void ilu_place(const IluHost& H, int nvar, int64_t n, int64_t blocks, MgA
   g.ph = vec(tail); g.sh = vec(tail);
 }
 
+// foff of the fp32 copy (ilu_f32_node_floats per node, one behind the other): n + 1 entries
+inline std::vector<int64_t> ilu_f32_offsets(int64_t n, const int64_t* bptr, const IluHost& H, int nvar) {
+  std::vector<int64_t> foff((size_t)n + 1, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t len = H.nown.empty() ? bptr[i + 1] - bptr[i] : (int64_t)H.nown[(size_t)i];
+    foff[(size_t)i + 1] = foff[(size_t)i] + ilu_f32_node_floats(nvar, len, H.nlow[(size_t)i]);
+  }
+  return foff;
+}
+
+// The third allocation, measured and placed like the two of ilu_place: the offsets, then the floats (MgArena aligns both)
+template <class Upload>
+inline void ilu_place_f32(const std::vector<int64_t>& foff, MgArena& f32, IluDev& g, Upload&& upload) {
+  const size_t bytes = foff.size() * sizeof(int64_t);
+  void* at = f32.take(bytes);
+  if (at) upload(at, (const void*)foff.data(), bytes);
+  g.foff = (const int64_t*)at;
+  g.val32 = (float*)f32.take((size_t)std::max<int64_t>(foff.back(), 1) * sizeof(float));
+}
+
 // ---- the iteration's scalars, its launch shapes and the layout of its work buffer: host code without HIP, so that a CPU build
 // can test the layout (tests/host_solve_dist_shim.cpp) ----
 
@@ -836,7 +876,7 @@ struct SolveScal {
   int32_t flag;                            // bit 0: alpha / omega / a norm is zero or not finite; bit 1: rho == 0
   int32_t bad_blocks;
   int32_t f32_overflow;                    // blocks of the fp32 copy that hold an entry which is not finite in fp32 (k_scale_f32)
-  int32_t _pad;
+  int32_t ilu_overflow;                    // entries of the ILU(0) factor that are finite in FP64 and not in fp32 (k_ilu_round_f32); this rank's own
 };
 
 constexpr int SPMV_NODES = 16;        // nodes per workgroup of k_spmv (256 threads)

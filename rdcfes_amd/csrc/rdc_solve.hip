@@ -999,6 +999,158 @@ __global__ __launch_bounds__(256) void k_ilu_bwd_owned(const int64_t* __restrict
   ilu_bwd_body<NV, true>(bptr, pcol, nlow, nown, fval, uinv, z, list, count);
 }
 
+// ---- the fp32 copy of the factor (option "ilu_factor_bits" = 32; layout: rdc_solve.h, ilu_f32_offset) ----
+//
+// The factorisation stays what it is; k_ilu_round_f32 rounds its lower and upper blocks into the copy, and the sweeps below stream
+// that instead of the FP64 runs: 8 lanes per node and 16-byte loads as k_spmv_f32, every value converted to double and fed to an
+// fma, so z, the sums and the U_ii^-1 epilogue are FP64.  A lane adds its own entries in ascending order, then a fixed butterfly.
+
+// The copy of every owned node from the factor: a lane takes the positions p = lane, lane + 8, ... of the node's runs (nown: its
+// owned positions, on lists with ghost columns; null: the whole row), skips the diagonal block, and stores the zero padding of
+// the rows of both runs.  Counts the entries that are finite in FP64 and not in fp32: the sweeps then stay with the FP64 factor.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_round_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ nlow,
+                                                       const int32_t* __restrict__ nown, const double* __restrict__ fval,
+                                                       const int64_t* __restrict__ foff, int64_t n_owned, float* __restrict__ val32,
+                                                       SolveScal* __restrict__ scal) {
+  const int lane = threadIdx.x & (F32_LANES - 1);
+  const int64_t node = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  if (node >= n_owned) return;
+  const int64_t b0 = bptr[node], len = nown ? (int64_t)nown[node] : bptr[node + 1] - b0, nl = nlow[node], f0 = foff[node];
+  int bad = 0;
+  for (int64_t p = lane; p < len; p += F32_LANES) {
+    if (p == nl) continue;
+#pragma unroll
+    for (int a = 0; a < NV; a++)
+#pragma unroll
+      for (int b = 0; b < NV; b++) {
+        const double v = fval[ilu_value_offset(b0, NV, len, nl, a, p, b)];
+        const float f = (float)v;
+        bad += finite_d(v) && !solve_finite_f32(f);
+        val32[ilu_f32_offset(f0, NV, len, nl, a, p, b)] = f;
+      }
+  }
+  const int64_t nup = len - nl - 1;
+  const int64_t sl = f32_row_stride(NV, nl), su = f32_row_stride(NV, nup);
+  if (lane < sl - nl * NV)   // at most 3 padding floats per row
+#pragma unroll
+    for (int a = 0; a < NV; a++) val32[f0 + a * sl + nl * NV + lane] = 0.0f;
+  if (lane < su - nup * NV)
+#pragma unroll
+    for (int a = 0; a < NV; a++) val32[f0 + NV * sl + a * su + nup * NV + lane] = 0.0f;
+  if (bad) atomicAdd(&scal->ilu_overflow, bad);
+}
+
+// ilu_run_product on a run of the fp32 copy, in all 8 lanes: vrow holds NV rows of stride f32_row_stride(NV, blocks), L = blocks *
+// NV of them entries.  The loop is that of k_spmv_f32: every load is unconditional, a position past the run's end re-reads the
+// run's last column and is zeroed afterwards, and the next step's columns are requested a step ahead.
+template <int NV>
+__device__ __forceinline__ void ilu_run_product_f32(const float* __restrict__ vrow, int L, const int32_t* __restrict__ cols, const double* x,
+                                                    int lane, double (&acc)[NV]) {
+#pragma unroll
+  for (int a = 0; a < NV; a++) acc[a] = 0.0;
+  if (L > 0) {
+    const int Lp = (L + 3) & ~3;
+    auto columns = [&](int j, int32_t (&cn)[4], int (&cb)[4]) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const int jj = min(j + e, L - 1), k = jj / NV;
+        cb[e] = jj - k * NV;
+        cn[e] = cols[k];
+      }
+    };
+    int32_t cn[4], nn[4];
+    int cb[4], nb[4];
+    columns(4 * lane, cn, cb);
+    for (int j = 4 * lane; j < Lp; j += 4 * F32_LANES) {
+      columns(j + 4 * F32_LANES, nn, nb);
+      f32x4 v[NV];
+#pragma unroll
+      for (int a = 0; a < NV; a++) v[a] = __builtin_nontemporal_load((const f32x4*)(vrow + (int64_t)a * Lp + j));
+      double xv[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) xv[e] = x[(int64_t)cn[e] * NV + cb[e]];
+      __builtin_amdgcn_sched_barrier(0);   // keep the three groups of loads ahead of the arithmetic
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        xv[e] = j + e < L ? xv[e] : 0.0;
+        cn[e] = nn[e];
+        cb[e] = nb[e];
+      }
+#pragma unroll
+      for (int a = 0; a < NV; a++) {
+        acc[a] = fma((double)v[a].x, xv[0], acc[a]);
+        acc[a] = fma((double)v[a].y, xv[1], acc[a]);
+        acc[a] = fma((double)v[a].z, xv[2], acc[a]);
+        acc[a] = fma((double)v[a].w, xv[3], acc[a]);
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NV; a++)
+#pragma unroll
+    for (int off = F32_LANES / 2; off >= 1; off >>= 1) acc[a] += __shfl_xor(acc[a], off, F32_LANES);
+}
+
+// k_ilu_fwd on the fp32 copy (serves lists with ghost columns as it is: the lower run is the node's first, whatever follows)
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_fwd_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                     const int32_t* __restrict__ nlow, const int64_t* __restrict__ foff,
+                                                     const float* __restrict__ val32, const double* __restrict__ y, double* z,
+                                                     const int32_t* __restrict__ list, int64_t count) {
+  const int lane = threadIdx.x & (F32_LANES - 1);
+  const int64_t at = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  const bool live = at < count;
+  const int64_t node = live ? list[at] : 0;
+  double acc[NV];
+  ilu_run_product_f32<NV>(val32 + foff[node], live ? nlow[node] * NV : 0, pcol + bptr[node], z, lane, acc);
+  double t = acc[0];
+#pragma unroll
+  for (int a = 1; a < NV; a++) t = lane == a ? acc[a] : t;
+  if (live && lane < NV) z[node * NV + lane] = y[node * NV + lane] - t;
+}
+
+// ilu_bwd_body on the fp32 copy: the upper run lies behind the NV padded rows of the lower one; U_ii^-1 is the FP64 array
+template <int NV, bool OWNED>
+__device__ __forceinline__ void ilu_bwd_f32_body(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                 const int32_t* __restrict__ nlow, const int32_t* __restrict__ nown,
+                                                 const int64_t* __restrict__ foff, const float* __restrict__ val32,
+                                                 const double* __restrict__ uinv, double* z, const int32_t* __restrict__ list,
+                                                 int64_t count) {
+  const int lane = threadIdx.x & (F32_LANES - 1);
+  const int64_t at = (int64_t)blockIdx.x * F32_NODES + (threadIdx.x / F32_LANES);
+  const bool live = at < count;
+  const int64_t node = live ? list[at] : 0;
+  const int64_t b0 = bptr[node], len = OWNED ? (int64_t)nown[node] : bptr[node + 1] - b0, nl = nlow[node];
+  double acc[NV];
+  ilu_run_product_f32<NV>(val32 + foff[node] + NV * f32_row_stride(NV, nl), live ? (int)(len - nl - 1) * NV : 0, pcol + b0 + nl + 1, z, lane,
+                          acc);
+  if (live && lane < NV) {
+    const double* __restrict__ urow = uinv + (node * NV + lane) * NV;
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) t = fma(urow[q], z[node * NV + q] - acc[q], t);
+    z[node * NV + lane] = t;
+  }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_bwd_f32(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                     const int32_t* __restrict__ nlow, const int64_t* __restrict__ foff,
+                                                     const float* __restrict__ val32, const double* __restrict__ uinv, double* z,
+                                                     const int32_t* __restrict__ list, int64_t count) {
+  ilu_bwd_f32_body<NV, false>(bptr, pcol, nlow, nullptr, foff, val32, uinv, z, list, count);
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_ilu_bwd_f32_owned(const int64_t* __restrict__ bptr, const int32_t* __restrict__ pcol,
+                                                           const int32_t* __restrict__ nlow, const int32_t* __restrict__ nown,
+                                                           const int64_t* __restrict__ foff, const float* __restrict__ val32,
+                                                           const double* __restrict__ uinv, double* z, const int32_t* __restrict__ list,
+                                                           int64_t count) {
+  ilu_bwd_f32_body<NV, true>(bptr, pcol, nlow, nown, foff, val32, uinv, z, list, count);
+}
+
 // First use of every kernel instantiation. A code object lists template instantiations by first use; this list keeps the order
 // they have had since each was added, whatever order the launch code below uses them in, so that the device assembly of two
 // revisions can be compared byte for byte.
@@ -1011,6 +1163,8 @@ __global__ __launch_bounds__(256) void k_ilu_bwd_owned(const int64_t* __restrict
   (const void*)k_gs_fused<NV, false>, (const void*)k_gs_f32_fused<NV>
 #define ILU_KERNELS_OF(NV) (const void*)k_ilu_copy<NV>, (const void*)k_ilu_factor<NV>, (const void*)k_ilu_fwd<NV>, (const void*)k_ilu_bwd<NV>
 #define ILU_OWNED_KERNELS_OF(NV) (const void*)k_ilu_copy_owned<NV>, (const void*)k_ilu_factor_owned<NV>, (const void*)k_ilu_bwd_owned<NV>
+#define ILU_F32_KERNELS_OF(NV)                                                                                                  \
+  (const void*)k_ilu_round_f32<NV>, (const void*)k_ilu_fwd_f32<NV>, (const void*)k_ilu_bwd_f32<NV>, (const void*)k_ilu_bwd_f32_owned<NV>
 [[maybe_unused]] const void* const KERNEL_ORDER[] = {
     (const void*)k_spmv<3, 1>, (const void*)k_spmv<3, 0>, (const void*)k_spmv<5, 1>, (const void*)k_spmv<5, 0>,
     (const void*)k_spmv_f32<3, 1>, (const void*)k_spmv_f32<3, 0>, (const void*)k_spmv_f32<5, 1>, (const void*)k_spmv_f32<5, 0>,
@@ -1019,11 +1173,13 @@ __global__ __launch_bounds__(256) void k_ilu_bwd_owned(const int64_t* __restrict
     (const void*)k_reduce, (const void*)k_advance, (const void*)k_halo_pack<3>, (const void*)k_halo_pack<5>,
     (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
     (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>,
-    GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5), ILU_OWNED_KERNELS_OF(3), ILU_OWNED_KERNELS_OF(5)};
+    GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5), ILU_OWNED_KERNELS_OF(3), ILU_OWNED_KERNELS_OF(5),
+    ILU_F32_KERNELS_OF(3), ILU_F32_KERNELS_OF(5)};
 #undef KERNELS_OF
 #undef GS_KERNELS_OF
 #undef ILU_KERNELS_OF
 #undef ILU_OWNED_KERNELS_OF
+#undef ILU_F32_KERNELS_OF
 
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
@@ -1314,24 +1470,38 @@ hipError_t ilu_setup(const SolveDev& d, const Work& w) {
       hipLaunchKernelGGL((k_ilu_factor<NV>), cgrid, block, 0, d.stream, d.bptr, g.pcol, g.nlow, g.colour, g.val, g.uinv, g.nodes + c0, count,
                          w.scal);
   }
+  if (g.want32)   // the fp32 copy the sweeps stream ("ilu_factor_bits" = 32); its overflow count travels in the record of bad_blocks
+    hipLaunchKernelGGL((k_ilu_round_f32<NV>), dim3((unsigned)op_blocks(d.n_owned, F32)), block, 0, d.stream, d.bptr, g.nlow, g.nown,
+                       (const double*)g.val, g.foff, d.n_owned, g.val32, w.scal);
   return hipGetLastError();
 }
 
 // out = (LU)^-1 in: forward over the colours ascending, backward descending, one launch per colour each way (colour 0 forward is the
 // copy of `in`, since out is another vector).  Enqueues only; a fixed linear operator for fixed values.  Writes the owned entries
 // of `out` and needs no communication: across ranks the factor is rank-local, and the ghost tail of `out` is filled by the exchange
-// of the operator application that follows.
+// of the operator application that follows.  f32: the sweeps stream the fp32 copy of the factor (the same launches, 8 lanes per node).
 template <int NV>
-hipError_t ilu_apply(const SolveDev& d, const double* in, double* out) {
+hipError_t ilu_apply(const SolveDev& d, const double* in, double* out, bool f32) {
   const IluDev& g = *d.ilu;
+  const Form lanes = f32 ? F32 : SCALED;
   for (int c = 0; c < g.n_colours; c++) {
     const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
-    hipLaunchKernelGGL((k_ilu_fwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
-                       (const double*)g.val, in, out, g.nodes + c0, count);
+    if (f32)
+      hipLaunchKernelGGL((k_ilu_fwd_f32<NV>), dim3((unsigned)op_blocks(count, lanes)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.foff,
+                         (const float*)g.val32, in, out, g.nodes + c0, count);
+    else
+      hipLaunchKernelGGL((k_ilu_fwd<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
+                         (const double*)g.val, in, out, g.nodes + c0, count);
   }
   for (int c = g.n_colours - 1; c >= 0; c--) {
     const int64_t c0 = g.cptr_host[c], count = g.cptr_host[c + 1] - c0;
-    if (g.nown)
+    if (f32 && g.nown)
+      hipLaunchKernelGGL((k_ilu_bwd_f32_owned<NV>), dim3((unsigned)op_blocks(count, lanes)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow,
+                         g.nown, g.foff, (const float*)g.val32, (const double*)g.uinv, out, g.nodes + c0, count);
+    else if (f32)
+      hipLaunchKernelGGL((k_ilu_bwd_f32<NV>), dim3((unsigned)op_blocks(count, lanes)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.foff,
+                         (const float*)g.val32, (const double*)g.uinv, out, g.nodes + c0, count);
+    else if (g.nown)
       hipLaunchKernelGGL((k_ilu_bwd_owned<NV>), dim3((unsigned)op_blocks(count, SCALED)), dim3(256), 0, d.stream, d.bptr, g.pcol, g.nlow, g.nown,
                          (const double*)g.val, (const double*)g.uinv, out, g.nodes + c0, count);
     else
@@ -1348,7 +1518,7 @@ enum Right { RIGHT_NONE, RIGHT_MG, RIGHT_ILU };
 
 template <int NV>
 hipError_t right_apply(const SolveDev& d, const Work& w, Form form, Right right, const double* in, double* out) {
-  return right == RIGHT_MG ? mg_cycle<NV>(d, w, form, in, out) : ilu_apply<NV>(d, in, out);
+  return right == RIGHT_MG ? mg_cycle<NV>(d, w, form, in, out) : ilu_apply<NV>(d, in, out, d.ilu->bits == 32);
 }
 
 template <int NV>
@@ -1395,6 +1565,7 @@ hipError_t prologue(const SolveDev& d, const Work& w, int precond, bool mixed, R
   SOLVE_HIP(read());
   s->bad_blocks = d.host_rec->bad_blocks;
   s->form = mixed && d.host_rec->f32_overflow == 0 ? F32 : SCALED;   // an entry of D^-1 A does not fit fp32: iterate on the FP64 values
+  if (ilu) d.ilu->bits = d.ilu->want32 && d.host_rec->ilu_overflow == 0 ? 32 : 64;   // ... of the factor: the FP64 sweeps (this rank's own choice)
   return hipSuccess;
 }
 
@@ -1493,7 +1664,7 @@ hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int
     SOLVE_HIP(prologue<NV>(d, w, (int)RDC_PRECOND_ILU0, false, [&] { return read_record(d, w); }, &start));
     *bad_blocks = start.bad_blocks;
     if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is applied, `out` stays what it was
-    SOLVE_HIP(ilu_apply<NV>(d, in, out));
+    SOLVE_HIP(ilu_apply<NV>(d, in, out, d.ilu->bits == 32));
     return hipStreamSynchronize(d.stream);
   });
 }

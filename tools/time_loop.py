@@ -2,7 +2,7 @@
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
     python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
-                              [--ab [precond|precision|dist|smoother]] [--dump DIR]
+                              [--ilu-bits 32|64] [--ab [precond|precision|dist|smoother|ilu_bits]] [--dump DIR]
     python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--ab precond]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
@@ -23,8 +23,11 @@ the partitioned entry is rdc_solve_dist_mg, whose cycle adds the sized callbacks
 (multigrid) in the order damped Jacobi, Gauss-Seidel, Gauss-Seidel, damped Jacobi.  --smoother 1 is the multicolour Gauss-Seidel
 smoother of the cycle (option "mg_smoother"; single partition, --precond 3), --gs-fuse 0 gives every level one launch per colour
 (option "mg_gs_fuse"); every record of a multigrid solve has the smoother, with Gauss-Seidel the colours per level, and the
-kernel launches of one cycle (counted from the level sizes and colours: tools/time_loop.py, cycle_launches).  --dump writes the
-state after the last step as DIR/state.npy (+ conn, xyz).
+kernel launches of one cycle (counted from the level sizes and colours: tools/time_loop.py, cycle_launches).  --ilu-bits 32
+(--precond 4 or 5, with or without --mixed and --ranks) sets the option "ilu_factor_bits": the sweeps of the ILU(0) stream an fp32
+copy of the FP64 factor, and every record has ilu_factor_bits, what they streamed; --ab ilu_bits runs the loop in the order 64, 32,
+32, 64 (with --mixed the legs at 64 run on the FP64 operator, since the FP64 factor has no mixed form: they are today's ILU(0),
+the legs at 32 the fp32 operator with the fp32 factor).  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
@@ -77,7 +80,8 @@ def cycle_launches(levels, colours=None, fuse=True, fused_nodes=512):
     return 1 + 3 * last + sum(smooth(l) for l in range(last + 1))
 
 
-def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None, smoother=0, gs_fuse=1):
+def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None, smoother=0, gs_fuse=1,
+        ilu_bits=64):
     """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
     on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there).
     comm: a halo.SolveComm -- the solve is solve_dist across its ranks (the background shares are then those of the local nodes)."""
@@ -89,6 +93,8 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
     if precond == 3 and comm is None:   # across partitions the smoother is damped Jacobi, and the option would be refused
         ctx.set_option("mg_smoother", smoother)
         ctx.set_option("mg_gs_fuse", gs_fuse)
+    if precond in (4, 5):
+        ctx.set_option("ilu_factor_bits", ilu_bits)
     out = []
     for k in range(steps):
         ctx.assemble_pihna(params)
@@ -118,7 +124,7 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
                     out[-1].update(mg_colours=colours, mg_gs_fuse=gs_fuse)
         if precond in (4, 5):
             setup_ms, nbytes, colours = ctx.ilu_stats()
-            out[-1].update(ilu_setup_ms=setup_ms, ilu_bytes=nbytes, ilu_colours=colours)
+            out[-1].update(ilu_setup_ms=setup_ms, ilu_bytes=nbytes, ilu_colours=colours, ilu_factor_bits=ctx.ilu_factor_bits())
     return out
 
 
@@ -159,11 +165,11 @@ def rank_main(rank, world, port, a):
                     ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
                     if rank == 0:
                         print(json.dumps(dict(precond=precond)), flush=True)
-                for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=a.mixed, comm=comm):
+                for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=a.mixed, comm=comm, ilu_bits=a.ilu_bits):
                     if rank == 0:          # every figure of the solve is global and the same on every rank
                         keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
                         keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if precond == 3 else ()     # rank 0's own levels
-                        keep += ("ilu_setup_ms", "ilu_bytes", "ilu_colours") if precond == 5 else ()        # rank 0's own factor
+                        keep += ("ilu_setup_ms", "ilu_bytes", "ilu_colours", "ilu_factor_bits") if precond == 5 else ()        # rank 0's own factor
                         print(json.dumps({k: rec[k] for k in keep}), flush=True)
         dist.barrier()
     finally:
@@ -180,7 +186,8 @@ def main():
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--smoother", type=int, choices=(0, 1), default=0)
     ap.add_argument("--gs-fuse", type=int, choices=(0, 1), default=1)
-    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist", "smoother"), default=None)
+    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist", "smoother", "ilu_bits"), default=None)
+    ap.add_argument("--ilu-bits", type=int, choices=(32, 64), default=64)
     ap.add_argument("--dump", default=None)
     ap.add_argument("--ranks", type=int, default=1)
     ap.add_argument("--backend", choices=("gloo", "nccl"), default="gloo")
@@ -189,10 +196,13 @@ def main():
         a.precond = 3
     if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or a.ab == "dist"):
         ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
-    if a.precond == 4 and (a.mixed or a.ranks > 1 or a.ab in ("precision", "dist")):
-        ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only (across ranks: --precond 5)")
-    if a.precond == 5 and (a.mixed or a.ab == "precision"):
-        ap.error("the rank-local block ILU(0) (--precond 5) is FP64 only")
+    f32 = a.ilu_bits == 32 or a.ab == "ilu_bits"
+    if (f32 or a.ab == "ilu_bits") and a.precond not in (4, 5):
+        ap.error("--ilu-bits and --ab ilu_bits belong to the block ILU(0): --precond 4 or 5")
+    if a.precond == 4 and ((a.mixed and not f32) or a.ranks > 1 or a.ab in ("precision", "dist")):
+        ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only (across ranks: --precond 5; --mixed: --ilu-bits 32)")
+    if a.precond == 5 and not f32 and (a.mixed or a.ab == "precision"):
+        ap.error("the rank-local block ILU(0) (--precond 5) is FP64 only, unless --ilu-bits 32")
     if a.ranks > 1 and a.ab not in (None, "precond"):
         ap.error("--ranks takes --ab precond only")
     if a.ranks > 1 and a.ab == "precond" and a.mixed:
@@ -214,28 +224,30 @@ def main():
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
-        runs = [(a.precond, a.mixed, False, a.smoother)]
+        runs = [(a.precond, a.mixed, False, a.smoother, a.ilu_bits)]
         if a.ab == "precond":
-            runs = [(pc, a.mixed, False, a.smoother) for pc in ((2, 3, 3, 2) if a.mixed else (2, 3, 4, 4, 3, 2))]
+            runs = [(pc, a.mixed, False, a.smoother, a.ilu_bits) for pc in ((2, 3, 3, 2) if a.mixed and not f32 else (2, 3, 4, 4, 3, 2))]
         elif a.ab == "precision":
-            runs = [(a.precond, mixed, False, a.smoother) for mixed in (False, True, True, False)]
+            runs = [(a.precond, mixed, False, a.smoother, a.ilu_bits) for mixed in (False, True, True, False)]
         elif a.ab == "dist":
-            runs = [(a.precond, a.mixed, d, 0) for d in (False, True, True, False)]
+            runs = [(a.precond, a.mixed, d, 0, a.ilu_bits) for d in (False, True, True, False)]
         elif a.ab == "smoother":
-            runs = [(3, a.mixed, False, sm) for sm in (0, 1, 1, 0)]
+            runs = [(3, a.mixed, False, sm, 64) for sm in (0, 1, 1, 0)]
+        elif a.ab == "ilu_bits":
+            runs = [(a.precond, a.mixed and bits == 32, False, 0, bits) for bits in (64, 32, 32, 64)]
         comm = None
         if a.ab == "dist":      # world size 1: no peers, no process group
             from rdcfes_amd import SolveComm, partition
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
             comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3)
-        for precond, mixed, dist_entry, smoother in runs:
+        for precond, mixed, dist_entry, smoother, ilu_bits in runs:
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
-                                  smoother=smoother if precond == 3 else None,
+                                  smoother=smoother if precond == 3 else None, ilu_bits=ilu_bits if precond in (4, 5) else None,
                                   entry=("rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") + ", world size 1" if dist_entry else "rdc_solve")))
             for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None,
-                           smoother=smoother, gs_fuse=a.gs_fuse):
+                           smoother=smoother, gs_fuse=a.gs_fuse, ilu_bits=ilu_bits):
                 print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
