@@ -371,8 +371,8 @@ typedef struct rdc_solve_params {
 
 typedef struct rdc_solve_info {
   int32_t reason;        /* RDC_SOLVE_* */
-  int32_t iterations;    /* BiCGStab iterations = pairs of matrix-vector products, restarts included */
-  int32_t restarts;
+  int32_t iterations;    /* BiCGStab iterations = pairs of matrix-vector products, restarts included; with "solve_method" = 1 (below): Arnoldi steps = operator applications inside the GMRES cycles, bounded by max_its */
+  int32_t restarts;      /* BiCGStab: recomputations of the true residual that did not end the solve; GMRES: cycles begun after the first */
   int32_t bad_blocks;    /* diagonal blocks the preconditioner could not invert */
   double rhs_norm;       /* ||D^-1 b||_2 */
   double residual_norm;  /* TRUE ||D^-1 (b - A x)||_2 of the returned x: the quantity the stopping test is about */
@@ -581,6 +581,40 @@ int rdc_solve_ilu_local_apply(rdc_ctx* ctx, const double* d_in, double* d_out);
  * rdc_solve_ilu_download.  uinv = U_ii^-1, n_owned * nvar^2 doubles, row-major per node.  Either pointer may be NULL.
  * RDC_ERR_STATE if no producer has run on this mesh. */
 int rdc_solve_ilu_local_download(rdc_ctx* ctx, double* val, double* uinv);
+
+/* ---- restarted GMRES(m) next to BiCGStab (rdc_solve and rdc_solve_mixed; additive: RDC_ABI_VERSION stays 3) ----
+ * Three solver settings of rdc_set_option choose the Krylov method of the two single-partition entries:
+ *   "solve_method"   0 = BiCGStab (the default: everything above), 1 = GMRES; any other value is RDC_ERR_INVALID
+ *   "gmres_restart"  1 .. 128, default 30 (PETSc's default); outside that range RDC_ERR_INVALID
+ *   "gmres_refine"   0 = one classical Gram-Schmidt pass per step (PETSc's default), 1 = always a second pass (CGS2)
+ * With "solve_method" = 1 the two entries run right-preconditioned GMRES(m) on the same system D^-1 A x = D^-1 b (D by precond 0, 1,
+ * 2; block Jacobi for 3, 4, 5) with the same right preconditioner M (none, the multigrid cycle, the ILU(0) sweeps): what PETSc's
+ * KSPGMRES does by default.  The stopping test, rhs_scale, the reasons and every guarantee above carry over: RDC_SOLVE_BAD_DIAGONAL
+ * leaves x untouched, b = 0 gives x = 0, no NaN or inf is ever written into x, and residual_norm is the TRUE ||D^-1 (b - A x)|| of
+ * the returned x: every cycle starts from, and ends with, the FP64 residual of x, which alone decides.  iterations counts Arnoldi
+ * steps (a cycle always takes at least one), restarts the cycles begun after the first.  RDC_SOLVE_BREAKDOWN: the operator is
+ * singular on the Krylov space.  Deterministic: no floating-point atomics, two solves return the same bytes.
+ * The state (restart + 1 basis vectors of n_owned * nvar doubles, and a few KB) is an allocation of its own, made at the first GMRES
+ * solve on a mesh, remade when "gmres_restart" grows, freed with the mesh; RDC_ERR_ALLOC with the byte count if it cannot be made.
+ * With "solve_method" = 0 nothing of it is allocated, launched or read.
+ * rdc_solve_dist and rdc_solve_dist_mg return RDC_ERR_UNSUPPORTED under "solve_method" = 1, before any callback is called and with
+ * x untouched: allreduce_sum carries at most 8 doubles, and a GMRES step sums up to restart + 1. */
+/* The last GMRES solve on this mesh: *restart = the restart length it ran with, *basis_bytes = device bytes of its basis
+ * ((restart + 1) * n_owned * nvar * 8), *cycles = the cycles it began (restarts + 1; 0 if it needed no step).  Any pointer may be
+ * NULL.  RDC_ERR_STATE before any GMRES solve on this mesh. */
+int rdc_solve_gmres_stats(rdc_ctx* ctx, int32_t* restart, int64_t* basis_bytes, int32_t* cycles);
+/* Test hook, read-only like rdc_solve_mg_apply: the Arnoldi process itself, which a converged solve cannot show (the true residual
+ * at every restart repairs a process that is subtly wrong, at the price of iterations).  The call first does what a solve with
+ * `precond` (mixed != 0: rdc_solve_mixed) does before its first iteration, then sets v_0 = d_v0 / ||d_v0|| and runs `steps` Arnoldi
+ * steps, 1 <= steps <= "gmres_restart", with exactly the kernels and the host loop of a cycle; "gmres_refine" is honoured.
+ * d_v0: DEVICE, n_owned*nvar doubles.  d_V: DEVICE, receives the *steps_done + 1 basis vectors, n_owned*nvar doubles each (room for
+ * steps + 1).  H: HOST, (restart + 1) x restart doubles, column-major: the raw Hessenberg matrix before any rotation, zeros where no
+ * entry was computed.  *steps_done < steps if h_{j+1,j} = 0 (that step counts; the last vector is then the zero remainder) or a
+ * step was not finite (it does not count).  RDC_ERR_UNSUPPORTED on a context with ghost nodes; RDC_ERR_INVALID for a null pointer,
+ * steps out of range, an unknown precond, or diagonal blocks that cannot be inverted (nothing is run).  Never modifies the CSR
+ * values or the rhs; works whatever "solve_method" is.  Synchronises. */
+int rdc_solve_gmres_arnoldi(rdc_ctx* ctx, int precond, int mixed, const double* d_v0, int steps, double* d_V, double* H,
+                            int32_t* steps_done);
 
 /* ---- partitioned solve (additive: RDC_ABI_VERSION stays 3): the BiCGStab of rdc_solve / rdc_solve_mixed across ranks, on
  * contexts with one ghost layer (n_owned < n_nodes; owned nodes first, ghosts behind them).  Every rank calls with its own

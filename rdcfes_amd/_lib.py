@@ -75,6 +75,8 @@ SIGNATURES = {
     "rdc_solve_ilu_download": (C.c_int, [ctx_p, P(dbl), P(dbl)]),
     "rdc_solve_ilu_local_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p]),
     "rdc_solve_ilu_local_download": (C.c_int, [ctx_p, P(dbl), P(dbl)]),
+    "rdc_solve_gmres_stats": (C.c_int, [ctx_p, P(C.c_int32), P(C.c_int64), P(C.c_int32)]),
+    "rdc_solve_gmres_arnoldi": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, P(dbl), P(C.c_int32)]),
     "rdc_solve_dist_plan": (C.c_int, [ctx_p, i64, P(i32)]),
     "rdc_solve_dist": (C.c_int, [ctx_p, P(SolveParams), P(SolveCommStruct), C.c_int, C.c_void_p, P(SolveInfo)]),
     "rdc_solve_dist_plan_peers": (C.c_int, [ctx_p, i32, P(i64), P(i64)]),

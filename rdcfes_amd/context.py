@@ -80,6 +80,8 @@ class AssemblyContext:
 
     def set_option(self, key, value):
         self._ck(self._lib.rdc_set_option(self._h, key.encode(), int(value)))
+        if key == "gmres_restart":
+            self._gmres_restart = int(value)   # the shape of the Hessenberg matrix gmres_arnoldi returns
 
     def set_tet4_cluster(self, mode):
         """rdc_tet4_cluster_mode: 0 = off (default), 1 = the TET4 cluster kernel where the mesh has no pair lists (Gmsh and
@@ -343,7 +345,11 @@ class AssemblyContext:
         anew by every solve (ilu_stats(); not on a ghosted context, not in solve_dist; the factor is FP64, so not with mixed=True --
         unless set_option("ilu_factor_bits", 32): the sweeps then stream an fp32 copy of the FP64 factor, with or without
         mixed=True, and ilu_factor_bits() tells what they streamed).
-        precond=PRECOND_ILU0_LOCAL: the rank-local form of solve_dist; without ghosts it returns the bytes of PRECOND_ILU0."""
+        precond=PRECOND_ILU0_LOCAL: the rank-local form of solve_dist; without ghosts it returns the bytes of PRECOND_ILU0.
+        set_option("solve_method", 1): right-preconditioned restarted GMRES(m) in place of BiCGStab, on the same system with the
+        same preconditioners and stopping test (m: set_option("gmres_restart", 1 .. 128), default 30; set_option("gmres_refine", 1):
+        a second Gram-Schmidt pass per step).  info.iterations then counts Arnoldi steps, info.restarts the cycles after the first;
+        gmres_stats() tells what the basis costs.  Default 0 = BiCGStab; not in solve_dist."""
         if (x is None) == (field is None):
             raise ValueError("give either a device address or field=")
         if field is not None:
@@ -450,6 +456,37 @@ class AssemblyContext:
         dinv = np.empty((n, nv, nv), dtype=np.float64)
         self._ck(self._lib.rdc_solve_mg_level_download(self._h, int(level), _dp(val) if level else None, _dp(dinv)))
         return val, dinv
+
+    def gmres_stats(self):
+        """rdc_solve_gmres_stats -> (restart length, device bytes of the basis, cycles) of the last GMRES solve on this mesh"""
+        m, nbytes, cycles = C.c_int32(), C.c_int64(), C.c_int32()
+        self._ck(self._lib.rdc_solve_gmres_stats(self._h, C.byref(m), C.byref(nbytes), C.byref(cycles)))
+        return m.value, nbytes.value, cycles.value
+
+    def gmres_arnoldi_device(self, v0_ptr, steps, precond, V_ptr, H, mixed=False):
+        """rdc_solve_gmres_arnoldi on device addresses: v0 (n_owned*nvar doubles) in, the basis vectors into V (room for steps + 1),
+        the raw Hessenberg matrix into the host array H ((restart + 1) x restart, column-major).  Returns the steps done.  A test hook."""
+        done = C.c_int32()
+        self._ck(self._lib.rdc_solve_gmres_arnoldi(self._h, int(precond), 1 if mixed else 0, C.c_void_p(int(v0_ptr)), int(steps),
+                                                   C.c_void_p(int(V_ptr)), _dp(H), C.byref(done)))
+        return done.value
+
+    def gmres_arnoldi(self, v0, steps, precond, mixed=False):
+        """numpy in, numpy out (tests): (V [steps_done + 1][n], H [restart + 1][restart]) of `steps` Arnoldi steps from v0 / ||v0||
+        as a GMRES solve with `precond` would take them; restart = the option "gmres_restart" as this wrapper last set it"""
+        import torch
+        v0 = np.ascontiguousarray(v0, dtype=np.float64).reshape(-1)
+        n = self.n_owned * self.nvar
+        if v0.size != n:
+            raise ValueError("v0 must have n_owned * nvar entries")
+        restart = getattr(self, "_gmres_restart", 30)
+        dev = torch.device("cuda", self.device)
+        vd = torch.from_numpy(v0).to(dev)
+        Vd = torch.zeros((int(steps) + 1) * n, dtype=torch.float64, device=dev)
+        H = np.zeros((restart, restart + 1), dtype=np.float64)   # column-major (restart + 1) x restart
+        torch.cuda.synchronize(dev)
+        done = self.gmres_arnoldi_device(vd.data_ptr(), steps, precond, Vd.data_ptr(), H, mixed)
+        return Vd.cpu().numpy().reshape(int(steps) + 1, n)[:done + 1], H.T.copy()
 
     def ilu_stats(self):
         """(device ms the last ILU(0) solve spent on the copy of D^-1 A and its factorisation, device bytes the factor holds, colours)"""

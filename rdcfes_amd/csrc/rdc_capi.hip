@@ -42,7 +42,8 @@ struct Buffers {
   // mg_gs: the colour lists of every level (first multigrid solve with the Gauss-Seidel smoother)
   // ilu_f32: the offsets and the floats of the fp32 copy of that factor (first ILU solve or hook with "ilu_factor_bits" = 32; ilu_place_f32)
   // ilu_idx / ilu_val: the lists, and the factor / U_ii^-1 / vectors, of the block ILU(0) (first solve with RDC_PRECOND_ILU0; rdc_solve.h, ilu_place)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
+  // gmres: the state of restarted GMRES (first solve with "solve_method" = 1, or the Arnoldi hook; rdc_solve.h, gmres_carve)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32, gmres; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -74,6 +75,10 @@ struct SolveState {
   std::vector<int32_t> send_nodes;   // host copy of the plan's send list
   MgHalo halo0;
   std::vector<std::vector<int64_t>> mg_off;   // per level >= 1: send and ghost offsets in doubles, what MgLevelDev::send_off / ghost_off point at
+  int gmres_cap = 0;         // the restart length buf.solve.gmres was allocated for (0: not allocated)
+  GmresState gmres = GmresState();   // ... and its layout for the restart length of the call at hand
+  bool gmres_solved = false; // a GMRES solve has run on this mesh: gmres_restart / gmres_cycles describe the last one
+  int gmres_restart = 0, gmres_cycles = 0;
 };
 
 // What is only meaningful for the uploaded mesh; rdc_mesh_upload starts from MeshState().
@@ -134,6 +139,10 @@ struct rdc_ctx {
   int mg_smoother = 0;                         // option "mg_smoother": 0 = damped block Jacobi, 1 = multicolour Gauss-Seidel
   int mg_gs_fuse = 1;                          // option "mg_gs_fuse": small levels sweep in one launch (0: one launch per colour everywhere)
   int ilu_factor_bits = 64;                    // option "ilu_factor_bits": what the ILU(0) sweeps stream, the FP64 factor or its fp32 copy (32)
+  int solve_method = 0;                        // option "solve_method": 0 = BiCGStab, 1 = restarted GMRES (rdc_solve, rdc_solve_mixed)
+  int gmres_restart = GMRES_DEFAULT_RESTART;   // option "gmres_restart": 1 .. GMRES_MAX_RESTART
+  int gmres_refine = 0;                        // option "gmres_refine": 1 = always a second Gram-Schmidt pass
+  GmresRec* gmres_rec = nullptr;               // pinned: the record the host reads per Arnoldi step
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call
@@ -677,6 +686,7 @@ int rdc_ctx_destroy(rdc_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   free_group(c, c->buf);
   if (c->solve_rec) (void)hipHostFree(c->solve_rec);
+  if (c->gmres_rec) (void)hipHostFree(c->gmres_rec);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->pack_event) (void)hipEventDestroy(c->pack_event);
   if (c->solid_part1_event) (void)hipEventDestroy(c->solid_part1_event);
@@ -732,6 +742,21 @@ int rdc_set_option(rdc_ctx* c, const char* key, int value) {
   if (!std::strcmp(key, "ilu_factor_bits")) {   // a solver setting too: every ILU(0) solve and hook reads it
     if (value != 64 && value != 32) return fail(c, RDC_ERR_INVALID, "ilu_factor_bits is 64 or 32, not %d", value);
     c->ilu_factor_bits = value;
+    return RDC_OK;
+  }
+  if (!std::strcmp(key, "solve_method")) {   // the Krylov method of rdc_solve and rdc_solve_mixed
+    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "solve_method is 0 (BiCGStab) or 1 (GMRES), not %d", value);
+    c->solve_method = value;
+    return RDC_OK;
+  }
+  if (!std::strcmp(key, "gmres_restart")) {
+    if (value < 1 || value > GMRES_MAX_RESTART) return fail(c, RDC_ERR_INVALID, "gmres_restart is 1 .. %d, not %d", GMRES_MAX_RESTART, value);
+    c->gmres_restart = value;
+    return RDC_OK;
+  }
+  if (!std::strcmp(key, "gmres_refine")) {
+    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "gmres_refine is 0 or 1, not %d", value);
+    c->gmres_refine = value;
     return RDC_OK;
   }
   if (!std::strcmp(key, "const_rows")) {   // rdc_const_rows.h: a contract with the caller about the value array, not a tuning knob of a kernel
@@ -1399,6 +1424,37 @@ static int ilu_view(rdc_ctx* c, SolveDev* d) {
   return RDC_OK;
 }
 
+// The state of restarted GMRES for the option "gmres_restart" as it stands: one allocation that gmres_carve (rdc_solve.h) measures
+// and then carves, made at the first call that needs it on a mesh and remade when the restart length has grown.  d must come from
+// solve_view(want_work).
+static int gmres_view(rdc_ctx* c, SolveDev* d) {
+  const HostPrep& P = c->ms.prep;
+  SolveState& S = c->ms.solve;
+  const int m = c->gmres_restart;
+  if (m > S.gmres_cap) {
+    const size_t bytes = gmres_carve(P.nvar, P.n_owned, m, nullptr).bytes;
+    S.gmres_cap = 0;
+    int rc = dev_alloc(c, c->buf.solve.gmres, bytes);
+    if (rc) return rc;   // the message gives the byte count
+    S.gmres_cap = m;
+  }
+  if (!c->gmres_rec) RDC_HIP(c, hipHostMalloc((void**)&c->gmres_rec, sizeof(GmresRec), hipHostMallocDefault));
+  S.gmres = gmres_carve(P.nvar, P.n_owned, m, (double*)c->buf.solve.gmres.p);
+  d->gmres = &S.gmres;
+  d->gmres_rec = c->gmres_rec;
+  d->gmres_refine = c->gmres_refine != 0;
+  return RDC_OK;
+}
+
+int rdc_solve_gmres_stats(rdc_ctx* c, int32_t* restart, int64_t* basis_bytes, int32_t* cycles) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh || !c->ms.solve.gmres_solved) return fail(c, RDC_ERR_STATE, "no GMRES solve (\"solve_method\" = 1) has run on this mesh");
+  if (restart) *restart = c->ms.solve.gmres_restart;
+  if (basis_bytes) *basis_bytes = (int64_t)(c->ms.solve.gmres_restart + 1) * c->ms.prep.n_owned * c->ms.prep.nvar * (int64_t)sizeof(double);
+  if (cycles) *cycles = c->ms.solve.gmres_cycles;
+  return RDC_OK;
+}
+
 int rdc_solve_ilu_stats(rdc_ctx* c, float* setup_ms, int64_t* bytes, int32_t* n_colours) {
   if (!c) return RDC_ERR_INVALID;
   if (!c->ms.have_mesh || !c->ms.solve.ilu_ready) return fail(c, RDC_ERR_STATE, "no solve with the block ILU(0) preconditioner has run on this mesh");
@@ -1529,7 +1585,13 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
     if ((rc = ilu_view(c, &d))) return rc;
     c->ms.solve.ilu_factored = false;
   }
+  if (c->solve_method == 1 && (rc = gmres_view(c, &d))) return rc;
   RDC_HIP(c, solve_run(d, q, d_x, info, mixed));
+  if (d.gmres) {
+    c->ms.solve.gmres_solved = true;
+    c->ms.solve.gmres_restart = d.gmres->restart;
+    c->ms.solve.gmres_cycles = d.gmres->cycles;
+  }
   if (q.precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
   if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
   c->ms.solve.mg_values = p->precond == RDC_PRECOND_MULTIGRID;
@@ -1539,6 +1601,40 @@ static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_so
 int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, false); }
 
 int rdc_solve_mixed(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, true); }
+
+int rdc_solve_gmres_arnoldi(rdc_ctx* c, int precond, int mixed, const double* d_v0, int steps, double* d_V, double* H, int32_t* steps_done) {
+  if (!c) return RDC_ERR_INVALID;
+  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
+  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt
+  if (!d_v0 || !d_V || !H || !steps_done) return fail(c, RDC_ERR_INVALID, "null argument");
+  if (!known_precond(precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
+  if (steps < 1 || steps > c->gmres_restart)
+    return fail(c, RDC_ERR_INVALID, "steps must be 1 .. \"gmres_restart\" = %d, not %d", c->gmres_restart, steps);
+  if (mixed && (precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL) && c->ilu_factor_bits != 32)
+    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: mixed = 0, or \"ilu_factor_bits\" = 32", precond);
+  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, precond == RDC_PRECOND_MULTIGRID);
+  *steps_done = 0;
+  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
+  SolveDev d;
+  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
+  int rc = solve_view(c, true, mixed != 0, &d);
+  if (rc) return rc;
+  if (precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
+  if (precond == RDC_PRECOND_ILU0_LOCAL) precond = RDC_PRECOND_ILU0;   // no ghosts: the owned square is the matrix
+  if (precond == RDC_PRECOND_ILU0) {
+    if ((rc = ilu_view(c, &d))) return rc;
+    c->ms.solve.ilu_factored = false;
+  }
+  if ((rc = gmres_view(c, &d))) return rc;
+  int done = 0, bad = 0, bits = 64;
+  RDC_HIP(c, solve_gmres_arnoldi(d, precond, mixed != 0, d_v0, steps, d_V, H, &done, &bad, &bits));
+  if (precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
+  if (mixed) c->ms.solve.f32_copy = bits == 32 && bad == 0;
+  c->ms.solve.mg_values = precond == RDC_PRECOND_MULTIGRID;
+  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks or pivots are not invertible: nothing was run", bad);
+  *steps_done = done;
+  return RDC_OK;
+}
 
 int rdc_solve_mg_apply(rdc_ctx* c, int mixed, const double* d_in, double* d_out) {
   if (!c) return RDC_ERR_INVALID;
@@ -1776,6 +1872,9 @@ static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solv
   if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
   c->ms.solve.mg_values = false;   // the work buffer takes the layout of a partitioned solve
   if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
+  if (c->solve_method == 1)
+    return fail(c, RDC_ERR_UNSUPPORTED, "GMRES across partitions is not implemented (\"solve_method\" = 1): allreduce_sum carries at most %d doubles "
+                "and a GMRES step sums up to \"gmres_restart\" + 1; set \"solve_method\" to 0 for %s", DIST_RECORD, sized ? "rdc_solve_dist_mg" : "rdc_solve_dist");
   if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum || (sized && (!sized->exchange_sized_begin || !sized->exchange_sized_end)))
     return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
   if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");

@@ -9,6 +9,8 @@
 // ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp); on a
 // pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).  The fp32 copy of
 // the factor has a layout of its own beside them (ilu_f32_offset, ilu_f32_offsets, ilu_place_f32; tests/host_solve_ilu_f32_shim.cpp).
+// Restarted GMRES: the Givens step, the back substitution and the layout of its state (gmres_givens_step, gmres_back_substitute,
+// gmres_carve; tests/host_solve_gmres_shim.cpp, tests/host_solve_gmres_main.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -945,6 +947,105 @@ inline int dist_plan_check(int64_t n_owned, const int64_t* bptr, const int32_t* 
   return 0;
 }
 
+// ---- restarted GMRES(m) (option "solve_method" = 1): the small dense part of a cycle and the layout of its state,
+// host+device and free of HIP, so that a CPU build can test exactly this code (tests/host_solve_gmres_shim.cpp) ----
+constexpr int GMRES_MAX_RESTART = 128;      // largest "gmres_restart"
+constexpr int GMRES_DEFAULT_RESTART = 30;   // PETSc's default
+
+// flags of a step (GmresRec::flag)
+enum {
+  GMRES_NOT_FINITE = 1,     // an inner product, a norm or a rotation is not finite: the column was not taken
+  GMRES_HAPPY = 2,          // h_{j+1,j} = 0: the Krylov space is exhausted, the column was taken and the cycle ends
+  GMRES_SINGULAR = 4,       // the whole rotated column is zero (the operator is singular on the space): the column was not taken
+  GMRES_Y_NOT_FINITE = 8    // the back substitution left an entry of y that is not finite: x was not updated
+};
+
+// what the host reads once per Arnoldi step (and once more behind the update of x)
+struct GmresRec {
+  double est;         // |g_{j+1}|: the residual norm the rotations claim
+  double hnext;       // h_{j+1,j}
+  double wn2;         // (w, w) before the orthogonalisation
+  int32_t flag;
+  int32_t overflow;   // entries of x whose update would not have been finite and that kept their value
+};
+
+// The Givens step of column j.  hcol: the raw column, entries 0 .. j + 1.  rcol: receives the column with the rotations 0 .. j - 1
+// applied and the new rotation j formed on it (rcol[j] = the diagonal entry of R, rcol[j + 1] = 0).  cs, sn: the rotations;
+// g: the rotated right-hand side, g[j + 1] is written and |g[j + 1]| is the residual estimate.  Returns 0, GMRES_NOT_FINITE (an
+// entry of hcol, or the new diagonal entry, is not finite) or GMRES_SINGULAR (the rotated column is zero in rows j and j + 1); in
+// the two latter cases cs, sn and g stay what they were, so that nothing non-finite is propagated.
+RDC_SOLVE_HD int gmres_givens_step(int j, const double* hcol, double* rcol, double* cs, double* sn, double* g) {
+  for (int i = 0; i <= j + 1; i++)
+    if (!solve_finite(hcol[i])) return GMRES_NOT_FINITE;
+  for (int i = 0; i <= j + 1; i++) rcol[i] = hcol[i];
+  for (int i = 0; i < j; i++) {
+    const double a = rcol[i], b = rcol[i + 1];
+    rcol[i] = cs[i] * a + sn[i] * b;
+    rcol[i + 1] = cs[i] * b - sn[i] * a;
+  }
+  const double a = rcol[j], b = rcol[j + 1];
+  const double d = hypot(a, b);
+  if (!solve_finite(d)) return GMRES_NOT_FINITE;
+  if (d == 0.0) return GMRES_SINGULAR;
+  const double c = a / d, s = b / d;
+  cs[j] = c; sn[j] = s;
+  rcol[j] = d; rcol[j + 1] = 0.0;
+  g[j + 1] = -s * g[j];
+  g[j] = c * g[j];
+  return 0;
+}
+
+// y = R^-1 g for the leading k columns (R: column-major with leading dimension ld, upper triangular after the rotations).
+// false: an entry of y is not finite (y is then unspecified and must not be used).
+RDC_SOLVE_HD bool gmres_back_substitute(int ld, int k, const double* R, const double* g, double* y) {
+  bool ok = true;
+  for (int i = k - 1; i >= 0; i--) {
+    double s = g[i];
+    for (int l = i + 1; l < k; l++) s -= R[(int64_t)l * ld + i] * y[l];
+    y[i] = s / R[(int64_t)i * ld + i];
+    if (!solve_finite(y[i])) ok = false;
+  }
+  return ok;
+}
+
+// The state of GMRES on the device, an allocation of its own: the one statement of its layout.  Without a base nothing is placed
+// and `bytes` is what to allocate.  m = restart.  V: the basis, m + 1 vectors of `stride` doubles (slot j + 1 also holds the raw
+// w of step j); H: the raw Hessenberg matrix, R: its rotated form, both column-major (m + 1) x m; cs, sn [m]; g [m + 1]; y [m];
+// hpass [m + 1]: the coefficients of the orthogonalisation pass at hand; scal: [0] = beta^2 of the start, [1] = 1 / h_{j+1,j},
+// [2] = 1.0; partials: (m + 1) x vec_blocks, component-major (component c of workgroup b at c * vec_blocks + b); rec: the record.
+struct GmresState {
+  double *V, *H, *R, *cs, *sn, *g, *y, *hpass, *scal, *partials;
+  GmresRec* rec;
+  int restart;
+  int64_t n, stride, vec_blocks, partial_count;
+  size_t basis_bytes, bytes;
+  int cycles;   // out: the cycles of the last solve
+};
+
+constexpr int GMRES_SCALARS = 8;
+
+inline GmresState gmres_carve(int nvar, int64_t n_owned, int restart, double* base) {
+  GmresState g = GmresState();
+  const int m = restart;
+  g.restart = m;
+  g.n = n_owned * nvar;
+  g.stride = std::max<int64_t>(g.n, 1);
+  g.vec_blocks = vec_blocks(g.n);
+  g.partial_count = (int64_t)(m + 1) * std::max<int64_t>(g.vec_blocks, 1);
+  int64_t used = 0;
+  auto take = [&](int64_t doubles) { double* at = base ? base + used : nullptr; used += doubles; return at; };
+  g.V = take((int64_t)(m + 1) * g.stride);
+  g.basis_bytes = (size_t)used * sizeof(double);
+  g.H = take((int64_t)(m + 1) * m); g.R = take((int64_t)(m + 1) * m);
+  g.cs = take(m); g.sn = take(m); g.g = take(m + 1); g.y = take(m); g.hpass = take(m + 1);
+  g.scal = take(GMRES_SCALARS);
+  g.partials = take(g.partial_count);
+  g.rec = (GmresRec*)take((int64_t)(sizeof(GmresRec) / sizeof(double)));
+  g.bytes = (size_t)used * sizeof(double);
+  return g;
+}
+static_assert(sizeof(GmresRec) % sizeof(double) == 0, "the record is carved in doubles");
+
 }  // namespace rdc
 
 #if defined(__HIPCC__)
@@ -974,6 +1075,10 @@ struct SolveDev {
   DistDims dist;                       // n_nodes, interior nodes, length of the send list
   const int32_t* send_nodes = nullptr; // device copy of the send list (owned local node ids, send order)
   int* comm_rc = nullptr;              // out: the first non-zero return of a callback; nothing is called after it
+  // restarted GMRES (option "solve_method" = 1; single partition only).  gmres == nullptr is BiCGStab, and nothing below is read.
+  GmresState* gmres = nullptr;         // the state (gmres_carve), placed
+  GmresRec* gmres_rec = nullptr;       // pinned: the record the host reads per Arnoldi step
+  bool gmres_refine = false;           // option "gmres_refine": always a second Gram-Schmidt pass
 };
 
 // what solve_run returns after a callback has failed (*SolveDev::comm_rc tells its value)
@@ -995,6 +1100,12 @@ hipError_t solve_mg_apply(const SolveDev& d, bool mixed, const double* in, doubl
 // in and out hold n_owned * nvar doubles and do not overlap; d.ilu is set, d.comm is not.  *bad_blocks > 0: a diagonal block or a
 // pivot U_ii is not invertible, nothing was applied.  Synchronises.
 hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int* bad_blocks);
+// Test hook (rdc_solve_gmres_arnoldi): behind the prologue of a solve with `precond` (the same host function), v_0 = v0 / ||v0|| and
+// `steps` Arnoldi steps with the kernels and the host loop of a cycle; d.gmres is set, d.mg / d.ilu as that solve needs them.  Copies
+// the *steps_done + 1 basis vectors into V (device) and the raw Hessenberg matrix into H (host, (restart + 1) x restart, column-major).
+// *bad_blocks > 0: nothing was run.  Synchronises.
+hipError_t solve_gmres_arnoldi(const SolveDev& d, int precond, bool mixed, const double* v0, int steps, double* V, double* H,
+                               int* steps_done, int* bad_blocks, int* matrix_bits);
 // where the D^-1 of the last single-partition set-up lies in d.work (n_owned * nvar * nvar doubles)
 const double* solve_dinv(const SolveDev& d);
 

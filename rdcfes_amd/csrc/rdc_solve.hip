@@ -42,9 +42,16 @@
 // operator application inside the cycle, and on the levels below the matrix the kernel that last writes a vector also fills the
 // level's send buffer (k_restrict_pack, k_prolong_pack, k_smooth_pack), so that a coarse exchange costs no launch.
 //
+// Restarted GMRES(m) (option "solve_method" = 1): the second Krylov method of rdc_solve and rdc_solve_mixed, on the same
+// system with the same right preconditioners.  Its orthogonalisation is two launches per step, k_gmres_dots (all inner products
+// of a step, every basis vector read once) and k_gmres_orth (the update, every basis vector read once); k_gmres_finalize sums
+// their partials in a fixed order and runs the Givens step in device memory, and the host reads one record per step.  Its state
+// is an allocation of its own (rdc_solve.h, gmres_carve).  Single partition only.
+//
 // Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy, multigrid cycle and communicator are
 // arguments), `apply` the one entry to y = A_l x on any level in any form; `carve` (rdc_solve.h) is the one statement of the work
-// buffer's layout.
+// buffer's layout.  `open_solve` is what every solve does before its first iteration, `run` the BiCGStab driver, `run_gmres` the
+// GMRES driver with `gmres_step` as its one Arnoldi step.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -1181,6 +1188,220 @@ __global__ __launch_bounds__(256) void k_ilu_bwd_f32_owned(const int64_t* __rest
 #undef ILU_OWNED_KERNELS_OF
 #undef ILU_F32_KERNELS_OF
 
+// ---- restarted GMRES(m) (option "solve_method" = 1): classical Gram-Schmidt on the basis V, one launch for all
+// inner products of a step and one for the update.  State and layout: GmresState (rdc_solve.h).  Every sum has a fixed order
+// (a thread's own entries ascending, the wave butterfly, the four waves in order, the workgroups through k_gmres_finalize): no
+// floating-point atomics, no dependence on the launch shape, two solves bitwise equal. ----
+
+enum { GMRES_STAGE_DOTS = 0, GMRES_STAGE_DOTS2 = 1, GMRES_STAGE_NORM = 2, GMRES_STAGE_START = 3 };
+
+// (v_k, w) for k < nbasis and (w, w), one launch: a workgroup keeps its VEC_PER_BLOCK chunk of w in registers and streams the
+// matching chunk of every basis vector once.  Partials component-major: component k of this workgroup at partials[k * nparts + block].
+__global__ __launch_bounds__(256) void k_gmres_dots(const double* __restrict__ V, int64_t stride, int nbasis, const double* __restrict__ w,
+                                                    int64_t n, double* __restrict__ partials, int64_t nparts) {
+  __shared__ double sh[GMRES_MAX_RESTART + 1][4];
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+  double wv[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    wv[q] = i < n ? __builtin_nontemporal_load(w + i) : 0.0;
+  }
+  const int wave = threadIdx.x >> 6;
+  for (int k = 0; k <= nbasis; k++) {
+    double s = 0.0;
+    if (k < nbasis) {
+      const double* __restrict__ vk = V + (int64_t)k * stride;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int64_t i = i0 + q * 256;
+        if (i < n) s = fma(__builtin_nontemporal_load(vk + i), wv[q], s);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++) s = fma(wv[q], wv[q], s);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[k][wave] = s;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k <= nbasis; k += 256) partials[(int64_t)k * nparts + blockIdx.x] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
+}
+
+// w -= sum_k h_k v_k (k < nbasis, ascending), in place in the slot of w, with the partials of ||w||^2 (component 0).  Reads w once
+// and every v_k once.  A flagged step (an inner product was not finite) leaves w alone.
+__global__ __launch_bounds__(256) void k_gmres_orth(const double* __restrict__ V, int64_t stride, int nbasis, double* __restrict__ w,
+                                                    int64_t n, const double* __restrict__ h, double* __restrict__ partials,
+                                                    const GmresRec* __restrict__ rec) {
+  if (rec->flag & GMRES_NOT_FINITE) return;   // uniform
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+  double wv[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    wv[q] = i < n ? __builtin_nontemporal_load(w + i) : 0.0;
+  }
+  for (int k = 0; k < nbasis; k++) {
+    const double hk = h[k];
+    const double* __restrict__ vk = V + (int64_t)k * stride;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int64_t i = i0 + q * 256;
+      if (i < n) wv[q] = fma(-hk, __builtin_nontemporal_load(vk + i), wv[q]);
+    }
+  }
+  double c[1] = {0.0};
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) {
+      w[i] = wv[q];
+      c[0] = fma(wv[q], wv[q], c[0]);
+    }
+  }
+  block_partials<1>(c, partials);
+}
+
+// The sums of `ncomp` components of component-major partials in a fixed order (one workgroup of 1024), four components at a time,
+// and what the step does with them.  DOTS: h_{0..j,j} of the first Gram-Schmidt pass and (w, w); DOTS2: the second pass, added to
+// the first; NORM: h_{j+1,j} = ||w||, the Givens step of column j in device memory, and the record; START (the hook): beta^2.
+__global__ __launch_bounds__(1024) void k_gmres_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage, int j,
+                                                         GmresState G) {
+  __shared__ double sh[4][1024];
+  __shared__ double tot[GMRES_MAX_RESTART + 1];
+  GmresRec* rec = G.rec;
+  if (stage != GMRES_STAGE_DOTS && stage != GMRES_STAGE_START && (rec->flag & GMRES_NOT_FINITE)) {   // a flagged step wrote no partials
+    if (threadIdx.x == 0 && stage == GMRES_STAGE_NORM) rec->hnext = 0.0;
+    return;
+  }
+  for (int c0 = 0; c0 < ncomp; c0 += 4) {
+    const int nc = min(4, ncomp - c0);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = threadIdx.x; i < nparts; i += 1024)
+      for (int c = 0; c < nc; c++) s[c] += partials[(int64_t)(c0 + c) * nparts + i];
+    for (int c = 0; c < 4; c++) sh[c][threadIdx.x] = s[c];
+    __syncthreads();
+    for (int off = 512; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off)
+        for (int c = 0; c < nc; c++) sh[c][threadIdx.x] += sh[c][threadIdx.x + off];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0)
+      for (int c = 0; c < nc; c++) tot[c0 + c] = sh[c][0];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const int ld = G.restart + 1;
+  double* hcol = G.H + (int64_t)j * ld;
+  if (stage == GMRES_STAGE_START) {
+    G.scal[0] = tot[0];
+  } else if (stage == GMRES_STAGE_DOTS || stage == GMRES_STAGE_DOTS2) {
+    bool ok = true;
+    for (int k = 0; k <= j; k++) {
+      const double hk = stage == GMRES_STAGE_DOTS ? tot[k] : hcol[k] + tot[k];
+      G.hpass[k] = tot[k];
+      hcol[k] = hk;
+      ok = ok && finite_d(tot[k]) && finite_d(hk);
+    }
+    ok = ok && finite_d(tot[j + 1]);
+    if (stage == GMRES_STAGE_DOTS) {
+      rec->wn2 = tot[j + 1];
+      rec->flag = ok ? 0 : GMRES_NOT_FINITE;
+    } else if (!ok) {
+      rec->flag |= GMRES_NOT_FINITE;
+    }
+  } else {
+    const double hn = sqrt(tot[0]);
+    hcol[j + 1] = hn;
+    rec->hnext = hn;
+    const int f = gmres_givens_step(j, hcol, G.R + (int64_t)j * ld, G.cs, G.sn, G.g);
+    if (f) {
+      rec->flag |= f;
+      return;
+    }
+    rec->est = fabs(G.g[j + 1]);
+    if (hn == 0.0) rec->flag |= GMRES_HAPPY;
+    else G.scal[1] = 1.0 / hn;
+  }
+}
+
+// v_0 = src / beta with beta^2 in device memory (the ||r||^2 of k_residual, or the START sum of the hook); g = beta e_0 and a clean
+// record.  beta = 0 or not finite: flagged, and v_0 is not written.
+__global__ __launch_bounds__(256) void k_gmres_start(const double* __restrict__ src, const double* __restrict__ beta2, double* __restrict__ v0,
+                                                     int64_t n, GmresState G) {
+  const double beta = sqrt(*beta2);
+  const bool ok = finite_d(beta) && beta > 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    G.g[0] = beta;
+    G.scal[2] = 1.0;
+    G.rec->est = beta; G.rec->hnext = 0.0; G.rec->wn2 = 0.0;
+    G.rec->flag = ok ? 0 : GMRES_NOT_FINITE;
+    G.rec->overflow = 0;
+  }
+  if (!ok) return;
+  const double inv = 1.0 / beta;
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) v0[i] = src[i] * inv;
+  }
+}
+
+// v_{j+1} = w / h_{j+1,j}, in place, the factor from device memory; a flagged step (not finite, or h_{j+1,j} = 0) leaves w alone
+__global__ __launch_bounds__(256) void k_gmres_scale(double* __restrict__ w, int64_t n, const double* __restrict__ inv,
+                                                     const GmresRec* __restrict__ rec) {
+  if (rec->flag) return;   // uniform
+  const double s = *inv;
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) w[i] = __builtin_nontemporal_load(w + i) * s;
+  }
+}
+
+// y = R^-1 g for the leading k columns (one thread: k <= 128)
+__global__ void k_gmres_solve_y(int k, GmresState G) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (!gmres_back_substitute(G.restart + 1, k, G.R, G.g, G.y)) G.rec->flag |= GMRES_Y_NOT_FINITE;
+}
+
+// u = sum_k y_k v_k (k < K, ascending), or, ADD, x += that sum.  An entry of x whose update would not be finite keeps its value and
+// is counted (an integer counter), as k_update_xr does it.  A y that is not finite: nothing is written.
+template <bool ADD>
+__global__ __launch_bounds__(256) void k_gmres_combine(const double* __restrict__ V, int64_t stride, int K, const double* __restrict__ y,
+                                                       double* __restrict__ out, int64_t n, GmresRec* __restrict__ rec) {
+  if (rec->flag & GMRES_Y_NOT_FINITE) return;   // uniform
+  const int64_t i0 = (int64_t)blockIdx.x * VEC_PER_BLOCK + threadIdx.x;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < K; k++) {
+    const double yk = y[k];
+    const double* __restrict__ vk = V + (int64_t)k * stride;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int64_t i = i0 + q * 256;
+      if (i < n) s[q] = fma(yk, __builtin_nontemporal_load(vk + i), s[q]);
+    }
+  }
+  int bad = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int64_t i = i0 + q * 256;
+    if (i < n) {
+      if (ADD) {
+        const double xn = out[i] + s[q];
+        if (finite_d(xn)) out[i] = xn;
+        else bad++;
+      } else {
+        out[i] = s[q];
+      }
+    }
+  }
+  if (ADD && bad) atomicAdd(&rec->overflow, bad);
+}
+
 // ---- host side.  Launch shapes: the formulas of rdc_solve.h (op_blocks, op_parts, vec_blocks) and per_thread ----
 dim3 per_thread(int64_t items) { return dim3((unsigned)cdiv(items, 256)); }                                   // one thread per item
 
@@ -1569,33 +1790,57 @@ hipError_t prologue(const SolveDev& d, const Work& w, int precond, bool mixed, R
   return hipSuccess;
 }
 
+// the norms of the record into info, with the reason
+void report(const SolveScal& rec, rdc_solve_info* info, int reason) {
+  info->reason = reason;
+  info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
+  info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
+}
+
+// The opening of a solve, whatever its method: the prologue with the first residual, and the outcomes that need no iteration (a
+// diagonal block that cannot be inverted, a residual that is not finite, b = 0, an initial guess that already passes).  *done: info
+// is complete; otherwise *form is what the operator applications stream and *tol the bound on the residual norm.
+template <int NV>
+hipError_t open_solve(const SolveDev& d, const Work& w, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed, Form* form,
+                      double* tol, bool* done) {
+  const SolveScal& rec = *d.host_rec;
+  *done = true;
+  Start start;
+  SOLVE_HIP(prologue<NV>(d, w, (int)p.precond, mixed, [&] { return residual<NV>(d, w, x, p.rhs_scale, true); }, &start));
+  info->bad_blocks = start.bad_blocks;
+  *form = start.form;
+  info->matrix_bits = start.form == F32 ? 32 : 64;
+  if (start.bad_blocks > 0) { report(rec, info, RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
+  if (rec.flag) { report(rec, info, RDC_SOLVE_NOT_FINITE); return hipSuccess; }
+  if (rec.bn2 == 0.0) {   // b = 0: x = 0
+    SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)(d.comm ? d.dist.n_nodes * NV : w.n) * sizeof(double), d.stream));
+    SOLVE_HIP(hipStreamSynchronize(d.stream));
+    report(rec, info, RDC_SOLVE_CONVERGED);
+    info->residual_norm = info->plain_residual_norm = 0.0;
+    return hipSuccess;
+  }
+  *tol = std::max(p.rel_tol * std::sqrt(rec.bn2), p.abs_tol);
+  if (std::sqrt(rec.rn2) <= *tol) { report(rec, info, RDC_SOLVE_CONVERGED); return hipSuccess; }
+  *done = false;
+  return hipSuccess;
+}
+
+inline Right right_of(const rdc_solve_params& p) {
+  return p.precond == RDC_PRECOND_MULTIGRID ? RIGHT_MG
+         : p.precond == RDC_PRECOND_ILU0 || p.precond == RDC_PRECOND_ILU0_LOCAL ? RIGHT_ILU : RIGHT_NONE;
+}
+
 template <int NV>
 hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   const Work w = carve(d.nvar, d.n_owned, d.work, d.comm ? &d.dist : nullptr);
   const SolveScal& rec = *d.host_rec;   // across partitions: the all-reduced scalars, the same bits on every rank, so every branch below is collective
-  auto report = [&](int reason) {
-    info->reason = reason;
-    info->rhs_norm = std::sqrt(rec.bn2); info->residual_norm = std::sqrt(rec.rn2);
-    info->plain_rhs_norm = std::sqrt(rec.bn2_plain); info->plain_residual_norm = std::sqrt(rec.rn2_plain);
-  };
-  const Right right = p.precond == RDC_PRECOND_MULTIGRID ? RIGHT_MG
-                      : p.precond == RDC_PRECOND_ILU0 || p.precond == RDC_PRECOND_ILU0_LOCAL ? RIGHT_ILU : RIGHT_NONE;
-  Start start;
-  SOLVE_HIP(prologue<NV>(d, w, (int)p.precond, mixed, [&] { return residual<NV>(d, w, x, p.rhs_scale, true); }, &start));
-  info->bad_blocks = start.bad_blocks;
-  const Form form = start.form;
-  info->matrix_bits = form == F32 ? 32 : 64;
-  if (start.bad_blocks > 0) { report(RDC_SOLVE_BAD_DIAGONAL); return hipSuccess; }
-  if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
-  if (rec.bn2 == 0.0) {   // b = 0: x = 0
-    SOLVE_HIP(hipMemsetAsync(x, 0, (size_t)(d.comm ? d.dist.n_nodes * NV : w.n) * sizeof(double), d.stream));
-    SOLVE_HIP(hipStreamSynchronize(d.stream));
-    report(RDC_SOLVE_CONVERGED);
-    info->residual_norm = info->plain_residual_norm = 0.0;
-    return hipSuccess;
-  }
-  const double tol = std::max(p.rel_tol * std::sqrt(rec.bn2), p.abs_tol);
-  if (std::sqrt(rec.rn2) <= tol) { report(RDC_SOLVE_CONVERGED); return hipSuccess; }
+  auto report = [&](int reason) { rdc::report(rec, info, reason); };
+  const Right right = right_of(p);
+  Form form = SCALED;
+  double tol = 0.0;
+  bool done = false;
+  SOLVE_HIP(open_solve<NV>(d, w, p, x, info, mixed, &form, &tol, &done));
+  if (done) return hipSuccess;
   int breakdowns = 0;
   for (;;) {
     if (info->iterations >= p.max_its) {
@@ -1616,6 +1861,117 @@ hipError_t run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solv
     SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));
     if (rec.flag) { report(RDC_SOLVE_NOT_FINITE); return hipSuccess; }
     if (std::sqrt(rec.rn2) <= tol) { report(RDC_SOLVE_CONVERGED); return hipSuccess; }
+    info->restarts++;
+  }
+}
+
+// ---- restarted GMRES(m), host side ----
+
+// the one host read of an Arnoldi step: the record, behind everything enqueued so far
+hipError_t gmres_read(const SolveDev& d, const GmresState& G) {
+  SOLVE_HIP(hipMemcpyAsync(d.gmres_rec, G.rec, sizeof(GmresRec), hipMemcpyDeviceToHost, d.stream));
+  return hipStreamSynchronize(d.stream);
+}
+
+// v_0 = src / beta, g = beta e_0: the start of a cycle (beta2: device address of beta^2)
+hipError_t gmres_start(const SolveDev& d, const GmresState& G, const double* src, const double* beta2) {
+  hipLaunchKernelGGL(k_gmres_start, dim3((unsigned)std::max<int64_t>(G.vec_blocks, 1)), dim3(256), 0, d.stream, src, beta2, G.V, G.n, G);
+  return hipGetLastError();
+}
+
+// Arnoldi step j: w = D^-1 A (M v_j) into slot j + 1, one or two classical Gram-Schmidt passes against v_0 .. v_j, the norm, the
+// Givens step, the scaling, and the record on the host.  Vector passes with one Gram-Schmidt pass, beside the operator and M:
+// (j + 2) reads for the inner products, (j + 2) reads and 1 write for the update, 1 read and 1 write for the scaling: 2 j + 7.
+template <int NV>
+hipError_t gmres_step(const SolveDev& d, const Work& w, const GmresState& G, Form form, Right right, int j) {
+  double* vj = G.V + (int64_t)j * G.stride;
+  double* wn = G.V + (int64_t)(j + 1) * G.stride;
+  double* in = vj;
+  if (right != RIGHT_NONE) {
+    in = right == RIGHT_MG ? d.mg->ph : d.ilu->ph;
+    SOLVE_HIP(right_apply<NV>(d, w, form, right, vj, in));
+  }
+  SOLVE_HIP(apply_halo<NV>(d, w, form, in, wn, nullptr));
+  const dim3 vg((unsigned)G.vec_blocks), vb(256);
+  for (int pass = 0; pass < (d.gmres_refine ? 2 : 1); pass++) {
+    hipLaunchKernelGGL(k_gmres_dots, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, (const double*)wn, G.n, G.partials, G.vec_blocks);
+    hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, j + 2,
+                       pass ? (int)GMRES_STAGE_DOTS2 : (int)GMRES_STAGE_DOTS, j, G);
+    hipLaunchKernelGGL(k_gmres_orth, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, wn, G.n, (const double*)G.hpass, G.partials,
+                       (const GmresRec*)G.rec);
+  }
+  hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, 1, (int)GMRES_STAGE_NORM, j, G);
+  hipLaunchKernelGGL(k_gmres_scale, vg, vb, 0, d.stream, wn, G.n, (const double*)(G.scal + 1), (const GmresRec*)G.rec);
+  SOLVE_HIP(hipGetLastError());
+  return gmres_read(d, G);
+}
+
+// The Arnoldi steps of one cycle from v_0: until stop(steps taken) says so, a step is flagged, or `max_steps` are taken.  *taken:
+// the columns that may be used (a step flagged NOT_FINITE or SINGULAR is not among them); *run: the operator applications.
+template <int NV, class Stop>
+hipError_t gmres_arnoldi(const SolveDev& d, const Work& w, const GmresState& G, Form form, Right right, int max_steps, Stop&& stop,
+                         int* taken, int* run) {
+  const GmresRec& rec = *d.gmres_rec;
+  *taken = *run = 0;
+  while (*taken < max_steps) {
+    SOLVE_HIP(gmres_step<NV>(d, w, G, form, right, *taken));
+    ++*run;
+    if (rec.flag & (GMRES_NOT_FINITE | GMRES_SINGULAR)) break;
+    ++*taken;
+    if ((rec.flag & GMRES_HAPPY) || stop(*taken)) break;
+  }
+  return hipSuccess;
+}
+
+// x += M (V y) for the leading k columns: the back substitution, the sum (fused into the update of x without a right
+// preconditioner), one application of M.  Enqueues only; the record (overflow, a y that is not finite) travels with the next read.
+template <int NV>
+hipError_t gmres_update(const SolveDev& d, const Work& w, const GmresState& G, Form form, Right right, int k, double* x) {
+  const dim3 vg((unsigned)G.vec_blocks), vb(256);
+  hipLaunchKernelGGL(k_gmres_solve_y, dim3(1), dim3(64), 0, d.stream, k, G);
+  if (right == RIGHT_NONE) {
+    hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, x, G.n, G.rec);
+  } else {
+    double* z = right == RIGHT_MG ? d.mg->ph : d.ilu->ph;
+    hipLaunchKernelGGL((k_gmres_combine<false>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, w.s, G.n, G.rec);
+    SOLVE_HIP(right_apply<NV>(d, w, form, right, w.s, z));
+    hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)z, (int64_t)0, 1, (const double*)(G.scal + 2), x, G.n, G.rec);
+  }
+  SOLVE_HIP(hipGetLastError());
+  return hipMemcpyAsync(d.gmres_rec, G.rec, sizeof(GmresRec), hipMemcpyDeviceToHost, d.stream);
+}
+
+// Right-preconditioned GMRES(m) on the system of run(): every cycle starts from the true FP64 residual, which also decides.
+template <int NV>
+hipError_t run_gmres(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
+  const Work w = carve(d.nvar, d.n_owned, d.work);
+  GmresState& G = *d.gmres;
+  const SolveScal& rec = *d.host_rec;
+  const GmresRec& grec = *d.gmres_rec;
+  const Right right = right_of(p);
+  Form form = SCALED;
+  double tol = 0.0;
+  bool done = false;
+  G.cycles = 0;
+  SOLVE_HIP(open_solve<NV>(d, w, p, x, info, mixed, &form, &tol, &done));
+  if (done) return hipSuccess;
+  for (;;) {
+    G.cycles++;
+    SOLVE_HIP(gmres_start(d, G, w.r, &w.scal->rn2));
+    int k = 0, steps = 0;
+    const int left = p.max_its - info->iterations;   // >= 1: a cycle always takes a step
+    SOLVE_HIP(gmres_arnoldi<NV>(d, w, G, form, right, std::min(G.restart, left), [&](int) { return grec.est <= tol; }, &k, &steps));
+    info->iterations += steps;
+    const int step_flag = grec.flag;
+    if (k > 0) SOLVE_HIP(gmres_update<NV>(d, w, G, form, right, k, x));
+    SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));   // the true residual of x decides, and is the next cycle's start
+    if (rec.flag || (step_flag & GMRES_NOT_FINITE) || (k > 0 && (grec.overflow || (grec.flag & GMRES_Y_NOT_FINITE)))) {
+      report(rec, info, RDC_SOLVE_NOT_FINITE);
+      return hipSuccess;
+    }
+    if (std::sqrt(rec.rn2) <= tol) { report(rec, info, RDC_SOLVE_CONVERGED); return hipSuccess; }
+    if (step_flag & GMRES_SINGULAR) { report(rec, info, RDC_SOLVE_BREAKDOWN); return hipSuccess; }
+    if (info->iterations >= p.max_its) { report(rec, info, RDC_SOLVE_MAX_ITS); return hipSuccess; }
     info->restarts++;
   }
 }
@@ -1675,7 +2031,41 @@ hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rd
   *info = rdc_solve_info();
   info->matrix_bits = 64;
   return timed(d.stream, &info->device_ms, [&] {
-    return by_nvar(d.nvar, [&](auto nv) { return run<decltype(nv)::value>(d, p, x, info, mixed); });
+    return by_nvar(d.nvar, [&](auto nv) {
+      constexpr int NV = decltype(nv)::value;
+      return d.gmres ? run_gmres<NV>(d, p, x, info, mixed) : run<NV>(d, p, x, info, mixed);
+    });
+  });
+}
+
+hipError_t solve_gmres_arnoldi(const SolveDev& d, int precond, bool mixed, const double* v0, int steps, double* V, double* H,
+                               int* steps_done, int* bad_blocks, int* matrix_bits) {
+  return by_nvar(d.nvar, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    const Work w = carve(d.nvar, d.n_owned, d.work);
+    const GmresState& G = *d.gmres;
+    rdc_solve_params p = rdc_solve_params();
+    p.precond = precond;
+    const Right right = right_of(p);
+    Start start;
+    SOLVE_HIP(prologue<NV>(d, w, precond, mixed, [&] { return read_record(d, w); }, &start));
+    *bad_blocks = start.bad_blocks;
+    *matrix_bits = start.form == F32 ? 32 : 64;
+    *steps_done = 0;
+    if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is run
+    const size_t hbytes = (size_t)(G.restart + 1) * G.restart * sizeof(double);
+    SOLVE_HIP(hipMemsetAsync(G.H, 0, hbytes, d.stream));
+    hipLaunchKernelGGL(k_gmres_dots, dim3((unsigned)G.vec_blocks), dim3(256), 0, d.stream, (const double*)G.V, G.stride, 0, v0, G.n, G.partials,
+                       G.vec_blocks);
+    hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, 1, (int)GMRES_STAGE_START, 0, G);
+    SOLVE_HIP(gmres_start(d, G, v0, G.scal));
+    SOLVE_HIP(gmres_read(d, G));
+    int run = 0;
+    if (!(d.gmres_rec->flag & GMRES_NOT_FINITE))
+      SOLVE_HIP(gmres_arnoldi<NV>(d, w, G, start.form, right, steps, [](int) { return false; }, steps_done, &run));
+    SOLVE_HIP(hipMemcpyAsync(V, G.V, (size_t)(*steps_done + 1) * G.stride * sizeof(double), hipMemcpyDeviceToDevice, d.stream));
+    SOLVE_HIP(hipMemcpyAsync(H, G.H, hbytes, hipMemcpyDeviceToHost, d.stream));
+    return hipStreamSynchronize(d.stream);
   });
 }
 

@@ -2,7 +2,8 @@
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
     python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
-                              [--ilu-bits 32|64] [--ab [precond|precision|dist|smoother|ilu_bits]] [--dump DIR]
+                              [--ilu-bits 32|64] [--method bicgstab|gmres] [--restart N]
+                              [--ab [precond|precision|dist|smoother|ilu_bits|method]] [--dump DIR]
     python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--ab precond]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
@@ -27,7 +28,10 @@ kernel launches of one cycle (counted from the level sizes and colours: tools/ti
 (--precond 4 or 5, with or without --mixed and --ranks) sets the option "ilu_factor_bits": the sweeps of the ILU(0) stream an fp32
 copy of the FP64 factor, and every record has ilu_factor_bits, what they streamed; --ab ilu_bits runs the loop in the order 64, 32,
 32, 64 (with --mixed the legs at 64 run on the FP64 operator, since the FP64 factor has no mixed form: they are today's ILU(0),
-the legs at 32 the fp32 operator with the fp32 factor).  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
+the legs at 32 the fp32 operator with the fp32 factor).  --method gmres (one partition) sets the option "solve_method": restarted
+GMRES(m) in place of BiCGStab, m = --restart (option "gmres_restart", default 30); iterations are then Arnoldi steps, restarts the
+cycles after the first, and every record has the method, the restart length and the device bytes of the basis; --ab method runs
+the loop in the order BiCGStab, GMRES, GMRES, BiCGStab with --precond (and --mixed).  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
@@ -81,7 +85,7 @@ def cycle_launches(levels, colours=None, fuse=True, fused_nodes=512):
 
 
 def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_step=None, mixed=False, comm=None, smoother=0, gs_fuse=1,
-        ilu_bits=64):
+        ilu_bits=64, method="bicgstab", restart=30):
     """the loop on an uploaded context whose FIELD_OLD_SOLUTION is set; returns one dict per step.
     on_step(k, phase, ctx) is called with phase 'assembled' and 'solved' (tests look at the state there).
     comm: a halo.SolveComm -- the solve is solve_dist across its ranks (the background shares are then those of the local nodes)."""
@@ -95,6 +99,9 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         ctx.set_option("mg_gs_fuse", gs_fuse)
     if precond in (4, 5):
         ctx.set_option("ilu_factor_bits", ilu_bits)
+    if comm is None:                    # across partitions the method is BiCGStab, and the option would be refused
+        ctx.set_option("solve_method", 1 if method == "gmres" else 0)
+        ctx.set_option("gmres_restart", restart)
     out = []
     for k in range(steps):
         ctx.assemble_pihna(params)
@@ -114,6 +121,8 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         out.append(dict(step=k + 1, assembly_ms=asm_ms, solve_ms=info.device_ms, iterations=info.iterations, restarts=info.restarts,
                         reason=info.reason, matrix_bits=info.matrix_bits, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
                         background_nodes=nodes, background_elems=elems))
+        if method == "gmres" and comm is None:
+            out[-1].update(method="gmres", gmres_restart=restart, gmres_basis_bytes=ctx.gmres_stats()[1] if info.iterations else 0)
         if precond == 3:
             setup_ms, level_bytes = ctx.mg_stats()
             out[-1].update(mg_setup_ms=setup_ms, mg_level_bytes=level_bytes, mg_levels=ctx.mg_levels())
@@ -186,7 +195,9 @@ def main():
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--smoother", type=int, choices=(0, 1), default=0)
     ap.add_argument("--gs-fuse", type=int, choices=(0, 1), default=1)
-    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist", "smoother", "ilu_bits"), default=None)
+    ap.add_argument("--ab", nargs="?", const="precond", choices=("precond", "precision", "dist", "smoother", "ilu_bits", "method"), default=None)
+    ap.add_argument("--method", choices=("bicgstab", "gmres"), default="bicgstab")
+    ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--ilu-bits", type=int, choices=(32, 64), default=64)
     ap.add_argument("--dump", default=None)
     ap.add_argument("--ranks", type=int, default=1)
@@ -203,6 +214,10 @@ def main():
         ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only (across ranks: --precond 5; --mixed: --ilu-bits 32)")
     if a.precond == 5 and not f32 and (a.mixed or a.ab == "precision"):
         ap.error("the rank-local block ILU(0) (--precond 5) is FP64 only, unless --ilu-bits 32")
+    if (a.method == "gmres" or a.ab == "method") and (a.ranks > 1 or a.ab == "dist"):
+        ap.error("GMRES (--method gmres, --ab method) runs on one partition: rdc_solve and rdc_solve_mixed")
+    if not 1 <= a.restart <= 128:
+        ap.error("--restart is 1 .. 128")
     if a.ranks > 1 and a.ab not in (None, "precond"):
         ap.error("--ranks takes --ab precond only")
     if a.ranks > 1 and a.ab == "precond" and a.mixed:
@@ -225,6 +240,9 @@ def main():
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
         runs = [(a.precond, a.mixed, False, a.smoother, a.ilu_bits)]
+        methods = ("bicgstab", "gmres", "gmres", "bicgstab") if a.ab == "method" else None
+        if methods:
+            runs = runs * len(methods)
         if a.ab == "precond":
             runs = [(pc, a.mixed, False, a.smoother, a.ilu_bits) for pc in ((2, 3, 3, 2) if a.mixed and not f32 else (2, 3, 4, 4, 3, 2))]
         elif a.ab == "precision":
@@ -241,13 +259,15 @@ def main():
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
             comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3)
-        for precond, mixed, dist_entry, smoother, ilu_bits in runs:
+        for leg, (precond, mixed, dist_entry, smoother, ilu_bits) in enumerate(runs):
+            method = methods[leg] if methods else a.method
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
                                   smoother=smoother if precond == 3 else None, ilu_bits=ilu_bits if precond in (4, 5) else None,
+                                  method=method, restart=a.restart if method == "gmres" else None,
                                   entry=("rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") + ", world size 1" if dist_entry else "rdc_solve")))
             for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None,
-                           smoother=smoother, gs_fuse=a.gs_fuse, ilu_bits=ilu_bits):
+                           smoother=smoother, gs_fuse=a.gs_fuse, ilu_bits=ilu_bits, method=method, restart=a.restart):
                 print(json.dumps(rec), flush=True)
         if a.dump:
             d = Path(a.dump)
