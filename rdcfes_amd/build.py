@@ -22,6 +22,7 @@ LIB = LIBDIR / "librdc_assembly.so"
 
 SOURCES = [
     "rdc_capi.hip",
+    "rdc_capi_solve.hip",
     "rdc_meshprep.cpp",
     "rdc_model_pihna.hip",
     "rdc_model_ripf.hip",

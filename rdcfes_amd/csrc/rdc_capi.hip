@@ -9,147 +9,62 @@
 #include <type_traits>
 #include <utility>
 
-#include "rdc_internal.h"
-#include "rdc_const_rows.h"
+#include "rdc_capi_internal.h"
 #include "rdc_parts.h"
 #include "rdc_tet4_ev.h"
 #include "rdc_tet4_cl.h"
 #include "rdc_solid.h"
-#include "rdc_solve.h"
 
 using namespace rdc;
 
 namespace {
 
-struct DevBuf { void* p = nullptr; size_t bytes = 0; bool owned = true; };   // owned = false: bound by the caller (rdc_field_bind_device)
-
-// Device buffers, in groups that follow the device views (MeshDev, Rg2Dev, EvDev, ClDev ...).  A group holds DevBufs and
-// nothing else, so it can be walked as an array (free_group): a new buffer is one more name in its group.
-struct Buffers {
-  struct { DevBuf conn, xyz, bptr, eslot, elem_order, first_mask, first_rhs, pair_elem, pair_local, node_pair_ptr, wg_node_ptr; } mesh;
-  // TET4 pair lists; nlist and ploc are read by k_tet4_rg5 only, eid (pair -> element) is uploaded at the first assembly of a model with per-element inputs
-  struct { DevBuf desc, pair, chunk, sdesc, contrib, aux, ntab, nlist, ploc, eid; } rg2;
-  struct { DevBuf nl_ptr, nlist, ploc; } hx;   // node-staged generic row gather (HEX8)
-  // element-visit lists; perm = workgroup order of the two-part assembly, ticket = cluster counters of the resident kernel
-  struct { DevBuf desc, nlist, vloc, vslot, ntab, bpart, perm, ticket; } ev;
-  struct { DevBuf desc, ntab, eid, pair, pslot; } cl;        // cluster lists of the producer / consumer HEX8 kernels
-  struct { DevBuf ke, fe, gptr, gsrc, brow; } two_pass;      // solid two-pass assembly: element matrices + gather lists
-  struct { DevBuf elem_material, materials, side_elem, side_id, side_disp; } solid_in;
-  // linear solve (rdc_solve.hip): block column list (first matvec / solve), work vectors (first solve); fp32 copy of D^-1 A
-  // and the offsets of its padded rows (first mixed solve / rdc_csr_scale_f32)
-  // mg_idx / mg_val: every list, and every matrix / D_l^-1 / vector, of the multigrid levels (first multigrid solve)
-  // send: the send list of a partitioned solve (rdc_solve_dist_plan)
-  // mg_gs: the colour lists of every level (first multigrid solve with the Gauss-Seidel smoother)
-  // ilu_f32: the offsets and the floats of the fp32 copy of that factor (first ILU solve or hook with "ilu_factor_bits" = 32; ilu_place_f32)
-  // ilu_idx / ilu_val: the lists, and the factor / U_ii^-1 / vectors, of the block ILU(0) (first solve with RDC_PRECOND_ILU0; rdc_solve.h, ilu_place)
-  // gmres: the state of restarted GMRES (first solve with "solve_method" = 1, or the Arnoldi hook; rdc_solve.h, gmres_carve)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32, gmres; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
-  struct { DevBuf val, rhs, packed; } out;
-  // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
-  struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
-  DevBuf field[RDC_FIELD_COUNT];
-};
-
-// Linear solve (rdc_solve.hip): what buf.solve holds for the uploaded mesh
-struct SolveState {
-  bool bcol_ready = false;   // bcol holds this mesh's block column list
-  bool voff_ready = false;   // voff / val32 are laid out for this mesh
-  bool f32_copy = false;     // val32 holds a usable fp32 copy (of the values at the time it was built)
-  bool mg_ready = false;     // mg_idx / mg_val hold this mesh's hierarchy, mg describes it
-  bool mg_dist = false;      // ... and it is the one of rdc_solve_dist_mg (ghost layers; mg_off holds the offsets of its exchanges)
-  MgDev mg;
-  // mg_val and the D^-1 of the work buffer hold what the last rdc_solve_mg_apply or multigrid solve built, and nothing has run
-  // over them since (rdc_solve_mg_level_download).  Set by those two; cleared on entry to every other call that runs or plans a
-  // solve (rdc_solve*, rdc_solve_dist*) and to rdc_csr_scale_f32; the queries (rdc_solve_mg_levels / _stats / _colours) leave it.
-  bool mg_values = false;
-  bool gs_ready = false;     // mg_gs holds the colour lists of this mesh's (single-partition) hierarchy, gs describes them
-  MgGsDev gs;
-  std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
-  bool ilu_ready = false;    // ilu_idx / ilu_val hold this mesh's lists, ilu describes them, ilu_host is their host copy
-  bool ilu_factored = false; // ... and ilu_val holds the factor of the last rdc_solve_ilu_apply / _local_apply or solve with RDC_PRECOND_ILU0 / _ILU0_LOCAL
-  IluDev ilu;
-  IluHost ilu_host;          // (IluDev::cptr_host points into it; rdc_solve_ilu_download permutes with it)
-  bool plan_ready = false;   // send holds this mesh's send list, dist its checked dimensions (rdc_solve_dist_plan)
-  DistDims dist;
-  bool peers_ready = false;  // halo0 is the plan with its per-peer segments (rdc_solve_dist_plan_peers)
-  std::vector<int32_t> send_nodes;   // host copy of the plan's send list
-  MgHalo halo0;
-  std::vector<std::vector<int64_t>> mg_off;   // per level >= 1: send and ghost offsets in doubles, what MgLevelDev::send_off / ghost_off point at
-  int gmres_cap = 0;         // the restart length buf.solve.gmres was allocated for (0: not allocated)
-  GmresState gmres = GmresState();   // ... and its layout for the restart length of the call at hand
-  bool gmres_solved = false; // a GMRES solve has run on this mesh: gmres_restart / gmres_cycles describe the last one
-  int gmres_restart = 0, gmres_cycles = 0;
-};
-
-// What is only meaningful for the uploaded mesh; rdc_mesh_upload starts from MeshState().
-struct MeshState {
-  bool have_mesh = false;
-  HostPrep prep;
-  HostPrepEv prep_ev;              // element-visit lists (PIHNA TET4, shipped pattern); .ok = available
-  bool ev_tried = false;           // the element-visit lists of this mesh have been built (or found impossible)
-  int64_t ev_perm_interior = -2;   // "interior_nodes" value the uploaded workgroup order was built for
-  PartSplit ev_part1;              // the split of that order: its leading interior workgroups, the rows complete after them
-  struct ClusterLists {            // cluster lists of the HEX8 producer / consumer kernels or of k_tet4_cl (ensure_cluster_lists)
-    int state = 0;                 // 0 = not built yet, 1 = ready, -1 = not available for this mesh (two-pass / the pair kernels are used)
-    int waves = 31, order = 1, interior = -1;   // the options "solid_cl_waves", pair order and "interior_nodes" they were built with
-    int n_wg = 0;                  // all clusters
-    PartSplit part1;               // their leading clusters of interior nodes, the rows complete after those
-    size_t max_row_doubles = 0;
-    int64_t n_pairs = 0, n_elem_visits = 0;   // statistics (rdc_tet4_cluster_info)
-  } cl;
-  bool solid_gather_ready = false, rg5_eid_ready = false;   // buf.two_pass, buf.rg2.eid hold this mesh's lists
-  SolveState solve;
-  int64_t part1_nodes = -1;          // rows [0, part1_nodes) were complete after the LAST part-1 call (-1: none since the upload)
-  bool part1_packed = false;         // part 1 of the current step has packed the owned records (consumed by part 2)
-  bool solid_part1_pending = false;
-  int32_t n_materials = 0;   // what rdc_solid_set_materials / rdc_solid_set_sides left in buf.solid_in
-  int64_t n_sides = 0;
-  int64_t field_count[RDC_FIELD_COUNT] = {};
-};
-
 thread_local char g_create_error[512] = "";
 
 }  // namespace
 
-// Three kinds of state: what lives as long as the context (below), the tuning options (opt), and what belongs to the
-// uploaded mesh (ms, with the device buffers in buf).
-struct rdc_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  char err[512] = "";
-  int strategy = RDC_SCATTER_AUTO;
-  int variant = RDC_VARIANT_AUTO;
-  int tet4_cl_mode = 0;         // rdc_tet4_cluster_mode
-  int tet4_cl_active = 0;       // the last assembly call launched k_tet4_cl
-  size_t tet4_cl_lds = 0;       // dynamic LDS of that launch
-  Options opt;
-  MeshState ms;
-  Buffers buf;
-  ConstRows const_rows;         // the a rows of the value array that PIHNA element-visit launches may leave (rdc_const_rows.h); coords_out outlives the mesh
-  hipEvent_t pack_event = nullptr;  // two-part assembly: recorded behind part 1's pack of the owned node records
-  // chunked hand-back (rdc_csr_download_rows_async): a copy stream of the context's own and a small pool of completion events
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t copy_fence = nullptr;            // recorded on the context's stream at call time: the copy starts behind the work enqueued so far
-  static constexpr int N_TICKETS = 16;
-  hipEvent_t ticket[N_TICKETS] = {};
-  int next_ticket = 0;
-  hipEvent_t solid_part1_event = nullptr;   // recorded behind part 1 of a two-part solid assembly (the sides of part 2 wait for it)
-  SolveScal* solve_rec = nullptr;   // pinned: the one record the host reads per iteration of the linear solve
-  int mg_omega_permille = MG_OMEGA_PERMILLE;   // option "mg_omega": damping of the multigrid smoother, in thousandths
-  int mg_smoother = 0;                         // option "mg_smoother": 0 = damped block Jacobi, 1 = multicolour Gauss-Seidel
-  int mg_gs_fuse = 1;                          // option "mg_gs_fuse": small levels sweep in one launch (0: one launch per colour everywhere)
-  int ilu_factor_bits = 64;                    // option "ilu_factor_bits": what the ILU(0) sweeps stream, the FP64 factor or its fp32 copy (32)
-  int solve_method = 0;                        // option "solve_method": 0 = BiCGStab, 1 = restarted GMRES (rdc_solve, rdc_solve_mixed)
-  int gmres_restart = GMRES_DEFAULT_RESTART;   // option "gmres_restart": 1 .. GMRES_MAX_RESTART
-  int gmres_refine = 0;                        // option "gmres_refine": 1 = always a second Gram-Schmidt pass
-  GmresRec* gmres_rec = nullptr;               // pinned: the record the host reads per Arnoldi step
-  // timing
-  bool timing = false;
-  std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call
-  size_t ev_used = 0;           // events handed out since the last rdc_timing_sum_ms / enable
-  size_t max_lds = 64 * 1024;
-  int n_cu = 256;
-};
+// the helpers rdc_capi_solve.hip shares (rdc_capi_internal.h)
+namespace rdc {
+
+int fail(rdc_ctx* c, int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  if (c) vsnprintf(c->err, sizeof(c->err), fmt, ap);
+  else vsnprintf(g_create_error, sizeof(g_create_error), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+int dev_free(rdc_ctx* c, DevBuf& b) {
+  if (b.p && b.owned) {
+    hipError_t e = hipFree(b.p);
+    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "hipFree failed: %s", hipGetErrorString(e));
+  }
+  b = DevBuf();
+  return RDC_OK;
+}
+
+int dev_alloc(rdc_ctx* c, DevBuf& b, size_t bytes) {
+  if (b.p && b.owned && b.bytes >= bytes && bytes > 0) return RDC_OK;
+  int rc = dev_free(c, b);
+  if (rc) return rc;
+  if (bytes == 0) bytes = 8;
+  hipError_t e = hipMalloc(&b.p, bytes);
+  if (e != hipSuccess) {
+    b = DevBuf();
+    return fail(c, RDC_ERR_ALLOC, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  }
+  b.bytes = bytes;
+  b.owned = true;
+  return RDC_OK;
+}
+
+int set_device(rdc_ctx* c) {
+  RDC_HIP(c, hipSetDevice(c->device));
+  return RDC_OK;
+}
+
+}  // namespace rdc
 
 namespace {
 
@@ -211,30 +126,6 @@ EvDev ev_view(const rdc_ctx* c) {
   return v;
 }
 
-int fail(rdc_ctx* c, int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  if (c) vsnprintf(c->err, sizeof(c->err), fmt, ap);
-  else vsnprintf(g_create_error, sizeof(g_create_error), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define RDC_HIP(ctx, call)                                                                       \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) return fail(ctx, RDC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-int dev_free(rdc_ctx* c, DevBuf& b) {
-  if (b.p && b.owned) {
-    hipError_t e = hipFree(b.p);
-    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "hipFree failed: %s", hipGetErrorString(e));
-  }
-  b = DevBuf();
-  return RDC_OK;
-}
-
 // frees every buffer of a group (a struct or array of DevBufs and nothing else)
 template <class G>
 void free_group(rdc_ctx* c, G& g) {
@@ -244,34 +135,6 @@ void free_group(rdc_ctx* c, G& g) {
 }
 template <class G, class... Rest>
 void free_group(rdc_ctx* c, G& g, Rest&... rest) { free_group(c, g); free_group(c, rest...); }
-
-int dev_alloc(rdc_ctx* c, DevBuf& b, size_t bytes) {
-  if (b.p && b.owned && b.bytes >= bytes && bytes > 0) return RDC_OK;
-  int rc = dev_free(c, b);
-  if (rc) return rc;
-  if (bytes == 0) bytes = 8;
-  hipError_t e = hipMalloc(&b.p, bytes);
-  if (e != hipSuccess) {
-    b = DevBuf();
-    return fail(c, RDC_ERR_ALLOC, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  }
-  b.bytes = bytes;
-  b.owned = true;
-  return RDC_OK;
-}
-
-template <class T>
-int dev_upload(rdc_ctx* c, DevBuf& b, const std::vector<T>& v) {
-  int rc = dev_alloc(c, b, v.size() * sizeof(T));
-  if (rc) return rc;
-  if (!v.empty()) RDC_HIP(c, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-  return RDC_OK;
-}
-
-int set_device(rdc_ctx* c) {
-  RDC_HIP(c, hipSetDevice(c->device));
-  return RDC_OK;
-}
 
 int64_t field_width(const rdc_ctx* c, int field) {
   switch (field) {
@@ -728,42 +591,12 @@ int rdc_set_kernel_variant(rdc_ctx* c, int v) {
 
 int rdc_set_option(rdc_ctx* c, const char* key, int value) {
   if (!c || !key) return RDC_ERR_INVALID;
-  if (!std::strcmp(key, "mg_omega")) {   // a solver setting, not a tuning option of the assembly: kept beside their table
-    if (value < 1 || value > 1999) return fail(c, RDC_ERR_INVALID, "mg_omega is the damping in thousandths, 1 .. 1999, not %d", value);
-    c->mg_omega_permille = value;
-    return RDC_OK;
-  }
-  const bool smoother = !std::strcmp(key, "mg_smoother");
-  if (smoother || !std::strcmp(key, "mg_gs_fuse")) {   // solver settings as well
-    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "%s is 0 or 1, not %d", key, value);
-    (smoother ? c->mg_smoother : c->mg_gs_fuse) = value;
-    return RDC_OK;
-  }
-  if (!std::strcmp(key, "ilu_factor_bits")) {   // a solver setting too: every ILU(0) solve and hook reads it
-    if (value != 64 && value != 32) return fail(c, RDC_ERR_INVALID, "ilu_factor_bits is 64 or 32, not %d", value);
-    c->ilu_factor_bits = value;
-    return RDC_OK;
-  }
-  if (!std::strcmp(key, "solve_method")) {   // the Krylov method of rdc_solve and rdc_solve_mixed
-    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "solve_method is 0 (BiCGStab) or 1 (GMRES), not %d", value);
-    c->solve_method = value;
-    return RDC_OK;
-  }
-  if (!std::strcmp(key, "gmres_restart")) {
-    if (value < 1 || value > GMRES_MAX_RESTART) return fail(c, RDC_ERR_INVALID, "gmres_restart is 1 .. %d, not %d", GMRES_MAX_RESTART, value);
-    c->gmres_restart = value;
-    return RDC_OK;
-  }
-  if (!std::strcmp(key, "gmres_refine")) {
-    if (value != 0 && value != 1) return fail(c, RDC_ERR_INVALID, "gmres_refine is 0 or 1, not %d", value);
-    c->gmres_refine = value;
-    return RDC_OK;
-  }
   if (!std::strcmp(key, "const_rows")) {   // rdc_const_rows.h: a contract with the caller about the value array, not a tuning knob of a kernel
     if (!const_rows_mode_ok(value)) return fail(c, RDC_ERR_INVALID, "%s", CONST_ROWS_REFUSED);
     c->const_rows.mode = value;
     return RDC_OK;
   }
+  if (solve_option_known(key)) return solve_options_set(c->sopt, key, value, c->err, sizeof(c->err));   // the two tables of rdc_options.h
   return options_set(c->opt, key, value, c->err, sizeof(c->err));
 }
 
@@ -1251,705 +1084,6 @@ int rdc_tet4_cluster_info(rdc_ctx* c, int32_t* mode, int32_t* active, int64_t* n
   if (n_elem_visits) *n_elem_visits = lists ? L.n_elem_visits : 0;
   if (lds_bytes) *lds_bytes = c->tet4_cl_active ? (int64_t)c->tet4_cl_lds : 0;
   return RDC_OK;
-}
-
-// what rdc_solve.hip needs of the context; uploads the block column list the first time (4 bytes per node block)
-static int solve_view(rdc_ctx* c, bool want_work, bool want_f32, SolveDev* d) {
-  int rc = set_device(c);
-  if (rc) return rc;
-  const HostPrep& P = c->ms.prep;
-  if (P.nvar != 3 && P.nvar != 5) return fail(c, RDC_ERR_UNSUPPORTED, "the linear solve kernels exist for 3 and 5 unknowns per node, not %d", P.nvar);
-  if (!c->ms.solve.bcol_ready) {
-    if ((rc = dev_upload(c, c->buf.solve.bcol, P.bcol))) return rc;
-    RDC_HIP(c, hipStreamSynchronize(c->stream));
-    c->ms.solve.bcol_ready = true;
-  }
-  d->nvar = P.nvar; d->n_owned = P.n_owned; d->n_nodes = P.n_node;
-  d->bptr = (const int64_t*)c->buf.mesh.bptr.p; d->bcol = (const int32_t*)c->buf.solve.bcol.p;
-  d->val = (const double*)c->buf.out.val.p; d->rhs = (const double*)c->buf.out.rhs.p;
-  d->stream = c->stream;
-  if (want_work) {
-    if ((rc = dev_alloc(c, c->buf.solve.work, solve_work_bytes(P.nvar, P.n_owned)))) return rc;
-    if (!c->solve_rec) RDC_HIP(c, hipHostMalloc((void**)&c->solve_rec, sizeof(SolveScal), hipHostMallocDefault));
-    d->work = (double*)c->buf.solve.work.p;
-    d->host_rec = c->solve_rec;
-  }
-  if (want_f32) {
-    if (!c->ms.solve.voff_ready) {   // float offset of every owned node's padded rows (rdc_solve.h, f32_row_stride)
-      std::vector<int64_t> voff((size_t)P.n_owned + 1, 0);
-      for (int64_t n = 0; n < P.n_owned; n++) voff[(size_t)n + 1] = voff[(size_t)n] + P.nvar * f32_row_stride(P.nvar, P.bptr[(size_t)n + 1] - P.bptr[(size_t)n]);
-      if ((rc = dev_upload(c, c->buf.solve.voff, voff))) return rc;
-      RDC_HIP(c, hipStreamSynchronize(c->stream));
-      if ((rc = dev_alloc(c, c->buf.solve.val32, (size_t)voff.back() * sizeof(float)))) return rc;
-      c->ms.solve.voff_ready = true;
-    }
-    d->voff = (const int64_t*)c->buf.solve.voff.p;
-    d->val32 = (float*)c->buf.solve.val32.p;
-  }
-  return RDC_OK;
-}
-
-// The multigrid hierarchy of the mesh: built on the host and uploaded at the first multigrid solve (rdc_solve.h, mg_build),
-// two allocations that mg_place (rdc_solve.h) measures and then carves into the arrays of every level.  d must come from
-// solve_view(want_work).
-// measures and allocates the two arenas of a hierarchy, places it (mg_place) and uploads its lists
-static int mg_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps, const std::vector<MgHalo>* halos) {
-  const HostPrep& P = c->ms.prep;
-  MgDev& g = c->ms.solve.mg;
-  const int64_t blocks = P.bptr[(size_t)P.n_owned];
-  MgArena idx, val;
-  mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {}, halos);   // no bases: measures
-  int rc;
-  if ((rc = dev_alloc(c, c->buf.solve.mg_idx, idx.used))) return rc;
-  if ((rc = dev_alloc(c, c->buf.solve.mg_val, val.used))) return rc;
-  idx = MgArena{(char*)c->buf.solve.mg_idx.p};
-  val = MgArena{(char*)c->buf.solve.mg_val.p};
-  hipError_t e = hipSuccess;
-  mg_place(steps, P.nvar, P.n_owned, blocks, idx, val, g, [&](void* at, const void* list, size_t bytes) {
-    if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
-  }, halos);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host lists go out of scope
-  if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the multigrid lists failed: %s", hipGetErrorString(e));
-  return RDC_OK;
-}
-
-// The colour lists of the Gauss-Seidel smoother, one per level of the hierarchy `steps` describes: coloured on the host, validated,
-// and uploaded into one allocation that mg_gs_place measures and then carves (first solve with "mg_smoother" = 1 on a mesh).
-static int gs_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps) {
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  std::vector<MgColours> cols(steps.size() + 1);
-  for (size_t l = 0; l < cols.size(); l++) {
-    const bool ok = l == 0 ? mg_colour(P.n_owned, P.bptr.data(), P.bcol.data(), cols[0])
-                           : mg_colour(steps[l - 1].n, steps[l - 1].bptr.data(), steps[l - 1].bcol.data(), cols[l]);
-    if (!ok)
-      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern of multigrid level %d is not structurally symmetric: two coupled nodes share "
-                  "a colour, and a Gauss-Seidel sweep (\"mg_smoother\" = 1) over such colours would race", (int)l);
-  }
-  MgArena arena;
-  MgGsDev g;
-  mg_gs_place(cols, arena, g, [](void*, const void*, size_t) {});   // no base: measures
-  int rc = dev_alloc(c, c->buf.solve.mg_gs, arena.used);
-  if (rc) return rc;
-  arena = MgArena{(char*)c->buf.solve.mg_gs.p};
-  S.gs_cols = std::move(cols);
-  hipError_t e = hipSuccess;
-  mg_gs_place(S.gs_cols, arena, S.gs, [&](void* at, const void* list, size_t bytes) {
-    if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
-  });
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the colour lists failed: %s", hipGetErrorString(e));
-  S.gs_ready = true;
-  return RDC_OK;
-}
-
-static int mg_view(rdc_ctx* c, SolveDev* d) {
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  MgDev& g = S.mg;
-  if (S.mg_dist) S.mg_ready = S.mg_dist = false;
-  const bool want_gs = c->mg_smoother == 1 && !S.gs_ready;   // the hierarchy of a mesh is always the same: its colours outlive a rebuild
-  if (!S.mg_ready || want_gs) {
-    std::vector<MgLevelHost> steps;
-    if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
-      return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
-    int rc;
-    if (want_gs && (rc = gs_upload(c, steps))) return rc;   // first: a refusal leaves the context as it was
-    if (!S.mg_ready && (rc = mg_upload(c, steps, nullptr))) return rc;
-    S.mg_ready = true;
-  }
-  g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
-  g.omega = 1e-3 * c->mg_omega_permille;
-  d->mg = &g;
-  if (c->mg_smoother == 1) {
-    S.gs.fuse = c->mg_gs_fuse != 0;
-    d->gs = &S.gs;
-  }
-  return RDC_OK;
-}
-
-// The lists of the block ILU(0) of the mesh (rdc_solve.h, ilu_build: colours, rows in elimination order), built on the host and
-// uploaded at the first solve with RDC_PRECOND_ILU0 or RDC_PRECOND_ILU0_LOCAL, and the two allocations ilu_place measures and then
-// carves.  One set per mesh serves both values: on a context with ghost nodes -- only the callers of the rank-local factor get here
-// with one -- the lists are those of the owned square and M p and M s have a ghost tail; without ghosts they are what they always
-// were.  d must come from solve_view.
-static int ilu_view(rdc_ctx* c, SolveDev* d) {
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  if (!S.ilu_ready) {
-    IluHost H;
-    int64_t where = -1;
-    const int bad = ilu_build(P.n_owned, P.bptr.data(), P.bcol.data(), H, &where, P.n_owned < P.n_node);
-    if (bad == 1)
-      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern is not structurally symmetric: two coupled nodes share a colour, and the "
-                  "block ILU(0) (precond %d) eliminates colour by colour", (int)RDC_PRECOND_ILU0);
-    if (bad) return fail(c, RDC_ERR_UNSUPPORTED, "node %lld has no diagonal block in the pattern: no block ILU(0)", (long long)where);
-    const int64_t blocks = P.bptr[(size_t)P.n_owned];
-    MgArena idx, val;
-    IluDev g;
-    ilu_place(H, P.nvar, P.n_owned, blocks, idx, val, g, [](void*, const void*, size_t) {}, P.n_node);   // no bases: measures
-    int rc;
-    if ((rc = dev_alloc(c, c->buf.solve.ilu_idx, idx.used))) return rc;
-    if ((rc = dev_alloc(c, c->buf.solve.ilu_val, val.used))) return rc;
-    idx = MgArena{(char*)c->buf.solve.ilu_idx.p};
-    val = MgArena{(char*)c->buf.solve.ilu_val.p};
-    S.ilu_host = std::move(H);
-    hipError_t e = hipSuccess;
-    ilu_place(S.ilu_host, P.nvar, P.n_owned, blocks, idx, val, S.ilu, [&](void* at, const void* list, size_t bytes) {
-      if (e == hipSuccess) e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream);
-    }, P.n_node);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "upload of the ILU(0) lists failed: %s", hipGetErrorString(e));
-    S.ilu_ready = true;
-    S.ilu_factored = false;
-  }
-  S.ilu.want32 = c->ilu_factor_bits == 32;
-  if (S.ilu.want32 && !S.ilu.val32) {   // the third allocation: the fp32 copy of the factor, from the first call that wants it
-    const std::vector<int64_t> foff = ilu_f32_offsets(P.n_owned, P.bptr.data(), S.ilu_host, P.nvar);
-    MgArena f32;
-    IluDev g;
-    ilu_place_f32(foff, f32, g, [](void*, const void*, size_t) {});   // no base: measures
-    int rc;
-    if ((rc = dev_alloc(c, c->buf.solve.ilu_f32, f32.used))) return rc;
-    f32 = MgArena{(char*)c->buf.solve.ilu_f32.p};
-    hipError_t e = hipSuccess;
-    ilu_place_f32(foff, f32, S.ilu, [&](void* at, const void* list, size_t bytes) { e = hipMemcpyAsync(at, list, bytes, hipMemcpyHostToDevice, c->stream); });
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // foff is a local
-    if (e != hipSuccess) {
-      S.ilu.foff = nullptr; S.ilu.val32 = nullptr;
-      return fail(c, RDC_ERR_HIP, "upload of the offsets of the fp32 ILU(0) factor failed: %s", hipGetErrorString(e));
-    }
-  }
-  d->ilu = &S.ilu;
-  return RDC_OK;
-}
-
-// The state of restarted GMRES for the option "gmres_restart" as it stands: one allocation that gmres_carve (rdc_solve.h) measures
-// and then carves, made at the first call that needs it on a mesh and remade when the restart length has grown.  d must come from
-// solve_view(want_work).
-static int gmres_view(rdc_ctx* c, SolveDev* d) {
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  const int m = c->gmres_restart;
-  if (m > S.gmres_cap) {
-    const size_t bytes = gmres_carve(P.nvar, P.n_owned, m, nullptr).bytes;
-    S.gmres_cap = 0;
-    int rc = dev_alloc(c, c->buf.solve.gmres, bytes);
-    if (rc) return rc;   // the message gives the byte count
-    S.gmres_cap = m;
-  }
-  if (!c->gmres_rec) RDC_HIP(c, hipHostMalloc((void**)&c->gmres_rec, sizeof(GmresRec), hipHostMallocDefault));
-  S.gmres = gmres_carve(P.nvar, P.n_owned, m, (double*)c->buf.solve.gmres.p);
-  d->gmres = &S.gmres;
-  d->gmres_rec = c->gmres_rec;
-  d->gmres_refine = c->gmres_refine != 0;
-  return RDC_OK;
-}
-
-int rdc_solve_gmres_stats(rdc_ctx* c, int32_t* restart, int64_t* basis_bytes, int32_t* cycles) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.gmres_solved) return fail(c, RDC_ERR_STATE, "no GMRES solve (\"solve_method\" = 1) has run on this mesh");
-  if (restart) *restart = c->ms.solve.gmres_restart;
-  if (basis_bytes) *basis_bytes = (int64_t)(c->ms.solve.gmres_restart + 1) * c->ms.prep.n_owned * c->ms.prep.nvar * (int64_t)sizeof(double);
-  if (cycles) *cycles = c->ms.solve.gmres_cycles;
-  return RDC_OK;
-}
-
-int rdc_solve_ilu_stats(rdc_ctx* c, float* setup_ms, int64_t* bytes, int32_t* n_colours) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.ilu_ready) return fail(c, RDC_ERR_STATE, "no solve with the block ILU(0) preconditioner has run on this mesh");
-  if (setup_ms) *setup_ms = c->ms.solve.ilu.setup_ms;
-  if (bytes) *bytes = (int64_t)(c->buf.solve.ilu_idx.bytes + c->buf.solve.ilu_val.bytes + c->buf.solve.ilu_f32.bytes);
-  if (n_colours) *n_colours = c->ms.solve.ilu.n_colours;
-  return RDC_OK;
-}
-
-int rdc_solve_ilu_factor_bits(rdc_ctx* c, int32_t* bits) {
-  if (!c || !bits) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.ilu_ready || !c->ms.solve.ilu.bits)
-    return fail(c, RDC_ERR_STATE, "no solve or apply hook with the block ILU(0) preconditioner has run on this mesh");
-  *bits = c->ms.solve.ilu.bits;
-  return RDC_OK;
-}
-
-int rdc_solve_mg_levels(rdc_ctx* c, int32_t* n_levels, int64_t* nodes, int64_t* blocks, int cap) {
-  if (!c || !n_levels || cap < 0 || (cap > 0 && (!nodes || !blocks))) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
-  *n_levels = c->ms.solve.mg.n_levels;
-  for (int l = 0; l < c->ms.solve.mg.n_levels && l < cap; l++) { nodes[l] = c->ms.solve.mg.lv[l].n; blocks[l] = c->ms.solve.mg.lv[l].blocks; }
-  return RDC_OK;
-}
-
-int rdc_solve_mg_stats(rdc_ctx* c, float* setup_ms, int64_t* level_bytes) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.mg_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve has run on this mesh");
-  if (setup_ms) *setup_ms = c->ms.solve.mg.setup_ms;
-  if (level_bytes) *level_bytes = (int64_t)(c->buf.solve.mg_idx.bytes + c->buf.solve.mg_val.bytes);
-  return RDC_OK;
-}
-
-int rdc_solve_mg_colours(rdc_ctx* c, int32_t* n_colours, int cap) {
-  if (!c || cap < 0 || (cap > 0 && !n_colours)) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh || !c->ms.solve.gs_ready) return fail(c, RDC_ERR_STATE, "no multigrid solve with the Gauss-Seidel smoother has run on this mesh");
-  for (int l = 0; l < c->ms.solve.gs.n_levels && l < cap; l++) n_colours[l] = c->ms.solve.gs.lv[l].n_colours;
-  return RDC_OK;
-}
-
-int rdc_csr_matvec(rdc_ctx* c, const double* d_x, double* d_y) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
-  SolveDev d;
-  int rc = solve_view(c, false, false, &d);
-  if (rc) return rc;
-  RDC_HIP(c, solve_matvec(d, d_x, d_y));
-  return RDC_OK;
-}
-
-// with_right: the preconditioners applied from the right on top of block Jacobi's system count (the solve entries)
-static bool known_precond(int precond, bool with_right) {
-  return precond == RDC_PRECOND_NONE || precond == RDC_PRECOND_JACOBI || precond == RDC_PRECOND_BLOCK_JACOBI ||
-         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL));
-}
-
-int rdc_csr_scale_f32(rdc_ctx* c, int precond) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (!known_precond(precond, false)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
-  c->ms.solve.f32_copy = false;
-  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt, for `precond`
-  SolveDev d;
-  int rc = solve_view(c, true, true, &d);
-  if (rc) return rc;
-  int bad = 0, overflow = 0;
-  if (c->ms.prep.n_owned > 0) RDC_HIP(c, solve_scale_f32(d, precond, &bad, &overflow));
-  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks are not invertible: no fp32 copy", bad);
-  if (overflow > 0) return fail(c, RDC_ERR_INVALID, "%d blocks of D^-1 A hold an entry that is not finite in fp32: no fp32 copy", overflow);
-  c->ms.solve.f32_copy = true;
-  return RDC_OK;
-}
-
-int rdc_csr_matvec_f32(rdc_ctx* c, const double* d_x, double* d_y) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (!d_x || !d_y) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (!c->ms.solve.f32_copy) return fail(c, RDC_ERR_INVALID, "this mesh has no fp32 copy: call rdc_csr_scale_f32 or rdc_solve_mixed first");
-  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
-  SolveDev d;
-  int rc = solve_view(c, false, true, &d);
-  if (rc) return rc;
-  RDC_HIP(c, solve_matvec_f32(d, d_x, d_y));
-  return RDC_OK;
-}
-
-// the single-partition entries on a context with ghost nodes (multigrid: the cycle is asked for)
-static int refuse_ghosted(rdc_ctx* c, bool multigrid) {
-  if (multigrid && c->mg_smoother == 1)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
-                "partitions needs a rule for the ghost values and is not implemented", (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
-  return fail(c, RDC_ERR_UNSUPPORTED, "the context has ghost nodes (%lld owned of %lld): a solve across partitions needs a halo "
-              "exchange inside every iteration and is not implemented; rdc_csr_matvec works on such a context",
-              (long long)c->ms.prep.n_owned, (long long)c->ms.prep.n_node);
-}
-
-static int solve_call(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info, bool mixed) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;
-  if (!p || !d_x || !info) return fail(c, RDC_ERR_INVALID, "null argument");
-  if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
-  if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
-    return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
-  if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
-  if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
-  if (mixed && p->precond == RDC_PRECOND_ILU0 && c->ilu_factor_bits != 32)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve, not rdc_solve_mixed", (int)RDC_PRECOND_ILU0);
-  if (mixed && p->precond == RDC_PRECOND_ILU0_LOCAL && c->ilu_factor_bits != 32)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve or rdc_solve_dist, "
-                "not rdc_solve_mixed", (int)RDC_PRECOND_ILU0_LOCAL);
-  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, p->precond == RDC_PRECOND_MULTIGRID);
-  if (c->ms.prep.n_owned == 0) {   // no rows, no unknowns: nothing to launch
-    *info = rdc_solve_info();
-    info->matrix_bits = 64;
-    return RDC_OK;
-  }
-  SolveDev d;
-  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
-  int rc = solve_view(c, true, mixed, &d);
-  if (rc) return rc;
-  if (p->precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
-  rdc_solve_params q = *p;
-  if (q.precond == RDC_PRECOND_ILU0_LOCAL) q.precond = RDC_PRECOND_ILU0;   // no ghosts: the owned square is the matrix
-  if (q.precond == RDC_PRECOND_ILU0) {
-    if ((rc = ilu_view(c, &d))) return rc;
-    c->ms.solve.ilu_factored = false;
-  }
-  if (c->solve_method == 1 && (rc = gmres_view(c, &d))) return rc;
-  RDC_HIP(c, solve_run(d, q, d_x, info, mixed));
-  if (d.gmres) {
-    c->ms.solve.gmres_solved = true;
-    c->ms.solve.gmres_restart = d.gmres->restart;
-    c->ms.solve.gmres_cycles = d.gmres->cycles;
-  }
-  if (q.precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
-  if (mixed) c->ms.solve.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
-  c->ms.solve.mg_values = p->precond == RDC_PRECOND_MULTIGRID;
-  return RDC_OK;
-}
-
-int rdc_solve(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, false); }
-
-int rdc_solve_mixed(rdc_ctx* c, const rdc_solve_params* p, double* d_x, rdc_solve_info* info) { return solve_call(c, p, d_x, info, true); }
-
-int rdc_solve_gmres_arnoldi(rdc_ctx* c, int precond, int mixed, const double* d_v0, int steps, double* d_V, double* H, int32_t* steps_done) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt
-  if (!d_v0 || !d_V || !H || !steps_done) return fail(c, RDC_ERR_INVALID, "null argument");
-  if (!known_precond(precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
-  if (steps < 1 || steps > c->gmres_restart)
-    return fail(c, RDC_ERR_INVALID, "steps must be 1 .. \"gmres_restart\" = %d, not %d", c->gmres_restart, steps);
-  if (mixed && (precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL) && c->ilu_factor_bits != 32)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) has an FP64 factor only: mixed = 0, or \"ilu_factor_bits\" = 32", precond);
-  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, precond == RDC_PRECOND_MULTIGRID);
-  *steps_done = 0;
-  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
-  SolveDev d;
-  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
-  int rc = solve_view(c, true, mixed != 0, &d);
-  if (rc) return rc;
-  if (precond == RDC_PRECOND_MULTIGRID && (rc = mg_view(c, &d))) return rc;
-  if (precond == RDC_PRECOND_ILU0_LOCAL) precond = RDC_PRECOND_ILU0;   // no ghosts: the owned square is the matrix
-  if (precond == RDC_PRECOND_ILU0) {
-    if ((rc = ilu_view(c, &d))) return rc;
-    c->ms.solve.ilu_factored = false;
-  }
-  if ((rc = gmres_view(c, &d))) return rc;
-  int done = 0, bad = 0, bits = 64;
-  RDC_HIP(c, solve_gmres_arnoldi(d, precond, mixed != 0, d_v0, steps, d_V, H, &done, &bad, &bits));
-  if (precond == RDC_PRECOND_ILU0) c->ms.solve.ilu_factored = true;
-  if (mixed) c->ms.solve.f32_copy = bits == 32 && bad == 0;
-  c->ms.solve.mg_values = precond == RDC_PRECOND_MULTIGRID;
-  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks or pivots are not invertible: nothing was run", bad);
-  *steps_done = done;
-  return RDC_OK;
-}
-
-int rdc_solve_mg_apply(rdc_ctx* c, int mixed, const double* d_in, double* d_out) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;
-  if (!d_in || !d_out) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, true);
-  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
-  SolveDev d;
-  if (mixed) c->ms.solve.f32_copy = false;   // rebuilt from the current values by this call
-  int rc = solve_view(c, true, mixed != 0, &d);
-  if (rc) return rc;
-  if ((rc = mg_view(c, &d))) return rc;
-  int bad = 0, bits = 64;
-  RDC_HIP(c, solve_mg_apply(d, mixed != 0, d_in, d_out, &bad, &bits));
-  if (mixed) c->ms.solve.f32_copy = bits == 32 && bad == 0;
-  c->ms.solve.mg_values = true;
-  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks of the multigrid levels are not invertible: no cycle was applied", bad);
-  return RDC_OK;
-}
-
-// the two hooks of one application; local: rdc_solve_ilu_local_apply, which takes a context with ghost nodes (the factor of its owned square)
-static int ilu_apply_call(rdc_ctx* c, const double* d_in, double* d_out, bool local) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;   // D^-1 in the work buffer is rebuilt
-  if (!d_in || !d_out) return fail(c, RDC_ERR_INVALID, "null vector");
-  if (!local && c->ms.prep.n_owned < c->ms.prep.n_node) return refuse_ghosted(c, false);
-  if (c->ms.prep.n_owned == 0) return RDC_OK;   // no rows
-  SolveDev d;
-  int rc = solve_view(c, true, false, &d);
-  if (rc) return rc;
-  if ((rc = ilu_view(c, &d))) return rc;
-  c->ms.solve.ilu_factored = false;
-  int bad = 0;
-  RDC_HIP(c, solve_ilu_apply(d, d_in, d_out, &bad));
-  c->ms.solve.ilu_factored = true;
-  if (bad > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks or ILU(0) pivots are not invertible: nothing was applied", bad);
-  return RDC_OK;
-}
-
-int rdc_solve_ilu_apply(rdc_ctx* c, const double* d_in, double* d_out) { return ilu_apply_call(c, d_in, d_out, false); }
-
-int rdc_solve_ilu_local_apply(rdc_ctx* c, const double* d_in, double* d_out) { return ilu_apply_call(c, d_in, d_out, true); }
-
-// the two downloads.  Both write a node-block CSR over the columns the factor has: private position p of a node goes to the block of the
-// same column in the CSR row (bcol ascends, and the owned columns of a row are its leading ones), rows of own = the node's owned
-// blocks, nodes one behind the other.  Without ghosts own is the whole row, and this is the layout of the CSR values.
-static int ilu_download_call(rdc_ctx* c, double* val, double* uinv, bool local) {
-  if (!c) return RDC_ERR_INVALID;
-  const SolveState& S = c->ms.solve;
-  if (!c->ms.have_mesh || !S.ilu_ready || !S.ilu_factored)
-    return fail(c, RDC_ERR_STATE, "no rdc_solve_ilu_apply or solve with the block ILU(0) preconditioner has run on this mesh");
-  const HostPrep& P = c->ms.prep;
-  if (!local && P.n_owned < P.n_node) return refuse_ghosted(c, false);
-  int rc = set_device(c);
-  if (rc) return rc;
-  const int nv = P.nvar;
-  const int64_t n = P.n_owned, blocks = P.bptr[(size_t)n];
-  std::vector<double> priv(val ? (size_t)blocks * nv * nv : 0);
-  if (val && blocks) RDC_HIP(c, hipMemcpyAsync(priv.data(), S.ilu.val, priv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (uinv && n) RDC_HIP(c, hipMemcpyAsync(uinv, S.ilu.uinv, (size_t)n * nv * nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  RDC_HIP(c, hipStreamSynchronize(c->stream));
-  if (val) {
-    int64_t o0 = 0;   // owned blocks of the nodes before i
-    for (int64_t i = 0; i < n; i++) {
-      const int64_t b0 = P.bptr[(size_t)i], nl = S.ilu_host.nlow[(size_t)i];
-      const int64_t own = S.ilu_host.nown.empty() ? P.bptr[(size_t)i + 1] - b0 : S.ilu_host.nown[(size_t)i];
-      for (int64_t p = 0; p < own; p++) {
-        const int64_t k = std::lower_bound(P.bcol.begin() + b0, P.bcol.begin() + b0 + own, S.ilu_host.pcol[(size_t)(b0 + p)]) - (P.bcol.begin() + b0);
-        for (int a = 0; a < nv; a++)
-          for (int b = 0; b < nv; b++)
-            val[(int64_t)nv * nv * o0 + ((int64_t)a * own + k) * nv + b] = priv[(size_t)ilu_value_offset(b0, nv, own, nl, a, p, b)];
-      }
-      o0 += own;
-    }
-  }
-  return RDC_OK;
-}
-
-int rdc_solve_ilu_download(rdc_ctx* c, double* val, double* uinv) { return ilu_download_call(c, val, uinv, false); }
-
-int rdc_solve_ilu_local_download(rdc_ctx* c, double* val, double* uinv) { return ilu_download_call(c, val, uinv, true); }
-
-int rdc_solve_mg_level_download(rdc_ctx* c, int level, double* val, double* dinv) {
-  if (!c) return RDC_ERR_INVALID;
-  const SolveState& S = c->ms.solve;
-  if (!c->ms.have_mesh || !S.mg_ready || !S.mg_values)
-    return fail(c, RDC_ERR_STATE, "no rdc_solve_mg_apply or multigrid solve has run on this mesh, or a later call has overwritten what it built");
-  if (level < 0 || level >= S.mg.n_levels) return fail(c, RDC_ERR_INVALID, "level %d: the hierarchy has the levels 0 .. %d", level, S.mg.n_levels - 1);
-  if (level == 0 && val) return fail(c, RDC_ERR_INVALID, "level 0 is the matrix itself (rdc_csr_download): val must be NULL");
-  int rc = set_device(c);
-  if (rc) return rc;
-  const MgLevelDev& L = S.mg.lv[level];
-  const size_t nv2 = (size_t)c->ms.prep.nvar * c->ms.prep.nvar;
-  const double* d_dinv = L.dinv;
-  if (level == 0) {
-    SolveDev d;
-    if ((rc = solve_view(c, true, false, &d))) return rc;
-    d_dinv = solve_dinv(d);
-  }
-  if (val && L.blocks) RDC_HIP(c, hipMemcpyAsync(val, L.val, (size_t)L.blocks * nv2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (dinv && L.n) RDC_HIP(c, hipMemcpyAsync(dinv, d_dinv, (size_t)L.n * nv2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  RDC_HIP(c, hipStreamSynchronize(c->stream));
-  return RDC_OK;
-}
-
-int rdc_solve_dist_plan(rdc_ctx* c, int64_t n_send, const int32_t* send_nodes) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  if (n_send < 0 || (n_send > 0 && !send_nodes)) return fail(c, RDC_ERR_INVALID, "bad send list");
-  const HostPrep& P = c->ms.prep;
-  c->ms.solve.plan_ready = c->ms.solve.peers_ready = false;
-  c->ms.solve.mg_values = false;
-  if (c->ms.solve.mg_dist) c->ms.solve.mg_ready = c->ms.solve.mg_dist = false;   // a new plan drops the hierarchy built on the old one
-  c->ms.solve.halo0 = MgHalo();
-  const int64_t n_int = c->opt.interior_nodes > 0 ? c->opt.interior_nodes : 0;
-  int64_t where = 0;
-  switch (dist_plan_check(P.n_owned, P.bptr.data(), P.bcol.data(), n_int, n_send, send_nodes, &where)) {
-    case 1: return fail(c, RDC_ERR_INVALID, "send entry %lld is node %d, which is not one of the %lld owned nodes", (long long)where,
-                        (int)send_nodes[where], (long long)P.n_owned);
-    case 2: return fail(c, RDC_ERR_INVALID, "\"interior_nodes\" = %lld exceeds the %lld owned nodes", (long long)n_int, (long long)P.n_owned);
-    case 3: return fail(c, RDC_ERR_INVALID, "node %lld lies below \"interior_nodes\" = %lld but its row has a ghost column", (long long)where, (long long)n_int);
-    default: break;
-  }
-  int rc = set_device(c);
-  if (rc) return rc;
-  c->ms.solve.send_nodes.assign(send_nodes, send_nodes + n_send);
-  if ((rc = dev_upload(c, c->buf.solve.send, c->ms.solve.send_nodes))) return rc;
-  RDC_HIP(c, hipStreamSynchronize(c->stream));
-  c->ms.solve.dist.n_nodes = P.n_node; c->ms.solve.dist.n_int = n_int; c->ms.solve.dist.n_send = n_send;
-  c->ms.solve.plan_ready = true;
-  return RDC_OK;
-}
-
-int rdc_solve_dist_plan_peers(rdc_ctx* c, int32_t n_peers, const int64_t* send_count, const int64_t* ghost_count) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;
-  if (!c->ms.solve.plan_ready) return fail(c, RDC_ERR_STATE, "no send list: call rdc_solve_dist_plan first");
-  if (n_peers < 0 || (n_peers > 0 && (!send_count || !ghost_count))) return fail(c, RDC_ERR_INVALID, "bad peer counts");
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  MgHalo plan;
-  switch (mg_halo_plan(P.n_owned, P.n_node - P.n_owned, S.dist.n_send, S.send_nodes.data(), n_peers, send_count, ghost_count, plan)) {
-    case 0: break;
-    case 1: return fail(c, RDC_ERR_INVALID, "a peer count is negative");
-    case 2: return fail(c, RDC_ERR_INVALID, "the send counts of the %d peers do not add up to the %lld entries of the send list", (int)n_peers, (long long)S.dist.n_send);
-    case 3: return fail(c, RDC_ERR_INVALID, "the ghost counts of the %d peers do not add up to the %lld ghost nodes", (int)n_peers, (long long)(P.n_node - P.n_owned));
-    default: return fail(c, RDC_ERR_INVALID, "bad send list");
-  }
-  if (S.mg_dist) S.mg_ready = S.mg_dist = false;   // new peers drop the hierarchy built on the old ones
-  S.halo0 = std::move(plan);
-  S.peers_ready = true;
-  return RDC_OK;
-}
-
-// The hierarchy of rdc_solve_dist_mg: built collectively at the first such solve after a plan (rdc_solve.h: mg_dist_aggregate, the
-// exchange of aggregate numbers, mg_dist_coarsen; mg_dist_goes_on decides on all-reduced sums) and placed by mg_place with its
-// ghost layers.  The two collective calls of a step go through the communicator on a small device buffer.  *comm_rc: a callback's
-// non-zero return (the caller reports RDC_ERR_COMM).  d must carry the work buffer.
-static int mg_view_dist(rdc_ctx* c, SolveDev* d, const rdc_solve_comm_sized* comm, int* comm_rc) {
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  MgDev& g = S.mg;
-  if (S.mg_ready && !S.mg_dist) S.mg_ready = false;
-  if (!S.mg_ready) {
-    if (P.bptr[(size_t)P.n_owned] >= ((int64_t)1 << 31)) return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
-    std::vector<MgLevelHost> steps;
-    std::vector<MgHalo> halos(1, S.halo0);
-    const int peers = halos[0].peers();
-    // staging: [send ids | received ids | 2 sums], sized for level 0 (no level below has more to send or receive)
-    const int64_t ns0 = halos[0].n_send(), ng0 = halos[0].n_ghost;
-    int rc = dev_alloc(c, c->buf.solve.mg_stage, (size_t)(ns0 + ng0 + 8) * sizeof(double));
-    if (rc) return rc;
-    double* d_send = (double*)c->buf.solve.mg_stage.p; double* d_recv = d_send + ns0; double* d_sum = d_recv + ng0;
-    std::vector<double> ids_out, ids_in;
-    hipError_t e = hipSuccess;
-    const int64_t* bptr = P.bptr.data();
-    const int32_t* bcol = P.bcol.data();
-    const char* refused = nullptr;
-    for (;;) {
-      const MgHalo& F = halos.back();
-      MgLevelHost L;
-      ids_out.assign((size_t)F.n_send() + 1, 0.0);
-      mg_dist_aggregate(F, bptr, bcol, L, ids_out.data());
-      double sums[2] = {(double)F.n_owned, L.n < F.n_owned ? 1.0 : 0.0};
-      if ((e = hipMemcpyAsync(d_sum, sums, sizeof(sums), hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
-      if ((*comm_rc = comm->base.allreduce_sum(comm->base.user, d_sum, 2, (void*)c->stream))) break;
-      if ((e = hipMemcpyAsync(sums, d_sum, sizeof(sums), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
-      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
-      if (!mg_dist_goes_on((int)halos.size(), sums[0], sums[1])) break;
-      // the owners' aggregate numbers of this rank's ghosts: one exchange of width 1
-      std::vector<int64_t> so(F.send_off), go(F.ghost_off);
-      ids_in.assign((size_t)F.n_ghost + 1, -1.0);
-      if (F.n_send() && (e = hipMemcpyAsync(d_send, ids_out.data(), (size_t)F.n_send() * sizeof(double), hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
-      if ((*comm_rc = comm->exchange_sized_begin(comm->base.user, d_send, d_recv, peers, so.data(), go.data(), (void*)c->stream))) break;
-      if ((*comm_rc = comm->exchange_sized_end(comm->base.user, (void*)c->stream))) break;
-      if (F.n_ghost && (e = hipMemcpyAsync(ids_in.data(), d_recv, (size_t)F.n_ghost * sizeof(double), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
-      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
-      MgHalo C;
-      if (!mg_dist_coarsen(F, bptr, bcol, ids_in.data(), L, C)) { refused = "a multigrid level would have 2^31 node blocks or more, or a peer sent no aggregate number"; break; }
-      steps.push_back(std::move(L));
-      halos.push_back(std::move(C));
-      bptr = steps.back().bptr.data();
-      bcol = steps.back().bcol.data();
-    }
-    (void)hipStreamSynchronize(c->stream);
-    if (*comm_rc) return RDC_ERR_COMM;
-    if (e != hipSuccess) return fail(c, RDC_ERR_HIP, "building the multigrid levels failed: %s", hipGetErrorString(e));
-    if (refused) return fail(c, RDC_ERR_UNSUPPORTED, "%s", refused);
-    S.mg_off.assign(halos.size(), std::vector<int64_t>());
-    for (size_t l = 1; l < halos.size(); l++) {
-      for (int64_t o : halos[l].send_off) S.mg_off[l].push_back(o * P.nvar);
-      for (int64_t o : halos[l].ghost_off) S.mg_off[l].push_back(o * P.nvar);
-    }
-    if ((rc = mg_upload(c, steps, &halos))) return rc;
-    for (size_t l = 1; l < halos.size(); l++) {
-      g.lv[l].send_off = S.mg_off[l].data();
-      g.lv[l].ghost_off = S.mg_off[l].data() + peers + 1;
-    }
-    S.mg_ready = S.mg_dist = true;
-  }
-  g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
-  g.omega = 1e-3 * c->mg_omega_permille;
-  d->mg = &g;
-  d->peers = S.halo0.peers();
-  return RDC_OK;
-}
-
-// the two partitioned entries.  sized: rdc_solve_dist_mg, the multigrid preconditioner and nothing else; without it rdc_solve_dist
-static int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, const rdc_solve_comm_sized* sized, int mixed,
-                           double* d_x, rdc_solve_info* info) {
-  if (!c) return RDC_ERR_INVALID;
-  if (!c->ms.have_mesh) return fail(c, RDC_ERR_STATE, "no mesh uploaded");
-  c->ms.solve.mg_values = false;   // the work buffer takes the layout of a partitioned solve
-  if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
-  if (c->solve_method == 1)
-    return fail(c, RDC_ERR_UNSUPPORTED, "GMRES across partitions is not implemented (\"solve_method\" = 1): allreduce_sum carries at most %d doubles "
-                "and a GMRES step sums up to \"gmres_restart\" + 1; set \"solve_method\" to 0 for %s", DIST_RECORD, sized ? "rdc_solve_dist_mg" : "rdc_solve_dist");
-  if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum || (sized && (!sized->exchange_sized_begin || !sized->exchange_sized_end)))
-    return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
-  if (p->max_its < 1) return fail(c, RDC_ERR_INVALID, "max_its must be at least 1");
-  if (!(p->rel_tol >= 0.0) || !(p->abs_tol >= 0.0) || !std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol))
-    return fail(c, RDC_ERR_INVALID, "tolerances must be finite and not negative");
-  if (!std::isfinite(p->rhs_scale)) return fail(c, RDC_ERR_INVALID, "rhs_scale must be finite");
-  if (!known_precond(p->precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", (int)p->precond);
-  if (p->precond == RDC_PRECOND_ILU0)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour and is "
-                "not implemented: rdc_solve on a context without ghost nodes, or the rank-local factor (precond %d)", (int)RDC_PRECOND_ILU0,
-                (int)RDC_PRECOND_ILU0_LOCAL);
-  if (sized && p->precond != RDC_PRECOND_MULTIGRID)
-    return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
-                (int)RDC_PRECOND_MULTIGRID, (int)p->precond);
-  if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
-  const bool ilu_local = p->precond == RDC_PRECOND_ILU0_LOCAL;
-  if (ilu_local && mixed && c->ilu_factor_bits != 32)
-    return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve_dist with mixed = 0",
-                (int)RDC_PRECOND_ILU0_LOCAL);
-  if (sized && c->mg_smoother == 1)
-    return fail(c, RDC_ERR_UNSUPPORTED, "rdc_solve_dist_mg smooths with damped Jacobi only: a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
-                "partitions needs a rule for the ghost values and is not implemented");
-  const HostPrep& P = c->ms.prep;
-  SolveState& S = c->ms.solve;
-  if (P.n_owned < P.n_node && !S.plan_ready)
-    return fail(c, RDC_ERR_STATE, "the context has ghost nodes (%lld owned of %lld) and no send list: call rdc_solve_dist_plan first",
-                (long long)P.n_owned, (long long)P.n_node);
-  if (sized && P.n_owned < P.n_node && !S.peers_ready)
-    return fail(c, RDC_ERR_STATE, "the context has ghost nodes (%lld owned of %lld) and no peer counts: call rdc_solve_dist_plan_peers first",
-                (long long)P.n_owned, (long long)P.n_node);
-  if (sized && !S.peers_ready && S.halo0.send_off.empty()) {   // no ghosts and no peer counts: no peers
-    if (S.mg_dist) S.mg_ready = S.mg_dist = false;
-    S.halo0 = MgHalo();
-    S.halo0.n_owned = P.n_owned; S.halo0.send_off.assign(1, 0); S.halo0.ghost_off.assign(1, 0);
-    mg_halo_slots(S.halo0);
-  }
-  SolveDev d;
-  if (mixed) S.f32_copy = false;   // rebuilt from the current values by this call
-  int rc = solve_view(c, false, mixed != 0, &d);
-  if (rc) return rc;
-  d.dist = S.plan_ready ? S.dist : DistDims{P.n_node, 0, 0};
-  d.send_nodes = (const int32_t*)c->buf.solve.send.p;
-  if ((rc = dev_alloc(c, c->buf.solve.work, solve_work_bytes(P.nvar, P.n_owned, &d.dist)))) return rc;
-  if (!c->solve_rec) RDC_HIP(c, hipHostMalloc((void**)&c->solve_rec, sizeof(SolveScal), hipHostMallocDefault));
-  d.work = (double*)c->buf.solve.work.p;
-  d.host_rec = c->solve_rec;
-  int comm_rc = 0;
-  d.comm = comm; d.sized = sized; d.comm_rc = &comm_rc;
-  if (sized) {
-    rc = mg_view_dist(c, &d, sized, &comm_rc);
-    if (comm_rc) return fail(c, RDC_ERR_COMM, "a communication callback returned %d while the multigrid levels were built", comm_rc);
-    if (rc) return rc;
-  }
-  if (ilu_local) {
-    if ((rc = ilu_view(c, &d))) return rc;
-    S.ilu_factored = false;
-  }
-  const hipError_t e = solve_run(d, *p, d_x, info, mixed != 0);
-  if (ilu_local && !comm_rc && e == hipSuccess) S.ilu_factored = true;
-  if (comm_rc) {
-    (void)hipStreamSynchronize(c->stream);   // x holds the last iterate
-    return fail(c, RDC_ERR_COMM, "a communication callback returned %d; the solve was abandoned", comm_rc);
-  }
-  RDC_HIP(c, e);
-  if (mixed) S.f32_copy = info->matrix_bits == 32 && info->reason != RDC_SOLVE_BAD_DIAGONAL;
-  return RDC_OK;
-}
-
-int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) {
-  return solve_dist_call(c, p, comm, nullptr, mixed, d_x, info);
-}
-
-int rdc_solve_dist_mg(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed, double* d_x, rdc_solve_info* info) {
-  return solve_dist_call(c, p, comm ? &comm->base : nullptr, comm, mixed, d_x, info);
 }
 
 int rdc_clamp_nonnegative(rdc_ctx* c, int field) {

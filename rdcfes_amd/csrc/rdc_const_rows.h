@@ -26,8 +26,8 @@ template <class K>
 ConstRowsKey const_rows_key(const K& k) { return ConstRowsKey{k.Tsec_c, k.Tsec_h, k.Tdec, k.Tupt == 0.0}; }
 
 // option "const_rows" (rdc_set_option): 0 = every launch writes every row, 1 = as decided below (default), 2 = as 1, and the caller
-// promises not to write the value or coordinate arrays through the pointers it was given.  Kept beside the tuning table of
-// rdc_options.h, as the solver settings are: that table's keys are a fixed list the CPU suite holds it to
+// promises not to write the value or coordinate arrays through the pointers it was given.  Kept beside the two tables of
+// rdc_options.h: it is a contract, not a setting, and those tables' keys are fixed lists the CPU suite holds them to
 constexpr const char* CONST_ROWS_REFUSED = "const_rows must be 0 (always write every row), 1 or 2 (1, and the caller does not write through device pointers)";
 inline bool const_rows_mode_ok(const int v) { return v >= 0 && v <= 2; }
 

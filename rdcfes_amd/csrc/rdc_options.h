@@ -1,5 +1,6 @@
-// rdc_options.h — the tuning options of rdc_set_option (include/rdc_assembly.h): one table, from which the struct, the
-// key list and the setter are generated.  Host only (no HIP): the CPU suite compiles it with g++ (tests/host_options_shim.cpp).
+// rdc_options.h — what rdc_set_option (include/rdc_assembly.h) sets: the tuning options of the assembly and the settings of the
+// linear solve, one table each, from which the struct, the key list and the setter are generated.  Host only (no HIP): the CPU
+// suite compiles it with g++ (tests/host_options_shim.cpp).
 #ifndef RDC_OPTIONS_H
 #define RDC_OPTIONS_H
 
@@ -45,33 +46,49 @@ namespace rdc {
   X(ev_lds, int, 54000, RDC_ANY, v)                          /* LDS bytes per workgroup the element-visit clusters are sized for (next rdc_mesh_upload) */ \
   X(kernel, int, 0, RDC_ONLY(v == 0 || v == 1 || v == 2 || v == 3 || v == 5 || v == 7, "kernel must be 0, 1, 2, 3, 5 or 7, not %d", v), v) /* TET4: 1 = k_tet4_rowgather, 2 = rg2, 3 = rg3, 5 = rg5, 7 = element visits */
 
-struct Options {
+// The settings of the linear solve (rdc_capi_solve.hip), rows of the same shape.  The three bounds that rdc_solve.h owns stand here
+// as literals (this header knows no HIP); rdc_capi_internal.h holds them to MG_OMEGA_PERMILLE, GMRES_DEFAULT_RESTART, GMRES_MAX_RESTART.
+constexpr int SOLVE_OPT_MG_OMEGA = 600, SOLVE_OPT_GMRES_RESTART = 30, SOLVE_OPT_GMRES_MAX_RESTART = 128;
+#define RDC_SOLVE_OPTIONS(X)                                                                                                                           \
+  X(mg_omega, int, SOLVE_OPT_MG_OMEGA, RDC_ONLY(v >= 1 && v <= 1999, "mg_omega is the damping in thousandths, 1 .. 1999, not %d", v), v)               \
+  X(mg_smoother, int, 0, RDC_ONLY(v == 0 || v == 1, "mg_smoother is 0 or 1, not %d", v), v)    /* 0 = damped block Jacobi, 1 = multicolour Gauss-Seidel */ \
+  X(mg_gs_fuse, int, 1, RDC_ONLY(v == 0 || v == 1, "mg_gs_fuse is 0 or 1, not %d", v), v)      /* small levels sweep in one launch (0: one launch per colour everywhere) */ \
+  X(ilu_factor_bits, int, 64, RDC_ONLY(v == 64 || v == 32, "ilu_factor_bits is 64 or 32, not %d", v), v) /* what the ILU(0) sweeps stream: the FP64 factor or its fp32 copy */ \
+  X(solve_method, int, 0, RDC_ONLY(v == 0 || v == 1, "solve_method is 0 (BiCGStab) or 1 (GMRES), not %d", v), v) /* rdc_solve, rdc_solve_mixed */      \
+  X(gmres_restart, int, SOLVE_OPT_GMRES_RESTART, RDC_ONLY(v >= 1 && v <= SOLVE_OPT_GMRES_MAX_RESTART, "gmres_restart is 1 .. %d, not %d", SOLVE_OPT_GMRES_MAX_RESTART, v), v) \
+  X(gmres_refine, int, 0, RDC_ONLY(v == 0 || v == 1, "gmres_refine is 0 or 1, not %d", v), v)  /* 1 = always a second Gram-Schmidt pass */
+
+// of a table: the struct of its members, its key list, and its setter -- what rdc_set_option does with a key of that table: RDC_OK,
+// or RDC_ERR_INVALID with the message in err and o unchanged (a key of another table is unknown to it)
 #define RDC_OPTION_MEMBER(key, type, def, check, store) type key = def;
-  RDC_OPTIONS(RDC_OPTION_MEMBER)
-#undef RDC_OPTION_MEMBER
-};
-
-inline const char* const* option_keys(int* n) {
 #define RDC_OPTION_KEY(key, type, def, check, store) #key,
-  static const char* const keys[] = {RDC_OPTIONS(RDC_OPTION_KEY)};
-#undef RDC_OPTION_KEY
-  *n = (int)(sizeof(keys) / sizeof(keys[0]));
-  return keys;
-}
-
-// what rdc_set_option does: RDC_OK, or RDC_ERR_INVALID with the message in err and o unchanged
-inline int options_set(Options& o, const char* key, int value, char* err, size_t errlen) {
-  const int v = value;
 #define RDC_OPTION_SET(name, type, def, check, store) \
   if (!std::strcmp(key, #name)) {                     \
     check                                             \
     o.name = (store);                                 \
     return RDC_OK;                                    \
   }
-  RDC_OPTIONS(RDC_OPTION_SET)
-#undef RDC_OPTION_SET
-  std::snprintf(err, errlen, "unknown option '%s'", key);
-  return RDC_ERR_INVALID;
+#define RDC_OPTION_TABLE(Struct, TABLE, keys_fn, set_fn)                                           \
+  struct Struct { TABLE(RDC_OPTION_MEMBER) };                                                      \
+  inline const char* const* keys_fn(int* n) {                                                      \
+    static const char* const keys[] = {TABLE(RDC_OPTION_KEY)};                                     \
+    *n = (int)(sizeof(keys) / sizeof(keys[0]));                                                    \
+    return keys;                                                                                   \
+  }                                                                                                \
+  inline int set_fn(Struct& o, const char* key, int value, char* err, size_t errlen) {             \
+    const int v = value;                                                                           \
+    TABLE(RDC_OPTION_SET)                                                                          \
+    std::snprintf(err, errlen, "unknown option '%s'", key);                                        \
+    return RDC_ERR_INVALID;                                                                        \
+  }
+RDC_OPTION_TABLE(Options, RDC_OPTIONS, option_keys, options_set)
+RDC_OPTION_TABLE(SolveOptions, RDC_SOLVE_OPTIONS, solve_option_keys, solve_options_set)
+
+inline bool solve_option_known(const char* key) {   // which table rdc_set_option asks
+  int n = 0;
+  const char* const* keys = solve_option_keys(&n);
+  while (n > 0 && std::strcmp(key, keys[n - 1])) n--;
+  return n > 0;
 }
 
 }  // namespace rdc

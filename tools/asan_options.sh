@@ -1,5 +1,6 @@
 #!/bin/bash
-# AddressSanitizer + UBSan run of the option table (rdc_options.h) as a stand-alone host program: no device, no Python.
+# AddressSanitizer + UBSan run of the two option tables (rdc_options.h) and the validity rule of the solve artefacts
+# (rdc_solve_state.h) as a stand-alone host program: no device, no Python.
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tests/_build
