@@ -598,9 +598,10 @@ int rdc_solve_ilu_local_download(rdc_ctx* ctx, double* val, double* uinv);
  * solve on a mesh, remade when "gmres_restart" grows, freed with the mesh; RDC_ERR_ALLOC with the byte count if it cannot be made.
  * With "solve_method" = 0 nothing of it is allocated, launched or read.
  * rdc_solve_dist and rdc_solve_dist_mg return RDC_ERR_UNSUPPORTED under "solve_method" = 1, before any callback is called and with
- * x untouched: allreduce_sum carries at most 8 doubles, and a GMRES step sums up to restart + 1. */
+ * x untouched: allreduce_sum carries at most 8 doubles, and a GMRES step sums up to restart + 1.  GMRES across ranks is an entry
+ * of its own with a communicator of its own, rdc_solve_dist_gmres (below, behind rdc_solve_dist_mg). */
 /* The last GMRES solve on this mesh: *restart = the restart length it ran with, *basis_bytes = device bytes of its basis
- * ((restart + 1) * n_owned * nvar * 8), *cycles = the cycles it began (restarts + 1; 0 if it needed no step).  Any pointer may be
+ * ((restart + 1) * n_owned * nvar * 8; behind rdc_solve_dist_gmres this rank's, whose slots have ghost tails: n_nodes for n_owned), *cycles = the cycles it began (restarts + 1; 0 if it needed no step).  Any pointer may be
  * NULL.  RDC_ERR_STATE before any GMRES solve on this mesh. */
 int rdc_solve_gmres_stats(rdc_ctx* ctx, int32_t* restart, int64_t* basis_bytes, int32_t* cycles);
 /* Test hook, read-only like rdc_solve_mg_apply: the Arnoldi process itself, which a converged solve cannot show (the true residual
@@ -699,6 +700,57 @@ typedef struct rdc_solve_comm_sized {
  * rdc_solve_mg_stats then report this rank's levels: the nodes it owns and the node blocks of its rows. */
 int rdc_solve_dist_mg(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed,
                       double* d_x, rdc_solve_info* info);
+
+/* ---- restarted GMRES(m) across ranks (additive: RDC_ABI_VERSION stays 3): the GMRES of rdc_solve / rdc_solve_mixed under
+ * "solve_method" = 1, on the contexts, plans and preconditioners of rdc_solve_dist and rdc_solve_dist_mg.  With RDC_PRECOND_ILU0_LOCAL
+ * this is what PETSc runs by default under mpirun: GMRES(30), one classical Gram-Schmidt pass, block Jacobi between the ranks,
+ * ILU(0) inside each.  The entry runs GMRES whatever "solve_method" is (the option chooses for the entries that have no method in
+ * their name) and honours "gmres_restart" and "gmres_refine".
+ *
+ * What is exchanged ("Across ranks").  Per Arnoldi step j: the ghost values of v_j (of M v_j with a right
+ * preconditioner), one exchange of the plan's size before the operator application, received straight into the ghost tail of the
+ * vector; one wide all-reduce of j + 2 doubles per Gram-Schmidt pass (h_0..j and (w, w) together; one pass, or two with
+ * "gmres_refine" = 1) and one of 1 double for the norm of the remainder: 2 or 3 wide all-reduces per step.  Per cycle, and once at
+ * the start: the ghost values of x and one allreduce_sum for the true residual (6 doubles the first time, 5 behind an update of x:
+ * the fifth carries the count of entries that would not have been finite, 4 otherwise).  Without multigrid a solve of `iterations`
+ * steps and `restarts` restarts therefore makes iterations + restarts + 2 exchanges, (2 or 3) * iterations wide all-reduces and
+ * restarts + 2 calls of allreduce_sum.  With RDC_PRECOND_MULTIGRID every application of the cycle (one per step, one per update of
+ * x) adds the exchanges of rdc_solve_dist_mg's cycle; the cycle has no inner product.  Dots and norms run over the owned rows only;
+ * everything that decides -- the residual estimate, the flags of a step, y -- is computed from all-reduced values, so every rank
+ * takes the same branch.
+ *
+ * The communicator.  `sized` is that of rdc_solve_dist_mg; its sized pair may be NULL unless p->precond == RDC_PRECOND_MULTIGRID.
+ * allreduce_sum_wide sums d_vals[0 .. n) over the ranks in place, 1 <= n <= 128 + 2, under the stream contract of allreduce_sum: the
+ * library has enqueued what produces d_vals on `hip_stream`, the sums are ordered on it when the callback returns, and every rank
+ * gets the same bits.  An MPI adapter: MPI_Allreduce of n doubles. */
+typedef struct rdc_solve_comm_wide {
+  rdc_solve_comm_sized sized;   /* the sized pair may be NULL unless p->precond == RDC_PRECOND_MULTIGRID */
+  int (*allreduce_sum_wide)(void* user, double* d_vals, int32_t n, void* hip_stream);   /* in place, n <= 128 + 2 */
+} rdc_solve_comm_wide;
+/* The contract of rdc_solve_dist (mixed: of its mixed form), with GMRES(m) as the method.  precond: RDC_PRECOND_NONE, _JACOBI,
+ * _BLOCK_JACOBI; RDC_PRECOND_ILU0_LOCAL (mixed != 0 only with "ilu_factor_bits" = 32, as in rdc_solve_dist); RDC_PRECOND_MULTIGRID
+ * through the sized exchanges and the rank-local hierarchy of rdc_solve_dist_mg (RDC_ERR_STATE on a ghosted context without peer
+ * counts, RDC_ERR_UNSUPPORTED under "mg_smoother" = 1).  RDC_PRECOND_ILU0 is RDC_ERR_UNSUPPORTED.  RDC_ERR_INVALID for a NULL
+ * callback (the sized pair only if the multigrid is asked for); RDC_ERR_STATE on a context with ghost nodes and no plan.  Every
+ * refusal comes before any callback and leaves x untouched.  Everything rdc_solve_dist promises carries over: rdc_solve_info is
+ * global and identical on every rank, the ghost rows of x are filled on exit, b = 0 gives x = 0, RDC_SOLVE_BAD_DIAGONAL on every rank
+ * leaves the owned rows untouched, a callback that returns non-zero gives RDC_ERR_COMM and no further callback, no NaN or inf is ever
+ * written into x, residual_norm is the true FP64 residual.  iterations counts Arnoldi steps, restarts the cycles after the first;
+ * rdc_solve_gmres_stats then reports this rank's basis.  A context without ghosts and a communicator of world size 1 returns, bit for
+ * bit (info and x), what rdc_solve / rdc_solve_mixed return under "solve_method" = 1.  Blocks the host until done.  Never modifies
+ * the CSR values or the rhs.  Not implemented across ranks: RDC_PRECOND_ILU0, "mg_smoother" = 1, a merged single-reduction
+ * orthogonalisation. */
+int rdc_solve_dist_gmres(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_comm_wide* comm, int mixed,
+                         double* d_x, rdc_solve_info* info);
+/* Test hook: the collective form of rdc_solve_gmres_arnoldi, on the communicator, plan and preconditioners of rdc_solve_dist_gmres.
+ * Every rank passes its owned rows of v_0 (d_v0: DEVICE, n_owned*nvar doubles) and receives its owned rows of the basis (d_V: DEVICE,
+ * *steps_done + 1 vectors of n_owned*nvar doubles, room for steps + 1); H (HOST, (restart + 1) x restart, column-major) and
+ * *steps_done are identical on every rank.  Callbacks: one allreduce_sum (6 doubles: the counters of the set-up, so that all ranks
+ * refuse singular blocks together), with RDC_PRECOND_MULTIGRID those that build the hierarchy, one wide all-reduce of 1 double for
+ * ||v_0||, then per step what a step of rdc_solve_dist_gmres makes.  Refusals as rdc_solve_dist_gmres, and steps out of
+ * 1 .. "gmres_restart" or bad diagonal blocks on any rank are RDC_ERR_INVALID on every rank.  Synchronises. */
+int rdc_solve_dist_gmres_arnoldi(rdc_ctx* ctx, const rdc_solve_comm_wide* comm, int precond, int mixed, const double* d_v0, int steps,
+                                 double* d_V, double* H, int32_t* steps_done);
 
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */

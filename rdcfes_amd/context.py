@@ -403,6 +403,72 @@ class AssemblyContext:
         self._ck(rc)
         return info
 
+    def _dist_plan_for(self, comm):
+        """the send list of comm, and its peer counts if it has the sized exchange, uploaded once per mesh and communicator"""
+        if self._dist_plan is comm:
+            return
+        self.solve_dist_plan(comm.send_nodes)
+        if getattr(comm, "sized_struct", None) is not None:
+            sc, gc = (np.ascontiguousarray(a, dtype=np.int64) for a in comm.peer_counts)
+            i64p = C.POINTER(C.c_int64)
+            self._ck(self._lib.rdc_solve_dist_plan_peers(self._h, sc.size, sc.ctypes.data_as(i64p), gc.ctypes.data_as(i64p)))
+        self._dist_plan = comm
+
+    def solve_dist_gmres(self, comm, x=None, *, field=None, rel_tol=1e-8, abs_tol=0.0, max_its=10000, precond=PRECOND_BLOCK_JACOBI,
+                         rhs_scale=1.0, mixed=False):
+        """rdc_solve_dist_gmres: right-preconditioned restarted GMRES(m) across the ranks of comm, which must be a
+        halo.SolveComm(..., wide=True).  Arguments, x and the returned SolveInfo as solve_dist; iterations counts Arnoldi steps and
+        restarts the cycles after the first, as in solve under set_option("solve_method", 1).  GMRES runs whatever "solve_method"
+        is; "gmres_restart" and "gmres_refine" are honoured.  precond: PRECOND_NONE, _JACOBI, _BLOCK_JACOBI, PRECOND_ILU0_LOCAL
+        (block Jacobi between the ranks, ILU(0) inside each: PETSc's default under mpirun) and PRECOND_MULTIGRID (the rank-local
+        hierarchy of solve_dist).  An exception raised inside a callback of comm is re-raised here."""
+        wide = getattr(comm, "wide_struct", None)
+        if wide is None:
+            raise ValueError("solve_dist_gmres needs a communicator with the wide all-reduce: SolveComm(..., wide=True)")
+        if (x is None) == (field is None):
+            raise ValueError("give either a device address or field=")
+        if field is not None:
+            x = self.field_device_ptr(int(field), self.n_node * self.nvar)
+        self._dist_plan_for(comm)
+        p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
+        info = SolveInfo()
+        comm.error = None
+        rc = self._lib.rdc_solve_dist_gmres(self._h, C.byref(p), C.byref(wide), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
+        if comm.error is not None:
+            err, comm.error = comm.error, None
+            raise err
+        self._ck(rc)
+        return info
+
+    def gmres_arnoldi_dist(self, comm, v0, steps, precond, mixed=False):
+        """rdc_solve_dist_gmres_arnoldi, numpy in, numpy out (tests; collective): v0 = this rank's owned rows (n_owned * nvar) ->
+        (V [steps_done + 1][n_owned * nvar], this rank's owned rows of the basis; H [restart + 1][restart], the same on every
+        rank).  comm: SolveComm(..., wide=True); restart as in gmres_arnoldi."""
+        import torch
+        wide = getattr(comm, "wide_struct", None)
+        if wide is None:
+            raise ValueError("gmres_arnoldi_dist needs a communicator with the wide all-reduce: SolveComm(..., wide=True)")
+        v0 = np.ascontiguousarray(v0, dtype=np.float64).reshape(-1)
+        n = self.n_owned * self.nvar
+        if v0.size != n:
+            raise ValueError("v0 must have n_owned * nvar entries")
+        self._dist_plan_for(comm)
+        restart = getattr(self, "_gmres_restart", 30)
+        dev = torch.device("cuda", self.device)
+        vd = torch.from_numpy(v0).to(dev)
+        Vd = torch.zeros(max((int(steps) + 1) * n, 1), dtype=torch.float64, device=dev)
+        H = np.zeros((restart, restart + 1), dtype=np.float64)   # column-major (restart + 1) x restart
+        done = C.c_int32()
+        torch.cuda.synchronize(dev)
+        comm.error = None
+        rc = self._lib.rdc_solve_dist_gmres_arnoldi(self._h, C.byref(wide), int(precond), 1 if mixed else 0, C.c_void_p(vd.data_ptr()),
+                                                    int(steps), C.c_void_p(Vd.data_ptr()), _dp(H), C.byref(done))
+        if comm.error is not None:
+            err, comm.error = comm.error, None
+            raise err
+        self._ck(rc)
+        return Vd.cpu().numpy()[:(int(steps) + 1) * n].reshape(int(steps) + 1, n)[:done.value + 1], H.T.copy()
+
     def mg_levels(self):
         """[(nodes, node blocks)] of every level of the hierarchy of the last multigrid solve on this mesh, level 0 = the matrix"""
         n = C.c_int32()

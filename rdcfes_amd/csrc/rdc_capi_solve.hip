@@ -167,28 +167,31 @@ int ilu_view(rdc_ctx* c, SolveDev* d) {
 
 // The state of restarted GMRES for the option "gmres_restart" as it stands: one allocation that gmres_carve (rdc_solve.h) measures
 // and then carves, made at the first call that needs it on a mesh and remade when the restart length has grown.  d must come from
-// solve_view(want_work).
-int gmres_view(rdc_ctx* c, SolveDev* d) {
+// solve_view(want_work).  dist: the partitioned form, whose slots have ghost tails and which has the buffer of the wide all-reduce;
+// it is a little larger than the other for the same restart length, so the bytes at hand decide as well.
+int gmres_view(rdc_ctx* c, SolveDev* d, bool dist) {
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   const int m = c->sopt.gmres_restart;
-  if (m > S.gmres_cap) {
-    const size_t bytes = gmres_carve(P.nvar, P.n_owned, m, nullptr).bytes;
+  const int64_t n_nodes = dist ? P.n_node : -1;
+  const size_t bytes = gmres_carve(P.nvar, P.n_owned, m, nullptr, n_nodes).bytes;
+  if (m > S.gmres_cap || bytes > c->buf.solve.gmres.bytes) {
     S.gmres_cap = 0;
     int rc = dev_alloc(c, c->buf.solve.gmres, bytes);
     if (rc) return rc;   // the message gives the byte count
     S.gmres_cap = m;
   }
   if (!c->gmres_rec) RDC_HIP(c, hipHostMalloc((void**)&c->gmres_rec, sizeof(GmresRec), hipHostMallocDefault));
-  S.gmres = gmres_carve(P.nvar, P.n_owned, m, (double*)c->buf.solve.gmres.p);
+  S.gmres = gmres_carve(P.nvar, P.n_owned, m, (double*)c->buf.solve.gmres.p, n_nodes);
   d->gmres = &S.gmres;
   d->gmres_rec = c->gmres_rec;
   d->gmres_refine = c->sopt.gmres_refine != 0;
   return RDC_OK;
 }
 
-// what a partitioned entry adds to a call; sized: rdc_solve_dist_mg (null: rdc_solve_dist); rc: a callback's non-zero return
-struct DistCall { const rdc_solve_comm* comm; const rdc_solve_comm_sized* sized; int rc; };
+// what a partitioned entry adds to a call; sized: the levels below the matrix exchange (rdc_solve_dist_mg, and rdc_solve_dist_gmres
+// with the multigrid; null otherwise); wide: rdc_solve_dist_gmres and its hook; rc: a callback's non-zero return
+struct DistCall { const rdc_solve_comm* comm; const rdc_solve_comm_sized* sized; const rdc_solve_comm_wide* wide; int rc; };
 
 // The hierarchy of rdc_solve_dist_mg: built collectively at the first such solve after a plan (rdc_solve.h: mg_dist_aggregate, the
 // exchange of aggregate numbers, mg_dist_coarsen; mg_dist_goes_on decides on all-reduced sums) and placed by mg_place with its
@@ -285,14 +288,14 @@ int solve_do(rdc_ctx* c, const SolveCall& call, int32_t* precond, DistCall* dist
   if (dist) {
     d.dist = S.plan_ready ? S.dist : DistDims{P.n_node, 0, 0};
     d.send_nodes = (const int32_t*)c->buf.solve.send.p;
-    d.comm = dist->comm; d.sized = dist->sized; d.comm_rc = &dist->rc;
+    d.comm = dist->comm; d.sized = dist->sized; d.wide = dist->wide; d.comm_rc = &dist->rc;
   }
   int rc = solve_view(c, true, call.mixed, &d, dist ? &d.dist : nullptr);
   if (rc) return rc;
   if (call.multigrid() && (rc = dist ? mg_view_dist(c, &d, dist->sized, &dist->rc) : mg_view(c, &d))) return rc;
   if (precond && *precond == RDC_PRECOND_ILU0_LOCAL && P.n_owned == P.n_node) *precond = RDC_PRECOND_ILU0;
   if (call.ilu() && (rc = ilu_view(c, &d))) return rc;
-  if (call.gmres && (rc = gmres_view(c, &d))) return rc;
+  if (call.gmres && (rc = gmres_view(c, &d, dist != nullptr))) return rc;
   const hipError_t e = run(d);
   o->ran = e == hipSuccess;
   o->comm_failed = dist && dist->rc;
@@ -430,28 +433,21 @@ int ilu_download_call(rdc_ctx* c, double* val, double* uinv, bool local) {
   return RDC_OK;
 }
 
-// the two partitioned entries.  sized: rdc_solve_dist_mg, the multigrid preconditioner and nothing else; without it rdc_solve_dist
-int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, const rdc_solve_comm_sized* sized, int mixed,
-                    double* d_x, rdc_solve_info* info) {
-  int rc = solve_enter(c, SolveEntry::DIST);   // the work buffer takes the layout of a partitioned solve
-  if (rc) return rc;
-  if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
-  if (c->sopt.solve_method == 1)
-    return fail(c, RDC_ERR_UNSUPPORTED, "GMRES across partitions is not implemented (\"solve_method\" = 1): allreduce_sum carries at most %d doubles "
-                "and a GMRES step sums up to \"gmres_restart\" + 1; set \"solve_method\" to 0 for %s", DIST_RECORD, sized ? "rdc_solve_dist_mg" : "rdc_solve_dist");
-  if (!comm->exchange_begin || !comm->exchange_end || !comm->allreduce_sum || (sized && (!sized->exchange_sized_begin || !sized->exchange_sized_end)))
-    return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
-  if ((rc = check_solve_params(c, p))) return rc;
-  if (p->precond == RDC_PRECOND_ILU0)
+// What every partitioned entry refuses of a preconditioner and of the state of the context, behind its own argument checks.
+// sized: the call exchanges on the levels below the matrix (it runs the multigrid); mg_entry: it is rdc_solve_dist_mg, which runs
+// nothing else; any_precond: the entry takes the multigrid beside the others (rdc_solve_dist_gmres).  A context without ghosts and
+// without peer counts gets the halo of no peers.
+int dist_ready(rdc_ctx* c, int precond, bool sized, bool mg_entry, bool any_precond, int mixed) {
+  if (precond == RDC_PRECOND_ILU0)
     return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour and is "
                 "not implemented: rdc_solve on a context without ghost nodes, or the rank-local factor (precond %d)", (int)RDC_PRECOND_ILU0,
                 (int)RDC_PRECOND_ILU0_LOCAL);
-  if (sized && p->precond != RDC_PRECOND_MULTIGRID)
+  if (!any_precond && mg_entry && precond != RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
-                (int)RDC_PRECOND_MULTIGRID, (int)p->precond);
-  if (!sized && p->precond == RDC_PRECOND_MULTIGRID)
+                (int)RDC_PRECOND_MULTIGRID, precond);
+  if (!any_precond && !mg_entry && precond == RDC_PRECOND_MULTIGRID)
     return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
-  if (p->precond == RDC_PRECOND_ILU0_LOCAL && mixed && c->sopt.ilu_factor_bits != 32)
+  if (precond == RDC_PRECOND_ILU0_LOCAL && mixed && c->sopt.ilu_factor_bits != 32)
     return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve_dist with mixed = 0",
                 (int)RDC_PRECOND_ILU0_LOCAL);
   if (sized && c->sopt.mg_smoother == 1)
@@ -471,8 +467,32 @@ int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm*
     S.halo0.n_owned = P.n_owned; S.halo0.send_off.assign(1, 0); S.halo0.ghost_off.assign(1, 0);
     mg_halo_slots(S.halo0);
   }
-  DistCall dc{comm, sized, 0};
-  return solve_run_call(c, SolveCall{SolveEntry::DIST, p->precond, mixed != 0, false}, p, d_x, info, &dc);
+  return RDC_OK;
+}
+
+// the callbacks a partitioned call will use: the three of the base, the sized pair if it exchanges below the matrix, the wide all-reduce
+bool comm_complete(const rdc_solve_comm* comm, const rdc_solve_comm_sized* sized, const rdc_solve_comm_wide* wide) {
+  return comm->exchange_begin && comm->exchange_end && comm->allreduce_sum && (!sized || (sized->exchange_sized_begin && sized->exchange_sized_end)) &&
+         (!wide || wide->allreduce_sum_wide);
+}
+
+// the three partitioned solves.  sized: rdc_solve_dist_mg, the multigrid preconditioner and nothing else; wide: rdc_solve_dist_gmres,
+// GMRES whatever "solve_method" says, with every preconditioner of the other two; neither: rdc_solve_dist
+int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, const rdc_solve_comm_sized* sized,
+                    const rdc_solve_comm_wide* wide, int mixed, double* d_x, rdc_solve_info* info) {
+  int rc = solve_enter(c, SolveEntry::DIST);   // the work buffer takes the layout of a partitioned solve
+  if (rc) return rc;
+  if (!p || !d_x || !info || !comm) return fail(c, RDC_ERR_INVALID, "null argument");
+  if (!wide && c->sopt.solve_method == 1)
+    return fail(c, RDC_ERR_UNSUPPORTED, "GMRES across partitions is not implemented (\"solve_method\" = 1): allreduce_sum carries at most %d doubles "
+                "and a GMRES step sums up to \"gmres_restart\" + 1; set \"solve_method\" to 0 for %s", DIST_RECORD, sized ? "rdc_solve_dist_mg" : "rdc_solve_dist");
+  const bool mg_entry = sized != nullptr;
+  if (wide) sized = p->precond == RDC_PRECOND_MULTIGRID ? &wide->sized : nullptr;
+  if (!comm_complete(comm, sized, wide)) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
+  if ((rc = check_solve_params(c, p))) return rc;
+  if ((rc = dist_ready(c, p->precond, sized != nullptr, mg_entry, wide != nullptr, mixed))) return rc;
+  DistCall dc{comm, sized, wide, 0};
+  return solve_run_call(c, SolveCall{SolveEntry::DIST, p->precond, mixed != 0, wide != nullptr}, p, d_x, info, &dc);
 }
 
 }  // namespace
@@ -484,7 +504,8 @@ int rdc_solve_gmres_stats(rdc_ctx* c, int32_t* restart, int64_t* basis_bytes, in
   const SolveValid& valid = c->ms.solve.valid;
   if (!c->ms.have_mesh || !valid.gmres_solved) return fail(c, RDC_ERR_STATE, "no GMRES solve (\"solve_method\" = 1) has run on this mesh");
   if (restart) *restart = valid.gmres_restart;
-  if (basis_bytes) *basis_bytes = (int64_t)(valid.gmres_restart + 1) * c->ms.prep.n_owned * c->ms.prep.nvar * (int64_t)sizeof(double);
+  if (basis_bytes)   // (gmres_carve: a partitioned solve's slots have ghost tails)
+    *basis_bytes = (int64_t)(valid.gmres_restart + 1) * (valid.gmres_dist ? c->ms.prep.n_node : c->ms.prep.n_owned) * c->ms.prep.nvar * (int64_t)sizeof(double);
   if (cycles) *cycles = valid.gmres_cycles;
   return RDC_OK;
 }
@@ -656,7 +677,34 @@ int rdc_solve_dist_plan_peers(rdc_ctx* c, int32_t n_peers, const int64_t* send_c
   return RDC_OK;
 }
 
-int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) { return solve_dist_call(c, p, comm, nullptr, mixed, d_x, info); }
-int rdc_solve_dist_mg(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed, double* d_x, rdc_solve_info* info) { return solve_dist_call(c, p, comm ? &comm->base : nullptr, comm, mixed, d_x, info); }
+int rdc_solve_dist(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm* comm, int mixed, double* d_x, rdc_solve_info* info) { return solve_dist_call(c, p, comm, nullptr, nullptr, mixed, d_x, info); }
+int rdc_solve_dist_mg(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm_sized* comm, int mixed, double* d_x, rdc_solve_info* info) { return solve_dist_call(c, p, comm ? &comm->base : nullptr, comm, nullptr, mixed, d_x, info); }
+int rdc_solve_dist_gmres(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm_wide* comm, int mixed, double* d_x, rdc_solve_info* info) { return solve_dist_call(c, p, comm ? &comm->sized.base : nullptr, nullptr, comm, mixed, d_x, info); }
+
+int rdc_solve_dist_gmres_arnoldi(rdc_ctx* c, const rdc_solve_comm_wide* comm, int precond, int mixed, const double* d_v0, int steps, double* d_V,
+                                 double* H, int32_t* steps_done) {
+  int rc = solve_enter(c, SolveEntry::ARNOLDI);   // D^-1 in the work buffer is rebuilt, and the buffer takes the layout of a partitioned solve
+  if (rc) return rc;
+  if (!comm || !d_v0 || !d_V || !H || !steps_done) return fail(c, RDC_ERR_INVALID, "null argument");
+  const rdc_solve_comm_sized* sized = precond == RDC_PRECOND_MULTIGRID ? &comm->sized : nullptr;
+  if (!comm_complete(&comm->sized.base, sized, comm)) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
+  if (!known_precond(precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
+  if (steps < 1 || steps > c->sopt.gmres_restart)
+    return fail(c, RDC_ERR_INVALID, "steps must be 1 .. \"gmres_restart\" = %d, not %d", c->sopt.gmres_restart, steps);
+  if ((rc = dist_ready(c, precond, sized != nullptr, false, true, mixed))) return rc;
+  *steps_done = 0;
+  int done = 0;
+  SolveOutcome o;
+  DistCall dc{&comm->sized.base, sized, comm, 0};
+  SolveCall call{SolveEntry::ARNOLDI, precond, mixed != 0, true};
+  call.dist = true;
+  rc = solve_do(c, call, &precond, &dc, &o, [&](const SolveDev& d) {
+    return solve_gmres_arnoldi(d, precond, mixed != 0, d_v0, steps, d_V, H, &done, &o.bad_blocks, &o.matrix_bits);
+  });
+  if (rc) return rc;
+  if (o.bad_blocks > 0) return fail(c, RDC_ERR_INVALID, "%d diagonal blocks or pivots are not invertible: nothing was run", o.bad_blocks);
+  *steps_done = done;
+  return RDC_OK;
+}
 
 }  // extern "C"

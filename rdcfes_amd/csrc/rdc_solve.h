@@ -10,7 +10,8 @@
 // pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).  The fp32 copy of
 // the factor has a layout of its own beside them (ilu_f32_offset, ilu_f32_offsets, ilu_place_f32; tests/host_solve_ilu_f32_shim.cpp).
 // Restarted GMRES: the Givens step, the back substitution and the layout of its state (gmres_givens_step, gmres_back_substitute,
-// gmres_carve; tests/host_solve_gmres_shim.cpp, tests/host_solve_gmres_main.cpp).
+// gmres_carve; tests/host_solve_gmres_shim.cpp, tests/host_solve_gmres_main.cpp; the partitioned form of the state, with ghosted basis
+// slots and the buffer of the wide all-reduce: tests/host_solve_gmres_dist_shim.cpp, tests/host_solve_gmres_dist_main.cpp).
 //
 // Pattern (HostPrep::bptr / bcol): node n owns the blocks [bptr[n], bptr[n+1]); block k of the node couples it to
 // node bcol[bptr[n] + k] (ascending in k).  The nvar rows of a node share that list, and the values of the node lie
@@ -1013,8 +1014,13 @@ RDC_SOLVE_HD bool gmres_back_substitute(int ld, int k, const double* R, const do
 // w of step j); H: the raw Hessenberg matrix, R: its rotated form, both column-major (m + 1) x m; cs, sn [m]; g [m + 1]; y [m];
 // hpass [m + 1]: the coefficients of the orthogonalisation pass at hand; scal: [0] = beta^2 of the start, [1] = 1 / h_{j+1,j},
 // [2] = 1.0; partials: (m + 1) x vec_blocks, component-major (component c of workgroup b at c * vec_blocks + b); rec: the record.
+// Across ranks (rdc_solve_dist_gmres; n_nodes >= n_owned given): a slot has the stride of a ghosted vector, n_nodes * nvar, so that
+// the exchange of an operator application receives straight into the tail of v_j; every sum, scaling and combination still runs
+// over the n owned entries of a slot and never touches its tail.  red [m + 2]: this rank's sums of a step, which the wide
+// all-reduce turns into the global ones in place (j + 2 values of a Gram-Schmidt pass, or 1).  Without n_nodes there is no red and
+// the layout is that of the single-partition solve, byte for byte.
 struct GmresState {
-  double *V, *H, *R, *cs, *sn, *g, *y, *hpass, *scal, *partials;
+  double *V, *H, *R, *cs, *sn, *g, *y, *hpass, *scal, *red, *partials;
   GmresRec* rec;
   int restart;
   int64_t n, stride, vec_blocks, partial_count;
@@ -1023,13 +1029,14 @@ struct GmresState {
 };
 
 constexpr int GMRES_SCALARS = 8;
+constexpr int GMRES_WIDE_MAX = GMRES_MAX_RESTART + 2;   // what allreduce_sum_wide may be asked for at most (a step sums j + 2 <= restart + 1)
 
-inline GmresState gmres_carve(int nvar, int64_t n_owned, int restart, double* base) {
+inline GmresState gmres_carve(int nvar, int64_t n_owned, int restart, double* base, int64_t n_nodes = -1) {
   GmresState g = GmresState();
   const int m = restart;
   g.restart = m;
   g.n = n_owned * nvar;
-  g.stride = std::max<int64_t>(g.n, 1);
+  g.stride = std::max<int64_t>(std::max(n_nodes, n_owned) * nvar, 1);
   g.vec_blocks = vec_blocks(g.n);
   g.partial_count = (int64_t)(m + 1) * std::max<int64_t>(g.vec_blocks, 1);
   int64_t used = 0;
@@ -1039,6 +1046,7 @@ inline GmresState gmres_carve(int nvar, int64_t n_owned, int restart, double* ba
   g.H = take((int64_t)(m + 1) * m); g.R = take((int64_t)(m + 1) * m);
   g.cs = take(m); g.sn = take(m); g.g = take(m + 1); g.y = take(m); g.hpass = take(m + 1);
   g.scal = take(GMRES_SCALARS);
+  g.red = n_nodes >= 0 ? take(m + 2) : nullptr;
   g.partials = take(g.partial_count);
   g.rec = (GmresRec*)take((int64_t)(sizeof(GmresRec) / sizeof(double)));
   g.bytes = (size_t)used * sizeof(double);
@@ -1075,10 +1083,11 @@ struct SolveDev {
   DistDims dist;                       // n_nodes, interior nodes, length of the send list
   const int32_t* send_nodes = nullptr; // device copy of the send list (owned local node ids, send order)
   int* comm_rc = nullptr;              // out: the first non-zero return of a callback; nothing is called after it
-  // restarted GMRES (option "solve_method" = 1; single partition only).  gmres == nullptr is BiCGStab, and nothing below is read.
+  // restarted GMRES (option "solve_method" = 1, and rdc_solve_dist_gmres).  gmres == nullptr is BiCGStab, and nothing below is read.
   GmresState* gmres = nullptr;         // the state (gmres_carve), placed
   GmresRec* gmres_rec = nullptr;       // pinned: the record the host reads per Arnoldi step
   bool gmres_refine = false;           // option "gmres_refine": always a second Gram-Schmidt pass
+  const rdc_solve_comm_wide* wide = nullptr;   // rdc_solve_dist_gmres: comm = &wide->sized.base, and the all-reduce of a step's sums
 };
 
 // what solve_run returns after a callback has failed (*SolveDev::comm_rc tells its value)
@@ -1103,7 +1112,8 @@ hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int
 // Test hook (rdc_solve_gmres_arnoldi): behind the prologue of a solve with `precond` (the same host function), v_0 = v0 / ||v0|| and
 // `steps` Arnoldi steps with the kernels and the host loop of a cycle; d.gmres is set, d.mg / d.ilu as that solve needs them.  Copies
 // the *steps_done + 1 basis vectors into V (device) and the raw Hessenberg matrix into H (host, (restart + 1) x restart, column-major).
-// *bad_blocks > 0: nothing was run.  Synchronises.
+// *bad_blocks > 0: nothing was run.  Synchronises.  With d.comm and d.wide (rdc_solve_dist_gmres_arnoldi): collective, v0 and V hold
+// this rank's owned rows, the norm of v0 and every sum are global, H is the same on every rank.
 hipError_t solve_gmres_arnoldi(const SolveDev& d, int precond, bool mixed, const double* v0, int steps, double* V, double* H,
                                int* steps_done, int* bad_blocks, int* matrix_bits);
 // where the D^-1 of the last single-partition set-up lies in d.work (n_owned * nvar * nvar doubles)

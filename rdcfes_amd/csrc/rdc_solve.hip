@@ -46,7 +46,11 @@
 // system with the same right preconditioners.  Its orthogonalisation is two launches per step, k_gmres_dots (all inner products
 // of a step, every basis vector read once) and k_gmres_orth (the update, every basis vector read once); k_gmres_finalize sums
 // their partials in a fixed order and runs the Givens step in device memory, and the host reads one record per step.  Its state
-// is an allocation of its own (rdc_solve.h, gmres_carve).  Single partition only.
+// is an allocation of its own (rdc_solve.h, gmres_carve).  Across ranks (rdc_solve_dist_gmres): the same driver with a communicator,
+// as for BiCGStab.  The basis slots get the stride of a ghosted vector, so that apply_halo receives straight into the tail of v_j
+// (one k_halo_pack per step fills the send buffer; the pack is not folded into k_gmres_scale, which would need the node-to-slot
+// lists of the plan on the device); k_gmres_finalize becomes k_gmres_reduce, the wide all-reduce callback and k_gmres_advance, two
+// per step (three with "gmres_refine"); the overflow counter of the update of x rides in the record of the true residual behind it.
 //
 // Host side (below the kernels): `iteration` is the one BiCGStab iteration (fp32 copy, multigrid cycle and communicator are
 // arguments), `apply` the one entry to y = A_l x on any level in any form; `carve` (rdc_solve.h) is the one statement of the work
@@ -364,21 +368,25 @@ __global__ __launch_bounds__(1024) void k_finalize(const double* __restrict__ pa
 // Partitioned solve: k_finalize in two halves with the all-reduce between them.  k_reduce: this partition's sums, in the same
 // fixed order, into rec[0 .. 4); counters (the first residual of a solve): rec[4], rec[5] = this partition's bad_blocks and
 // f32_overflow, counts as doubles (exact below 2^53).  A flagged iteration (the flag is the same on every partition) sends zeros.
+// extra (GMRES across ranks, the true residual behind an update of x; never with counters): rec[4] = this partition's count of
+// entries of x that kept their value (GmresRec::overflow), so that it becomes global in the same all-reduce.
 __global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage,
-                                                 const SolveScal* __restrict__ scal, double* __restrict__ rec, int counters) {
+                                                 const SolveScal* __restrict__ scal, double* __restrict__ rec, int counters,
+                                                 const int32_t* __restrict__ extra) {
   __shared__ double sh[4][1024];
   const bool skip = stage != STAGE_INIT && scal->flag != 0;
   sum_partials(partials, nparts, ncomp, skip, sh);
   if (threadIdx.x != 0) return;
   for (int c = 0; c < 4; c++) rec[c] = sh[c][0];
-  rec[4] = counters ? (double)scal->bad_blocks : 0.0;
+  rec[4] = counters ? (double)scal->bad_blocks : extra ? (double)*extra : 0.0;
   rec[5] = counters ? (double)scal->f32_overflow : 0.0;
   rec[6] = 0.0; rec[7] = 0.0;
 }
 
 // k_advance: the scalars from the all-reduced record (one thread).  Every partition computes the same bits from the same bits.
-__global__ void k_advance(const double* __restrict__ rec, int stage, SolveScal* __restrict__ scal, int counters) {
+__global__ void k_advance(const double* __restrict__ rec, int stage, SolveScal* __restrict__ scal, int counters, int32_t* __restrict__ extra) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (extra) *extra = rec[4] < 2147483647.0 ? (int32_t)rec[4] : 2147483647;   // the global count, saturated
   if (stage != STAGE_INIT && scal->flag != 0) return;
   if (counters) {
     scal->bad_blocks = (int32_t)rec[4];
@@ -1264,17 +1272,9 @@ __global__ __launch_bounds__(256) void k_gmres_orth(const double* __restrict__ V
 }
 
 // The sums of `ncomp` components of component-major partials in a fixed order (one workgroup of 1024), four components at a time,
-// and what the step does with them.  DOTS: h_{0..j,j} of the first Gram-Schmidt pass and (w, w); DOTS2: the second pass, added to
-// the first; NORM: h_{j+1,j} = ||w||, the Givens step of column j in device memory, and the record; START (the hook): beta^2.
-__global__ __launch_bounds__(1024) void k_gmres_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage, int j,
-                                                         GmresState G) {
-  __shared__ double sh[4][1024];
-  __shared__ double tot[GMRES_MAX_RESTART + 1];
-  GmresRec* rec = G.rec;
-  if (stage != GMRES_STAGE_DOTS && stage != GMRES_STAGE_START && (rec->flag & GMRES_NOT_FINITE)) {   // a flagged step wrote no partials
-    if (threadIdx.x == 0 && stage == GMRES_STAGE_NORM) rec->hnext = 0.0;
-    return;
-  }
+// into tot (shared memory; valid for every thread on return).
+__device__ __forceinline__ void gmres_sum_partials(const double* __restrict__ partials, int64_t nparts, int ncomp, double (&sh)[4][1024],
+                                                   double* tot) {
   for (int c0 = 0; c0 < ncomp; c0 += 4) {
     const int nc = min(4, ncomp - c0);
     double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1291,7 +1291,18 @@ __global__ __launch_bounds__(1024) void k_gmres_finalize(const double* __restric
       for (int c = 0; c < nc; c++) tot[c0 + c] = sh[c][0];
     __syncthreads();
   }
-  if (threadIdx.x != 0) return;
+}
+
+// a flagged step wrote no partials: the stages behind its first sum have nothing to add up
+__device__ __forceinline__ bool gmres_stage_skipped(int stage, const GmresRec* rec) {
+  return stage != GMRES_STAGE_DOTS && stage != GMRES_STAGE_START && (rec->flag & GMRES_NOT_FINITE);
+}
+
+// What a step does with its sums (one thread).  DOTS: h_{0..j,j} of the first Gram-Schmidt pass and (w, w); DOTS2: the second pass,
+// added to the first; NORM: h_{j+1,j} = ||w||, the Givens step of column j in device memory, and the record; START (the hook):
+// beta^2.  tot: the sums, of this partition or, across ranks, of all of them -- the same bits in give the same bits out.
+__device__ __forceinline__ void gmres_advance(const double* tot, int stage, int j, const GmresState& G) {
+  GmresRec* rec = G.rec;
   const int ld = G.restart + 1;
   double* hcol = G.H + (int64_t)j * ld;
   if (stage == GMRES_STAGE_START) {
@@ -1324,6 +1335,41 @@ __global__ __launch_bounds__(1024) void k_gmres_finalize(const double* __restric
     if (hn == 0.0) rec->flag |= GMRES_HAPPY;
     else G.scal[1] = 1.0 / hn;
   }
+}
+
+// The sums of a step's partials and what the step does with them, in one launch: the single-partition form.
+__global__ __launch_bounds__(1024) void k_gmres_finalize(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage, int j,
+                                                         GmresState G) {
+  __shared__ double sh[4][1024];
+  __shared__ double tot[GMRES_MAX_RESTART + 1];
+  if (gmres_stage_skipped(stage, G.rec)) {
+    if (threadIdx.x == 0 && stage == GMRES_STAGE_NORM) G.rec->hnext = 0.0;
+    return;
+  }
+  gmres_sum_partials(partials, nparts, ncomp, sh, tot);
+  if (threadIdx.x != 0) return;
+  gmres_advance(tot, stage, j, G);
+}
+
+// Across ranks: k_gmres_finalize in two halves with the wide all-reduce between them.  k_gmres_reduce: this rank's sums, in the same
+// fixed order, into G.red[0 .. ncomp).  A skipped stage (the flag is the same on every rank) sends zeros.
+__global__ __launch_bounds__(1024) void k_gmres_reduce(const double* __restrict__ partials, int64_t nparts, int ncomp, int stage, GmresState G) {
+  __shared__ double sh[4][1024];
+  __shared__ double tot[GMRES_MAX_RESTART + 1];
+  const bool skip = gmres_stage_skipped(stage, G.rec);
+  if (!skip) gmres_sum_partials(partials, nparts, ncomp, sh, tot);
+  for (int k = threadIdx.x; k < ncomp; k += 1024) G.red[k] = skip ? 0.0 : tot[k];
+}
+
+// k_gmres_advance: the scalar work of the step on the all-reduced sums (one thread).  Every rank computes the same bits from the
+// same bits: the estimate, the flags and, later, y are global, and every branch the host takes on the record is collective.
+__global__ void k_gmres_advance(int stage, int j, GmresState G) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (gmres_stage_skipped(stage, G.rec)) {
+    if (stage == GMRES_STAGE_NORM) G.rec->hnext = 0.0;
+    return;
+  }
+  gmres_advance(G.red, stage, j, G);
 }
 
 // v_0 = src / beta with beta^2 in device memory (the ||r||^2 of k_residual, or the START sum of the hook); g = beta e_0 and a clean
@@ -1493,16 +1539,17 @@ hipError_t apply_halo(const SolveDev& d, const Work& w, Form form, double* x, do
 
 // the scalars of a stage from the partials of the kernel before it.  With a communicator the sums cross the partitions on their
 // way (k_reduce, allreduce_sum, k_advance); counters: the record also carries bad_blocks and f32_overflow (first residual).
-hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage, bool counters = false) {
+// extra (with a communicator only): a rank-local int32 counter that rides in the record as its fifth value and comes back global.
+hipError_t finalize(const SolveDev& d, const Work& w, int64_t nparts, int ncomp, int stage, bool counters = false, int32_t* extra = nullptr) {
   if (!d.comm) {
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage, w.scal);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, d.stream, (const double*)w.partials, nparts, ncomp, stage,
-                     (const SolveScal*)w.scal, w.rec, (int)counters);
+                     (const SolveScal*)w.scal, w.rec, (int)counters, (const int32_t*)extra);
   SOLVE_HIP(hipGetLastError());
-  SOLVE_HIP(callback(d, d.comm->allreduce_sum(d.comm->user, w.rec, counters ? 6 : ncomp, (void*)d.stream)));
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, d.stream, (const double*)w.rec, stage, w.scal, (int)counters);
+  SOLVE_HIP(callback(d, d.comm->allreduce_sum(d.comm->user, w.rec, counters ? 6 : extra ? 5 : ncomp, (void*)d.stream)));
+  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, d.stream, (const double*)w.rec, stage, w.scal, (int)counters, extra);
   return hipGetLastError();
 }
 
@@ -1513,15 +1560,22 @@ hipError_t read_record(const SolveDev& d, const Work& w) {
 }
 
 // true residual of x: r = r_hat = D^-1 (b - A x), p = v = 0, scalars as at the start; this is also the restart
-// (across partitions: the ghost values of x are exchanged first; first: the record carries the counters of setup)
+// (across partitions: the ghost values of x are exchanged first; first: the record carries the counters of setup; extra: finalize)
 template <int NV>
-hipError_t residual(const SolveDev& d, const Work& w, double* x, double scale, bool first = false) {
+hipError_t residual(const SolveDev& d, const Work& w, double* x, double scale, bool first = false, int32_t* extra = nullptr) {
   SOLVE_HIP(apply_halo<NV>(d, w, PLAIN, x, w.t, nullptr));
   if (w.node_blocks)   // a partition may own no node; the single-partition entry never gets here without one
     hipLaunchKernelGGL((k_residual<NV>), dim3((unsigned)w.node_blocks), dim3(256), 0, d.stream, d.rhs, scale, (const double*)w.t,
                        (const double*)w.dinv, w.r, w.rh, w.p, w.v, d.n_owned, w.partials);
   SOLVE_HIP(hipGetLastError());
-  SOLVE_HIP(finalize(d, w, w.node_blocks, 4, STAGE_INIT, first && d.comm));
+  SOLVE_HIP(finalize(d, w, w.node_blocks, 4, STAGE_INIT, first && d.comm, d.comm ? extra : nullptr));
+  return read_record(d, w);
+}
+
+// The read of a collective hook that computes no residual (solve_gmres_arnoldi across ranks): the counters of the set-up cross the
+// ranks as they do behind the first residual of a solve, beside sums that are zero, so that every rank refuses or runs together.
+hipError_t share_counters(const SolveDev& d, const Work& w) {
+  SOLVE_HIP(finalize(d, w, 0, 4, STAGE_INIT, true));
   return read_record(d, w);
 }
 
@@ -1879,9 +1933,26 @@ hipError_t gmres_start(const SolveDev& d, const GmresState& G, const double* src
   return hipGetLastError();
 }
 
+// What a step does with the partials of the kernel before it (GMRES_STAGE_*).  With a communicator the sums cross the ranks on their
+// way: k_gmres_reduce, the wide all-reduce of `ncomp` doubles in place in G.red, k_gmres_advance.
+hipError_t gmres_finalize(const SolveDev& d, const GmresState& G, int ncomp, int stage, int j) {
+  if (!d.comm) {
+    hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, ncomp, stage, j, G);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_gmres_reduce, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, ncomp, stage, G);
+  SOLVE_HIP(hipGetLastError());
+  SOLVE_HIP(callback(d, d.wide->allreduce_sum_wide(d.comm->user, G.red, ncomp, (void*)d.stream)));
+  hipLaunchKernelGGL(k_gmres_advance, dim3(1), dim3(64), 0, d.stream, stage, j, G);
+  return hipGetLastError();
+}
+
 // Arnoldi step j: w = D^-1 A (M v_j) into slot j + 1, one or two classical Gram-Schmidt passes against v_0 .. v_j, the norm, the
 // Givens step, the scaling, and the record on the host.  Vector passes with one Gram-Schmidt pass, beside the operator and M:
 // (j + 2) reads for the inner products, (j + 2) reads and 1 write for the update, 1 read and 1 write for the scaling: 2 j + 7.
+// Across ranks the operator's exchange receives into the ghost tail of v_j itself (or of M v_j), the sums run over the owned
+// entries, and a step makes one wide all-reduce per Gram-Schmidt pass (j + 2 doubles) and one for the norm (1 double).  A rank that
+// owns no node launches no vector kernel and adds zeros.
 template <int NV>
 hipError_t gmres_step(const SolveDev& d, const Work& w, const GmresState& G, Form form, Right right, int j) {
   double* vj = G.V + (int64_t)j * G.stride;
@@ -1894,14 +1965,13 @@ hipError_t gmres_step(const SolveDev& d, const Work& w, const GmresState& G, For
   SOLVE_HIP(apply_halo<NV>(d, w, form, in, wn, nullptr));
   const dim3 vg((unsigned)G.vec_blocks), vb(256);
   for (int pass = 0; pass < (d.gmres_refine ? 2 : 1); pass++) {
-    hipLaunchKernelGGL(k_gmres_dots, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, (const double*)wn, G.n, G.partials, G.vec_blocks);
-    hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, j + 2,
-                       pass ? (int)GMRES_STAGE_DOTS2 : (int)GMRES_STAGE_DOTS, j, G);
-    hipLaunchKernelGGL(k_gmres_orth, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, wn, G.n, (const double*)G.hpass, G.partials,
-                       (const GmresRec*)G.rec);
+    if (vg.x) hipLaunchKernelGGL(k_gmres_dots, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, (const double*)wn, G.n, G.partials, G.vec_blocks);
+    SOLVE_HIP(gmres_finalize(d, G, j + 2, pass ? (int)GMRES_STAGE_DOTS2 : (int)GMRES_STAGE_DOTS, j));
+    if (vg.x) hipLaunchKernelGGL(k_gmres_orth, vg, vb, 0, d.stream, (const double*)G.V, G.stride, j + 1, wn, G.n, (const double*)G.hpass, G.partials,
+                                 (const GmresRec*)G.rec);
   }
-  hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, 1, (int)GMRES_STAGE_NORM, j, G);
-  hipLaunchKernelGGL(k_gmres_scale, vg, vb, 0, d.stream, wn, G.n, (const double*)(G.scal + 1), (const GmresRec*)G.rec);
+  SOLVE_HIP(gmres_finalize(d, G, 1, (int)GMRES_STAGE_NORM, j));
+  if (vg.x) hipLaunchKernelGGL(k_gmres_scale, vg, vb, 0, d.stream, wn, G.n, (const double*)(G.scal + 1), (const GmresRec*)G.rec);
   SOLVE_HIP(hipGetLastError());
   return gmres_read(d, G);
 }
@@ -1930,21 +2000,24 @@ hipError_t gmres_update(const SolveDev& d, const Work& w, const GmresState& G, F
   const dim3 vg((unsigned)G.vec_blocks), vb(256);
   hipLaunchKernelGGL(k_gmres_solve_y, dim3(1), dim3(64), 0, d.stream, k, G);
   if (right == RIGHT_NONE) {
-    hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, x, G.n, G.rec);
+    if (vg.x) hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, x, G.n, G.rec);
   } else {
     double* z = right == RIGHT_MG ? d.mg->ph : d.ilu->ph;
-    hipLaunchKernelGGL((k_gmres_combine<false>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, w.s, G.n, G.rec);
+    if (vg.x) hipLaunchKernelGGL((k_gmres_combine<false>), vg, vb, 0, d.stream, (const double*)G.V, G.stride, k, (const double*)G.y, w.s, G.n, G.rec);
     SOLVE_HIP(right_apply<NV>(d, w, form, right, w.s, z));
-    hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)z, (int64_t)0, 1, (const double*)(G.scal + 2), x, G.n, G.rec);
+    if (vg.x) hipLaunchKernelGGL((k_gmres_combine<true>), vg, vb, 0, d.stream, (const double*)z, (int64_t)0, 1, (const double*)(G.scal + 2), x, G.n, G.rec);
   }
   SOLVE_HIP(hipGetLastError());
   return hipMemcpyAsync(d.gmres_rec, G.rec, sizeof(GmresRec), hipMemcpyDeviceToHost, d.stream);
 }
 
 // Right-preconditioned GMRES(m) on the system of run(): every cycle starts from the true FP64 residual, which also decides.
+// Across ranks (rdc_solve_dist_gmres) both records hold all-reduced values, the same bits on every rank, so every branch below is
+// collective; the one rank-local value, the overflow count of the update of x, becomes global in the all-reduce of the true
+// residual behind it and is read once more after that.
 template <int NV>
 hipError_t run_gmres(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
-  const Work w = carve(d.nvar, d.n_owned, d.work);
+  const Work w = carve(d.nvar, d.n_owned, d.work, d.comm ? &d.dist : nullptr);
   GmresState& G = *d.gmres;
   const SolveScal& rec = *d.host_rec;
   const GmresRec& grec = *d.gmres_rec;
@@ -1964,7 +2037,8 @@ hipError_t run_gmres(const SolveDev& d, const rdc_solve_params& p, double* x, rd
     info->iterations += steps;
     const int step_flag = grec.flag;
     if (k > 0) SOLVE_HIP(gmres_update<NV>(d, w, G, form, right, k, x));
-    SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale));   // the true residual of x decides, and is the next cycle's start
+    SOLVE_HIP(residual<NV>(d, w, x, p.rhs_scale, false, k > 0 ? &G.rec->overflow : nullptr));   // the true residual of x decides, and is the next cycle's start
+    if (d.comm && k > 0) SOLVE_HIP(gmres_read(d, G));
     if (rec.flag || (step_flag & GMRES_NOT_FINITE) || (k > 0 && (grec.overflow || (grec.flag & GMRES_Y_NOT_FINITE)))) {
       report(rec, info, RDC_SOLVE_NOT_FINITE);
       return hipSuccess;
@@ -2042,28 +2116,34 @@ hipError_t solve_gmres_arnoldi(const SolveDev& d, int precond, bool mixed, const
                                int* steps_done, int* bad_blocks, int* matrix_bits) {
   return by_nvar(d.nvar, [&](auto nv) {
     constexpr int NV = decltype(nv)::value;
-    const Work w = carve(d.nvar, d.n_owned, d.work);
+    const Work w = carve(d.nvar, d.n_owned, d.work, d.comm ? &d.dist : nullptr);
     const GmresState& G = *d.gmres;
     rdc_solve_params p = rdc_solve_params();
     p.precond = precond;
     const Right right = right_of(p);
     Start start;
-    SOLVE_HIP(prologue<NV>(d, w, precond, mixed, [&] { return read_record(d, w); }, &start));
+    SOLVE_HIP(prologue<NV>(d, w, precond, mixed, [&] { return d.comm ? share_counters(d, w) : read_record(d, w); }, &start));
     *bad_blocks = start.bad_blocks;
     *matrix_bits = start.form == F32 ? 32 : 64;
     *steps_done = 0;
     if (start.bad_blocks > 0) return hipSuccess;   // as the solve: nothing is run
     const size_t hbytes = (size_t)(G.restart + 1) * G.restart * sizeof(double);
     SOLVE_HIP(hipMemsetAsync(G.H, 0, hbytes, d.stream));
-    hipLaunchKernelGGL(k_gmres_dots, dim3((unsigned)G.vec_blocks), dim3(256), 0, d.stream, (const double*)G.V, G.stride, 0, v0, G.n, G.partials,
-                       G.vec_blocks);
-    hipLaunchKernelGGL(k_gmres_finalize, dim3(1), dim3(1024), 0, d.stream, (const double*)G.partials, G.vec_blocks, 1, (int)GMRES_STAGE_START, 0, G);
+    if (G.vec_blocks)
+      hipLaunchKernelGGL(k_gmres_dots, dim3((unsigned)G.vec_blocks), dim3(256), 0, d.stream, (const double*)G.V, G.stride, 0, v0, G.n, G.partials,
+                         G.vec_blocks);
+    SOLVE_HIP(gmres_finalize(d, G, 1, (int)GMRES_STAGE_START, 0));
     SOLVE_HIP(gmres_start(d, G, v0, G.scal));
     SOLVE_HIP(gmres_read(d, G));
     int run = 0;
     if (!(d.gmres_rec->flag & GMRES_NOT_FINITE))
       SOLVE_HIP(gmres_arnoldi<NV>(d, w, G, start.form, right, steps, [](int) { return false; }, steps_done, &run));
-    SOLVE_HIP(hipMemcpyAsync(V, G.V, (size_t)(*steps_done + 1) * G.stride * sizeof(double), hipMemcpyDeviceToDevice, d.stream));
+    if (G.stride == std::max<int64_t>(G.n, 1)) {
+      SOLVE_HIP(hipMemcpyAsync(V, G.V, (size_t)(*steps_done + 1) * G.stride * sizeof(double), hipMemcpyDeviceToDevice, d.stream));
+    } else if (G.n) {   // ghosted slots: the owned rows of every vector, one behind the other
+      SOLVE_HIP(hipMemcpy2DAsync(V, (size_t)G.n * sizeof(double), G.V, (size_t)G.stride * sizeof(double), (size_t)G.n * sizeof(double),
+                                 (size_t)(*steps_done + 1), hipMemcpyDeviceToDevice, d.stream));
+    }
     SOLVE_HIP(hipMemcpyAsync(H, G.H, hbytes, hipMemcpyDeviceToHost, d.stream));
     return hipStreamSynchronize(d.stream);
   });

@@ -15,17 +15,21 @@ struct SolveValid {
   bool ilu_factored = false;  // ilu_val holds the factor of the last ILU(0) hook or solve
   bool gmres_solved = false;  // a GMRES solve has run on this mesh: gmres_restart / gmres_cycles describe the last one
   int gmres_restart = 0, gmres_cycles = 0;
+  bool gmres_dist = false;    // ... and it was a partitioned one (rdc_solve_dist_gmres): its basis slots have ghost tails
 };
 
 // rdc_csr_scale_f32 (a mixed call: it builds the copy) | rdc_solve, _mixed | rdc_solve_gmres_arnoldi | rdc_solve_mg_apply |
-// rdc_solve_ilu_apply, _local_apply | rdc_solve_dist, _dist_mg | rdc_solve_dist_plan, _plan_peers (these two only enter)
+// rdc_solve_ilu_apply, _local_apply | rdc_solve_dist, _dist_mg, _dist_gmres | rdc_solve_dist_plan, _plan_peers (these two only enter).
+// rdc_solve_dist_gmres_arnoldi is ARNOLDI with SolveCall::dist.
 enum class SolveEntry { SCALE_F32, SOLVE, ARNOLDI, MG_APPLY, ILU_APPLY, DIST, DIST_PLAN };
 
 struct SolveCall {
   SolveEntry entry;
   int precond = RDC_PRECOND_NONE;   // as the caller gave it
   bool mixed = false;               // the call rebuilds the fp32 copy from the current values
-  bool gmres = false;               // the call needs the state of GMRES ("solve_method" = 1, the Arnoldi hook)
+  bool gmres = false;               // the call needs the state of GMRES ("solve_method" = 1, rdc_solve_dist_gmres, the Arnoldi hooks)
+  bool dist = false;                // the call is partitioned (entry DIST implies it; the collective Arnoldi hook sets it)
+  bool partitioned() const { return dist || entry == SolveEntry::DIST; }
   bool ilu() const { return entry == SolveEntry::ILU_APPLY || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL; }
   bool multigrid() const { return entry == SolveEntry::MG_APPLY || precond == RDC_PRECOND_MULTIGRID; }
 };
@@ -55,9 +59,10 @@ inline void solve_valid_leave(SolveValid& v, const SolveCall& call, const SolveO
   if (!o.ran || o.comm_failed) return;
   if (call.mixed) v.f32_copy = o.matrix_bits == 32 && o.bad_blocks == 0 && o.reason != RDC_SOLVE_BAD_DIAGONAL;
   if (call.ilu()) v.ilu_factored = true;
-  v.mg_values = call.multigrid() && call.entry != SolveEntry::DIST;   // a partitioned hierarchy has ghost layers: no download
-  if (call.entry != SolveEntry::SOLVE || !call.gmres) return;
+  v.mg_values = call.multigrid() && !call.partitioned();   // a partitioned hierarchy has ghost layers: no download
+  if ((call.entry != SolveEntry::SOLVE && call.entry != SolveEntry::DIST) || !call.gmres) return;
   v.gmres_solved = true;
+  v.gmres_dist = call.entry == SolveEntry::DIST;
   v.gmres_restart = o.gmres_restart;
   v.gmres_cycles = o.gmres_cycles;
 }

@@ -11,7 +11,9 @@ import torch
 import torch.distributed as dist
 
 from .params import (ALLREDUCE_SUM_FN, EXCHANGE_BEGIN_FN, EXCHANGE_END_FN, EXCHANGE_SIZED_BEGIN_FN, SolveCommSizedStruct,
-                     SolveCommStruct)
+                     SolveCommStruct, SolveCommWideStruct)
+
+WIDE_MAX = 130   # doubles of the longest wide all-reduce: "gmres_restart" <= 128, and a step sums up to restart + 1 (+ 1 spare)
 
 
 class HaloExchange:
@@ -126,12 +128,18 @@ class SolveComm:
     move the ghost values of a level below the matrix, whose per-peer slices come with the call, over ONE peer list (`peers`: every
     rank this one sends to or receives from, ascending); peer_counts are the plan's segment lengths over that list for
     rdc_solve_dist_plan_peers.  The gloo staging buffers serve them too: no level has more to move than the plan.  Without it
-    solve_dist(precond=PRECOND_MULTIGRID) stays RDC_ERR_UNSUPPORTED."""
+    solve_dist(precond=PRECOND_MULTIGRID) stays RDC_ERR_UNSUPPORTED.
 
-    def __init__(self, lp, nvar: int, device, group=None, sized=False):
+    wide=True adds what GMRES across ranks needs (rdc_solve_comm_wide, AssemblyContext.solve_dist_gmres and gmres_arnoldi_dist):
+    allreduce_wide adds up to 130 doubles over the ranks, the inner products of one Gram-Schmidt pass in one message.  It implies
+    the sized callbacks when the plan has peers (the multigrid preconditioner needs them).  wide_allreduces counts its calls and
+    wide_lengths lists the lengths it saw."""
+
+    def __init__(self, lp, nvar: int, device, group=None, sized=False, wide=False):
         self.group, self.nvar, self.rank = group, int(nvar), lp.rank
         self.dev = torch.device(device)
         peers = sorted(set(lp.send_ids) | set(lp.recv_ids))
+        sized = sized or (wide and bool(peers))
         self.send_peers = [q for q in peers if q in lp.send_ids and len(lp.send_ids[q])]
         self.recv_peers = [q for q in peers if q in lp.recv_ids and len(lp.recv_ids[q])]
         self.send_nodes = (np.concatenate([np.asarray(lp.send_ids[q]) for q in self.send_peers]) if self.send_peers
@@ -155,6 +163,8 @@ class SolveComm:
             mk = lambda rows: torch.empty((rows, self.nvar), dtype=torch.float64, pin_memory=pin)
             self.send_host, self.recv_host = mk(self.n_send), mk(self.n_ghost)
             self.vals_host = torch.empty(8, dtype=torch.float64, pin_memory=pin)
+            if wide:
+                self.wide_host = torch.empty(WIDE_MAX, dtype=torch.float64, pin_memory=pin)
         self.exchanges = self.allreduces = self.sized_exchanges = 0
         self.peers = peers
         self.peer_counts = (np.array([len(lp.send_ids.get(q, ())) for q in peers], dtype=np.int64),
@@ -175,6 +185,11 @@ class SolveComm:
         if sized:
             self._cb_sized = (EXCHANGE_SIZED_BEGIN_FN(self._guard(self._c_sized_begin)), EXCHANGE_END_FN(self._guard(self._c_sized_end)))
             self.sized_struct = SolveCommSizedStruct(self.struct, *self._cb_sized)
+        self.wide_struct, self.wide_allreduces, self.wide_lengths = None, 0, []
+        if wide:
+            self._cb_wide = ALLREDUCE_SUM_FN(self._guard(self._c_allreduce_wide))
+            inner = self.sized_struct if sized else SolveCommSizedStruct(self.struct)   # no peers: the sized pair stays NULL
+            self.wide_struct = SolveCommWideStruct(inner, self._cb_wide)
 
     # -- raw addresses -> torch
     def _view(self, addr, rows):
@@ -221,6 +236,11 @@ class SolveComm:
             v.__cuda_array_interface__ = {"shape": (8,), "typestr": "<f8", "data": (d_vals, False), "version": 2, "strides": None}
             self._views[key] = torch.as_tensor(v, device=self.dev)
         return self.allreduce(self._views[key][:n], self._stream(stream))
+
+    def _c_allreduce_wide(self, user, d_vals, n, stream):
+        if not 1 <= n <= WIDE_MAX:
+            raise ValueError(f"the library asks for a wide all-reduce of {n} doubles, outside 1 .. {WIDE_MAX}")
+        return self.allreduce_wide(self._flat(d_vals, WIDE_MAX)[:n], self._stream(stream))
 
     def _flat(self, addr, count):
         """zero-copy [count] view of device memory at addr"""
@@ -304,6 +324,23 @@ class SolveComm:
             self._pending = []
             if self._recv is not None and self.n_ghost:
                 self._recv.copy_(self.recv_host, non_blocking=True)
+        return 0
+
+    def allreduce_wide(self, vals, stream):
+        """vals: [n] device doubles, n <= 130, summed over the ranks in place"""
+        self.wide_allreduces += 1
+        self.wide_lengths.append(int(vals.numel()))
+        if self.world == 1:
+            return 0
+        with torch.cuda.stream(stream):
+            if self.host_staged:
+                h = self.wide_host[:vals.numel()]
+                h.copy_(vals, non_blocking=True)
+                stream.synchronize()
+                dist.all_reduce(h, group=self.group)
+                vals.copy_(h, non_blocking=True)
+            else:
+                dist.all_reduce(vals, group=self.group)
         return 0
 
     def allreduce(self, vals, stream):

@@ -125,6 +125,11 @@ class SolveCommSizedStruct(C.Structure):
     _fields_ = [("base", SolveCommStruct), ("exchange_sized_begin", EXCHANGE_SIZED_BEGIN_FN), ("exchange_sized_end", EXCHANGE_END_FN)]
 
 
+class SolveCommWideStruct(C.Structure):
+    """rdc_solve_comm_wide: rdc_solve_comm_sized and the all-reduce of up to 130 doubles (rdc_solve_dist_gmres)."""
+    _fields_ = [("sized", SolveCommSizedStruct), ("allreduce_sum_wide", ALLREDUCE_SUM_FN)]
+
+
 # reference parameter key -> struct field
 PIHNA_KEYS = {
     "time_step": "time_step",

@@ -4,7 +4,8 @@ the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shi
     python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
                               [--ilu-bits 32|64] [--method bicgstab|gmres] [--restart N]
                               [--ab [precond|precision|dist|smoother|ilu_bits|method]] [--dump DIR]
-    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--ab precond]
+    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--method bicgstab|gmres] [--restart N]
+                              [--ab precond|method]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
@@ -31,12 +32,16 @@ copy of the FP64 factor, and every record has ilu_factor_bits, what they streame
 the legs at 32 the fp32 operator with the fp32 factor).  --method gmres (one partition) sets the option "solve_method": restarted
 GMRES(m) in place of BiCGStab, m = --restart (option "gmres_restart", default 30); iterations are then Arnoldi steps, restarts the
 cycles after the first, and every record has the method, the restart length and the device bytes of the basis; --ab method runs
-the loop in the order BiCGStab, GMRES, GMRES, BiCGStab with --precond (and --mixed).  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
+the loop in the order BiCGStab, GMRES, GMRES, BiCGStab with --precond (and --mixed).  With --ranks N (N = 1 included: the partitioned
+entry at world size 1 in this process) or --ab dist, --method gmres is rdc_solve_dist_gmres, GMRES(m) across ranks through a
+communicator with the wide all-reduce, whatever the preconditioner (2, 3, 5); --ab dist --method gmres times rdc_solve under
+"solve_method" = 1 against it in the order rdc_solve, rdc_solve_dist_gmres, rdc_solve_dist_gmres, rdc_solve.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
 no halo update of its own.  --ab (= --ab precond) with --ranks runs the loop from the same initial state in the order block Jacobi,
-multigrid, rank-local ILU(0), rank-local ILU(0), multigrid, block Jacobi in the same processes.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
+multigrid, rank-local ILU(0), rank-local ILU(0), multigrid, block Jacobi in the same processes, --ab method in the order BiCGStab, GMRES,
+GMRES, BiCGStab with --precond.  Prints per rank the owned / interior / ghost nodes and the bytes of one exchange, and per step the
 iterations and the global true residual.  Rank r uses GPU r modulo the number of GPUs: on a one-GPU machine the ranks share it,
 and with --backend gloo every message is staged through the host -- such a run checks correctness and measures nothing."""
 import argparse
@@ -99,9 +104,9 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         ctx.set_option("mg_gs_fuse", gs_fuse)
     if precond in (4, 5):
         ctx.set_option("ilu_factor_bits", ilu_bits)
-    if comm is None:                    # across partitions the method is BiCGStab, and the option would be refused
-        ctx.set_option("solve_method", 1 if method == "gmres" else 0)
-        ctx.set_option("gmres_restart", restart)
+    # across partitions the method is in the entry's name, and rdc_solve_dist would refuse "solve_method" = 1
+    ctx.set_option("solve_method", 1 if method == "gmres" and comm is None else 0)
+    ctx.set_option("gmres_restart", restart)
     out = []
     for k in range(steps):
         ctx.assemble_pihna(params)
@@ -112,7 +117,8 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         if comm is None:
             info = ctx.solve(u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
         else:
-            info = ctx.solve_dist(comm, u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
+            dist_solve = ctx.solve_dist_gmres if method == "gmres" else ctx.solve_dist
+            info = dist_solve(comm, u.data_ptr(), rel_tol=rel_tol, precond=precond, max_its=max_its, mixed=mixed)
         if on_step:
             on_step(k, "solved", ctx)
         ctx.clamp_nonnegative(0)
@@ -121,7 +127,7 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
         out.append(dict(step=k + 1, assembly_ms=asm_ms, solve_ms=info.device_ms, iterations=info.iterations, restarts=info.restarts,
                         reason=info.reason, matrix_bits=info.matrix_bits, residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
                         background_nodes=nodes, background_elems=elems))
-        if method == "gmres" and comm is None:
+        if method == "gmres":
             out[-1].update(method="gmres", gmres_restart=restart, gmres_basis_bytes=ctx.gmres_stats()[1] if info.iterations else 0)
         if precond == 3:
             setup_ms, level_bytes = ctx.mg_stats()
@@ -159,7 +165,10 @@ def rank_main(rank, world, port, a):
             ctx.mesh_upload(4, lp.conn, lp.xyz, 5, n_owned=lp.n_owned)
             ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
             preconds = (2, 3, 5, 5, 3, 2) if a.ab == "precond" else (a.precond,)
-            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=3 in preconds)   # multigrid: rdc_solve_dist_mg
+            methods = ("bicgstab", "gmres", "gmres", "bicgstab") if a.ab == "method" else (a.method,) * len(preconds)
+            preconds = preconds * (len(methods) // len(preconds))
+            # multigrid: rdc_solve_dist_mg; GMRES: rdc_solve_dist_gmres
+            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=3 in preconds, wide="gmres" in methods)
             shared = world > torch.cuda.device_count()
             head = dict(rank=rank, gpu=gpu, owned_nodes=int(lp.n_owned), interior_nodes=int(lp.n_interior),
                         ghost_nodes=int(lp.xyz.shape[0] - lp.n_owned), halo_bytes_per_exchange=comm.bytes_per_exchange,
@@ -169,16 +178,18 @@ def rank_main(rank, world, port, a):
                 if r == rank:
                     print(json.dumps(head), flush=True)
                 dist.barrier()
-            for precond in preconds:
+            for precond, method in zip(preconds, methods):
                 if len(preconds) > 1:
                     ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
                     if rank == 0:
-                        print(json.dumps(dict(precond=precond)), flush=True)
-                for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=a.mixed, comm=comm, ilu_bits=a.ilu_bits):
+                        print(json.dumps(dict(precond=precond, method=method)), flush=True)
+                for rec in run(ctx, lp.conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=a.mixed, comm=comm, ilu_bits=a.ilu_bits,
+                               method=method, restart=a.restart):
                     if rank == 0:          # every figure of the solve is global and the same on every rank
                         keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
                         keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if precond == 3 else ()     # rank 0's own levels
                         keep += ("ilu_setup_ms", "ilu_bytes", "ilu_colours", "ilu_factor_bits") if precond == 5 else ()        # rank 0's own factor
+                        keep += ("method", "gmres_restart", "gmres_basis_bytes") if method == "gmres" else ()                  # rank 0's own basis
                         print(json.dumps({k: rec[k] for k in keep}), flush=True)
         dist.barrier()
     finally:
@@ -200,26 +211,30 @@ def main():
     ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--ilu-bits", type=int, choices=(32, 64), default=64)
     ap.add_argument("--dump", default=None)
-    ap.add_argument("--ranks", type=int, default=1)
+    ap.add_argument("--ranks", type=int, default=None)
     ap.add_argument("--backend", choices=("gloo", "nccl"), default="gloo")
     a = ap.parse_args()
+    world1 = a.ranks == 1        # asked for: the partitioned entry at world size 1, in this process
+    a.ranks = a.ranks or 1
     if a.ab == "smoother":
         a.precond = 3
-    if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or a.ab == "dist"):
+    if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or world1 or a.ab == "dist"):
         ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
     f32 = a.ilu_bits == 32 or a.ab == "ilu_bits"
     if (f32 or a.ab == "ilu_bits") and a.precond not in (4, 5):
         ap.error("--ilu-bits and --ab ilu_bits belong to the block ILU(0): --precond 4 or 5")
-    if a.precond == 4 and ((a.mixed and not f32) or a.ranks > 1 or a.ab in ("precision", "dist")):
+    if a.precond == 4 and ((a.mixed and not f32) or a.ranks > 1 or world1 or a.ab in ("precision", "dist")):
         ap.error("the block ILU(0) (--precond 4) is FP64 on one partition: rdc_solve only (across ranks: --precond 5; --mixed: --ilu-bits 32)")
     if a.precond == 5 and not f32 and (a.mixed or a.ab == "precision"):
         ap.error("the rank-local block ILU(0) (--precond 5) is FP64 only, unless --ilu-bits 32")
-    if (a.method == "gmres" or a.ab == "method") and (a.ranks > 1 or a.ab == "dist"):
-        ap.error("GMRES (--method gmres, --ab method) runs on one partition: rdc_solve and rdc_solve_mixed")
+    if a.ab == "method" and world1:
+        ap.error("--ab method at world size 1 in one process: leave --ranks out")
+    if world1 and a.ab not in (None, "dist"):
+        ap.error("--ranks 1 is the partitioned entry at world size 1 and takes no --ab but dist, which is the same comparison")
     if not 1 <= a.restart <= 128:
         ap.error("--restart is 1 .. 128")
-    if a.ranks > 1 and a.ab not in (None, "precond"):
-        ap.error("--ranks takes --ab precond only")
+    if a.ranks > 1 and a.ab not in (None, "precond", "method"):
+        ap.error("--ranks takes --ab precond and --ab method only")
     if a.ranks > 1 and a.ab == "precond" and a.mixed:
         ap.error("--ab precond with --ranks is FP64: the rank-local ILU(0) has no mixed form")
     if a.ranks > 1:
@@ -228,7 +243,9 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        print(json.dumps(dict(mesh=f"K({a.n})", ranks=a.ranks, backend=a.backend, rel_tol=a.rel_tol, precond=a.precond, mixed=a.mixed)), flush=True)
+        print(json.dumps(dict(mesh=f"K({a.n})", ranks=a.ranks, backend=a.backend, rel_tol=a.rel_tol, precond=a.precond, mixed=a.mixed,
+                              method=a.method if a.ab != "method" else "bicgstab, gmres, gmres, bicgstab",
+                              restart=a.restart if a.method == "gmres" or a.ab == "method" else None)), flush=True)
         mp.spawn(rank_main, args=(a.ranks, port, a), nprocs=a.ranks, join=True)
         return
     import torch
@@ -239,7 +256,7 @@ def main():
     with AssemblyContext(0) as ctx:
         ctx.mesh_upload(4, conn, xyz, 5)
         u0 = synth.pihna_fields(xyz)
-        runs = [(a.precond, a.mixed, False, a.smoother, a.ilu_bits)]
+        runs = [(a.precond, a.mixed, world1, a.smoother, a.ilu_bits)]
         methods = ("bicgstab", "gmres", "gmres", "bicgstab") if a.ab == "method" else None
         if methods:
             runs = runs * len(methods)
@@ -254,18 +271,19 @@ def main():
         elif a.ab == "ilu_bits":
             runs = [(a.precond, a.mixed and bits == 32, False, 0, bits) for bits in (64, 32, 32, 64)]
         comm = None
-        if a.ab == "dist":      # world size 1: no peers, no process group
+        if a.ab == "dist" or world1:      # world size 1: no peers, no process group
             from rdcfes_amd import SolveComm, partition
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
-            comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3)
+            comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3, wide=a.method == "gmres")
         for leg, (precond, mixed, dist_entry, smoother, ilu_bits) in enumerate(runs):
             method = methods[leg] if methods else a.method
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
                                   smoother=smoother if precond == 3 else None, ilu_bits=ilu_bits if precond in (4, 5) else None,
                                   method=method, restart=a.restart if method == "gmres" else None,
-                                  entry=("rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") + ", world size 1" if dist_entry else "rdc_solve")))
+                                  entry=("rdc_solve_dist_gmres" if method == "gmres" else "rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") +
+                                  ", world size 1" if dist_entry else "rdc_solve")))
             for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None,
                            smoother=smoother, gs_fuse=a.gs_fuse, ilu_bits=ilu_bits, method=method, restart=a.restart):
                 print(json.dumps(rec), flush=True)
