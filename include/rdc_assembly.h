@@ -354,6 +354,7 @@ int rdc_part1_nodes(const rdc_ctx* ctx, int64_t* n_nodes);
 #define RDC_PRECOND_MULTIGRID 3         /* block Jacobi's system, with an aggregation-multigrid cycle applied from the right (below) */
 #define RDC_PRECOND_ILU0 4              /* block Jacobi's system, with a multicolour block ILU(0) applied from the right (below); rdc_solve only */
 #define RDC_PRECOND_ILU0_LOCAL 5        /* the same with the ILU(0) of the rank's owned square: block Jacobi between the ranks, ILU(0) inside each (below); rdc_solve_dist, and rdc_solve without ghosts */
+#define RDC_PRECOND_MULTIGRID_GS_LOCAL 6 /* the cycle of RDC_PRECOND_MULTIGRID with the rank-local multicolour Gauss-Seidel smoother (below); rdc_solve_dist_mg, rdc_solve_dist_gmres, and rdc_solve without ghosts */
 
 #define RDC_SOLVE_CONVERGED     0
 #define RDC_SOLVE_MAX_ITS       1       /* x holds the last iterate */
@@ -564,6 +565,38 @@ int rdc_solve_ilu_download(rdc_ctx* ctx, double* val, double* uinv);
  * RDC_PRECOND_ILU0.  RDC_ERR_UNSUPPORTED, as there, for an owned square that is not structurally symmetric or lacks a diagonal
  * block; that refusal is taken by the rank alone, before its first callback.  Out of scope: an fp32 U_ii^-1, an ILU coupled
  * across ranks, overlapping partitions. */
+/* ---- RDC_PRECOND_MULTIGRID_GS_LOCAL (rdc_solve_dist_mg, rdc_solve_dist_gmres; additive: RDC_ABI_VERSION stays 3) ----
+ * RDC_PRECOND_MULTIGRID across ranks with the sweeps of "mg_smoother" = 1, a preconditioner of its own: Gauss-Seidel inside each
+ * rank, Jacobi between the ranks.  System, stopping test, norms, rdc_solve_info, the V(1,1) cycle from the right, the rank-local
+ * aggregates, the Galerkin levels and "mg_omega" are those of RDC_PRECOND_MULTIGRID.  The first sweep from zero on every level stays
+ * x = w D_l^-1 r; every other sweep is one undamped forward sweep x_n += D_l^-1 (r_n - (A_l x)_n) over this rank's own colour lists
+ * of the level (the greedy colours of the owned square: columns in the ghost layer are ignored), preceded by the exchange of x on
+ * that level.  During a sweep a ghost column reads the value that exchange received and is never written.  With more than one rank
+ * this is another operator than the sweep of "mg_smoother" = 1 on one partition (a coupling across partitions takes the old value),
+ * which is why it has a value of its own; RDC_PRECOND_MULTIGRID keeps every behaviour it has, its refusal of "mg_smoother" = 1
+ * across ranks included.  "mg_smoother" is not consulted under this value (0 and 1 return the same bytes); "mg_gs_fuse" and
+ * "mg_omega" are honoured, and "mg_gs_fuse" = 0 and 1 return the same bytes.
+ *   rdc_solve_dist_mg            accepted beside RDC_PRECOND_MULTIGRID, FP64 and mixed (level 0 then sweeps on the fp32 copy; after
+ *                                the FP32-overflow fall-back on the FP64 values).  The callbacks of the set-up and of an iteration
+ *                                are exactly those of RDC_PRECOND_MULTIGRID, at every world size: the smoother costs no message.  On
+ *                                level 0 the nodes of colour 0 below "interior_nodes" are swept between exchange_begin and
+ *                                exchange_end.  A rank that owns no node of a level launches nothing there and makes every callback.
+ *   rdc_solve_dist_gmres, rdc_solve_dist_gmres_arnoldi   accepted through the sized pair, as RDC_PRECOND_MULTIGRID is.
+ *   rdc_solve, rdc_solve_mixed, rdc_solve_gmres_arnoldi, no ghosts   accepted: the call returns the bytes (x and every field of
+ *                                rdc_solve_info) of RDC_PRECOND_MULTIGRID under "mg_smoother" = 1, under both methods.  With ghosts
+ *                                it refuses as it does for every value.
+ *   rdc_solve_dist               RDC_ERR_UNSUPPORTED naming rdc_solve_dist_mg, as for RDC_PRECOND_MULTIGRID.
+ *   rdc_solve_mg_apply           takes no preconditioner; on a context with ghosts it refuses as before.
+ * A context without ghosts and a communicator of world size 1 returns, bit for bit, what rdc_solve returns with
+ * RDC_PRECOND_MULTIGRID under "mg_smoother" = 1.  Two solves return the same bytes (no atomics, no counters).
+ * rdc_solve_mg_colours after such a partitioned solve reports THIS RANK's colours per level.  The lists share the allocation of
+ * "mg_smoother" = 1: a mesh holds one set.  Those of a partitioned hierarchy are dropped whenever that hierarchy is (a new plan, new
+ * peer counts, a multigrid solve on one partition, a mesh upload) and are built again by the next solve with this value; a
+ * single-partition solve with "mg_smoother" = 1 afterwards colours its own hierarchy again and returns what it always did.
+ * RDC_ERR_UNSUPPORTED if the owned square of a level of this rank is not structurally symmetric.  That refusal is taken by the rank
+ * alone and is NOT collective: it comes behind the collective set-up of the levels and before the first callback of the solve, so
+ * the other ranks must not be left waiting on it (a caller that cannot rule it out checks the return on every rank).  Out of
+ * scope: a smoother coupled across ranks, the level-0 pack folded into the sweep, overlap beyond colour 0. */
 /* ---- two read-only observation points that accept a context with ghost nodes (TEST HOOKS, as the pair above, which keep refusing one).
  * rdc_solve_ilu_local_apply: d_out = M d_in, ONE application of this rank's M, as the next rdc_solve_dist with
  * RDC_PRECOND_ILU0_LOCAL would apply it (the same host function: D^-1, the copy of the owned square of A^, its factorisation from
@@ -692,7 +725,8 @@ typedef struct rdc_solve_comm_sized {
                               const int64_t* recv_off, void* hip_stream);
   int (*exchange_sized_end)(void* user, void* hip_stream);
 } rdc_solve_comm_sized;
-/* The contract of rdc_solve_dist with p->precond = RDC_PRECOND_MULTIGRID; any other preconditioner is RDC_ERR_INVALID.
+/* The contract of rdc_solve_dist with p->precond = RDC_PRECOND_MULTIGRID (or RDC_PRECOND_MULTIGRID_GS_LOCAL, above: the same
+ * callbacks, other sweeps); any other preconditioner is RDC_ERR_INVALID.
  * RDC_ERR_STATE on a context with ghost nodes that lacks the plan or the peer counts.  A singular diagonal block on any level
  * of any rank gives RDC_SOLVE_BAD_DIAGONAL on every rank, x untouched.  A callback that returns non-zero (while the hierarchy
  * is built included) gives RDC_ERR_COMM and no further callback.  A context without ghosts and a communicator of world size
@@ -724,7 +758,7 @@ int rdc_solve_dist_mg(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solve_c
  * library has enqueued what produces d_vals on `hip_stream`, the sums are ordered on it when the callback returns, and every rank
  * gets the same bits.  An MPI adapter: MPI_Allreduce of n doubles. */
 typedef struct rdc_solve_comm_wide {
-  rdc_solve_comm_sized sized;   /* the sized pair may be NULL unless p->precond == RDC_PRECOND_MULTIGRID */
+  rdc_solve_comm_sized sized;   /* the sized pair may be NULL unless p->precond == RDC_PRECOND_MULTIGRID or RDC_PRECOND_MULTIGRID_GS_LOCAL */
   int (*allreduce_sum_wide)(void* user, double* d_vals, int32_t n, void* hip_stream);   /* in place, n <= 128 + 2 */
 } rdc_solve_comm_wide;
 /* The contract of rdc_solve_dist (mixed: of its mixed form), with GMRES(m) as the method.  precond: RDC_PRECOND_NONE, _JACOBI,

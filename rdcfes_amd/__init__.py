@@ -11,7 +11,7 @@ from .params import (PihnaParams, RipfParams, HccParams, SolidParams, SolidMater
 from .context import (AssemblyContext, RdcError, TET4, HEX8, SCATTER_AUTO, SCATTER_COLOURED,
                       SCATTER_ROWGATHER, FIELD_OLD_SOLUTION, FIELD_AUX_NODAL,
                       FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE, FIELD_PREV_SOLUTION, FIELD_TIME_DERIV,
-                      FIELD_RT_DOSE, FIELD_ELEM_TRACTS, PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL,
+                      FIELD_RT_DOSE, FIELD_ELEM_TRACTS, PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL, PRECOND_MULTIGRID_GS_LOCAL,
                       SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE, ERR_COMM)
 
 
@@ -29,6 +29,6 @@ __all__ = [
     "AssemblyContext", "RdcError", "TET4", "HEX8", "SCATTER_AUTO", "SCATTER_COLOURED",
     "SCATTER_ROWGATHER", "FIELD_OLD_SOLUTION", "FIELD_AUX_NODAL", "FIELD_UNDEFORMED_XYZ",
     "FIELD_ELEM_FIBRE", "FIELD_PREV_SOLUTION", "FIELD_TIME_DERIV", "FIELD_RT_DOSE", "FIELD_ELEM_TRACTS",
-    "SolveParams", "SolveInfo", "PRECOND_NONE", "PRECOND_JACOBI", "PRECOND_BLOCK_JACOBI", "PRECOND_MULTIGRID", "PRECOND_ILU0", "PRECOND_ILU0_LOCAL",
+    "SolveParams", "SolveInfo", "PRECOND_NONE", "PRECOND_JACOBI", "PRECOND_BLOCK_JACOBI", "PRECOND_MULTIGRID", "PRECOND_ILU0", "PRECOND_ILU0_LOCAL", "PRECOND_MULTIGRID_GS_LOCAL",
     "SOLVE_CONVERGED", "SOLVE_MAX_ITS", "SOLVE_BREAKDOWN", "SOLVE_BAD_DIAGONAL", "SOLVE_NOT_FINITE", "ERR_COMM", "SolveComm",
 ]

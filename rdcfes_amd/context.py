@@ -15,6 +15,7 @@ FIELD_PREV_SOLUTION, FIELD_TIME_DERIV, FIELD_RT_DOSE = 4, 5, 6
 FIELD_ELEM_TRACTS = FIELD_ELEM_FIBRE  # ADPM: same per-element slot
 VARIANT_AUTO, VARIANT_GENERIC = 0, 1
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL = 0, 1, 2, 3, 4, 5
+PRECOND_MULTIGRID_GS_LOCAL = 6   # the cycle of PRECOND_MULTIGRID with the rank-local multicolour Gauss-Seidel smoother
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 1, 2, 3, 4, 5, 6
 
@@ -346,6 +347,8 @@ class AssemblyContext:
         unless set_option("ilu_factor_bits", 32): the sweeps then stream an fp32 copy of the FP64 factor, with or without
         mixed=True, and ilu_factor_bits() tells what they streamed).
         precond=PRECOND_ILU0_LOCAL: the rank-local form of solve_dist; without ghosts it returns the bytes of PRECOND_ILU0.
+        precond=PRECOND_MULTIGRID_GS_LOCAL: the multigrid of solve_dist with the rank-local Gauss-Seidel smoother; without ghosts
+        it returns the bytes of PRECOND_MULTIGRID under set_option("mg_smoother", 1), whatever that option says.
         set_option("solve_method", 1): right-preconditioned restarted GMRES(m) in place of BiCGStab, on the same system with the
         same preconditioners and stopping test (m: set_option("gmres_restart", 1 .. 128), default 30; set_option("gmres_refine", 1):
         a second Gram-Schmidt pass per step).  info.iterations then counts Arnoldi steps, info.restarts the cycles after the first;
@@ -374,7 +377,9 @@ class AssemblyContext:
         rows: ignored in, the owners' values out), or field=FIELD_*.  The returned SolveInfo is the same on every rank.  The send
         list of comm is uploaded once per mesh.  An exception raised inside a callback of comm is re-raised here.
         precond=PRECOND_MULTIGRID needs a communicator with the sized exchange (SolveComm(..., sized=True)) and goes to
-        rdc_solve_dist_mg; its peer counts are uploaded with the plan.
+        rdc_solve_dist_mg; its peer counts are uploaded with the plan.  precond=PRECOND_MULTIGRID_GS_LOCAL goes the same way: that
+        cycle with the multicolour Gauss-Seidel sweep inside every rank and Jacobi between the ranks, the same callbacks, fewer
+        iterations; "mg_smoother" is not consulted, and mg_colours() then reports this rank's colours.
         precond=PRECOND_ILU0_LOCAL: block Jacobi between the ranks, the block ILU(0) of every rank's owned square inside it, applied
         from the right; the exchanges and all-reduces of block Jacobi, fewer iterations (not with mixed=True, unless set_option("ilu_factor_bits", 32): an fp32 copy
         of every rank's factor)."""
@@ -393,7 +398,7 @@ class AssemblyContext:
         p = SolveParams(float(rel_tol), float(abs_tol), float(rhs_scale), int(max_its), int(precond))
         info = SolveInfo()
         comm.error = None
-        if sized is not None and int(precond) == PRECOND_MULTIGRID:
+        if sized is not None and int(precond) in (PRECOND_MULTIGRID, PRECOND_MULTIGRID_GS_LOCAL):
             rc = self._lib.rdc_solve_dist_mg(self._h, C.byref(p), C.byref(sized), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
         else:
             rc = self._lib.rdc_solve_dist(self._h, C.byref(p), C.byref(comm.struct), 1 if mixed else 0, C.c_void_p(int(x)), C.byref(info))
@@ -420,7 +425,7 @@ class AssemblyContext:
         halo.SolveComm(..., wide=True).  Arguments, x and the returned SolveInfo as solve_dist; iterations counts Arnoldi steps and
         restarts the cycles after the first, as in solve under set_option("solve_method", 1).  GMRES runs whatever "solve_method"
         is; "gmres_restart" and "gmres_refine" are honoured.  precond: PRECOND_NONE, _JACOBI, _BLOCK_JACOBI, PRECOND_ILU0_LOCAL
-        (block Jacobi between the ranks, ILU(0) inside each: PETSc's default under mpirun) and PRECOND_MULTIGRID (the rank-local
+        (block Jacobi between the ranks, ILU(0) inside each: PETSc's default under mpirun) and PRECOND_MULTIGRID or PRECOND_MULTIGRID_GS_LOCAL (the rank-local
         hierarchy of solve_dist).  An exception raised inside a callback of comm is re-raised here."""
         wide = getattr(comm, "wide_struct", None)
         if wide is None:

@@ -55,6 +55,7 @@ struct SolveState {
   bool mg_dist = false;      // ... and it is the one of rdc_solve_dist_mg (ghost layers; mg_off holds the offsets of its exchanges)
   MgDev mg;
   bool gs_ready = false;     // mg_gs holds the colour lists of this mesh's (single-partition) hierarchy, gs describes them
+  bool gs_dist = false;      // ... no: of its partitioned hierarchy, per rank (RDC_PRECOND_MULTIGRID_GS_LOCAL); dropped with it
   MgGsDev gs;
   std::vector<MgColours> gs_cols;   // their host copy (MgGsLevel::cptr_host points into it)
   bool ilu_ready = false;    // ilu_idx / ilu_val hold this mesh's lists, ilu describes them, ilu_host is their host copy
@@ -65,6 +66,7 @@ struct SolveState {
   bool peers_ready = false;  // halo0 is the plan with its per-peer segments (rdc_solve_dist_plan_peers)
   std::vector<int32_t> send_nodes;   // host copy of the plan's send list
   MgHalo halo0;
+  std::vector<MgLevelHost> mg_dist_steps;   // the steps of the partitioned hierarchy, kept for the colouring of its levels
   std::vector<std::vector<int64_t>> mg_off;   // per level >= 1: send and ghost offsets in doubles, what MgLevelDev::send_off / ghost_off point at
   int gmres_cap = 0;         // the restart length buf.solve.gmres was allocated for (0: not allocated)
   GmresState gmres = GmresState();   // ... and its layout for the restart length of the call at hand

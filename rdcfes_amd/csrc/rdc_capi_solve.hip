@@ -73,8 +73,12 @@ int arena_upload(rdc_ctx* c, DevBuf* b0, DevBuf* b1, const char* what, Place&& p
 
 // A mesh holds one hierarchy: that of the single-partition solves, or that of rdc_solve_dist_mg with its ghost layers.  A call
 // that needs the other kind drops it, and so does what a distributed one was built on going away (a new plan, new peers).
+// A mesh also holds one set of colour lists.  Those of the single-partition hierarchy outlive it, since that hierarchy is always
+// the same; those of a partitioned one (gs_dist: RDC_PRECOND_MULTIGRID_GS_LOCAL) depend on the plan as it does -- the ghost
+// columns they ignore, the interior split of colour 0 -- and go whenever it goes or would go.
 void mg_drop_unless(SolveState& S, bool dist) {
   if (S.mg_ready && S.mg_dist != dist) S.mg_ready = S.mg_dist = false;
+  if (!dist && S.gs_ready && S.gs_dist) S.gs_ready = S.gs_dist = false;
 }
 
 // the two arenas of a hierarchy (mg_build or, with halos, the levels of mg_view_dist), carved by mg_place
@@ -86,8 +90,10 @@ int mg_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps, const std::vect
 }
 
 // The colour lists of the Gauss-Seidel smoother, one per level of the hierarchy `steps` describes: coloured on the host, validated,
-// and uploaded into one arena that mg_gs_place carves (first solve with "mg_smoother" = 1 on a mesh).
-int gs_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps) {
+// and uploaded into one arena that mg_gs_place carves (first solve with "mg_smoother" = 1 on a mesh).  dist: the hierarchy is a
+// partitioned one (RDC_PRECOND_MULTIGRID_GS_LOCAL): mg_colour ignores the ghost columns, so the lists are those of the owned square
+// of every level, and the nodes of colour 0 below "interior_nodes" are counted for the launch inside the exchange.
+int gs_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps, bool dist) {
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   std::vector<MgColours> cols(steps.size() + 1);
@@ -95,36 +101,41 @@ int gs_upload(rdc_ctx* c, const std::vector<MgLevelHost>& steps) {
     const bool ok = l == 0 ? mg_colour(P.n_owned, P.bptr.data(), P.bcol.data(), cols[0])
                            : mg_colour(steps[l - 1].n, steps[l - 1].bptr.data(), steps[l - 1].bcol.data(), cols[l]);
     if (!ok)
-      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern of multigrid level %d is not structurally symmetric: two coupled nodes share "
-                  "a colour, and a Gauss-Seidel sweep (\"mg_smoother\" = 1) over such colours would race", (int)l);
+      return fail(c, RDC_ERR_UNSUPPORTED, "the block pattern of %smultigrid level %d is not structurally symmetric: two coupled nodes share "
+                  "a colour, and a Gauss-Seidel sweep (%s) over such colours would race", dist ? "this rank's owned square of " : "", (int)l,
+                  dist ? "precond 6" : "\"mg_smoother\" = 1");
   }
   S.gs_cols = std::move(cols);   // MgGsLevel::cptr_host points into them
   int rc = arena_upload(c, &c->buf.solve.mg_gs, nullptr, "the colour lists", [&](MgArena* a, auto&& copy) { mg_gs_place(S.gs_cols, a[0], S.gs, copy); });
   S.gs_ready = rc == RDC_OK;
+  S.gs_dist = S.gs_ready && dist;
+  if (S.gs_dist) S.gs.int0 = mg_gs_interior(S.gs_cols[0], S.plan_ready ? S.dist.n_int : 0);
   return rc;
 }
 
 // The multigrid hierarchy of the mesh: built on the host and uploaded at the first multigrid solve (rdc_solve.h, mg_build).
 // d must come from solve_view(want_work).
-int mg_view(rdc_ctx* c, SolveDev* d) {
+// gs_local: RDC_PRECOND_MULTIGRID_GS_LOCAL, which sweeps with Gauss-Seidel whatever "mg_smoother" says
+int mg_view(rdc_ctx* c, SolveDev* d, bool gs_local) {
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   MgDev& g = S.mg;
   mg_drop_unless(S, false);
-  const bool want_gs = c->sopt.mg_smoother == 1 && !S.gs_ready;   // the hierarchy of a mesh is always the same: its colours outlive a rebuild
+  const bool gs = gs_local || c->sopt.mg_smoother == 1;
+  const bool want_gs = gs && !S.gs_ready;   // the hierarchy of a mesh is always the same: its colours outlive a rebuild
   if (!S.mg_ready || want_gs) {
     std::vector<MgLevelHost> steps;
     if (!mg_build(P.n_owned, P.bptr.data(), P.bcol.data(), steps))
       return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
     int rc;
-    if (want_gs && (rc = gs_upload(c, steps))) return rc;   // first: a refusal leaves the context as it was
+    if (want_gs && (rc = gs_upload(c, steps, false))) return rc;   // first: a refusal leaves the context as it was
     if (!S.mg_ready && (rc = mg_upload(c, steps, nullptr))) return rc;
     S.mg_ready = true;
   }
   g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
   g.omega = 1e-3 * c->sopt.mg_omega;
   d->mg = &g;
-  if (c->sopt.mg_smoother == 1) {
+  if (gs) {
     S.gs.fuse = c->sopt.mg_gs_fuse != 0;
     d->gs = &S.gs;
   }
@@ -196,13 +207,15 @@ struct DistCall { const rdc_solve_comm* comm; const rdc_solve_comm_sized* sized;
 // The hierarchy of rdc_solve_dist_mg: built collectively at the first such solve after a plan (rdc_solve.h: mg_dist_aggregate, the
 // exchange of aggregate numbers, mg_dist_coarsen; mg_dist_goes_on decides on all-reduced sums) and placed by mg_place with its
 // ghost layers.  The two collective calls of a step go through the communicator on a small device buffer.  d must carry the
-// work buffer.
-int mg_view_dist(rdc_ctx* c, SolveDev* d, const rdc_solve_comm_sized* comm, int* comm_rc) {
+// work buffer.  gs_local (RDC_PRECOND_MULTIGRID_GS_LOCAL): the colour lists of the levels too, from the steps the build keeps on the
+// host (mg_dist_steps), at the first such solve on the hierarchy; a refusal by the colouring comes before anything is uploaded.
+int mg_view_dist(rdc_ctx* c, SolveDev* d, const rdc_solve_comm_sized* comm, int* comm_rc, bool gs_local) {
   const HostPrep& P = c->ms.prep;
   SolveState& S = c->ms.solve;
   MgDev& g = S.mg;
   mg_drop_unless(S, true);
   if (!S.mg_ready) {
+    if (S.gs_dist) S.gs_ready = S.gs_dist = false;   // (of a hierarchy whose upload failed)
     if (P.bptr[(size_t)P.n_owned] >= ((int64_t)1 << 31)) return fail(c, RDC_ERR_UNSUPPORTED, "a multigrid level would have 2^31 node blocks or more");
     std::vector<MgLevelHost> steps;
     std::vector<MgHalo> halos(1, S.halo0);
@@ -252,16 +265,25 @@ int mg_view_dist(rdc_ctx* c, SolveDev* d, const rdc_solve_comm_sized* comm, int*
       for (int64_t o : halos[l].send_off) S.mg_off[l].push_back(o * P.nvar);
       for (int64_t o : halos[l].ghost_off) S.mg_off[l].push_back(o * P.nvar);
     }
+    if (gs_local && (rc = gs_upload(c, steps, true))) return rc;
     if ((rc = mg_upload(c, steps, &halos))) return rc;
+    S.mg_dist_steps = std::move(steps);
     for (size_t l = 1; l < halos.size(); l++) {
       g.lv[l].send_off = S.mg_off[l].data();
       g.lv[l].ghost_off = S.mg_off[l].data() + peers + 1;
     }
     S.mg_ready = S.mg_dist = true;
+  } else if (gs_local && !(S.gs_ready && S.gs_dist)) {
+    int rc = gs_upload(c, S.mg_dist_steps, true);
+    if (rc) return rc;
   }
   g.lv[0].bptr = d->bptr; g.lv[0].bcol = d->bcol;
   g.omega = 1e-3 * c->sopt.mg_omega;
   d->mg = &g;
+  if (gs_local) {
+    S.gs.fuse = c->sopt.mg_gs_fuse != 0;
+    d->gs = &S.gs;
+  }
   d->peers = S.halo0.peers();
   return RDC_OK;
 }
@@ -278,7 +300,8 @@ int solve_enter(rdc_ctx* c, SolveEntry entry) {
 // always in this order -- the work buffer and record (those of a partitioned solve if dist), the fp32 copy if the call is mixed, the
 // hierarchy, the ILU(0) lists, the state of GMRES; run(d) does the device work and notes in *o what it found; the flags follow
 // from the outcome.  *precond: RDC_PRECOND_ILU0_LOCAL becomes RDC_PRECOND_ILU0 on a context without ghost nodes, where the owned
-// square is the matrix.
+// square is the matrix; RDC_PRECOND_MULTIGRID_GS_LOCAL becomes RDC_PRECOND_MULTIGRID once the view carries the colour lists, which
+// are what tells rdc_solve.hip the smoother.
 template <class Run>
 int solve_do(rdc_ctx* c, const SolveCall& call, int32_t* precond, DistCall* dist, SolveOutcome* o, Run&& run) {
   const HostPrep& P = c->ms.prep;
@@ -292,7 +315,9 @@ int solve_do(rdc_ctx* c, const SolveCall& call, int32_t* precond, DistCall* dist
   }
   int rc = solve_view(c, true, call.mixed, &d, dist ? &d.dist : nullptr);
   if (rc) return rc;
-  if (call.multigrid() && (rc = dist ? mg_view_dist(c, &d, dist->sized, &dist->rc) : mg_view(c, &d))) return rc;
+  const bool gs_local = call.precond == RDC_PRECOND_MULTIGRID_GS_LOCAL;
+  if (call.multigrid() && (rc = dist ? mg_view_dist(c, &d, dist->sized, &dist->rc, gs_local) : mg_view(c, &d, gs_local))) return rc;
+  if (precond && gs_local) *precond = RDC_PRECOND_MULTIGRID;
   if (precond && *precond == RDC_PRECOND_ILU0_LOCAL && P.n_owned == P.n_node) *precond = RDC_PRECOND_ILU0;
   if (call.ilu() && (rc = ilu_view(c, &d))) return rc;
   if (call.gmres && (rc = gmres_view(c, &d, dist != nullptr))) return rc;
@@ -326,7 +351,8 @@ int matvec_call(rdc_ctx* c, const double* d_x, double* d_y, bool f32) {
 // with_right: the preconditioners applied from the right on top of block Jacobi's system count (the solve entries)
 bool known_precond(int precond, bool with_right) {
   return precond == RDC_PRECOND_NONE || precond == RDC_PRECOND_JACOBI || precond == RDC_PRECOND_BLOCK_JACOBI ||
-         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL));
+         (with_right && (precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL ||
+                        precond == RDC_PRECOND_MULTIGRID_GS_LOCAL));
 }
 
 // what every entry that takes rdc_solve_params refuses of them
@@ -442,15 +468,16 @@ int dist_ready(rdc_ctx* c, int precond, bool sized, bool mg_entry, bool any_prec
     return fail(c, RDC_ERR_UNSUPPORTED, "the block ILU(0) preconditioner (precond %d) across partitions needs a ghost exchange per colour and is "
                 "not implemented: rdc_solve on a context without ghost nodes, or the rank-local factor (precond %d)", (int)RDC_PRECOND_ILU0,
                 (int)RDC_PRECOND_ILU0_LOCAL);
-  if (!any_precond && mg_entry && precond != RDC_PRECOND_MULTIGRID)
-    return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d); rdc_solve_dist has the others, not %d",
-                (int)RDC_PRECOND_MULTIGRID, precond);
-  if (!any_precond && !mg_entry && precond == RDC_PRECOND_MULTIGRID)
+  const bool mg = precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_MULTIGRID_GS_LOCAL;
+  if (!any_precond && mg_entry && !mg)
+    return fail(c, RDC_ERR_INVALID, "rdc_solve_dist_mg is the multigrid solve (precond %d or %d); rdc_solve_dist has the others, not %d",
+                (int)RDC_PRECOND_MULTIGRID, (int)RDC_PRECOND_MULTIGRID_GS_LOCAL, precond);
+  if (!any_precond && !mg_entry && mg)
     return fail(c, RDC_ERR_UNSUPPORTED, "the multigrid preconditioner across partitions exchanges on every level: rdc_solve_dist_mg");
   if (precond == RDC_PRECOND_ILU0_LOCAL && mixed && c->sopt.ilu_factor_bits != 32)
     return fail(c, RDC_ERR_UNSUPPORTED, "the rank-local block ILU(0) preconditioner (precond %d) has an FP64 factor only: rdc_solve_dist with mixed = 0",
                 (int)RDC_PRECOND_ILU0_LOCAL);
-  if (sized && c->sopt.mg_smoother == 1)
+  if (sized && precond == RDC_PRECOND_MULTIGRID && c->sopt.mg_smoother == 1)   // (precond 6 has its rule and does not consult the option)
     return fail(c, RDC_ERR_UNSUPPORTED, "rdc_solve_dist_mg smooths with damped Jacobi only: a Gauss-Seidel sweep (\"mg_smoother\" = 1) across "
                 "partitions needs a rule for the ghost values and is not implemented");
   const HostPrep& P = c->ms.prep;
@@ -487,7 +514,7 @@ int solve_dist_call(rdc_ctx* c, const rdc_solve_params* p, const rdc_solve_comm*
     return fail(c, RDC_ERR_UNSUPPORTED, "GMRES across partitions is not implemented (\"solve_method\" = 1): allreduce_sum carries at most %d doubles "
                 "and a GMRES step sums up to \"gmres_restart\" + 1; set \"solve_method\" to 0 for %s", DIST_RECORD, sized ? "rdc_solve_dist_mg" : "rdc_solve_dist");
   const bool mg_entry = sized != nullptr;
-  if (wide) sized = p->precond == RDC_PRECOND_MULTIGRID ? &wide->sized : nullptr;
+  if (wide) sized = p->precond == RDC_PRECOND_MULTIGRID || p->precond == RDC_PRECOND_MULTIGRID_GS_LOCAL ? &wide->sized : nullptr;
   if (!comm_complete(comm, sized, wide)) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
   if ((rc = check_solve_params(c, p))) return rc;
   if ((rc = dist_ready(c, p->precond, sized != nullptr, mg_entry, wide != nullptr, mixed))) return rc;
@@ -686,7 +713,7 @@ int rdc_solve_dist_gmres_arnoldi(rdc_ctx* c, const rdc_solve_comm_wide* comm, in
   int rc = solve_enter(c, SolveEntry::ARNOLDI);   // D^-1 in the work buffer is rebuilt, and the buffer takes the layout of a partitioned solve
   if (rc) return rc;
   if (!comm || !d_v0 || !d_V || !H || !steps_done) return fail(c, RDC_ERR_INVALID, "null argument");
-  const rdc_solve_comm_sized* sized = precond == RDC_PRECOND_MULTIGRID ? &comm->sized : nullptr;
+  const rdc_solve_comm_sized* sized = precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_MULTIGRID_GS_LOCAL ? &comm->sized : nullptr;
   if (!comm_complete(&comm->sized.base, sized, comm)) return fail(c, RDC_ERR_INVALID, "the communicator lacks a callback");
   if (!known_precond(precond, true)) return fail(c, RDC_ERR_INVALID, "unknown preconditioner %d", precond);
   if (steps < 1 || steps > c->sopt.gmres_restart)

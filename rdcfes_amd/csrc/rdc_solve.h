@@ -4,7 +4,8 @@
 // aggregation multigrid (aggregates, coarse patterns, the lists of the Galerkin kernel; tests/host_solve_mg_shim.cpp) and
 // the one statement of where a hierarchy lies on the device (MgDev, mg_place; tests/host_solve_mg_main.cpp), the colour lists of the
 // Gauss-Seidel smoother (mg_colour, mg_gs_place; tests/host_solve_mg_gs_shim.cpp, tests/host_solve_mg_gs_main.cpp), and the hierarchy of a
-// ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp).  The multicolour
+// ghosted context, whose aggregates stay inside the partition (MgHalo, mg_dist_*; tests/host_solve_mg_dist_shim.cpp; its
+// levels coloured per rank, mg_gs_interior: tests/host_solve_mg_gs_dist_shim.cpp, tests/host_solve_mg_gs_dist_main.cpp).  The multicolour
 // block ILU(0) has its private layout and the factor step of a node among the host+device functions (ilu_value_offset, ilu_find,
 // ilu_factor_node) and its lists and placement among the host ones (ilu_build, ilu_place; tests/host_solve_ilu_shim.cpp); on a
 // pattern with ghost columns the same functions factor the owned square (tests/host_solve_ilu_dist_shim.cpp).  The fp32 copy of
@@ -726,7 +727,15 @@ struct MgGsDev {
   int n_levels = 0;
   MgGsLevel lv[MG_MAX_LEVELS];
   bool fuse = true;   // option "mg_gs_fuse"
+  int64_t int0 = 0;   // partitioned hierarchy: the leading nodes of colour 0 of level 0 that lie below "interior_nodes" (mg_gs_interior)
 };
+
+// Nodes are numbered interior first and a colour list ascends, so the interior nodes of colour 0 are a prefix of its list: their count.
+inline int64_t mg_gs_interior(const MgColours& C, int64_t n_int) {
+  if (C.n_colours() < 1) return 0;
+  const auto c0 = C.nodes.begin() + C.cptr[0], c1 = C.nodes.begin() + C.cptr[1];
+  return std::lower_bound(c0, c1, n_int, [](int32_t node, int64_t bound) { return (int64_t)node < bound; }) - c0;
+}
 
 template <class Upload>
 inline void mg_gs_place(const std::vector<MgColours>& cols, MgArena& arena, MgGsDev& g, Upload&& upload) {

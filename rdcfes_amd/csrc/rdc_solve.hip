@@ -817,6 +817,53 @@ __global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_f32_fused(const int64_t
     }
 }
 
+// Across ranks (RDC_PRECOND_MULTIGRID_GS_LOCAL, levels below the matrix): a sweep that is followed by the exchange of x fills the level's
+// send buffer as k_smooth_pack does, from the register the lane stores to x.  The arithmetic is that of gs_node<NV, false>.
+template <int NV>
+__device__ __forceinline__ void gs_node_pack(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                             const double* __restrict__ val, const double* __restrict__ dinv, const double* __restrict__ r,
+                                             double* x, int64_t node, bool live, int lane, const SendList& send) {
+  double acc[NV];
+  row_product<NV>(bptr, bcol, val, x, node, live, lane, acc);
+  if (live && lane < NV) {
+    const int64_t i = node * NV + lane;
+    const double* __restrict__ drow = dinv + i * NV;
+    double z = 0.0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) z = fma(drow[q], r[node * NV + q] - acc[q], z);
+    const double xn = x[i] + z;
+    x[i] = xn;
+    pack_entry<NV>(send, node, lane, xn);
+  }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_gs_pack(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                 const double* __restrict__ val, const double* __restrict__ dinv,
+                                                 const double* __restrict__ r, double* x, const int32_t* __restrict__ list, int64_t count,
+                                                 SendList send) {
+  const int64_t at = (int64_t)blockIdx.x * SPMV_NODES + (threadIdx.x >> 4);
+  const bool live = at < count;
+  gs_node_pack<NV>(bptr, bcol, val, dinv, r, x, live ? list[at] : 0, live, threadIdx.x & 15, send);
+}
+
+// one whole sweep in one workgroup (the exchange stands between two sweeps, so a launch never holds more than one)
+template <int NV>
+__global__ __launch_bounds__(GS_FUSED_THREADS) void k_gs_fused_pack(const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
+                                                                    const double* __restrict__ val, const double* __restrict__ dinv,
+                                                                    const double* __restrict__ r, double* x, const int32_t* __restrict__ list,
+                                                                    const int64_t* __restrict__ cptr, int n_colours, SendList send) {
+  for (int c = 0; c < n_colours; c++) {
+    const int64_t c1 = cptr[c + 1];
+    for (int64_t at0 = cptr[c]; at0 < c1; at0 += GS_FUSED_THREADS / 16) {
+      const int64_t at = at0 + (threadIdx.x >> 4);
+      const bool live = at < c1;
+      gs_node_pack<NV>(bptr, bcol, val, dinv, r, x, live ? list[at] : 0, live, threadIdx.x & 15, send);
+    }
+    __syncthreads();
+  }
+}
+
 // ---- multicolour block ILU(0) (precond 4): M = (LU)^-1 from the right, LU the block ILU(0) of A^ = D^-1 A ----
 //
 // The factor lives in a copy of A^ in a layout of its own (rdc_solve.h, ilu_value_offset: per node the lower blocks in elimination
@@ -1189,7 +1236,8 @@ __global__ __launch_bounds__(256) void k_ilu_bwd_f32_owned(const int64_t* __rest
     (const void*)k_restrict_pack<3>, (const void*)k_prolong_pack<3>, (const void*)k_smooth_pack<3>,
     (const void*)k_restrict_pack<5>, (const void*)k_prolong_pack<5>, (const void*)k_smooth_pack<5>,
     GS_KERNELS_OF(3), GS_KERNELS_OF(5), ILU_KERNELS_OF(3), ILU_KERNELS_OF(5), ILU_OWNED_KERNELS_OF(3), ILU_OWNED_KERNELS_OF(5),
-    ILU_F32_KERNELS_OF(3), ILU_F32_KERNELS_OF(5)};
+    ILU_F32_KERNELS_OF(3), ILU_F32_KERNELS_OF(5),
+    (const void*)k_gs_pack<3>, (const void*)k_gs_fused_pack<3>, (const void*)k_gs_pack<5>, (const void*)k_gs_fused_pack<5>};
 #undef KERNELS_OF
 #undef GS_KERNELS_OF
 #undef ILU_KERNELS_OF
@@ -1608,10 +1656,79 @@ hipError_t mg_apply(const SolveDev& d, const Work& w, int l, Form form, double* 
   return apply<NV>(d, &w, l, form, x, y, nullptr);
 }
 
+// The sweeps of gs_sweeps on a partitioned hierarchy, one at a time behind the exchange of x.  Level 0: k_halo_pack and the exchange
+// of the plan's size; with one launch per colour the nodes of colour 0 below n_int -- a prefix of its ascending list,
+// MgGsDev::int0 of them -- run inside the exchange: they read no ghost, and no node of a colour reads another.  A level below: the
+// sized exchange of the send buffer its last writer filled; a sweep that another follows fills it again (k_gs_pack,
+// k_gs_fused_pack).  A rank that owns no node of the level launches nothing and makes every callback.
+template <int NV>
+hipError_t gs_sweeps_dist(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, int sweeps) {
+  const MgLevelDev& L = d.mg->lv[l];
+  const MgGsLevel& C = d.gs->lv[l];
+  const bool f32 = l == 0 && form == F32, fused = d.gs->fuse && L.n <= MG_GS_FUSED_NODES;
+  const double* val = l ? (const double*)L.val : d.val;
+  const double* dinv = l ? (const double*)L.dinv : (const double*)w.dinv;
+  const int64_t* bptr = l ? L.bptr : d.bptr;
+  const int32_t* bcol = l ? L.bcol : d.bcol;
+  auto colour_part = [&](int64_t c0, int64_t count, bool pack) {   // the nodes C.nodes[c0 .. c0 + count), one launch
+    if (count <= 0) return;
+    const dim3 grid((unsigned)op_blocks(count, f32 ? F32 : SCALED)), block(256);
+    if (f32)
+      hipLaunchKernelGGL((k_gs_f32<NV>), grid, block, 0, d.stream, bptr, bcol, d.voff, (const float*)d.val32, r, x, C.nodes + c0, count);
+    else if (pack)
+      hipLaunchKernelGGL((k_gs_pack<NV>), grid, block, 0, d.stream, bptr, bcol, val, dinv, r, x, C.nodes + c0, count, send_list(L));
+    else
+      hipLaunchKernelGGL((l ? k_gs<NV, false> : k_gs<NV, true>), grid, block, 0, d.stream, bptr, bcol, val, dinv, r, x, C.nodes + c0, count);
+  };
+  for (int s = 0; s < sweeps; s++) {
+    const bool pack = packs(d, l) && s + 1 < sweeps;
+    int first = 0;   // the first colour that is still to run behind the exchange
+    if (l == 0) {
+      if (d.dist.n_send) {
+        hipLaunchKernelGGL((k_halo_pack<NV>), per_thread(d.dist.n_send * NV), dim3(256), 0, d.stream, d.send_nodes, d.dist.n_send,
+                           (const double*)x, w.send);
+        SOLVE_HIP(hipGetLastError());
+      }
+      SOLVE_HIP(callback(d, d.comm->exchange_begin(d.comm->user, w.send, x + d.n_owned * NV, (void*)d.stream)));
+      const bool split = !fused && L.n && C.n_colours > 0;
+      if (split) colour_part(C.cptr_host[0], d.gs->int0, false);
+      SOLVE_HIP(hipGetLastError());
+      SOLVE_HIP(callback(d, d.comm->exchange_end(d.comm->user, (void*)d.stream)));
+      if (split) {
+        colour_part(C.cptr_host[0] + d.gs->int0, C.cptr_host[1] - C.cptr_host[0] - d.gs->int0, false);
+        first = 1;
+      }
+    } else if (d.sized) {
+      SOLVE_HIP(callback(d, d.sized->exchange_sized_begin(d.comm->user, L.send, x + L.n * NV, d.peers, L.send_off, L.ghost_off, (void*)d.stream)));
+      SOLVE_HIP(callback(d, d.sized->exchange_sized_end(d.comm->user, (void*)d.stream)));
+    }
+    if (!L.n) continue;
+    if (fused) {
+      const dim3 one(1), block(GS_FUSED_THREADS);
+      if (f32)
+        hipLaunchKernelGGL((k_gs_f32_fused<NV>), one, block, 0, d.stream, bptr, bcol, d.voff, (const float*)d.val32, r, x, C.nodes, C.cptr,
+                           C.n_colours, 1);
+      else if (pack)
+        hipLaunchKernelGGL((k_gs_fused_pack<NV>), one, block, 0, d.stream, bptr, bcol, val, dinv, r, x, C.nodes, C.cptr, C.n_colours, send_list(L));
+      else
+        hipLaunchKernelGGL((l ? k_gs_fused<NV, false> : k_gs_fused<NV, true>), one, block, 0, d.stream, bptr, bcol, val, dinv, r, x, C.nodes,
+                           C.cptr, C.n_colours, 1);
+    } else {
+      for (int c = first; c < C.n_colours; c++) colour_part(C.cptr_host[c], C.cptr_host[c + 1] - C.cptr_host[c], pack);
+    }
+    SOLVE_HIP(hipGetLastError());
+  }
+  return hipSuccess;
+}
+
 // `sweeps` forward Gauss-Seidel sweeps on level l over its colour lists (d.gs): x_n += D_l^-1 (r_n - (A_l x)_n) in place.  A level
 // of at most MG_GS_FUSED_NODES nodes takes one launch of one workgroup for all of them, any other one launch per colour and sweep.
+// Across ranks (RDC_PRECOND_MULTIGRID_GS_LOCAL) the sweep is Gauss-Seidel inside the rank and Jacobi between the ranks: the ghost
+// values a sweep reads are those of the exchange that precedes it, one per sweep as the damped-Jacobi sweep has it for its
+// operator, so the callbacks of a cycle are those of mg_smooth without colour lists.
 template <int NV>
 hipError_t gs_sweeps(const SolveDev& d, const Work& w, int l, Form form, const double* r, double* x, int sweeps) {
+  if (d.comm) return gs_sweeps_dist<NV>(d, w, l, form, r, x, sweeps);
   const MgLevelDev& L = d.mg->lv[l];
   const MgGsLevel& C = d.gs->lv[l];
   if (!L.n) return hipSuccess;

@@ -31,7 +31,7 @@ struct SolveCall {
   bool dist = false;                // the call is partitioned (entry DIST implies it; the collective Arnoldi hook sets it)
   bool partitioned() const { return dist || entry == SolveEntry::DIST; }
   bool ilu() const { return entry == SolveEntry::ILU_APPLY || precond == RDC_PRECOND_ILU0 || precond == RDC_PRECOND_ILU0_LOCAL; }
-  bool multigrid() const { return entry == SolveEntry::MG_APPLY || precond == RDC_PRECOND_MULTIGRID; }
+  bool multigrid() const { return entry == SolveEntry::MG_APPLY || precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_MULTIGRID_GS_LOCAL; }
 };
 
 struct SolveOutcome {

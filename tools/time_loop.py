@@ -1,11 +1,11 @@
 """PIHNA time loop that never leaves the card: k steps of assemble -> solve (initial guess = old solution, in place in
 the storage of FIELD_OLD_SOLUTION) -> clamp_nonnegative on a Kuhn mesh K(n), shipped parameters, synth.pihna_fields.
 
-    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
+    python tools/time_loop.py --n 119 --steps 5 [--rel-tol 1e-8] [--precond 2|3|4|5|6] [--mixed] [--smoother 0|1] [--gs-fuse 0|1]
                               [--ilu-bits 32|64] [--method bicgstab|gmres] [--restart N]
                               [--ab [precond|precision|dist|smoother|ilu_bits|method]] [--dump DIR]
-    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5] [--method bicgstab|gmres] [--restart N]
-                              [--ab precond|method]
+    python tools/time_loop.py --n 32 --steps 3 --ranks 2 [--backend gloo|nccl] [--precond 2|3|5|6] [--method bicgstab|gmres] [--restart N]
+                              [--ab precond|method|smoother]
 
 Per step: assembly ms (rdc_timing_last_ms), solve ms (device time of rdc_solve), iterations, restarts, the true
 preconditioned residual, and the share of nodes / elements still in the exact background state (n = c = h = a = 0),
@@ -36,6 +36,11 @@ the loop in the order BiCGStab, GMRES, GMRES, BiCGStab with --precond (and --mix
 entry at world size 1 in this process) or --ab dist, --method gmres is rdc_solve_dist_gmres, GMRES(m) across ranks through a
 communicator with the wide all-reduce, whatever the preconditioner (2, 3, 5); --ab dist --method gmres times rdc_solve under
 "solve_method" = 1 against it in the order rdc_solve, rdc_solve_dist_gmres, rdc_solve_dist_gmres, rdc_solve.  --dump writes the state after the last step as DIR/state.npy (+ conn, xyz).
+--precond 6 is the cycle of --precond 3 with the rank-local multicolour Gauss-Seidel smoother (Gauss-Seidel inside each rank, Jacobi
+between the ranks; "mg_smoother" is not consulted), the form --ranks takes; every record has the multigrid figures and this rank's
+colours per level.  On one partition it runs what --precond 3 --smoother 1 runs; --precond 6 --ab dist times exactly that pair in the
+order rdc_solve (precond 3, smoother 1), rdc_solve_dist_mg (precond 6), rdc_solve_dist_mg, rdc_solve.  --ab smoother with --ranks runs
+the loop in the order precond 3, 6, 6, 3 in the same processes.
 
 --ranks N: one process per rank (recursive coordinate bisection, one ghost layer, interior nodes first), every step assemble ->
 rdc_solve_dist (--precond 3: rdc_solve_dist_mg, multigrid with rank-local aggregates) -> clamp on each rank's part; the solve leaves the owners' values in the ghost rows, so the next assembly needs
@@ -102,6 +107,10 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
     if precond == 3 and comm is None:   # across partitions the smoother is damped Jacobi, and the option would be refused
         ctx.set_option("mg_smoother", smoother)
         ctx.set_option("mg_gs_fuse", gs_fuse)
+    if precond == 3 and comm is not None:
+        ctx.set_option("mg_smoother", 0)
+    if precond == 6:                    # the rank-local Gauss-Seidel smoother: "mg_smoother" is not consulted
+        ctx.set_option("mg_gs_fuse", gs_fuse)
     if precond in (4, 5):
         ctx.set_option("ilu_factor_bits", ilu_bits)
     # across partitions the method is in the entry's name, and rdc_solve_dist would refuse "solve_method" = 1
@@ -129,14 +138,16 @@ def run(ctx, conn, params, steps, rel_tol=1e-8, precond=2, max_its=20000, on_ste
                         background_nodes=nodes, background_elems=elems))
         if method == "gmres":
             out[-1].update(method="gmres", gmres_restart=restart, gmres_basis_bytes=ctx.gmres_stats()[1] if info.iterations else 0)
-        if precond == 3:
+        if precond in (3, 6):
             setup_ms, level_bytes = ctx.mg_stats()
             out[-1].update(mg_setup_ms=setup_ms, mg_level_bytes=level_bytes, mg_levels=ctx.mg_levels())
-            if comm is None:
+            if comm is None and precond == 3:
                 colours = ctx.mg_colours() if smoother else None
                 out[-1].update(mg_smoother=smoother, cycle_launches=cycle_launches(out[-1]["mg_levels"], colours, bool(gs_fuse)))
                 if smoother:
                     out[-1].update(mg_colours=colours, mg_gs_fuse=gs_fuse)
+            if precond == 6:
+                out[-1].update(mg_colours=ctx.mg_colours(), mg_gs_fuse=gs_fuse)
         if precond in (4, 5):
             setup_ms, nbytes, colours = ctx.ilu_stats()
             out[-1].update(ilu_setup_ms=setup_ms, ilu_bytes=nbytes, ilu_colours=colours, ilu_factor_bits=ctx.ilu_factor_bits())
@@ -164,11 +175,11 @@ def rank_main(rank, world, port, a):
             ctx.set_option("interior_nodes", int(lp.n_interior))
             ctx.mesh_upload(4, lp.conn, lp.xyz, 5, n_owned=lp.n_owned)
             ctx.field_upload(0, synth.pihna_fields(xyz)[lp.node_global])
-            preconds = (2, 3, 5, 5, 3, 2) if a.ab == "precond" else (a.precond,)
+            preconds = (2, 3, 5, 5, 3, 2) if a.ab == "precond" else (3, 6, 6, 3) if a.ab == "smoother" else (a.precond,)
             methods = ("bicgstab", "gmres", "gmres", "bicgstab") if a.ab == "method" else (a.method,) * len(preconds)
             preconds = preconds * (len(methods) // len(preconds))
             # multigrid: rdc_solve_dist_mg; GMRES: rdc_solve_dist_gmres
-            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=3 in preconds, wide="gmres" in methods)
+            comm = SolveComm(lp, 5, torch.device("cuda", gpu), sized=3 in preconds or 6 in preconds, wide="gmres" in methods)
             shared = world > torch.cuda.device_count()
             head = dict(rank=rank, gpu=gpu, owned_nodes=int(lp.n_owned), interior_nodes=int(lp.n_interior),
                         ghost_nodes=int(lp.xyz.shape[0] - lp.n_owned), halo_bytes_per_exchange=comm.bytes_per_exchange,
@@ -187,7 +198,8 @@ def rank_main(rank, world, port, a):
                                method=method, restart=a.restart):
                     if rank == 0:          # every figure of the solve is global and the same on every rank
                         keep = ("step", "iterations", "restarts", "reason", "matrix_bits", "residual_norm", "rhs_norm", "solve_ms", "assembly_ms")
-                        keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if precond == 3 else ()     # rank 0's own levels
+                        keep += ("mg_setup_ms", "mg_level_bytes", "mg_levels") if precond in (3, 6) else ()     # rank 0's own levels
+                        keep += ("mg_colours", "mg_gs_fuse") if precond == 6 else ()                           # rank 0's own colours
                         keep += ("ilu_setup_ms", "ilu_bytes", "ilu_colours", "ilu_factor_bits") if precond == 5 else ()        # rank 0's own factor
                         keep += ("method", "gmres_restart", "gmres_basis_bytes") if method == "gmres" else ()                  # rank 0's own basis
                         print(json.dumps({k: rec[k] for k in keep}), flush=True)
@@ -218,8 +230,10 @@ def main():
     a.ranks = a.ranks or 1
     if a.ab == "smoother":
         a.precond = 3
-    if (a.smoother or a.ab == "smoother") and (a.precond != 3 or a.ranks > 1 or world1 or a.ab == "dist"):
-        ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition")
+    if (a.smoother or (a.ab == "smoother" and a.ranks == 1)) and (a.precond != 3 or a.ranks > 1 or world1 or a.ab == "dist"):
+        ap.error("the Gauss-Seidel smoother belongs to --precond 3 on one partition (across ranks: --precond 6, or --ab smoother with --ranks)")
+    if a.precond == 6 and a.ab not in (None, "dist", "method"):
+        ap.error("--precond 6 takes --ab dist and --ab method only")
     f32 = a.ilu_bits == 32 or a.ab == "ilu_bits"
     if (f32 or a.ab == "ilu_bits") and a.precond not in (4, 5):
         ap.error("--ilu-bits and --ab ilu_bits belong to the block ILU(0): --precond 4 or 5")
@@ -233,8 +247,8 @@ def main():
         ap.error("--ranks 1 is the partitioned entry at world size 1 and takes no --ab but dist, which is the same comparison")
     if not 1 <= a.restart <= 128:
         ap.error("--restart is 1 .. 128")
-    if a.ranks > 1 and a.ab not in (None, "precond", "method"):
-        ap.error("--ranks takes --ab precond and --ab method only")
+    if a.ranks > 1 and a.ab not in (None, "precond", "method", "smoother"):
+        ap.error("--ranks takes --ab precond, --ab method and --ab smoother only")
     if a.ranks > 1 and a.ab == "precond" and a.mixed:
         ap.error("--ab precond with --ranks is FP64: the rank-local ILU(0) has no mixed form")
     if a.ranks > 1:
@@ -266,6 +280,8 @@ def main():
             runs = [(a.precond, mixed, False, a.smoother, a.ilu_bits) for mixed in (False, True, True, False)]
         elif a.ab == "dist":
             runs = [(a.precond, a.mixed, d, 0, a.ilu_bits) for d in (False, True, True, False)]
+            if a.precond == 6:     # the single-partition leg is what the partitioned one must equal: precond 3 under "mg_smoother" = 1
+                runs = [(6 if d else 3, a.mixed, d, 0 if d else 1, a.ilu_bits) for d in (False, True, True, False)]
         elif a.ab == "smoother":
             runs = [(3, a.mixed, False, sm, 64) for sm in (0, 1, 1, 0)]
         elif a.ab == "ilu_bits":
@@ -275,14 +291,14 @@ def main():
             from rdcfes_amd import SolveComm, partition
             lp = partition.LocalPartition(rank=0, nparts=1, conn=conn, xyz=xyz, n_owned=xyz.shape[0], node_global=np.arange(xyz.shape[0]),
                                           elem_global=np.arange(conn.shape[0]), n_elem_owned=conn.shape[0])
-            comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond == 3, wide=a.method == "gmres")
+            comm = SolveComm(lp, 5, torch.device("cuda", 0), sized=a.precond in (3, 6), wide=a.method == "gmres")
         for leg, (precond, mixed, dist_entry, smoother, ilu_bits) in enumerate(runs):
             method = methods[leg] if methods else a.method
             ctx.field_upload(0, u0)
             print(json.dumps(dict(mesh=f"K({a.n})", tets=int(conn.shape[0]), unknowns=int(xyz.shape[0] * 5), rel_tol=a.rel_tol, precond=precond, mixed=mixed,
-                                  smoother=smoother if precond == 3 else None, ilu_bits=ilu_bits if precond in (4, 5) else None,
+                                  smoother=smoother if precond == 3 else 1 if precond == 6 else None, ilu_bits=ilu_bits if precond in (4, 5) else None,
                                   method=method, restart=a.restart if method == "gmres" else None,
-                                  entry=("rdc_solve_dist_gmres" if method == "gmres" else "rdc_solve_dist_mg" if precond == 3 else "rdc_solve_dist") +
+                                  entry=("rdc_solve_dist_gmres" if method == "gmres" else "rdc_solve_dist_mg" if precond in (3, 6) else "rdc_solve_dist") +
                                   ", world size 1" if dist_entry else "rdc_solve")))
             for rec in run(ctx, conn, p, a.steps, a.rel_tol, precond, a.max_its, mixed=mixed, comm=comm if dist_entry else None,
                            smoother=smoother, gs_fuse=a.gs_fuse, ilu_bits=ilu_bits, method=method, restart=a.restart):
