@@ -786,6 +786,51 @@ int rdc_solve_dist_gmres(rdc_ctx* ctx, const rdc_solve_params* p, const rdc_solv
 int rdc_solve_dist_gmres_arnoldi(rdc_ctx* ctx, const rdc_solve_comm_wide* comm, int precond, int mixed, const double* d_v0, int steps,
                                  double* d_V, double* H, int32_t* steps_done);
 
+/* ---- device-resident Newton solve of the solid system (additive, RDC_ABI_VERSION stays 3): what SolidSystem::solve() does
+ * through libMesh's NewtonSolver (src/solid_system.C:84-100,380), as the host mirror states it (rdcfes_amd/host/rdc_host.h,
+ * SolidSystem::solve), in one call that hands no matrix, rhs or vector back.  Single partition.
+ * The unknowns are the context's CURRENT coordinates: the start iterate on entry, as rdc_mesh_upload, rdc_mesh_update_coords or
+ * a device-side write left them, the result on exit.  Undeformed coordinates, fibre, materials and sides are those set in the
+ * context; pseudo_time comes with rdc_solid_params, so the caller runs the load steps.  Per Newton iteration:
+ *   1. rdc_solid_assemble (R and J), ||R||_2: RDC_NEWTON_CONVERGED_RESIDUAL if <= absolute_residual_tolerance or
+ *      <= relative_residual_tolerance * first residual; RDC_NEWTON_MAX_ITS if max_nonlinear_iterations have been taken;
+ *   2. J delta = -R from delta = 0 with rdc_solve (mixed: rdc_solve_mixed) and `linear`; RDC_SOLVE_MAX_ITS is used as it is;
+ *   3. u = u0 + step * delta, step = 1; with require_reduction a residual-only assembly there, and step is halved while ||R(u)|| is
+ *      not below ||R(u0)|| and step >= 1e-3 (u is always recomputed from the saved u0; a trial residual that is not finite halves);
+ *   4. ||step * delta||_2 <= relative_step_tolerance * ||u||_2: one residual-only assembly for last_residual, RDC_NEWTON_CONVERGED_STEP.
+ * A solver outcome is not an error status: the call returns RDC_OK and info->reason tells.  On return the CSR values and rhs are
+ * those of the last assembly of the call (the rhs always at the returned coordinates, unless they were restored).
+ * Refused before anything is launched: what rdc_solid_assemble refuses (nvar != 3: RDC_ERR_INVALID; undeformed coordinates, fibre
+ * or materials unset: RDC_ERR_STATE); a context with ghost nodes (RDC_ERR_UNSUPPORTED); parameters out of range, tolerances that
+ * are NaN, infinite or negative, an unknown precond (RDC_ERR_INVALID).  The linear solve refuses what rdc_solve / rdc_solve_mixed
+ * refuse, with their status; the coordinates are then the start iterate.  Reads the linear-solve settings of rdc_set_option. */
+typedef struct rdc_solid_newton_params {
+  int32_t max_nonlinear_iterations;      /* "solver/nonlinear/max_nonlinear_iterations"; 1 .. 1000 */
+  int32_t require_reduction;             /* "solver/nonlinear/require_reduction": halve the step while ||R|| does not go down */
+  double  relative_step_tolerance, relative_residual_tolerance, absolute_residual_tolerance;
+  rdc_solve_params linear;               /* rel_tol = "solver/linear/initial_linear_tolerance", max_its, precond; rhs_scale is ignored (the library uses -1) */
+  int32_t mixed;                         /* 0: rdc_solve, 1: rdc_solve_mixed */
+  int32_t reserved;
+} rdc_solid_newton_params;
+
+#define RDC_NEWTON_CONVERGED_RESIDUAL 0
+#define RDC_NEWTON_CONVERGED_STEP     1
+#define RDC_NEWTON_MAX_ITS            2
+#define RDC_NEWTON_LINEAR_FAILED      3   /* BAD_DIAGONAL, BREAKDOWN or NOT_FINITE of the linear solve: coordinates = last accepted iterate */
+#define RDC_NEWTON_NOT_FINITE         4   /* a residual norm was NaN/inf: coordinates = last iterate with a finite residual */
+
+typedef struct rdc_solid_newton_info {
+  int32_t reason, nonlinear_iterations, linear_iterations, assemblies, halvings, last_linear_reason;
+  double  first_residual, last_residual, last_step_norm, last_solution_norm;
+  float   device_ms; int32_t reserved;
+} rdc_solid_newton_info;
+
+int rdc_solid_newton(rdc_ctx* ctx, const rdc_solid_params* p, const rdc_solid_newton_params* np, rdc_solid_newton_info* info);
+/* per Newton iteration of the last call on this context: ||R|| before the solve, accepted step length, linear iterations, linear
+ * reason.  *n = the iterations the call took (one more if it ended with RDC_NEWTON_LINEAR_FAILED: that iteration is listed with
+ * step 0); the first min(*n, cap) entries of every array that is not NULL are written. */
+int rdc_solid_newton_history(rdc_ctx* ctx, int cap, double* residual, double* step, int32_t* lin_its, int32_t* lin_reason, int32_t* n);
+
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */
 int rdc_clamp_nonnegative(rdc_ctx* ctx, int field);

@@ -348,11 +348,80 @@ class SolidSystemGPU : public SolidSystem {
  public:
   SolidSystemGPU(EquationSystems& es, std::string name, unsigned int number) : SolidSystem(es, name, number) {}
 
+  // Opt-in: solve() makes ONE call, rdc_solid_newton, in place of NewtonSolver + PETSc: the Newton iteration of
+  // "solver/nonlinear/*" with the device-resident linear solve, and only the positions come back (no matrix, no rhs).
+  // Single partition.  The linear solver is the context's (rdc_set_option "solve_method", "mg_smoother", ...) with the
+  // preconditioner named here, "solver/linear/initial_linear_tolerance" and "solver/linear/max_linear_iterations".
+  bool solve_on_device = false;
+  int device_precond = RDC_PRECOND_BLOCK_JACOBI;
+  bool device_mixed = false;
+  rdc_solid_newton_info last_device = rdc_solid_newton_info();   // what that call reported
+
+  virtual void solve() override {
+    if (!solve_on_device) { SolidSystem::solve(); return; }
+    EquationSystems& es = this->get_equation_systems();
+    const MeshBase& mesh = es.get_mesh();
+    if (mesh.n_processors() > 1) throw std::runtime_error("SolidSystemGPU::solve_on_device: single partition only");
+    Binding& B = bind(es, this->name(), 3);
+    const rdc_solid_params p = upload_iterate(es, mesh, B);
+    rdc_solid_newton_params np = rdc_solid_newton_params();
+    np.max_nonlinear_iterations = es.parameters.get<int>("solver/nonlinear/max_nonlinear_iterations");
+    np.require_reduction = es.parameters.get<bool>("solver/nonlinear/require_reduction") ? 1 : 0;
+    np.relative_step_tolerance = es.parameters.get<Real>("solver/nonlinear/relative_step_tolerance");
+    np.relative_residual_tolerance = es.parameters.get<Real>("solver/nonlinear/relative_residual_tolerance");
+    np.absolute_residual_tolerance = es.parameters.get<Real>("solver/nonlinear/absolute_residual_tolerance");
+    np.linear.rel_tol = es.parameters.get<Real>("solver/linear/initial_linear_tolerance");
+    np.linear.abs_tol = 0.0;
+    np.linear.rhs_scale = -1.0;
+    np.linear.max_its = es.parameters.get<int>("solver/linear/max_linear_iterations");
+    np.linear.precond = device_precond;
+    np.mixed = device_mixed ? 1 : 0;
+    check(B.ctx, rdc_solid_newton(B.ctx, &p, &np, &last_device), "rdc_solid_newton");
+    // the positions: the coordinate array has the layout of a 3-variable nodal field, so the slot of the old solution, which the
+    // solid system does not use, is bound to it and downloaded as a field
+    const size_t nn = B.local_to_global_node.size();
+    std::vector<double> x(3 * nn);
+    double* d_xyz = nullptr;
+    check(B.ctx, rdc_mesh_coords_device_ptr(B.ctx, &d_xyz), "rdc_mesh_coords_device_ptr");
+    check(B.ctx, rdc_field_bind_device(B.ctx, RDC_FIELD_OLD_SOLUTION, d_xyz, (int64_t)x.size()), "rdc_field_bind_device");
+    check(B.ctx, rdc_field_download(B.ctx, RDC_FIELD_OLD_SOLUTION, x.data(), (int64_t)x.size()), "rdc_field_download(positions)");
+    for (dof_id_type l = 0; l < B.n_owned; l++) {
+      const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
+      for (unsigned int d = 0; d < 3; d++) this->solution->set(nd.dof_number(this->number(), this->var[d], 0), x[3 * l + d]);
+    }
+    this->solution->close();
+    this->update();   // SolidSystem::update(): current_local_solution, the mesh, "SolidSystem::displacement"
+  }
+
   virtual void assembly(bool get_residual, bool get_jacobian, bool /*apply_heterogeneous_constraints*/ = false,
                         bool /*apply_no_constraints*/ = false) override {
     EquationSystems& es = this->get_equation_systems();
     const MeshBase& mesh = es.get_mesh();
     Binding& B = bind(es, this->name(), 3);
+    const rdc_solid_params p = upload_iterate(es, mesh, B);
+    check(B.ctx, rdc_solid_assemble(B.ctx, &p, get_jacobian ? 1 : 0), "rdc_solid_assemble");
+    check(B.ctx, rdc_csr_download(B.ctx, get_jacobian ? B.val.data() : nullptr, B.rhs.data()), "rdc_csr_download");
+    // owned rows -> system.matrix / system.rhs (FEMSystem::assembly zeroes them first; complete rows: no stash traffic)
+    if (get_residual) this->rhs->zero();
+    if (get_jacobian) this->matrix->zero();
+    Mat A = get_jacobian ? cast_ref<PetscMatrix<Number>&>(*this->matrix).mat() : nullptr;
+    for (dof_id_type l = 0; l < B.n_owned; l++) {
+      const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
+      for (unsigned int a = 0; a < 3; a++) {
+        const PetscInt row = (PetscInt)nd.dof_number(this->number(), this->var[a], 0);
+        const PetscInt r = (PetscInt)(l * 3 + a), b = B.row_ptr[r], n = B.row_ptr[r + 1] - b;
+        if (get_jacobian) MatSetValues(A, 1, &row, n, &B.col_glob[b], &B.val[b], INSERT_VALUES);
+        if (get_residual) this->rhs->set(row, B.rhs[r]);
+      }
+    }
+    if (get_residual) this->rhs->close();
+    if (get_jacobian) this->matrix->close();
+  }
+
+ private:
+  // what assembly() and the device solve put into the context: once the materials and sides, every time the current iterate,
+  // the undeformed positions and the reference fibre; returns the parameters of the call
+  rdc_solid_params upload_iterate(EquationSystems& es, const MeshBase& mesh, Binding& B) {
     const System& aux = es.get_system<System>("SolidSystem::auxiliary");
     const System& fibre = es.get_system<System>("SolidSystem::fibre");
     const size_t nn = B.local_to_global_node.size(), ne = B.elem_ids.size();
@@ -390,24 +459,7 @@ class SolidSystemGPU : public SolidSystem {
     check(B.ctx, rdc_mesh_update_coords(B.ctx, x.data()), "rdc_mesh_update_coords");
     check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_UNDEFORMED_XYZ, X.data(), (int64_t)X.size()), "rdc_field_upload(undeformed)");
     check(B.ctx, rdc_field_upload(B.ctx, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()), "rdc_field_upload(fibre)");
-    const rdc_solid_params p = marshal::solid_params(es.parameters);
-    check(B.ctx, rdc_solid_assemble(B.ctx, &p, get_jacobian ? 1 : 0), "rdc_solid_assemble");
-    check(B.ctx, rdc_csr_download(B.ctx, get_jacobian ? B.val.data() : nullptr, B.rhs.data()), "rdc_csr_download");
-    // owned rows -> system.matrix / system.rhs (FEMSystem::assembly zeroes them first; complete rows: no stash traffic)
-    if (get_residual) this->rhs->zero();
-    if (get_jacobian) this->matrix->zero();
-    Mat A = get_jacobian ? cast_ref<PetscMatrix<Number>&>(*this->matrix).mat() : nullptr;
-    for (dof_id_type l = 0; l < B.n_owned; l++) {
-      const Node& nd = mesh.node_ref(B.local_to_global_node[l]);
-      for (unsigned int a = 0; a < 3; a++) {
-        const PetscInt row = (PetscInt)nd.dof_number(this->number(), this->var[a], 0);
-        const PetscInt r = (PetscInt)(l * 3 + a), b = B.row_ptr[r], n = B.row_ptr[r + 1] - b;
-        if (get_jacobian) MatSetValues(A, 1, &row, n, &B.col_glob[b], &B.val[b], INSERT_VALUES);
-        if (get_residual) this->rhs->set(row, B.rhs[r]);
-      }
-    }
-    if (get_residual) this->rhs->close();
-    if (get_jacobian) this->matrix->close();
+    return marshal::solid_params(es.parameters);
   }
 };
 

@@ -12,7 +12,9 @@ from .context import (AssemblyContext, RdcError, TET4, HEX8, SCATTER_AUTO, SCATT
                       SCATTER_ROWGATHER, FIELD_OLD_SOLUTION, FIELD_AUX_NODAL,
                       FIELD_UNDEFORMED_XYZ, FIELD_ELEM_FIBRE, FIELD_PREV_SOLUTION, FIELD_TIME_DERIV,
                       FIELD_RT_DOSE, FIELD_ELEM_TRACTS, PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL, PRECOND_MULTIGRID_GS_LOCAL,
-                      SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE, ERR_COMM)
+                      SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE, ERR_COMM,
+                      NEWTON_CONVERGED_RESIDUAL, NEWTON_CONVERGED_STEP, NEWTON_MAX_ITS, NEWTON_LINEAR_FAILED, NEWTON_NOT_FINITE)
+from .params import SolidNewtonParams, SolidNewtonInfo
 
 
 def __getattr__(name):
@@ -31,4 +33,6 @@ __all__ = [
     "FIELD_ELEM_FIBRE", "FIELD_PREV_SOLUTION", "FIELD_TIME_DERIV", "FIELD_RT_DOSE", "FIELD_ELEM_TRACTS",
     "SolveParams", "SolveInfo", "PRECOND_NONE", "PRECOND_JACOBI", "PRECOND_BLOCK_JACOBI", "PRECOND_MULTIGRID", "PRECOND_ILU0", "PRECOND_ILU0_LOCAL", "PRECOND_MULTIGRID_GS_LOCAL",
     "SOLVE_CONVERGED", "SOLVE_MAX_ITS", "SOLVE_BREAKDOWN", "SOLVE_BAD_DIAGONAL", "SOLVE_NOT_FINITE", "ERR_COMM", "SolveComm",
+    "SolidNewtonParams", "SolidNewtonInfo", "NEWTON_CONVERGED_RESIDUAL", "NEWTON_CONVERGED_STEP", "NEWTON_MAX_ITS", "NEWTON_LINEAR_FAILED",
+    "NEWTON_NOT_FINITE",
 ]

@@ -4,7 +4,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveCommSizedStruct, SolveCommStruct, SolveCommWideStruct, SolveInfo, SolveParams
+from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidNewtonInfo, SolidNewtonParams, SolidParams, SolveCommSizedStruct, SolveCommStruct, SolveCommWideStruct, SolveInfo, SolveParams
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "librdc_assembly.so"
 
@@ -84,7 +84,9 @@ SIGNATURES = {
     "rdc_solve_dist_gmres": (C.c_int, [ctx_p, P(SolveParams), P(SolveCommWideStruct), C.c_int, C.c_void_p, P(SolveInfo)]),
     "rdc_solve_dist_gmres_arnoldi": (C.c_int, [ctx_p, P(SolveCommWideStruct), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, P(dbl),
                                                P(C.c_int32)]),
-    "rdc_clamp_nonnegative": (C.c_int, [ctx_p, C.c_int]),
+    "rdc_solid_newton": (C.c_int, [ctx_p, P(SolidParams), P(SolidNewtonParams), P(SolidNewtonInfo)]),
+    "rdc_solid_newton_history": (C.c_int, [ctx_p, C.c_int, P(dbl), P(dbl), P(i32), P(i32), P(i32)]),
+    "rdc_clamp_nonnegative":(C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_ripf_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),
     "rdc_adpm_parcellation_integrals": (C.c_int, [ctx_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, i64,

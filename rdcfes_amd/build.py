@@ -38,6 +38,7 @@ SOURCES = [
     "rdc_solid_cl.hip",
     "rdc_prep_cl.cpp",
     "rdc_solve.hip",
+    "rdc_newton.hip",
 ]
 
 ARCH = os.environ.get("RDC_OFFLOAD_ARCH", "gfx950")

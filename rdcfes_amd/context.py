@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidParams, SolveInfo, SolveParams
+from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidNewtonInfo, SolidNewtonParams, SolidParams, SolveInfo, SolveParams
 
 TET4, HEX8 = 4, 8
 SCATTER_AUTO, SCATTER_COLOURED, SCATTER_ROWGATHER = 0, 1, 2
@@ -17,6 +17,7 @@ VARIANT_AUTO, VARIANT_GENERIC = 0, 1
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID, PRECOND_ILU0, PRECOND_ILU0_LOCAL = 0, 1, 2, 3, 4, 5
 PRECOND_MULTIGRID_GS_LOCAL = 6   # the cycle of PRECOND_MULTIGRID with the rank-local multicolour Gauss-Seidel smoother
 SOLVE_CONVERGED, SOLVE_MAX_ITS, SOLVE_BREAKDOWN, SOLVE_BAD_DIAGONAL, SOLVE_NOT_FINITE = 0, 1, 2, 3, 4
+NEWTON_CONVERGED_RESIDUAL, NEWTON_CONVERGED_STEP, NEWTON_MAX_ITS, NEWTON_LINEAR_FAILED, NEWTON_NOT_FINITE = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 1, 2, 3, 4, 5, 6
 
 
@@ -270,6 +271,35 @@ class AssemblyContext:
 
     def solid_assemble(self, p: SolidParams, request_jacobian=True):
         self._ck(self._lib.rdc_solid_assemble(self._h, C.byref(p), 1 if request_jacobian else 0))
+
+    # -- device-resident Newton solve of the solid system
+    def solid_newton(self, params: SolidParams, *, max_nonlinear_iterations, require_reduction, relative_step_tolerance,
+                     relative_residual_tolerance, absolute_residual_tolerance, rel_tol, max_its, precond=PRECOND_BLOCK_JACOBI,
+                     mixed=False) -> SolidNewtonInfo:
+        """rdc_solid_newton: SolidSystem::solve() in one call.  The unknowns are the context's current coordinates (start iterate
+        in, result out: coords_tensor(), or solid_post_process on them); params carries pseudo_time, so the caller runs the load
+        steps.  The keyword arguments are the "solver/nonlinear/*" options and, for the linear solve of every iteration, rel_tol =
+        "solver/linear/initial_linear_tolerance", max_its, precond and mixed as in solve(); the options of solve() that are set with
+        set_option ("solve_method", "mg_smoother", ...) hold.  No matrix, rhs or vector is handed back.  A solver outcome is not an
+        error: info.reason is one of NEWTON_*; solid_newton_history() lists the iterations."""
+        np_ = SolidNewtonParams(int(max_nonlinear_iterations), 1 if require_reduction else 0, float(relative_step_tolerance),
+                                float(relative_residual_tolerance), float(absolute_residual_tolerance),
+                                SolveParams(float(rel_tol), 0.0, -1.0, int(max_its), int(precond)), 1 if mixed else 0, 0)
+        info = SolidNewtonInfo()
+        self._ck(self._lib.rdc_solid_newton(self._h, C.byref(params), C.byref(np_), C.byref(info)))
+        return info
+
+    def solid_newton_history(self):
+        """rdc_solid_newton_history -> (residual, step, lin_its, lin_reason), one entry per Newton iteration of the last
+        solid_newton: ||R|| before the solve, the accepted step length, the linear iterations and the reason of that solve"""
+        n = C.c_int32()
+        self._ck(self._lib.rdc_solid_newton_history(self._h, 0, None, None, None, None, C.byref(n)))
+        res, step = np.zeros(n.value), np.zeros(n.value)
+        its, reason = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._ck(self._lib.rdc_solid_newton_history(self._h, n.value, _dp(res), _dp(step), its.ctypes.data_as(i32p),
+                                                    reason.ctypes.data_as(i32p), C.byref(n)))
+        return res, step, its, reason
 
     # -- results
     def csr_values_device_ptr(self):

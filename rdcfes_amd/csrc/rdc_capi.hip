@@ -550,6 +550,7 @@ int rdc_ctx_destroy(rdc_ctx* c) {
   free_group(c, c->buf);
   if (c->solve_rec) (void)hipHostFree(c->solve_rec);
   if (c->gmres_rec) (void)hipHostFree(c->gmres_rec);
+  if (c->newton_rec) (void)hipHostFree(c->newton_rec);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->pack_event) (void)hipEventDestroy(c->pack_event);
   if (c->solid_part1_event) (void)hipEventDestroy(c->solid_part1_event);

@@ -8,6 +8,7 @@
 #include "rdc_internal.h"
 #include "rdc_const_rows.h"
 #include "rdc_parts.h"
+#include "rdc_newton.h"
 #include "rdc_solve.h"
 #include "rdc_solve_state.h"
 
@@ -38,7 +39,8 @@ struct Buffers {
   // ilu_f32: the offsets and the floats of the fp32 copy of that factor (first ILU solve or hook with "ilu_factor_bits" = 32; ilu_place_f32)
   // ilu_idx / ilu_val: the lists, and the factor / U_ii^-1 / vectors, of the block ILU(0) (first solve with RDC_PRECOND_ILU0; rdc_solve.h, ilu_place)
   // gmres: the state of restarted GMRES (first solve with "solve_method" = 1, or the Arnoldi hook; rdc_solve.h, gmres_carve)
-  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32, gmres; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
+  // newton: the saved iterate, the update and the sums of the Newton loop of the solid system (first rdc_solid_newton; rdc_newton.h, newton_carve)
+  struct { DevBuf bcol, work, voff, val32, mg_idx, mg_val, send, mg_stage, mg_gs, ilu_idx, ilu_val, ilu_f32, gmres, newton; } solve;   // mg_stage: what the collective calls of the set-up of rdc_solve_dist_mg move
   struct { DevBuf val, rhs, packed; } out;
   // sized by the call that uses them: partial results of the reductions, ...; stamps = diagnostic phase stamps, allocated = armed (rdc_debug_stamps)
   struct { DevBuf wg_max, adpm_slot, solid_post, stamps; } scratch;
@@ -127,6 +129,8 @@ struct rdc_ctx {
   hipEvent_t solid_part1_event = nullptr;   // recorded behind part 1 of a two-part solid assembly (the sides of part 2 wait for it)
   rdc::SolveScal* solve_rec = nullptr;   // pinned: the one record the host reads per iteration of the linear solve
   rdc::GmresRec* gmres_rec = nullptr;    // pinned: the record the host reads per Arnoldi step
+  rdc::NewtonRec* newton_rec = nullptr;  // pinned: the record the host reads behind an assembly or a step of rdc_solid_newton
+  rdc::NewtonHistory newton_history;     // per Newton iteration of the last rdc_solid_newton
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;   // pairs (start, stop), one pair per timed assemble call

@@ -543,6 +543,13 @@ class SolidSystem : public ImplicitSystem {
   // what the last solve() did (the reference prints this through NewtonSolver's verbose mode)
   struct NewtonLog { int nonlinear_iterations = 0, linear_iterations = 0, assemblies = 0; Real first_residual = 0, last_residual = 0; bool converged = false; };
   NewtonLog last;
+  // Opt-in: solve() makes ONE call, rdc_solid_newton, in place of the loop below it: the same Newton iteration with the
+  // device-resident linear solve, and only the positions come back.  Single partition.  The linear solver is the context's
+  // (rdc_set_option "solve_method", ...) with the preconditioner named here; tolerances and caps are the DiffSolver options above.
+  bool solve_on_device = false;
+  int device_precond = RDC_PRECOND_BLOCK_JACOBI;
+  bool device_mixed = false;
+  rdc_solid_newton_info last_device = rdc_solid_newton_info();   // what that call reported
 
   std::string system_type() const { return "SolidSystem"; }
 
@@ -559,6 +566,7 @@ class SolidSystem : public ImplicitSystem {
  private:
   bool bound_ = false;
   void bind(rdc_ctx* c);
+  void solve_device();
 };
 
 inline void SolidSystem::init_data() {
@@ -637,8 +645,52 @@ inline void SolidSystem::assembly(bool get_residual, bool get_jacobian) {
   last.assemblies++;
 }
 
+// solve() on the device: what assembly() uploads, one rdc_solid_newton, the positions back
+inline void SolidSystem::solve_device() {
+  rdc_ctx* c = es_.context(name_, 3);
+  if (!bound_) bind(c);
+  System& aux = es_.get_system<System>("SolidSystem::auxiliary");
+  System& fibre = es_.get_system<System>("SolidSystem::fibre");
+  check(c, rdc_mesh_update_coords(c, current_local_solution.raw().data()), "rdc_mesh_update_coords");
+  check(c, rdc_field_upload(c, RDC_FIELD_UNDEFORMED_XYZ, aux.current_local_solution.raw().data(), aux.current_local_solution.size()), "undeformed coordinates");
+  const int64_t ne = es_.get_mesh().n_elem();
+  const unsigned int nf = fibre.n_vars();
+  std::vector<double> eta((size_t)ne * 3);
+  for (int64_t e = 0; e < ne; e++)
+    for (int d = 0; d < 3; d++) eta[(size_t)e * 3 + d] = fibre.current_local_solution(e * nf + d);
+  check(c, rdc_field_upload(c, RDC_FIELD_ELEM_FIBRE, eta.data(), (int64_t)eta.size()), "fibre field");
+  const rdc_solid_params p = marshal::solid_params(es_.parameters);
+  rdc_solid_newton_params np = rdc_solid_newton_params();
+  np.max_nonlinear_iterations = max_nonlinear_iterations;
+  np.require_reduction = require_residual_reduction ? 1 : 0;
+  np.relative_step_tolerance = relative_step_tolerance;
+  np.relative_residual_tolerance = relative_residual_tolerance;
+  np.absolute_residual_tolerance = absolute_residual_tolerance;
+  np.linear.rel_tol = initial_linear_tolerance;
+  np.linear.abs_tol = 0.0;
+  np.linear.rhs_scale = -1.0;
+  np.linear.max_its = max_linear_iterations;
+  np.linear.precond = device_precond;
+  np.mixed = device_mixed ? 1 : 0;
+  check(c, rdc_solid_newton(c, &p, &np, &last_device), "rdc_solid_newton");
+  last.nonlinear_iterations = last_device.nonlinear_iterations;
+  last.linear_iterations = last_device.linear_iterations;
+  last.assemblies = last_device.assemblies;
+  last.first_residual = last_device.first_residual;
+  last.last_residual = last_device.last_residual;
+  last.converged = last_device.reason == RDC_NEWTON_CONVERGED_RESIDUAL || last_device.reason == RDC_NEWTON_CONVERGED_STEP;
+  // the positions: the coordinate array has the layout of a 3-variable nodal field, so the slot of the old solution, which the
+  // solid system does not use, is bound to it and downloaded as a field
+  double* d_xyz = nullptr;
+  check(c, rdc_mesh_coords_device_ptr(c, &d_xyz), "rdc_mesh_coords_device_ptr");
+  check(c, rdc_field_bind_device(c, RDC_FIELD_OLD_SOLUTION, d_xyz, (int64_t)solution.raw().size()), "rdc_field_bind_device");
+  check(c, rdc_field_download(c, RDC_FIELD_OLD_SOLUTION, solution.raw().data(), (int64_t)solution.raw().size()), "positions");
+  update();
+}
+
 inline void SolidSystem::solve() {
   last = NewtonLog();
+  if (solve_on_device) { solve_device(); return; }
   std::vector<double> delta(solution.raw().size()), minus_r(delta.size());
   for (int it = 0;; it++) {
     assembly(true, true);

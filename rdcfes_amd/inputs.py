@@ -58,6 +58,20 @@ class SolidSetup:
                 _real(kv, h + "Young", 1.0e3), _real(kv, h + "Poisson", 0.3), _real(kv, h + "FibreStiffness", 0.0),
                 tuple(_real(kv, h + f"VolumetricStretchRatio/rate_{d}", 0.0) for d in range(3)))
 
+        # the DiffSolver options SolidSystem::init_data hands to NewtonSolver (src/solid_system.C:84-100), input() defaults
+        self._newton = dict(
+            max_nonlinear_iterations=int(_real(kv, "solver/nonlinear/max_nonlinear_iterations", 100)),
+            require_reduction=_bool(kv, "solver/nonlinear/require_reduction", False),
+            relative_step_tolerance=_real(kv, "solver/nonlinear/relative_step_tolerance", 1.0e-3),
+            relative_residual_tolerance=_real(kv, "solver/nonlinear/relative_residual_tolerance", 1.0e-8),
+            absolute_residual_tolerance=_real(kv, "solver/nonlinear/absolute_residual_tolerance", 1.0e-8),
+            max_its=int(_real(kv, "solver/linear/max_linear_iterations", 50000)),
+            rel_tol=_real(kv, "solver/linear/initial_linear_tolerance", 1.0e-3))
+
+    def newton_options(self) -> dict:
+        """the "solver/nonlinear/*" and "solver/linear/*" values, under the keyword names of AssemblyContext.solid_newton"""
+        return dict(self._newton)
+
     def params(self, pseudo_time: float) -> SolidParams:
         return SolidParams(pseudo_time, self.penalty, int(self.use_symmetry), 0)
 

@@ -104,7 +104,30 @@ class SolveInfo(C.Structure):
                 f"device_ms={self.device_ms:.3f}, matrix_bits={self.matrix_bits})")
 
 
-EXCHANGE_BEGIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)   # user, d_send, d_recv, hip_stream
+class SolidNewtonParams(C.Structure):
+    """rdc_solid_newton_params: the DiffSolver options of SolidSystem::init_data (src/solid_system.C:84-100) and the linear solve
+    of every Newton iteration (linear.rhs_scale is ignored: the library solves J delta = -R)."""
+    _fields_ = [("max_nonlinear_iterations", C.c_int32), ("require_reduction", C.c_int32), ("relative_step_tolerance", _D),
+                ("relative_residual_tolerance", _D), ("absolute_residual_tolerance", _D), ("linear", SolveParams),
+                ("mixed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SolidNewtonInfo(C.Structure):
+    """rdc_solid_newton_info: outcome of rdc_solid_newton; reason is one of NEWTON_* (rdcfes_amd.context)."""
+    _fields_ = [("reason", C.c_int32), ("nonlinear_iterations", C.c_int32), ("linear_iterations", C.c_int32),
+                ("assemblies", C.c_int32), ("halvings", C.c_int32), ("last_linear_reason", C.c_int32),
+                ("first_residual", _D), ("last_residual", _D), ("last_step_norm", _D), ("last_solution_norm", _D),
+                ("device_ms", C.c_float), ("reserved", C.c_int32)]
+
+    def __repr__(self):
+        return (f"SolidNewtonInfo(reason={self.reason}, nonlinear_iterations={self.nonlinear_iterations}, "
+                f"linear_iterations={self.linear_iterations}, assemblies={self.assemblies}, halvings={self.halvings}, "
+                f"last_linear_reason={self.last_linear_reason}, first_residual={self.first_residual:.6e}, "
+                f"last_residual={self.last_residual:.6e}, last_step_norm={self.last_step_norm:.6e}, "
+                f"last_solution_norm={self.last_solution_norm:.6e}, device_ms={self.device_ms:.3f})")
+
+
+EXCHANGE_BEGIN_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)   # user, d_send, d_recv, hip_stream
 EXCHANGE_END_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)                             # user, hip_stream
 ALLREDUCE_SUM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)     # user, d_vals, n, hip_stream
 
