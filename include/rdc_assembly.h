@@ -831,6 +831,45 @@ int rdc_solid_newton(rdc_ctx* ctx, const rdc_solid_params* p, const rdc_solid_ne
  * step 0); the first min(*n, cap) entries of every array that is not NULL are written. */
 int rdc_solid_newton_history(rdc_ctx* ctx, int cap, double* residual, double* step, int32_t* lin_its, int32_t* lin_reason, int32_t* n);
 
+/* ---- Newton solve of the solid system across ranks (additive: RDC_ABI_VERSION stays 3): the contract of rdc_solid_newton, across
+ * the ranks of `comm`.  Every rank calls with its own context, which may have one ghost layer (owned nodes first, ghosts behind
+ * them) and then carries the send list of rdc_solve_dist_plan (width nvar = 3: the coordinate array [node][3] is the dof layout).
+ * Parameters, info and rdc_solid_newton_history are those of rdc_solid_newton.
+ *
+ * What is global.  Every norm newton's decisions read -- ||R||, ||step delta||, ||u|| -- is the norm over the owned rows of all
+ * ranks, and rdc_solve_info of every linear solve is global, so every rank takes the same branch, and info and the history are
+ * identical on every rank, except info->device_ms, which is this rank's own.
+ *
+ * What the entry itself communicates.  (1) On entry ONE exchange of the coordinates: the library packs the owned coordinates of the
+ * plan's send nodes and calls exchange_begin / exchange_end with d_recv = the ghost tail of the coordinate array.  Ghost rows of the
+ * coordinates are ignored on entry and hold the owners' values on exit: after this exchange every rank moves its ghost coordinates
+ * itself, u = u0 + step * delta over ALL local nodes, from a delta whose ghost rows the partitioned linear entry returned holding
+ * the owners' values -- rdc_solve_dist, rdc_solve_dist_mg and rdc_solve_dist_gmres return them so whatever info->reason is -- by the
+ * same arithmetic on the same bits as the owner, so a ghost coordinate stays bit for bit its owner's through steps, halving trials
+ * and the restore.  (2) Before each host read one allreduce_sum of n = 8 doubles, the whole 64-byte record of the loop (three sums
+ * over the owned rows, five zeros): one behind each full assembly, each step or trial, and each measuring accept.  No linear entry
+ * makes an all-reduce of that length.  Everything else is what the linear entry exchanges.
+ *
+ * The linear solve.  "solve_method" = 1: rdc_solve_dist_gmres; otherwise linear.precond RDC_PRECOND_MULTIGRID or
+ * RDC_PRECOND_MULTIGRID_GS_LOCAL: rdc_solve_dist_mg; otherwise rdc_solve_dist; `mixed` is passed through.  Of `comm`,
+ * exchange_begin, exchange_end and allreduce_sum are always required, the sized pair only for the two multigrid preconditioners,
+ * allreduce_sum_wide only under "solve_method" = 1; the others may be NULL.  The linear entries keep their own refusals
+ * (RDC_PRECOND_ILU0, "mg_smoother" = 1 under RDC_PRECOND_MULTIGRID, missing peer counts, ...): their status comes back from the first
+ * solve, with the owned coordinates as on entry.
+ *
+ * Refused before any callback: what rdc_solid_newton refuses, except ghost nodes; RDC_ERR_STATE for a context with ghost nodes
+ * and no send list; RDC_ERR_INVALID for a NULL communicator or a required callback that is NULL.  Every one of these depends only on
+ * inputs that are the same on every rank (the mesh's nvar, what was set, the parameters, the options, the communicator's shape), so
+ * they are collective by construction: either every rank refuses or none does.
+ *
+ * A rank that owns no node takes part in every callback with zero sums and does not return early.  If a callback, of the loop or of
+ * a linear solve, returns non-zero the entry returns RDC_ERR_COMM, makes no further callback, and leaves the coordinates finite, as
+ * the last executed action left them.  NOT collective, as for the other partitioned entries: HIP errors, and a failure of an assembly
+ * in the middle of the loop; the other ranks then wait in their next callback, and ending them is the caller's business.
+ * On a context without ghosts, with a communicator of world size 1, the entry launches and returns what rdc_solid_newton does. */
+int rdc_solid_newton_dist(rdc_ctx* ctx, const rdc_solid_params* p, const rdc_solid_newton_params* np, const rdc_solve_comm_wide* comm,
+                          rdc_solid_newton_info* info);
+
 /* ---- post-solve nodal kernel: negativity clamp of check_solution,
  * src/pihna.C:785-790, applied in place to a device-resident field ---- */
 int rdc_clamp_nonnegative(rdc_ctx* ctx, int field);

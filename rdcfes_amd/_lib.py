@@ -85,6 +85,7 @@ SIGNATURES = {
     "rdc_solve_dist_gmres_arnoldi": (C.c_int, [ctx_p, P(SolveCommWideStruct), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, P(dbl),
                                                P(C.c_int32)]),
     "rdc_solid_newton": (C.c_int, [ctx_p, P(SolidParams), P(SolidNewtonParams), P(SolidNewtonInfo)]),
+    "rdc_solid_newton_dist": (C.c_int, [ctx_p, P(SolidParams), P(SolidNewtonParams), P(SolveCommWideStruct), P(SolidNewtonInfo)]),
     "rdc_solid_newton_history": (C.c_int, [ctx_p, C.c_int, P(dbl), P(dbl), P(i32), P(i32), P(i32)]),
     "rdc_clamp_nonnegative":(C.c_int, [ctx_p, C.c_int]),
     "rdc_pihna_volume_integrals": (C.c_int, [ctx_p, C.c_void_p, i64, C.POINTER(C.c_double)]),

@@ -6,7 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import HccParams, PihnaParams, RipfParams, SolidMaterial, SolidNewtonInfo, SolidNewtonParams, SolidParams, SolveInfo, SolveParams
+from .params import (HccParams, PihnaParams, RipfParams, SolidMaterial, SolidNewtonInfo, SolidNewtonParams, SolidParams, SolveCommSizedStruct,
+                     SolveCommWideStruct, SolveInfo, SolveParams)
 
 TET4, HEX8 = 4, 8
 SCATTER_AUTO, SCATTER_COLOURED, SCATTER_ROWGATHER = 0, 1, 2
@@ -289,9 +290,38 @@ class AssemblyContext:
         self._ck(self._lib.rdc_solid_newton(self._h, C.byref(params), C.byref(np_), C.byref(info)))
         return info
 
+    def solid_newton_dist(self, comm, params: SolidParams, *, max_nonlinear_iterations, require_reduction, relative_step_tolerance,
+                          relative_residual_tolerance, absolute_residual_tolerance, rel_tol, max_its, precond=PRECOND_BLOCK_JACOBI,
+                          mixed=False) -> SolidNewtonInfo:
+        """rdc_solid_newton_dist: solid_newton across the ranks of comm (halo.SolveComm), every rank calling with its own ghosted
+        context.  Arguments as solid_newton.  The norms the loop decides on are global, so the returned info and
+        solid_newton_history() are the same on every rank (device_ms is this rank's own).  Ghost coordinates are ignored on entry
+        and hold the owners' values on exit.  The linear solve of an iteration is rdc_solve_dist_gmres under
+        set_option("solve_method", 1), rdc_solve_dist_mg for PRECOND_MULTIGRID and PRECOND_MULTIGRID_GS_LOCAL, rdc_solve_dist
+        otherwise; comm needs the callbacks of that entry (SolveComm(..., sized=True) / wide=True) and the library refuses,
+        RdcError invalid, before any callback if one is missing.  The send list of comm is uploaded once per mesh, as in
+        solve_dist.  An exception raised inside a callback of comm is re-raised here."""
+        self._dist_plan_for(comm)
+        # the superset struct; what comm does not have stays NULL, and the library says which callback the dispatch misses
+        wide = getattr(comm, "wide_struct", None)
+        if wide is None:
+            sized = getattr(comm, "sized_struct", None)
+            wide = SolveCommWideStruct(sized if sized is not None else SolveCommSizedStruct(comm.struct))
+        np_ = SolidNewtonParams(int(max_nonlinear_iterations), 1 if require_reduction else 0, float(relative_step_tolerance),
+                                float(relative_residual_tolerance), float(absolute_residual_tolerance),
+                                SolveParams(float(rel_tol), 0.0, -1.0, int(max_its), int(precond)), 1 if mixed else 0, 0)
+        info = SolidNewtonInfo()
+        comm.error = None
+        rc = self._lib.rdc_solid_newton_dist(self._h, C.byref(params), C.byref(np_), C.byref(wide), C.byref(info))
+        if comm.error is not None:
+            err, comm.error = comm.error, None
+            raise err
+        self._ck(rc)
+        return info
+
     def solid_newton_history(self):
         """rdc_solid_newton_history -> (residual, step, lin_its, lin_reason), one entry per Newton iteration of the last
-        solid_newton: ||R|| before the solve, the accepted step length, the linear iterations and the reason of that solve"""
+        solid_newton or solid_newton_dist: ||R|| before the solve, the accepted step length, the linear iterations and the reason of that solve"""
         n = C.c_int32()
         self._ck(self._lib.rdc_solid_newton_history(self._h, 0, None, None, None, None, C.byref(n)))
         res, step = np.zeros(n.value), np.zeros(n.value)

@@ -13,6 +13,11 @@
 // Host traffic.  No matrix, rhs or vector crosses the bus between entry and exit.  Per Newton iteration the host reads the records
 // rdc_solve reads, and one 64-byte record (NewtonRec: three sums) behind the full assembly and one behind every step or trial:
 // ||R||^2 behind the assembly; ||step delta||^2, ||u||^2 and, where the step is tried, ||R(u)||^2 behind the step.
+//
+// Across ranks (rdc_solid_newton_dist).  The decisions are the same newton_next, fed global norms: every sum runs over the rows a
+// rank owns and the whole record crosses the ranks in one allreduce_sum of NEWTON_REC_DOUBLES doubles before each host read.
+// newton_linear_dispatch names the partitioned linear entry and the callbacks it needs; newton_carve_dist is the work memory with
+// a ghost tail behind delta (the partitioned entries fill it with the owners' values) and the send buffer of the entry exchange.
 #ifndef RDC_NEWTON_H
 #define RDC_NEWTON_H
 
@@ -40,6 +45,8 @@ struct NewtonWork {
   int64_t blocks = 0;              // workgroups of a pass over n entries: partials holds 2 per workgroup (k_newton_step)
   int64_t u0 = 0, delta = 0, partials = 0, rec = 0;
   size_t bytes = 0;
+  int64_t n_delta = 0;             // entries of delta: n_owned, or n behind newton_carve_dist (a ghost tail the linear solve fills)
+  int64_t send = 0, n_send = 0;    // newton_carve_dist: the packed coordinates of the plan's send nodes (3 per node); else empty
 };
 
 // the one statement of the layout; it only measures (nothing is dereferenced)
@@ -55,7 +62,52 @@ inline NewtonWork newton_carve(int64_t n_node, int64_t n_owned) {
   w.partials = at; at += up(2 * w.blocks);
   w.rec = at; at += NEWTON_REC_DOUBLES;
   w.bytes = (size_t)at * sizeof(double);
+  w.n_delta = w.n_owned;
+  w.send = w.rec;   // empty
   return w;
+}
+
+// The layout of rdc_solid_newton_dist: delta has all n entries (owned rows, then the ghost tail), and the send buffer of the one
+// exchange the entry makes itself lies before the record.  Without ghosts and with an empty send list every offset and the size
+// are those of newton_carve.
+inline NewtonWork newton_carve_dist(int64_t n_node, int64_t n_owned, int64_t n_send_nodes) {
+  NewtonWork w;
+  auto up = [](int64_t v) { return (v + NEWTON_ALIGN - 1) / NEWTON_ALIGN * NEWTON_ALIGN; };
+  w.n = 3 * n_node;
+  w.n_owned = 3 * n_owned;
+  w.n_delta = w.n;
+  w.n_send = 3 * n_send_nodes;
+  w.blocks = (w.n + NEWTON_CHUNK - 1) / NEWTON_CHUNK;
+  int64_t at = 0;
+  w.u0 = at; at += up(w.n);
+  w.delta = at; at += up(w.n_delta);
+  w.partials = at; at += up(2 * w.blocks);
+  w.send = at; at += up(w.n_send);
+  w.rec = at; at += NEWTON_REC_DOUBLES;
+  w.bytes = (size_t)at * sizeof(double);
+  return w;
+}
+
+// ---- the linear solve of rdc_solid_newton_dist: which partitioned entry runs, and which callbacks of rdc_solve_comm_wide must
+// not be NULL for it.  exchange_begin, exchange_end and allreduce_sum always are (the loop itself uses them).
+enum NewtonLinearEntry : int32_t { NEWTON_LINEAR_DIST = 0, NEWTON_LINEAR_DIST_MG = 1, NEWTON_LINEAR_DIST_GMRES = 2 };
+enum { NEWTON_NEEDS_SIZED = 1, NEWTON_NEEDS_WIDE = 2 };
+struct NewtonDispatch { NewtonLinearEntry entry; int32_t needs; };
+
+inline NewtonDispatch newton_linear_dispatch(int32_t precond, int32_t solve_method) {
+  const bool mg = precond == RDC_PRECOND_MULTIGRID || precond == RDC_PRECOND_MULTIGRID_GS_LOCAL;
+  NewtonDispatch d;
+  d.entry = solve_method == 1 ? NEWTON_LINEAR_DIST_GMRES : mg ? NEWTON_LINEAR_DIST_MG : NEWTON_LINEAR_DIST;
+  d.needs = (mg ? NEWTON_NEEDS_SIZED : 0) | (solve_method == 1 ? NEWTON_NEEDS_WIDE : 0);
+  return d;
+}
+
+inline bool newton_comm_complete(const rdc_solve_comm_wide& c, const NewtonDispatch& d) {
+  const rdc_solve_comm& b = c.sized.base;
+  if (!b.exchange_begin || !b.exchange_end || !b.allreduce_sum) return false;
+  if ((d.needs & NEWTON_NEEDS_SIZED) && (!c.sized.exchange_sized_begin || !c.sized.exchange_sized_end)) return false;
+  if ((d.needs & NEWTON_NEEDS_WIDE) && !c.allreduce_sum_wide) return false;
+  return true;
 }
 
 // ---- what the entry refuses of its parameters: null if they are fine, the message otherwise

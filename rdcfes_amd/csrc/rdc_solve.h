@@ -1125,6 +1125,9 @@ hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int
 // this rank's owned rows, the norm of v0 and every sum are global, H is the same on every rank.
 hipError_t solve_gmres_arnoldi(const SolveDev& d, int precond, bool mixed, const double* v0, int steps, double* V, double* H,
                                int* steps_done, int* bad_blocks, int* matrix_bits);
+// The pack kernel of the partitioned solves for a caller outside them (rdc_solid_newton_dist): send[i * nvar + a] =
+// x[send_nodes[i] * nvar + a] for the n_send entries of the plan's device send list.  nvar 3 or 5; enqueues, does not synchronise.
+hipError_t solve_halo_pack(int nvar, const int32_t* send_nodes, int64_t n_send, const double* x, double* send, hipStream_t stream);
 // where the D^-1 of the last single-partition set-up lies in d.work (n_owned * nvar * nvar doubles)
 const double* solve_dinv(const SolveDev& d);
 

@@ -2218,6 +2218,14 @@ hipError_t solve_ilu_apply(const SolveDev& d, const double* in, double* out, int
 
 const double* solve_dinv(const SolveDev& d) { return carve(d.nvar, d.n_owned, d.work).dinv; }
 
+hipError_t solve_halo_pack(int nvar, const int32_t* send_nodes, int64_t n_send, const double* x, double* send, hipStream_t stream) {
+  if (nvar != 3 && nvar != 5) return hipErrorInvalidValue;
+  if (n_send <= 0) return hipSuccess;
+  if (nvar == 3) hipLaunchKernelGGL((k_halo_pack<3>), per_thread(n_send * 3), dim3(256), 0, stream, send_nodes, n_send, x, send);
+  else hipLaunchKernelGGL((k_halo_pack<5>), per_thread(n_send * 5), dim3(256), 0, stream, send_nodes, n_send, x, send);
+  return hipGetLastError();
+}
+
 hipError_t solve_run(const SolveDev& d, const rdc_solve_params& p, double* x, rdc_solve_info* info, bool mixed) {
   *info = rdc_solve_info();
   info->matrix_bits = 64;
